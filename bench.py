@@ -12,7 +12,10 @@ every rank owns its own 1024 utterances and the path needs no collective (the st
 belongs to the accumulate stage, measured separately under "extra").
 
 Inputs (frames, model, batch descriptors) are resident in HBM before the timed region.  Timing:
-barrier + device sync on both sides of exactly K steps, MAX over ranks; rank 0 prints ONE JSON line.
+barrier + device sync on both sides of exactly K steps, MAX over ranks; rank 0 prints ONE JSON line.  That is all a plain run
+does; `--full` adds what is measured beside the headline (CPU baseline, held and fresh-batch loops, the E-step with its exchange,
+side measurements, other configurations) and writes the full record.  `--dump-outputs DIR` writes what the last timed step computed
+(the inputs are seeded: the same arguments give the same inputs), so that two builds can be compared output for output.
 Multi-GPU: one process per GPU.  Launched by torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the
 env), or by itself: `python bench.py --gpus N` with no launcher env spawns N rank processes (subprocess, before
 anything touches HIP; the parent never does), waits for them and exits non-zero if any of them failed.  The barrier /
@@ -87,7 +90,20 @@ def parse():
     p.add_argument('--c-covariance', type=float, default=1e-3, help='--workload C4: the variance floor of GMM.update_param (the reference driver passes 1e-6: init.py:30 -> Controller.py:151)')
     p.add_argument('--payload', default='auto', choices=['auto', 'f64', 'f32'],
                    help='wire format of the E-step exchange: auto = f32 when there is more than one rank (half the bytes on xGMI), f64 on one')
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='also measure everything beside the headline: the CPU baseline, the dynamic-programming kernels alone, the held, '
+                        'fresh-batch and PCIe-inclusive loops, the E-step with its exchange, the side measurements and other '
+                        'configurations (--cpu-baseline, --extra and --sustain apply here); the full record goes to bench_full.json.  '
+                        'Without it a run sets up, warms up, times the steps and prints the line')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last one computed as DIR/<name>.npy (float64; rank 0; a fixed, seeded sample '
+                        'of the utterances for the (N, T) matrices)')
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.dump_outputs and args.workload in ('C5shard', 'C4', 'C5'):
+        p.error('--dump-outputs is not supported for --workload %s' % args.workload)
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -382,11 +398,12 @@ def write_full_record(full):
     return first
 
 
-def emit(full, final):
+def emit(full, final, record=True):
     """rank 0: write the full record, print the compact line (and flush): called once as soon as the headline, the roofline and the CPU
-    leg are final, and again at the end with what the untimed extras added -- a late failure leaves the early line as the last one."""
+    leg are final, and again at the end with what the untimed extras added -- a late failure leaves the early line as the last one.
+    A plain run (no --full) prints its line once and writes no record (record=False)."""
     full = dict(full, final=final)
-    full['full_record'] = write_full_record(full)
+    full['full_record'] = write_full_record(full) if record else None
     print(compact_line(full))
     sys.stdout.flush()
 
@@ -592,6 +609,32 @@ def timed_steps(eng, batches, P, align, warmup, steps, barrier):
     score_ms, score_n = eng.kernel_time('score')
     fb_ms, fb_n = eng.kernel_time('fb')
     return elapsed, score_ms, score_n, fb_ms, fb_n
+
+
+DUMP_SAMPLE_UTTS = 64         # utterances whose (N, T) matrices --dump-outputs writes: 9.2 + 9.5 MB at the C4 shard's N = 62, T = 300
+
+
+def dump_outputs(batch, align, out_dir, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as float64 DIR/<name>.npy, so that two builds can be compared output
+    for output.  Per utterance of the batch: ln P(O) and the Baum-Welch passes run (forced alignment, --workload C3: the Viterbi score).
+    For a fixed, seeded sample of DUMP_SAMPLE_UTTS utterances (the whole batch's matrices are ~300 MB): the emissions ln b of the
+    emitting states (rows 1 .. N-2; the exit row is ln 0), the state posteriors gamma_t(i) = exp(ln gamma) in [0, 1] -- in the linear
+    domain because ln gamma is ln 0 wherever a state cannot be occupied at a frame -- and pi of the final pass (forced alignment: the
+    Viterbi path); `sample_utterances` says which.  Every value written is finite.  Returns the names written."""
+    pick = np.sort(np.random.default_rng(seed).choice(batch.U, size=min(DUMP_SAMPLE_UTTS, batch.U), replace=False))
+
+    def sample(what):
+        got = batch.get(what)
+        return np.stack([got[u] for u in pick])
+    out = dict(sample_utterances=pick, B=sample('B')[:, 1:-1])
+    if align:
+        out.update(point=batch.get('point'), path=sample('path'))
+    else:
+        out.update(logp=batch.get('logp'), npass=batch.get('npass'), posteriors=np.exp(sample('lgamma')), pi=sample('pi'))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.asarray(a, dtype=np.float64))
+    return sorted(out)
 
 
 
@@ -848,6 +891,9 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     args.gpus = world
+    if not args.full:                             # a plain run: set-up, warm-up, the timed steps, the line -- nothing beside the headline
+        args.cpu_baseline = args.extra = 0
+        args.sustain = 0.0
     if os.environ.get('POCCALA_HANG_DUMP'):       # diagnostics: where is every thread after N seconds
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ['POCCALA_HANG_DUMP']), repeat=True, file=sys.stderr)
@@ -928,21 +974,24 @@ def main():
     elapsed = ctl.allreduce_max(elapsed)
     if os.environ.get('POCCALA_TEST_DIE_RANK') == str(rank):      # tests/test_gpu_a_bench_ranks.py: a rank that dies behind the timed loop
         os._exit(7)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batches[(args.warmup + args.steps - 1) % nb], align, args.dump_outputs)       # (timed_steps alternates from batch 0)
     # the dynamic-programming kernels ALONE (outside the timed region): inside the loop their HIP events span the time their
     # workgroups wait for register-file room beside the next step's scoring waves, not the time they work
     dp_alone_ms = None
-    try:
-        for _ in range(3):
-            (batches[0].viterbi if align else batches[0].forward_backward)()
-        eng.sync()
-        eng.kernel_time('viterbi' if align else 'fb')
-        for _ in range(5):
-            (batches[0].viterbi if align else batches[0].forward_backward)()
-        eng.sync()
-        ms_, n_ = eng.kernel_time('viterbi' if align else 'fb')
-        dp_alone_ms = ms_ / max(n_, 1)
-    except Exception:                          # noqa: never the headline's problem
-        pass
+    if args.full:
+        try:
+            for _ in range(3):
+                (batches[0].viterbi if align else batches[0].forward_backward)()
+            eng.sync()
+            eng.kernel_time('viterbi' if align else 'fb')
+            for _ in range(5):
+                (batches[0].viterbi if align else batches[0].forward_backward)()
+            eng.sync()
+            ms_, n_ = eng.kernel_time('viterbi' if align else 'fb')
+            dp_alone_ms = ms_ / max(n_, 1)
+        except Exception:                      # noqa: never the headline's problem
+            pass
     tl['timed_loop_s'] = time.perf_counter() - t_mark
     t_mark = time.perf_counter()
 
@@ -1036,7 +1085,7 @@ def main():
 
     # The headline, its roofline and the CPU leg are final: the line goes out NOW (rank 0), before anything else can hang, fail or
     # outgrow a reader; it is printed again at the end with what the untimed measurements added (the driver reads the last line).
-    if rank == 0:
+    if rank == 0 and args.full:
         emit(make_full(None), final=False)
     # What follows (the held loops, the E-step with its exchange, side measurements) is outside the timed region and must not be able
     # to take the line with it: an exception is reported inside `extra`, and if it does not come back within --extra-timeout seconds
@@ -1080,7 +1129,7 @@ def main():
 
     extra = None
     comm_error = None
-    if world > 1 or os.environ.get('POCCALA_FORCE_DIST'):          # FORCE_DIST: exercise RCCL at world 1
+    if args.full and (world > 1 or os.environ.get('POCCALA_FORCE_DIST')):          # FORCE_DIST: exercise RCCL at world 1
         if os.environ.get('POCCALA_TEST_HANG_COMM'):               # tests: a communicator bootstrap that never returns -> the watchdog's job
             time.sleep(1e6)
         try:
@@ -1104,7 +1153,7 @@ def main():
             traceback.print_exc()
             extra = dict(error='%s: %s' % (type(e).__name__, e))
     if rank == 0:
-        emit(make_full(extra), final=True)
+        emit(make_full(extra), final=True, record=args.full)
         printed.set()
     barrier()
     for bt in batches:
@@ -1993,7 +2042,7 @@ def bench_c5_full(args, rank, world, local):
     run_c5_full(eng, tree, args.max_tokens, n_chunks=min(3, n_chunks), per=per)          # warm: batches, buffers, clocks
     ctl.barrier()
     r = run_c5_full(eng, tree, args.max_tokens, n_chunks=n_chunks, per=per)
-    rg = run_c5_full(eng, tree, args.max_tokens, ragged=True, n_chunks=n_chunks, per=per)
+    rg = run_c5_full(eng, tree, args.max_tokens, ragged=True, n_chunks=n_chunks, per=per) if args.full else None      # (ragged chunks: beside the line)
     ctl.barrier()
     wall = ctl.allreduce_max(r['wall_s'])
     if rank == 0:

@@ -229,3 +229,70 @@ def test_full_record_goes_to_a_file_not_to_stdout(tmp_path, monkeypatch, capsys)
         whole = _strict_loads(where.read_text())
         assert whole['extra']['configs']['C4']['ms_per_iteration'] == full['extra']['configs']['C4']['ms_per_iteration']
         assert whole['roofline']['sustained_value'] is None and whole['roofline']['note'] == full['roofline']['note']
+
+
+# ------------------------------------------------------------------------------------------------
+# a plain run and --dump-outputs
+# ------------------------------------------------------------------------------------------------
+class _FakeBatch(object):
+    """Batch.get's shapes for U equal utterances of N states x T frames, values from the utterance index, with the ln 0 entries a
+    sentence HMM's results hold: the exit row of ln b, the non-emitting rows of ln gamma and states unreachable at the last frames"""
+    def __init__(self, U, N, T):
+        self.U, self.N, self.T = U, N, T
+
+    def get(self, what):
+        if what == 'B':
+            out = [np.full((self.N, self.T), -float(u) - 1.0) for u in range(self.U)]
+            for b in out:
+                b[-1] = -np.inf
+            return out
+        if what == 'lgamma':
+            out = [np.full((self.N, self.T), -float(u) / 1024) for u in range(self.U)]
+            for g in out:
+                g[0] = g[-1] = -np.inf
+                g[-3:-1, -5:] = -np.inf
+            return out
+        if what in ('gamma', 'pi'):
+            return [np.full(self.N, float(u)) for u in range(self.U)]
+        if what == 'path':
+            return [np.full(self.T, u % self.N, dtype=np.int32) for u in range(self.U)]
+        return np.arange(self.U, dtype=np.int32 if what == 'npass' else np.float64)
+
+
+@pytest.mark.parametrize('align', [False, True])
+def test_dump_outputs_writes_a_fixed_sample_in_float64(tmp_path, align):
+    U, N, T = 1024, 62, 300                                          # the C4 shard's batch
+    names = bench.dump_outputs(_FakeBatch(U, N, T), align, str(tmp_path / 'a'))
+    assert names == sorted(['sample_utterances', 'B'] + (['point', 'path'] if align else ['logp', 'npass', 'posteriors', 'pi']))
+    files = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in names}
+    assert sorted(os.listdir(str(tmp_path / 'a'))) == sorted(n + '.npy' for n in names)
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in files.values())
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (n + '.npy'))) for n in names) <= 64 << 20
+    pick = files['sample_utterances'].astype(int)
+    assert len(pick) == bench.DUMP_SAMPLE_UTTS and len(set(pick.tolist())) == len(pick) and (np.diff(pick) > 0).all() and pick.max() < U
+    assert files['B'].shape == (len(pick), N - 2, T) and (files['B'][:, 0, 0] == -pick - 1).all()     # the emitting rows of the sampled utterances
+    if align:
+        assert files['path'].shape == (len(pick), T) and files['point'].shape == (U,)
+    else:
+        g = files['posteriors']
+        assert g.shape == (len(pick), N, T) and (g[:, 1, 0] == np.exp(-pick / 1024)).all() and (g[:, 0] == 0).all() and (g[:, -3:-1, -5:] == 0).all()
+        assert files['pi'].shape == (len(pick), N) and files['logp'].shape == (U,)
+    # the same arguments, the same sample
+    bench.dump_outputs(_FakeBatch(U, N, T), align, str(tmp_path / 'b'))
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'sample_utterances.npy')), files['sample_utterances'])
+    # a batch smaller than the sample: all of it
+    bench.dump_outputs(_FakeBatch(5, N, T), align, str(tmp_path / 'c'))
+    assert np.load(str(tmp_path / 'c' / 'sample_utterances.npy')).tolist() == [0, 1, 2, 3, 4]
+
+
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    monkeypatch.setattr('sys.argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr('sys.argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == 'out'
+    for bad in (['--steps', '0'], ['--workload', 'C5shard', '--dump-outputs', 'out']):
+        monkeypatch.setattr('sys.argv', ['bench.py'] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()

@@ -18,12 +18,13 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ['--utts', '32', '--mix', '256', '--steps', '2', '--warmup', '1', '--sustain', '0', '--cpu-baseline', '0']
+SMALL = ['--full', '--utts', '32', '--mix', '256', '--steps', '2', '--warmup', '1', '--sustain', '0', '--cpu-baseline', '0']      # (--full: the exchange)
 
 
 def _env(**extra):
@@ -156,3 +157,30 @@ def test_bench_config4_strong_scaling_line_two_ranks():
     assert r['fresh_batches']['statistics_same_bits_after_an_em_iteration'] is True
     assert len(r['em_iterations']) == 2 and all(e['ms'] > 0 for e in r['em_iterations'])
     assert r['kernel_ms_per_iteration_rank0']['reduce_scatter'] >= 0 and r['kernel_ms_per_iteration_rank0']['all_gather'] >= 0
+
+
+def test_plain_run_prints_one_line_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the timed steps and one final line, nothing beside them (no CPU
+    leg, no extras, no record file); --dump-outputs writes the last step's results, and the same arguments give the same inputs."""
+    cmd = [sys.executable, 'bench.py', '--gpus', '1', '--utts', '32', '--mix', '256', '--steps', '3', '--warmup', '1', '--dump-outputs']
+    runs = []
+    for k in range(2):
+        rc, out, err, dt = _run(cmd + [str(tmp_path / str(k))], _env(), 300)
+        assert rc == 0, err[-2000:]
+        lines = _json_lines(out)
+        assert len(lines) == 1, out[-3000:]
+        d = lines[0]
+        assert d['final'] is True and d['full_record'] is None and d['cpu_baseline'] is None and 'extra_error' not in d
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['dtype'] == 'f32-class (f16x2 split operands, f32 accumulate; f64 dynamic programming)'
+        assert d['value'] == pytest.approx(d['config']['frames_per_step_total'] / (d['ms_per_step'] * 1e-3), rel=1e-5)
+        assert d['roofline']['sustained_value'] is None and d['roofline']['estep_ms'] is None
+        runs.append({n[:-4]: np.load(str(tmp_path / str(k) / n)) for n in os.listdir(str(tmp_path / str(k)))})
+    a, b = runs
+    assert sorted(a) == ['B', 'logp', 'npass', 'pi', 'posteriors', 'sample_utterances']
+    assert all(x.dtype == np.float64 and np.isfinite(x).all() for x in a.values())
+    assert a['logp'].shape == (32,) and a['B'].shape == (32, 60, 300) and a['posteriors'].shape == (32, 62, 300)
+    # gamma_t(.) is a distribution over the states at every frame
+    assert a['posteriors'].min() >= 0.0
+    np.testing.assert_allclose(a['posteriors'].sum(axis=1), 1.0, atol=1e-6)
+    for n in a:
+        np.testing.assert_allclose(a[n], b[n], rtol=1e-9, atol=1e-9, err_msg=n)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/full; mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q -W ignore 2>&1 | tail -25 > $O/tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -8 $O/tests.log; tail -2 $O/smoke.log; tail -3 $O/bench.err; python - <<'P'
 import json
 d=json.loads(open('gpurun_out/full/bench.json').read().strip().splitlines()[-1])
