@@ -315,11 +315,16 @@ int pcl_model_conditioning(pcl_ctx *ctx, float *cond, float *cond_max);
 int pcl_model_split_info(pcl_ctx *ctx, int *n_off, int *limit);
 /* Diagnostics of the coarse pass over the off-pipe mixtures (csrc/gmm_score_coarse.hip; counted only under env PCL_COARSE_STATS=1):
  * *pairs = (frame, mixture) pairs evaluated in direct form since the last reset -- the pairs the bound on the matrix pipe could not rule
- * out; every other pair of an off-pipe mixture was proven to lie 2^-36 below its frame's likelihood.  reset != 0 clears the count. */
+ * out; every other pair of an off-pipe mixture was proven to lie 2^-36 below its frame's likelihood, or its tile was flagged and rescored in
+ * direct form (below).  reset != 0 clears the count. */
 int pcl_coarse_counter(pcl_ctx *ctx, unsigned long long *pairs, int reset);
 /* ... and *tiles_given_up (may be NULL) = tiles of 256 frames x one state on which the pass gave up -- a wave had evaluated more than
- * max(4096, 2 x the state's off-pipe mixtures) pairs: the state's on-pipe part is no reference for those frames -- and which the direct-form
- * subset kernel rescored in the same call (as it does tiles with a feature out of the f16 range).  Same results either way. */
+ * max(4096, 2 x the state's off-pipe mixtures) pairs: the state's on-pipe part is no reference for those frames; in the state's last
+ * stage of mixture tiles, with a tile of the stage left untested -- and which the direct-form subset kernel rescored in the same call (as
+ * it does tiles with a feature out of the f16 range).  Same results either way.  The pass also flags (without counting it here) a tile
+ * with a frame whose threshold the f16 slot's clamp to +-5e4 log2 units from the state's K0 raised above what its reference asked for
+ * (what the pipe wrote more than ~3.5e4 nats below K0, or -inf: no on-pipe mixture) and which ruled out a pair whose bound is not below
+ * what the frame's reference at the end (the pipe's value or the largest exact value) asks for: such a pair is not proven negligible. */
 int pcl_coarse_counters(pcl_ctx *ctx, unsigned long long *pairs, unsigned long long *tiles_given_up, int reset);
 
 /* How much of a CU the matrix-core scoring kernel takes.  0 (default): three workgroups per CU, the fastest for the kernel alone.

@@ -28,8 +28,10 @@
 // whose on-pipe part says little settles after the first rows of its first tile); the result is log-added to the pipe's in float64:
 // ln b = ln(e^pipe + e^tight), the reference's sum over all mixtures -- deterministic (a lane owns its frame; no atomics).  Frames whose
 // scaled features leave the f16 range raise the tile's flag and the direct-form subset kernel rescoring flagged tiles follows in the
-// same call, as for the main kernel.  States stay on this route up to 99 % off-pipe mixtures (pcl_model_upload); beyond, the on-pipe
-// part is too thin a reference (with none at all and every mixture collapsed the bound under the floored variance sits far above the
+// same call, as for the main kernel.  So does a frame whose threshold the f16 slot's clamp to [-5e4, 5e4] raised above what its reference
+// asked for (ln b1 more than ~3.5e4 nats below K0, or -inf: no on-pipe mixture), unless every pair it ruled out lies below what its
+// reference at the end (the pipe's value or the largest exact value) asks for: such a pair is not proven negligible otherwise.  States
+// stay on this route up to 99 % off-pipe mixtures (pcl_model_upload); beyond, the on-pipe part is too thin a reference (with none at all and every mixture collapsed the bound under the floored variance sits far above the
 // true values and every pair passes) and whole states take the direct form with its partial-distance test.
 //
 // Layout of the tight mixtures: [J][Mpad32/32 tiles][2 pieces][KS8][64 lanes][8 f16], the state's bad_idx list in order, 32 per tile,
@@ -213,9 +215,20 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
     const float kg = (NP == 1) ? kgap[tile.state] : 0.f;      // >= (the state's largest k2) - K0
     double pipe_ln[NT];
     float tcur[NT];                           // (f16-exact)
-    auto set_threshold = [&](int c, float t) {
-        // one product: the frame's share of the linear terms' rounding, EPS1 (k2max - threshold) (see coarse_derive_kernel)
+    // The threshold a reference t asks for: one product: less the frame's share of the linear terms' rounding, EPS1 (k2max - threshold)
+    // (see coarse_derive_kernel).  t = -inf (no reference yet: a state without on-pipe mixtures) asks for -inf.
+    auto asked_for = [&](float t) {
         if constexpr (NP == 1) t -= (float)EPS1 * __builtin_fmaxf(kg - t, 0.f);
+        return t;
+    };
+    // The clamp to the f16 slot's [-TMAX, TMAX] can RAISE a threshold above what its reference asked for (a reference more than ~5e4 log2
+    // units below K0, or none): a pair ruled out under such a threshold is not proven negligible.  So what a frame ruled out is checked
+    // at the end instead: vout = the largest bound (the accumulator + the threshold it was relative to) of a pair the lane ruled out for
+    // it; every such pair is proven iff vout stays below what the frame's final reference (its pipe value or largest exact value) asks
+    // for.  Below an unclamped threshold that holds by construction (the threshold is at most what an earlier, lower reference asked for).
+    float vout[NT];
+    auto set_threshold = [&](int c, float t) {
+        t = asked_for(t);
         // rounded so that the f16 value is not ABOVE what was asked for (a higher threshold could miss a pair): less 2^-10 |t|
         t = t - __builtin_fabsf(t) * 0.0009765625f;
         t = __builtin_fminf(__builtin_fmaxf(t, -TMAX), TMAX);
@@ -225,9 +238,10 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
     };
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
+        vout[c] = -INFINITY;
         pipe_ln[c] = valid[c] ? out[oidx[c]] : 0.0;
         const double t2 = pipe_ln[c] * LOG2E - (double)COARSE_MARGIN - (double)k0f;
-        set_threshold(c, valid[c] ? (t2 > -1.0e30 ? (float)t2 : -TMAX) : TMAX);
+        set_threshold(c, valid[c] ? (t2 > -1.0e30 ? (float)t2 : -INFINITY) : TMAX);
     }
 
     // A stage = MT mixture tiles (one product: 4 tiles' leading pieces, 20 KB at D = 39; three: 2 tiles, both pieces), by LDS-DMA one
@@ -263,8 +277,9 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
     // frames far from all of them a likelihood so low that every tight mixture passes, and a lane per pair with gathered rows is several
     // times the direct-form kernel's cost per pair (config 4's seventh EM iteration: 673 such states, 252 ms of coarse pass against the
     // 45 ms their direct form takes).  A wave that has evaluated more than max(4096, 2 x tight mixtures) pairs -- 3 % of its 64 frames'
-    // -- gives up: the workgroup raises the tile's flag at the next stage boundary and the direct-form subset kernel rescoring flagged
-    // tiles does the tile (nothing has been written yet: results leave the kernel at its end).
+    // -- gives up: the workgroup raises the tile's flag at the next stage boundary (in the last stage: after the stage loop, if a tile of
+    // the stage was left untested) and the direct-form subset kernel rescoring flagged tiles does the tile (nothing has been written yet:
+    // results leave the kernel at its end).
     int n_eval = 0;                           // wave-uniform
     double tmaxL = -INFINITY, tsumL = 0.0;
     auto flush = [&]() {
@@ -395,7 +410,16 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
             float gm = acc[c][0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) gm = __builtin_fmaxf(gm, acc[c][r]);
-            if (!__any(gm >= 0.f)) continue;                     // the common case: nobody of this tile can reach any of the 32 frames
+            if (!__any(gm >= 0.f)) {                             // the common case: nobody of this tile can reach any of the 32 frames
+                vout[c] = __builtin_fmaxf(vout[c], gm + tcur[c]);
+                continue;
+            }
+            {
+                float go = -INFINITY;                            // (the rows that did not pass)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) go = __builtin_fmaxf(go, acc[c][r] < 0.f ? acc[c][r] : -INFINITY);
+                vout[c] = __builtin_fmaxf(vout[c], go + tcur[c]);
+            }
             unsigned int mask = 0u;                              // (the rows that passed, as bits: no dynamic index into the accumulator registers)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mask |= (acc[c][r] >= 0.f ? 1u : 0u) << r;
@@ -418,8 +442,13 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
                     const float dlt = tcur[c] - t_mfma;
                     if (__any(dlt > 0.f)) {
                         unsigned int again = 0u;
+                        float go = -INFINITY;                    // (the rows still waiting that the raised threshold rules out)
 #pragma unroll
-                        for (int rr = 0; rr < 16; ++rr) again |= (acc[c][rr] >= dlt ? 1u : 0u) << rr;
+                        for (int rr = 0; rr < 16; ++rr) {
+                            again |= (acc[c][rr] >= dlt ? 1u : 0u) << rr;
+                            if (rr >= r && ((mask >> rr) & 1u) && acc[c][rr] < dlt) go = __builtin_fmaxf(go, acc[c][rr]);
+                        }
+                        vout[c] = __builtin_fmaxf(vout[c], go + t_mfma);
                         mask &= again;
                         hit = (mask >> r) & 1u;
                         bal = __ballot(hit);
@@ -452,13 +481,44 @@ __global__ __launch_bounds__(WG, PCL_COARSE_MINW) void gmm_score_coarse_kernel(
         }
         if (st + 1 < n_stages) dma((st + 1) & 1, st + 1);
         if (wave_active) {
+            int i = 0;
 #pragma unroll 1
-            for (int i = 0; i < MT && n_eval <= budget; ++i)
+            for (; i < MT && n_eval <= budget; ++i)
                 if (st * MT + i < n_mtiles) process(st * MT + i, &abuf[st & 1][i * PCS * 64]);
-            if (n_eval > budget && lane == 0) s_bail[(st + 1) & 1] = 1;
+            // (in the last stage only a tile left untested counts: a wave that crossed the budget on the state's last tile has tested every pair)
+            if (n_eval > budget && (st + 1 < n_stages || st * MT + i < n_mtiles) && lane == 0) s_bail[(st + 1) & 1] = 1;
         }
     }
     if (qn) flush();
+    // Two ways out at the end, read before anything is written (same as a give-up at a stage boundary): the give-up of the LAST stage,
+    // which has no next stage boundary to be read at, and a frame whose threshold the clamp raised above what its final reference asks for
+    // (vout above: a pair it ruled out is not proven negligible).
+#ifndef PCL_COARSE_CLAMP_REPRO                // mutation build (tools/gpu_mutation_check.sh): pairs ruled out under a clamped threshold stand
+    {
+        bool unproven = false;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            const double tm = __shfl(tmaxL, c * 32 + col, 64);
+            const double ref = ::fmax(pipe_ln[c] * LOG2E, tm);           // (log2; -inf: no reference at all)
+            const float fin = asked_for(ref > -1.0e30 ? (float)(ref - (double)COARSE_MARGIN - (double)k0f) : -INFINITY);
+            const float vo = __builtin_fmaxf(vout[c], __shfl_xor(vout[c], 32, 64));     // (the two halves hold 16 mixtures of a tile each)
+            unproven |= valid[c] && vo >= fin;
+        }
+        if (__any(unproven) && lane == 0) s_ovf = 1;
+    }
+#endif
+    __syncthreads();
+#ifdef PCL_COARSE_LASTSTAGE_REPRO             // mutation build (tools/gpu_mutation_check.sh): the tiles the last stage skipped stay untested, unflagged
+    const bool bail = false;
+#else
+    const bool bail = s_bail[n_stages & 1] != 0;
+#endif
+    if (bail || s_ovf) {
+        if (threadIdx.x == 0) flags[blockIdx.x] = 1;
+        if (counters && lane == 0 && n_eval) atomicAdd(counters, (unsigned long long)n_eval);
+        if (bail && counters && threadIdx.x == 0) atomicAdd(counters + 1, 1ull);     // (tiles given up: the budget's way out only)
+        return;
+    }
     constexpr double LN2 = 0.693147180559945309417232121458;
     if (lane < SLOTS && tsumL > 0.0) {
         // lane L = c * 32 + col finishes frame slot L: its own col, the c-th of its frames

@@ -4,7 +4,9 @@
 What must hold: (1) no pair that matters is ever ruled out -- ln b against the oracle on models whose mixtures span six decades of variance,
 with frames sitting exactly on collapsed mixtures, near them, and far from everything; (2) the bound does rule out nearly everything (the
 count of exactly evaluated pairs); (3) frames whose scaled features leave the f16 range fall back to the direct-form kernel; (4) states without
-a single on-pipe mixture start from a threshold of -inf and settle; (5) zero-weight and padding mixtures never surface."""
+a single on-pipe mixture start from a threshold of -inf and settle; (5) zero-weight and padding mixtures never surface; (6) a give-up in
+the last stage of mixture tiles flags the tile like one at a stage boundary; (7) a threshold the f16 slot's clamp raised above what its
+reference asked for rules nothing out unproven."""
 import os
 
 import numpy as np
@@ -98,7 +100,7 @@ def check(tag, got, mean, var, w, x):
     return hold(tag, 'ln b', got[fin], ref[fin], 5e-6, (F32_LOGLIK_ATOL + bound)[fin])
 
 
-@pytest.mark.parametrize('seed,D,passes', [(11, 39, 1), (12, 39, 1), (13, 13, 1), (14, 26, 1), (11, 39, 3), (13, 13, 3)])
+@pytest.mark.parametrize('seed,D,passes', [(11, 39, 1), (12, 39, 1), (13, 13, 1), (14, 26, 1), (15, 47, 1), (11, 39, 3), (13, 13, 3)])
 def test_coarse_pass_against_the_oracle_over_six_decades_of_variance(seed, D, passes):
     rng = np.random.default_rng(seed)
     J, M = 8, 96
@@ -186,6 +188,145 @@ def test_the_pass_gives_up_where_its_reference_says_nothing():
     eng = _engine(PCL_COARSE_SPLIT_MAX=1.0)
     try:
         assert np.array_equal(score_all(eng, mean, var, w, x), got)
+    finally:
+        eng.close()
+
+
+def _cluster(rng, n, D, at, spread, var):
+    """n mixtures with means at + U(-spread, spread) per feature and variance var (a scalar or (n, D))"""
+    mean = at + rng.uniform(-spread, spread, (n, D))
+    return mean, np.broadcast_to(var, (n, D)).copy()
+
+
+def last_stage_model(D, seed):
+    """M = 224, three states whose frames make EVERY pair of their early off-pipe tiles pass the bound (collapsed mixtures, variance 1e-6,
+    within 0.02 per feature of each other: the bound under the floored variance is a few log2 units below the true maximum while the true
+    values are thousands below it) and sit 0.5 sigma from a mixture of the state's LAST tile, which carries the frame:
+      A: off-pipe mixtures 0-127 (4 tiles) + 96 broad ones on the pipe; frames on 96-127;
+      B: off-pipe 0-99 (tiles 0-2 and a partial tile 3 of 4 mixtures) + 124 broad ones; frames on 96-99;
+      C: all 224 off-pipe (7 tiles): 0-95 at 1.75 per feature away (ruled out, even under the clamped threshold of a state without
+         on-pipe mixtures), 96-223 at the frames; frames on 192-223 (tile 6).
+    A wave (64 frames) that has evaluated more than max(4096, 2 x off-pipe) = 4096 pairs stops: every pair passes, a tile adds 2048, so
+    the budget is crossed in the tile after the second one that passes -- tile 2 of A and B, tile 5 of C -- and the last tile is never
+    tested.  One product (4 tiles a stage): one stage for A and B, stages 0-3 / 4-6 for C; three products (2 a stage): the crossing is in
+    the last stage for A and B, in stage 2 of 0-3 for C (given up at the boundary of stage 3).  (Frames near tiles 4-6 only would cross on
+    C's last tile itself, with every pair tested.)  The states sit 2.5 per feature apart: every other (state, frame) pair is ruled out."""
+    rng = np.random.default_rng(seed)
+    M = 224
+    mean, var = np.zeros((3, M, D)), np.zeros((3, M, D))
+    at = [-2.5, 0.0, 2.5]
+    tight = lambda n, a: _cluster(rng, n, D, a, 0.02, 1e-6 * rng.uniform(0.5, 2.0, (n, D)))
+    broad = lambda n, a: (a + 0.5 * rng.standard_normal((n, D)), rng.uniform(0.5, 2.0, (n, D)))
+    for j, n_t in ((0, 128), (1, 100)):
+        mean[j, :n_t], var[j, :n_t] = tight(n_t, at[j])
+        mean[j, n_t:], var[j, n_t:] = broad(M - n_t, at[j])
+    mean[2, :96], var[2, :96] = tight(96, at[2] + 1.75)
+    mean[2, 96:], var[2, 96:] = tight(128, at[2])
+    w = np.full((3, M), 1.0 / M)
+    xs = []
+    for j, lo, hi in ((0, 96, 128), (1, 96, 100), (2, 192, 224)):
+        m = rng.integers(lo, hi, 256)
+        xs.append(mean[j, m] + 0.5 * np.sqrt(var[j, m]) * rng.standard_normal((256, D)))    # (one 256-frame tile of each state)
+    return mean, var, w, np.concatenate(xs).astype(np.float32)
+
+
+@pytest.mark.parametrize('D,passes', [(39, 1), (39, 3), (47, 1)])
+def test_coarse_pass_gives_up_in_its_last_stage(D, passes):
+    """A give-up in the LAST stage has no next stage boundary to be read at: the kernel reads it after the stage loop, flags the tile and
+    the direct-form subset kernel rescores it (before, the tile's last mixture tiles were silently left out: ln b of these frames lost
+    the mixture that carries them).  Against the oracle; the counters show the path was taken: each state's own tile given up, no other."""
+    mean, var, w, x = last_stage_model(D, 51 + D + passes)
+    eng = _engine(PCL_COARSE_SPLIT_MAX=1.0, PCL_COARSE_STATS=1, PCL_COARSE_PASSES=passes)
+    try:
+        got = score_all(eng, mean, var, w, x)
+        n_off, limit = eng.model_split_info()
+        assert limit == 224 and list(n_off) == [128, 100, 224]
+        exact, given_up = eng.coarse_counters()
+        note('coarse pass, give-up in the last stage, D=%d, %d product(s)' % (D, passes), '[pairs evaluated exactly, tiles given up]', [exact, given_up])
+        assert given_up == 3, given_up
+        check('coarse pass, give-up in the last stage D=%d' % D, got, mean, var, w, x)
+    finally:
+        eng.close()
+
+
+def test_clamped_threshold_with_no_on_pipe_mixture():
+    """PCL_COARSE_SPLIT_MAX=1, states whose mixtures ALL have variance <= 2^-10 (the pipe writes -inf: the threshold starts at the clamp,
+    -5e4 log2 units from K0), and frames 1.5-5 per feature from every mean: the bound (here the true value, 739 |x - mu|^2 log2 units
+    down) rules out every pair, though ln b is finite.  The clamp raised the threshold above what the reference asked for (-inf): nothing
+    was proven, the tile is flagged and rescored in direct form (before: ln b = -inf).  Beside them frames ON the means: exact values lift
+    the threshold, nothing is flagged there."""
+    rng = np.random.default_rng(61)
+    J, M, D = 2, 64, 39
+    mean, var = np.zeros((J, M, D)), np.zeros((J, M, D))
+    mean[0], var[0] = _cluster(rng, M, D, 0.0, 0.3, 2.0 ** -10)
+    mean[1], var[1] = _cluster(rng, M, D, 0.0, 0.3, 2.0 ** -10 * rng.uniform(1e-3, 1.0, (M, D)))
+    w = rng.uniform(0.5, 1.0, (J, M))
+    w /= w.sum(1, keepdims=True)
+    on = mean[rng.integers(0, J, 256), rng.integers(0, M, 256)]
+    far = rng.uniform(1.5, 5.0, (256, D)) * rng.choice([-1.0, 1.0], (256, D))
+    x = np.concatenate([on, far]).astype(np.float32)
+    eng = _engine(PCL_COARSE_SPLIT_MAX=1.0, PCL_COARSE_STATS=1)
+    try:
+        got = score_all(eng, mean, var, w, x)
+        n_off, limit = eng.model_split_info()
+        assert limit == M and list(n_off) == [M, M]
+        exact, given_up = eng.coarse_counters()
+        note('coarse pass, clamped threshold, no on-pipe mixture', '[pairs evaluated exactly, tiles given up]', [exact, given_up])
+        assert given_up == 0
+        assert np.isfinite(got).all()
+        check('coarse pass, clamped threshold, no on-pipe mixture', got, mean, var, w, x)
+    finally:
+        eng.close()
+
+
+def default_limit_clamp_model(seed):
+    """M = 224 at the default split limit (221 off the pipe).  221 mixtures of variance 4e-3 on the corners of a cube, +-1.8 per feature
+    around their centre (off the pipe: cancelling terms ~2.3e4 log2 units; the floored variance of the bound is their own, so the
+    bound is their true value), and 3 on the pipe at the centre with variance 1e-3.  State 0 as such, state 1 the same with the on-pipe
+    mixtures' weights zero.  Frames: 256 ON corner means of the first tile (exact values lift the threshold: nothing flagged), 256 at
+    3.3 per feature further out from a corner: the corner is 7.6e4 log2 units down (~5.3e4 nats), the on-pipe part ~5e5 nats down --
+    state 0's reference asks for a threshold far below the clamp although it is finite, state 1's is -inf -- and every pair lies below
+    the clamped threshold (-5e4 from K0 = the corners' k2 - 2.3e4)."""
+    rng = np.random.default_rng(seed)
+    M, D = 224, 39
+    corners = 1.8 * rng.choice([-1.0, 1.0], (221, D))
+    corners -= corners.mean(0)
+    mean = np.zeros((2, M, D))
+    var = np.zeros((2, M, D))
+    mean[:, :221] = corners
+    var[:, :221] = 4e-3
+    mean[:, 221:] = rng.uniform(-0.05, 0.05, (3, D))
+    var[:, 221:] = 1e-3
+    w = np.full((2, M), 1.0 / M)
+    w[1, 221:] = 0.0
+    w[1] /= w[1].sum()
+    k = rng.integers(0, 32, 512)
+    x = mean[0, k].copy()
+    x[256:] += 3.3 * np.sign(mean[0, k[256:]])
+    return mean, var, w, x.astype(np.float32)
+
+
+def test_clamped_threshold_under_the_default_split_limit():
+    """The default limit (0.99) and the two ways a reference asks for a threshold below the clamp with on-pipe mixtures present: a
+    finite pipe value ~5e5 nats down (state 0: the on-pipe mixtures are narrow and far from the frame, the nearest off-pipe one is much
+    closer) and -inf (state 1: the on-pipe mixtures have weight zero).  Every off-pipe pair of the far frames is ruled out under the
+    clamped threshold; the tiles are flagged and rescored (before: state 0 kept the pipe's value, ~4.5e5 nats low; state 1 ln b = -inf)."""
+    mean, var, w, x = default_limit_clamp_model(71)
+    M = mean.shape[1]
+    eng = _engine(PCL_COARSE_STATS=1)
+    try:
+        eng.enable_timing(True)
+        got = score_all(eng, mean, var, w, x)
+        n_off, limit = eng.model_split_info()
+        assert limit == int(np.float32(0.99) * np.float32(M)) == 221 and list(n_off) == [221, 221]
+        assert eng.kernel_time('score_coarse')[1] == 1 and eng.kernel_time('score_direct')[1] == 0      # (split states, not whole ones)
+        exact, given_up = eng.coarse_counters()
+        note('coarse pass, clamped threshold, default split limit', '[pairs evaluated exactly, tiles given up]', [exact, given_up])
+        assert given_up == 0
+        pipe0 = po.gmm_point(x[256:].astype(np.float64), mean[0, 221:], var[0, 221:], w[0, 221:])
+        assert (pipe0 < -1e5).all() and (got[0, 256:] > pipe0 + 1e5).all()         # (the off-pipe mixtures carry the far frames)
+        assert np.isfinite(got).all()
+        check('coarse pass, clamped threshold, default split limit', got, mean, var, w, x)
     finally:
         eng.close()
 
