@@ -292,6 +292,61 @@ int pcl_stats_download(pcl_ctx *ctx, double *acc, double *alpha_acc, double *mea
 int pcl_mstep(pcl_ctx *ctx, double c_covariance);
 int pcl_model_download(pcl_ctx *ctx, double *mean, double *var, double *weight);
 
+/* ----------------------------------------------------------------- segmental GMM training (training scheme 1)
+ * After forced alignment every frame belongs to ONE GMM state (pcl_batch_regroup), and the reference makes each state's GMM
+ * from its own frames: AcousticModel.__cal_gmm (AcousticModel.py:532-561) runs ClusterInitialization.kmeans(algorithm=1)
+ * (Clustering.py:838-1044) when the model is new or its mixture count changed, then the stand-alone Clustering.GMM.em
+ * (Clustering.py:583-651, 695-719) -- one state at a time, in Python loops.  Here all J states go through each step at once.
+ *
+ * pcl_seg_create: frame_state[t] in [0,J) = the state that owns row t of the CURRENT frame matrix (n_frames_total = its rows), or
+ * -1 = the frame is not used (dropped utterances).  Builds on the device the per-state frame lists (counting sort, stable in frame
+ * order) and a copy of the frames in that order; the object does not refer to the context's frame matrix afterwards.  From the two
+ * arrays pcl_batch_regroup writes: frame_state = frame_unit * gmm_num + frame_k.  At most 65535 states.  Synchronous. */
+typedef struct pcl_seg pcl_seg;
+int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *frame_state, pcl_seg **out);
+int pcl_seg_destroy(pcl_seg *seg);
+/* pcl_seg_get selectors */
+#define PCL_SEG_COUNTS 0 /* (J,) int32: n_j                                                                                   */
+#define PCL_SEG_ORDER 1  /* (sum n_j,) int32: the frame rows of state 0, then state 1, ...: each in ascending row order       */
+#define PCL_SEG_ASSIGN 2 /* (sum n_j,) int32, same order: cluster of every frame after pcl_seg_kmeans (-1: state not trained) */
+#define PCL_SEG_SEEDS 3  /* (J,K) int32: position inside its state's list of every k-means++ seed (-1: none drawn)            */
+int pcl_seg_get(pcl_seg *seg, int what, void *host);
+/* Replaces ClusterInitialization.kmeans as __cal_gmm uses it, NOT its arithmetic: the reference's routine measures distance on the
+ * first coordinate only (cal_distance returns inside its loop, Clustering.py:797-801), moves one point per centre per sweep, keeps
+ * the seed point twice and draws from Python's global `random`.  This is textbook k-means++ (D^2 sampling, full squared Euclidean
+ * distance) + Lloyd, deterministic for a given seed:
+ *   uniforms   u(j,k), k = 0..K-1, of state j:  x = seed * 0x9E3779B97F4A7C15 + (j << 32) + k + 1 (mod 2^64);  x ^= x >> 30;
+ *              x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31;  u = (x >> 11) * 2^-53
+ *   seeds      first:  position min(floor(u(j,0) n_j), n_j - 1) of the state's list.  k-th: with D2[i] = the squared distance of frame i
+ *              to its nearest seed so far (float64), the first i whose running sum D2[0] + .. + D2[i] exceeds u(j,k) * total (a frame
+ *              that is a seed has D2 = 0 and is never drawn again; rounding put the target at or beyond the total: the last frame with
+ *              D2 > 0; total = 0, every frame sits on a seed: position min(floor(u n_j), n_j - 1))
+ *   sweeps     every frame to its nearest centre (lowest index on a tie; float64 arithmetic under PCL_F64, float32 under PCL_F32);
+ *              a state whose frames all kept their cluster is done, otherwise centre = mean of its cluster (float64 sums in a fixed
+ *              order; an empty cluster keeps its centre) and the next sweep follows, max_sweeps (>= 1) at most
+ * init_centres (J,K,D) float64 instead of seeding, or NULL.  sweeps_done (J,): assignment passes run, -1 for a state with fewer than K
+ * frames, which is left untouched (AcousticModel.py:549-551).  Then the context's model becomes (J,K,D) as the reference leaves it after
+ * clustering: mean = cluster mean, var = max(mean squared deviation from it, 1e-4) (cal_variance, Clustering.py:807-832, squared again
+ * by cov_matrix=True), weight = n_jk / n_j (an empty cluster: its centre, 1e-4, 0), every scoring layout re-derived as pcl_mstep does.
+ * A context holding a model of another shape (or none) first gets mean 0 / variance 1 / weight 1/K in every state.  1 <= K <= 8192.
+ * Synchronous. */
+int pcl_seg_kmeans(pcl_seg *seg, int K, uint64_t seed, int max_sweeps, int precision, const double *init_centres, int32_t *sweeps_done);
+int pcl_seg_centres(pcl_seg *seg, double *centres /* (J,K,D) of the last pcl_seg_kmeans */);
+/* Clustering.GMM.em (Clustering.py:695-719, smem=False) for all states at once, from the context's model (J states, M mixtures):
+ * loop body = expectation (:583-599) -> maximization (:624-651) -> the new parameters stored -> q_function (:607-616), repeated while
+ * Q - Q_prev > q_threshold (the reference: 1.28; Q_prev starts at -inf); the parameters of the step that fails the test are KEPT
+ * (:704 assigns before :706 tests).  The variance is taken about the NEW mean and floored at c_covariance; weight = Gamma_m / n_j.  Q
+ * uses this iteration's responsibilities with the new parameters, in closed form (csrc/gmm_segment.hip), with the constant the model
+ * was uploaded with (quirk Q1 by default).  A mixture no frame reached keeps mean and variance, gets weight 0 and adds 0 to Q (the
+ * reference: NaN).  Convergence is per state: a finished state is frozen and its frames are not scored again.  The E-step is the
+ * scoring + accumulate pass of pcl_batch_score / pcl_batch_accumulate in `precision`.
+ * iters (J,): loop bodies run (= M-steps), -1 for a state with fewer than M frames, which is left untouched (AcousticModel.py:549-551);
+ * q (J,): the last accepted Q (NaN for a skipped state); q_trace (J, max_iters) or NULL: Q after every loop body, NaN beyond.
+ * The context's E-step statistics are this call's work space: every loop body starts with pcl_stats_zero, so whatever
+ * pcl_batch_accumulate had summed there before is gone, and afterwards the block holds the call's last E-step.  Synchronous. */
+int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_iters, int precision, int32_t *iters, double *q,
+               double *q_trace);
+
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /
  * (2 var_jmd) (about 5e-7 * cond nats).  States with cond[j] > *cond_max (default 96, env PCL_MFMA_COND_MAX) are scored

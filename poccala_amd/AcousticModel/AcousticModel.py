@@ -4,7 +4,8 @@ Mirrored (starred): `embedded` :957-1014, `viterbi` :101
 :937-955, `VirtualState` :1029-1043, plus `init_unit` :164-226 / `init_parameter` :228-240 so that a
 per-utterance E-step or alignment can be written exactly as the reference's workers write it
 (`multi_embedded_training_1` :884-916, `multi_process_data` :723-768).  Batched equivalents that keep
-everything on the GPU are `estep_batch` / `align_batch`.  Orchestration (Pool fan-out, file walking,
+everything on the GPU are `estep_batch` / `align_batch`, and `train_segments_batch` / `train_segments_data` for training
+scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state).  Orchestration (Pool fan-out, file walking,
 flat start, audio) is out of scope.
 """
 import os
@@ -264,12 +265,9 @@ class AcousticModel(DataInitialization):
         parts = [self.eq_segment(block, gmm_num, mode='g') for block in data]
         return [np.concatenate([p_[k] for p_ in parts], axis=0) for k in range(gmm_num)]
 
-    def regroup_batch(self, labels, data_list, unit_hmms, precision=PCL_F64, engine=None):
-        """Forced alignment -> the re-estimation data of every GMM state, for many utterances, on the device: Viterbi
-        (`align_batch`'s kernels), then `pcl_batch_regroup` instead of discriminate + __save_data + __get_gmmdata
-        (AcousticModel.py:758-764, 629-644).  Returns ({unit: [S-2 arrays (n_k, D)]}, dropped): for each unit the frames
-        of its GMM states, in utterance then time order; an utterance whose path misses a label unit is dropped
-        (:754-757)."""
+    def _align_regroup(self, labels, data_list, unit_hmms, precision, engine):
+        """Viterbi + pcl_batch_regroup for many utterances.  Returns (batch -- still open --, units, idx, row_unit, frame_unit,
+        frame_k, dropped): dropped = the utterances whose path misses a label unit (AcousticModel.py:754-757)."""
         engine = engine or default_engine()
         b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
         b.score(precision)
@@ -280,12 +278,22 @@ class AcousticModel(DataInitialization):
             ids = np.repeat([idx[u] for u in lab], s - 2)
             row_unit.append(np.concatenate([[ids[0]], ids, [ids[-1]]]).astype(np.int32))     # entry / exit rows: first / last unit
         fu, fk = b.regroup(row_unit, s - 2)
+        dropped = [u for u, lab in enumerate(labels) if len(np.unique(fu[u])) < len(set(lab))]
+        return b, units, idx, row_unit, fu, fk, dropped
+
+    def regroup_batch(self, labels, data_list, unit_hmms, precision=PCL_F64, engine=None):
+        """Forced alignment -> the re-estimation data of every GMM state, for many utterances, on the device: Viterbi
+        (`align_batch`'s kernels), then `pcl_batch_regroup` instead of discriminate + __save_data + __get_gmmdata
+        (AcousticModel.py:758-764, 629-644).  Returns ({unit: [S-2 arrays (n_k, D)]}, dropped): for each unit the frames
+        of its GMM states, in utterance then time order; an utterance whose path misses a label unit is dropped
+        (:754-757)."""
+        b, units, idx, row_unit, fu, fk, dropped = self._align_regroup(labels, data_list, unit_hmms, precision, engine)
         b.close()
+        s = self.__state_num
         names = {i: u for u, i in idx.items()}
-        out, dropped = {}, []
+        out = {}
         for u, lab in enumerate(labels):
-            if len(np.unique(fu[u])) < len(set(lab)):
-                dropped.append(u)
+            if u in dropped:
                 continue
             data = np.asarray(data_list[u])
             for i in np.unique(fu[u]):
@@ -295,6 +303,77 @@ class AcousticModel(DataInitialization):
         d = np.asarray(data_list[0]).shape[1]
         return ({unit: [np.concatenate(parts, axis=0) if parts else np.zeros((0, d)) for parts in slots]
                  for unit, slots in out.items()}, dropped)
+
+    # ------------------------------------------------------------------ training scheme 1 (AcousticModel.training mode 1, :771-840)
+    @staticmethod
+    def _no_smem(smem):
+        if smem:
+            raise NotImplementedError('SMEM split / merge is outside the hot path (SURVEY section 2 row 3)')
+
+    def _train_segments(self, engine, seg, units, unit_hmms, init, mix_level, smem, c_covariance, seed, precision):
+        """ClusterInitialization.kmeans (when the model is new or its mixture count changes, __cal_gmm :552) + GMM.em for every
+        state of every unit at once, from the engine's model; the result goes back into the units' GMM objects."""
+        e = self.__state_num - 2
+        k = int(mix_level) if mix_level is not None else engine.M
+        try:
+            if init or k != engine.M:
+                seg.kmeans(k, seed=seed, precision=precision)
+            iters, q = seg.em(c_covariance=c_covariance, precision=precision)
+            counts = seg.counts.copy()
+        finally:
+            seg.close()
+        mean, var, w = engine.model_download()
+        out = {}
+        for ui, unit in enumerate(units):
+            js = slice(ui * e, (ui + 1) * e)
+            for kk in range(e):
+                j = ui * e + kk
+                if iters[j] >= 0:                                     # a state with fewer frames than mixtures keeps its model (:549-551)
+                    unit_hmms[unit].profunction[1 + kk].set_model(mean[j], var[j], w[j])
+            out[unit] = (iters[js].copy(), q[js].copy(), iters[js] < 0)
+        self.last_segment_counts = {unit: counts[ui * e:(ui + 1) * e] for ui, unit in enumerate(units)}
+        return out
+
+    def train_segments_batch(self, labels, data_list, unit_hmms, init=False, mix_level=None, smem=False, c_covariance=1e-3, seed=0,
+                             precision=PCL_F64, engine=None):
+        """Training scheme 1 for many utterances at once: forced alignment and regrouping as `regroup_batch` does them, then --
+        without the frames leaving the device -- clustering (init=True, or mix_level differs from the model's) and the stand-alone
+        EM of every GMM state of every unit in one batch of launches (AcousticModel.__cal_gmm, AcousticModel.py:532-561, for every
+        unit of multi_training :771-840).  The units' GMM objects receive the new parameters.  Returns {unit: (iters (S-2,),
+        q (S-2,), skipped (S-2,) bool)}; utterances whose path misses a label unit are dropped (:754-757) and listed in
+        `self.last_dropped`.  The clustering is textbook k-means++ / Lloyd, not the reference routine's arithmetic
+        (Clustering.ClusterInitialization)."""
+        self._no_smem(smem)
+        engine = engine or default_engine()
+        b, units, idx, row_unit, fu, fk, self.last_dropped = self._align_regroup(labels, data_list, unit_hmms, precision, engine)
+        try:
+            seg = b.segments(row_unit, self.__state_num - 2, dropped=self.last_dropped, regrouped=(fu, fk))
+        finally:
+            b.close()
+        return self._train_segments(engine, seg, units, unit_hmms, init, mix_level, smem, c_covariance, seed, precision)
+
+    def train_segments_data(self, unit_data, unit_hmms, init=False, mix_level=None, smem=False, c_covariance=1e-3, seed=0,
+                            precision=PCL_F64, engine=None):
+        """The same from already regrouped data, {unit: [S-2 arrays (n_k, D)]} (what `regroup_batch` returns and what
+        multi_training reads back from <unit>/data, AcousticModel.py:790-797); a unit without data is skipped."""
+        self._no_smem(smem)
+        engine = engine or default_engine()
+        units, idx, (mean, var, w), trans = self._model_arrays(unit_hmms)
+        e = self.__state_num - 2
+        blocks, state = [], []
+        for ui, unit in enumerate(units):
+            for kk, block in enumerate(unit_data.get(unit, [])):
+                block = np.asarray(block, dtype=np.float64)
+                if len(block):
+                    blocks.append(block)
+                    state.append(np.full(len(block), ui * e + kk, dtype=np.int32))
+        if not blocks:                                                # no unit has data: every state is skipped, nothing touches the GPU
+            self.last_segment_counts = {unit: np.zeros(e, dtype=np.int32) for unit in units}
+            return {unit: (np.full(e, -1, dtype=np.int32), np.full(e, np.nan), np.ones(e, dtype=bool)) for unit in units}
+        engine.load_model(mean, var, w)
+        engine.load_frames(np.concatenate(blocks, axis=0))
+        seg = engine.segments(np.concatenate(state))
+        return self._train_segments(engine, seg, units, unit_hmms, init, mix_level, smem, c_covariance, seed, precision)
 
     # ------------------------------------------------------------------ the reference's two workers, at batched speed
     # The reference fans its corpus out over a Pool, one call per utterance (AcousticModel.py:861-870, :709-712): every call

@@ -16,6 +16,19 @@ class DataDimensionError(Exception):
         return info
 
 
+class DataUnLoadError(Exception):
+    """Raised by Clustering.GMM.em on an object without data (Clustering.py:698-699)."""
+
+    def __init__(self, log=None):
+        self.log = log
+
+    def __str__(self):
+        info = 'no data loaded'
+        if self.log is not None:
+            self.log.note(info, cls='e')
+        return info
+
+
 class UnitFileExistsError(FileExistsError):
     """Exceptions.py:24-32."""
 

@@ -4,7 +4,9 @@ Same constructor, properties, `point`, `update_acc`, `update_param`, save/init o
 accumulators (the reference's .npy directory layout).  Scoring and the E-step statistics
 run on the GPU through libpoccala_hip.so; accumulators are kept in the reference's LOG domain on the
 host so that a reference `multi_embedded_training_2` can consume the files this class writes.
-Stand-alone EM / SMEM (Clustering.py:373-719 except update_acc/update_param) and the clustering
+The stand-alone EM (`GMM.em`, Clustering.py:583-651, 695-719) and `ClusterInitialization.kmeans` run on the GPU too
+(segmental training, include/poccala_hip.h pcl_seg_*); `kmeans` is textbook k-means++ / Lloyd, NOT the reference routine's
+arithmetic (see its docstring).  SMEM split / merge (Clustering.py:373-577) and the randomcenter / layercluster / SOM
 initialisers are out of scope.
 """
 import configparser
@@ -13,7 +15,7 @@ import time
 
 import numpy as np
 
-from ..Exceptions import DataDimensionError, NullLog
+from ..Exceptions import DataDimensionError, DataUnLoadError, NullLog
 from .._lib import PCL_F32, PCL_F64
 from ..runtime import scratch_engine
 from .DataInitialization import DataInitialization
@@ -131,6 +133,21 @@ class Clustering(DataInitialization):
         def model_arrays(self):
             """(mean (M,D), var (M,D), weight (M,)) as the engine takes them."""
             return (np.asarray(self.__mean, np.float64), self.diag_variance(), np.asarray(self.__alpha, np.float64))
+
+        def set_model(self, mean, var, alpha):
+            """New parameters from segmental training (mean (M,D), diagonal var (M,D), alpha (M,)); a changed mixture count
+            (AcousticModel.__cal_gmm sets gmm.mixture, AcousticModel.py:555) restarts the accumulators at ln 0 in the new shape."""
+            mean = np.array(mean, dtype=np.float64)
+            m = mean.shape[0]
+            if m != self.__mix_level:
+                self.__mix_level = m
+                self.__alpha_acc = -np.inf
+                self.__mean_acc = np.full((m, self.__dimension), -np.inf)
+                self.__covariance_acc = list(np.full((m, self.__dimension), -np.inf))
+                self.__acc = np.full((m,), -np.inf)
+            self.__mean = mean
+            self.__covariance = np.array([np.diag(r) for r in np.asarray(var, dtype=np.float64)])
+            self.__alpha = np.array(alpha, dtype=np.float64)
 
         # ---------------------------------------------------------------- A4  point (Clustering.py:740-767)
         def point(self, x, log=False, standard=False, record=False):
@@ -266,6 +283,78 @@ class Clustering(DataInitialization):
                     for i in range(self.__mix_level):
                         self.__covariance_acc[i] = log_sum_exp(np.stack([self.__covariance_acc[i], a[i]], axis=1), vector=True)
 
-        # ---------------------------------------------------------------- out of scope
-        def em(self, *a, **k):
-            raise NotImplementedError('stand-alone GMM EM / SMEM is outside the hot path (SURVEY section 2 row 3)')
+        # ---------------------------------------------------------------- stand-alone EM (Clustering.py:695-719)
+        def em(self, show_q=False, smem=False, c_covariance=1e-3):
+            """GMM.em on `self.data`: expectation -> maximization -> Q while Q grows by more than 1.28; the parameters of the last
+            (refused) step are kept, as the reference keeps them (:704-706).  Runs on the GPU (one state of pcl_seg_em); stores
+            mean / covariance / alpha as update_param does.  SMEM (smem=True, Clustering.py:373-577) is out of scope."""
+            if smem:
+                raise NotImplementedError('SMEM split / merge is outside the hot path (SURVEY section 2 row 3)')
+            self.log.note('training GMM_%d by EM, %d mixtures' % (self.__gmm_id, self.__mix_level), cls='i', show_console=show_q)
+            if self.__data is None or len(self.__data) == 0:
+                raise DataUnLoadError(self.log)
+            data = np.asarray(self.__data, dtype=np.float64)
+            if data.ndim != 2 or data.shape[1] != self.__dimension:
+                raise DataDimensionError(self.__dimension, data.shape[-1], self.log)
+            if len(data) < self.__mix_level:
+                raise ValueError('GMM.em: %d frames for %d mixtures' % (len(data), self.__mix_level))
+            eng = scratch_engine()
+            mean, var, w = self.model_arrays()
+            eng.load_model(mean[None], var[None], w[None])
+            eng.load_frames(data)
+            seg = eng.segments(np.zeros(len(data), dtype=np.int32))
+            try:
+                iters, q = seg.em(c_covariance=c_covariance, max_iters=1 << 20, precision=self.__precision)
+            finally:
+                seg.close()
+            mean, var, w = eng.model_download()
+            self.__mean = mean[0]
+            self.__covariance = np.array([np.diag(r) for r in var[0]])
+            self.__alpha = w[0]
+            self.em_iterations, self.em_q = int(iters[0]), float(q[0])
+
+    class ClusterInitialization(object):
+        """ClusterInitialization(data, k, dimension, log).kmeans as AcousticModel.__cal_gmm calls it (AcousticModel.py:553-554).
+
+        NOT the reference routine's arithmetic: that one measures distance on the first coordinate only (cal_distance returns
+        inside its loop, Clustering.py:797-801), moves one point per centre per sweep, keeps the seed point twice and draws from
+        Python's global `random`.  This is textbook k-means++ seeding (algorithm=1; D^2 sampling, full squared Euclidean distance)
+        or k uniformly drawn distinct rows (algorithm=0), then Lloyd sweeps, on the GPU (pcl_seg_kmeans), deterministic for `seed`.
+        The outputs follow the reference: mean, the square ROOT of the floored (1e-4) mean squared deviation -- or with
+        cov_matrix=True the (k,D,D) diagonal matrices of its square (cal_variance, Clustering.py:807-832) --, alpha = n_k / n, and the
+        data of every cluster."""
+
+        def __init__(self, data, k, dimension, log=None, precision='f64'):
+            self.__data = np.asarray(data, dtype=np.float64)
+            self.__k = int(k)
+            self.__dimension = int(dimension)
+            self.log = log if log is not None else NullLog()
+            self.__precision = PCL_F64 if precision == 'f64' else PCL_F32
+
+        def kmeans(self, algorithm=0, cov_matrix=False, seed=None, max_sweeps=100):
+            if algorithm not in (0, 1):
+                raise ValueError('kmeans: algorithm must be 0 (uniform seeds) or 1 (k-means++)')      # the reference raises ClassError
+            data, k = self.__data, self.__k
+            if data.ndim != 2 or data.shape[1] != self.__dimension:
+                raise DataDimensionError(self.__dimension, data.shape[-1], self.log)
+            if len(data) < k:
+                raise ValueError('kmeans: %d points for %d clusters' % (len(data), k))
+            if seed is None:
+                seed = int(np.random.randint(0, 2 ** 31 - 1))
+            init = None
+            if algorithm == 0:
+                init = data[np.random.default_rng(seed).choice(len(data), k, replace=False)][None]
+            eng = scratch_engine()
+            eng.load_frames(data)
+            seg = eng.segments(np.zeros(len(data), dtype=np.int32), J=1)
+            try:
+                seg.kmeans(k, seed=seed, max_sweeps=max_sweeps, precision=self.__precision, init_centres=init)
+                assign = seg.assignments()
+            finally:
+                seg.close()
+            mean, var, w = eng.model_download()
+            mean, var, alpha = mean[0], var[0], w[0]
+            clustered = [data[assign == c] for c in range(k)]
+            if cov_matrix:
+                return mean, np.array([np.diag(r) for r in var]), alpha, clustered
+            return mean, np.sqrt(var), alpha, clustered

@@ -15,6 +15,7 @@ PCL_F32, PCL_F64 = 0, 1
 PCL_MODEL_Q1_SUMVAR, PCL_MODEL_LOGDET = 0, 1
 PCL_ROW_ENTRY, PCL_ROW_EXIT = -1, -2
 PCL_MAX_PASS = 16
+SEG_GET = dict(counts=0, order=1, assign=2, seeds=3)
 GET = dict(B=0, alpha=1, beta=2, lgamma=3, ksai=4, gamma=5, pi=6, logp=7, npass=8, qtrace=9, path=10, point=11, ksai_nz=12)
 
 # every symbol include/poccala_hip.h declares: (restype, argtypes)
@@ -51,6 +52,12 @@ PROTOTYPES = {
     'pcl_accumulate_prune': (_i, [_vp, C.c_double]),
     'pcl_stats_download': (_i, [_vp, _vp, _vp, _vp, _vp]),
     'pcl_mstep': (_i, [_vp, _d]),
+    'pcl_seg_create': (_i, [_vp, C.c_int64, _i, _vp, C.POINTER(_vp)]),
+    'pcl_seg_destroy': (_i, [_vp]),
+    'pcl_seg_get': (_i, [_vp, _i, _vp]),
+    'pcl_seg_kmeans': (_i, [_vp, _i, C.c_uint64, _i, _i, _vp, _vp]),
+    'pcl_seg_centres': (_i, [_vp, _vp]),
+    'pcl_seg_em': (_i, [_vp, _d, _d, _i, _i, _vp, _vp, _vp]),
     'pcl_model_download': (_i, [_vp, _vp, _vp, _vp]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),

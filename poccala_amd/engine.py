@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, as_c, ptr
+from ._lib import GET, SEG_GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, as_c, ptr
 
 
 def device_count():
@@ -39,9 +39,10 @@ class Engine(object):
         self.device = int(device)
         self.J = self.M = self.D = 0
         self.n_units = self.S = 0
-        self.F = 0
+        self.F = self.FD = 0
         self._model_key = self._frames_key = None
         self._stream_pool, self._stream_pinned = {}, [None]       # Decoder.decode_stream: batches per chunk shape, staging buffer
+        self._segments = weakref.WeakSet()  # live Segments objects: closed with the engine
         self._batches = weakref.WeakSet()   # live batches: destroyed before the context (a sweep makes millions: dead ones leave by themselves)
         self._pinned = []    # page-locked host allocations (pinned_empty)
         self._pinned_sizes, self._pinned_named = {}, {}
@@ -57,6 +58,8 @@ class Engine(object):
         if getattr(self, '_ctx', None):
             for b in list(self._batches):
                 b.close()
+            for sg in list(self._segments):
+                sg.close()
             self._batches = weakref.WeakSet()
             self._stream_pool, self._stream_pinned = {}, [None]
             self._lib.pcl_sync(self._ctx)             # result copies into the page-locked buffers freed below may still be in flight
@@ -150,7 +153,7 @@ class Engine(object):
         if key is not None and key == self._frames_key:
             return
         self._check(self._lib.pcl_frames_upload(self._ctx, f.shape[0], f.shape[1], ptr(f), dt))
-        self.F = f.shape[0]
+        self.F, self.FD = f.shape[0], f.shape[1]
         self._frames_key = key
 
     # ------------------------------------------------------------------ streaming (BASELINE config 5: a corpus fed chunk by chunk)
@@ -167,7 +170,7 @@ class Engine(object):
     def swap_frames(self):
         """Wait for the staged copy and make that chunk the current frame matrix (batches created from now on index it)."""
         self._check(self._lib.pcl_frames_swap(self._ctx))
-        self.F = self._staged.shape[0]
+        self.F, self.FD = self._staged.shape
         self._staged = None
         self._frames_key = None
 
@@ -227,6 +230,11 @@ class Engine(object):
 
     def batch(self, N, T, frame_begin=None):
         return Batch(self, N, T, frame_begin)
+
+    def segments(self, frame_state, J=None):
+        """Per-state frame lists of the loaded frame matrix for segmental training (training scheme 1): frame_state[t] = the GMM
+        state that owns frame t, or -1 (unused).  J defaults to the loaded model's."""
+        return Segments(self, frame_state, self.J if J is None else J)
 
     # ------------------------------------------------------------------ unit inventory, label-built batches
     def load_units(self, unit_trans):
@@ -469,6 +477,7 @@ class Batch(object):
             engine._check(self._lib.pcl_batch_create(engine._ctx, self.U, ptr(self.N), ptr(self.T), ptr(fb),
                                                      C.byref(self._b)))
         engine._batches.add(self)
+        self._frame_begin = None if frame_begin is None else fb.copy()
         self._fetch_slots = set()                     # engine result slots with un-waited copies of this batch (fetch_async)
         n64, t64 = self.N.astype(np.int64), self.T.astype(np.int64)
         self._nt_off = np.concatenate([[0], np.cumsum(n64 * t64)])
@@ -663,6 +672,20 @@ class Batch(object):
         cut = lambda flat: [flat[self._t_off[u]:self._t_off[u + 1]] for u in range(self.U)]
         return cut(fu), cut(fk)
 
+    def segments(self, row_unit, gmm_num, dropped=(), regrouped=None):
+        """regroup() handed on to segmental training without the frames leaving the device: the owner state of every frame is
+        frame_unit * gmm_num + frame_k (unit i owns the states i*gmm_num ..), -1 for the frames of the utterances in `dropped`
+        and for the rows of the frame matrix that belong to no utterance of this batch.  `regrouped` = (frame_unit, frame_k) of an
+        earlier regroup() call saves a second one.  A batch created without frame_begin has its utterances back to back from row 0."""
+        fu, fk = regrouped if regrouped is not None else self.regroup(row_unit, gmm_num)
+        begin = self._frame_begin if self._frame_begin is not None else self._t_off[:-1]
+        state = np.full(self.eng.F, -1, dtype=np.int32)
+        drop = set(int(u) for u in dropped)
+        for u in range(self.U):
+            if u not in drop:
+                state[begin[u]:begin[u] + self.T[u]] = frame_state_of(fu[u], fk[u], gmm_num)
+        return Segments(self.eng, state, self.eng.J)
+
     def get(self, what):
         """List of per-utterance arrays (or a (U,...) array for per-utterance scalars)."""
         code = GET[what]
@@ -698,6 +721,95 @@ class Batch(object):
             raise KeyError(what)
         self._check(self._lib.pcl_batch_get(self._b, code, ptr(out)))
         return out
+
+
+def frame_state_of(frame_unit, frame_k, gmm_num):
+    """The two arrays pcl_batch_regroup writes -> the owner GMM state of every frame (-1 where either is negative)."""
+    fu, fk = np.asarray(frame_unit, dtype=np.int64), np.asarray(frame_k, dtype=np.int64)
+    return np.where((fu >= 0) & (fk >= 0), fu * int(gmm_num) + fk, -1).astype(np.int32)
+
+
+class Segments(object):
+    """The frames of every GMM state, on the device, for training scheme 1 (AcousticModel.__cal_gmm, AcousticModel.py:532-561):
+    `kmeans` then `em` make the engine's model from them, all states at once.  States with fewer frames than mixtures are left
+    untouched and reported as -1, as the reference skips them (:549-551)."""
+
+    def __init__(self, engine, frame_state, J):
+        self.eng = engine
+        self._lib = engine._lib
+        self._s = C.c_void_p()
+        st = as_c(frame_state, np.int32).reshape(-1)
+        self.J = int(J)
+        engine._check(self._lib.pcl_seg_create(engine._ctx, st.shape[0], self.J, ptr(st), C.byref(self._s)))
+        engine._segments.add(self)
+        self.counts = self._get('counts', self.J)
+        self.K = 0
+        self.D = engine.FD
+
+    def _get(self, what, n):
+        out = np.empty(n, dtype=np.int32)
+        self.eng._check(self._lib.pcl_seg_get(self._s, SEG_GET[what], ptr(out)))
+        return out
+
+    @property
+    def order(self):
+        """Frame rows of state 0, then state 1, ...: each in ascending row order."""
+        return self._get('order', int(self.counts.sum()))
+
+    def split(self, flat):
+        """A (sum n_j, ...) array in segment order as a list of per-state arrays."""
+        off = np.concatenate([[0], np.cumsum(self.counts)])
+        return [flat[off[j]:off[j + 1]] for j in range(self.J)]
+
+    def kmeans(self, K, seed=0, max_sweeps=100, precision=PCL_F32, init_centres=None):
+        """k-means++ seeding (or init_centres (J,K,D)) + Lloyd sweeps per state, then the engine's model becomes (J,K,D): cluster
+        means, floored mean squared deviations, n_jk / n_j.  NOT the reference routine's arithmetic (include/poccala_hip.h,
+        pcl_seg_kmeans): textbook k-means++ / Lloyd, deterministic for a seed.  Returns sweeps per state (-1: skipped)."""
+        sweeps = np.empty(self.J, dtype=np.int32)
+        ic = None
+        if init_centres is not None:
+            ic = as_c(init_centres, np.float64)
+            if ic.ndim != 3 or ic.shape[:2] != (self.J, int(K)):
+                raise ValueError('init_centres must be (J, K, D), got %s' % (ic.shape,))
+        self.eng._check(self._lib.pcl_seg_kmeans(self._s, int(K), int(seed) & ((1 << 64) - 1), int(max_sweeps), int(precision), ptr(ic), ptr(sweeps)))
+        self.K = int(K)
+        self.eng.J, self.eng.M, self.eng.D = self.J, int(K), self.D
+        self.eng._model_key = None
+        return sweeps
+
+    def assignments(self):
+        return self._get('assign', int(self.counts.sum()))
+
+    def seed_positions(self):
+        return self._get('seeds', self.J * self.K).reshape(self.J, self.K)
+
+    def centres(self):
+        out = np.empty((self.J, self.K, self.D))
+        self.eng._check(self._lib.pcl_seg_centres(self._s, ptr(out)))
+        return out
+
+    def em(self, c_covariance=1e-3, q_threshold=1.28, max_iters=100, precision=PCL_F32, trace=False):
+        """Clustering.GMM.em (Clustering.py:695-719, smem=False) for every state at once from the engine's model.  Returns
+        (iters, q): loop bodies run per state (-1: skipped, fewer frames than mixtures) and the last accepted Q; with trace=True also
+        the (J, max_iters) Q of every loop body (NaN beyond)."""
+        iters = np.empty(self.J, dtype=np.int32)
+        q = np.empty(self.J)
+        qt = np.empty((self.J, int(max_iters))) if trace else None
+        self.eng._check(self._lib.pcl_seg_em(self._s, float(c_covariance), float(q_threshold), int(max_iters), int(precision), ptr(iters), ptr(q), ptr(qt)))
+        self.eng._model_key = None
+        return (iters, q, qt) if trace else (iters, q)
+
+    def close(self):
+        if getattr(self, '_s', None):
+            if getattr(self.eng, '_ctx', None):
+                self._lib.pcl_seg_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------- sentence HMM construction
