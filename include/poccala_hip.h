@@ -99,7 +99,8 @@ int pcl_sync(pcl_ctx *ctx);
 /* name (cap bytes), compute units, HBM bytes */
 int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_bytes);
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
- * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce".
+ * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
+ * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather".
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -400,6 +401,49 @@ int pcl_mfcc(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, 
              double overlap, int nfft, int filterbanks, int rank, int flags, const double *twiddle_cos,
              const double *twiddle_sin, const double *mel_response, const double *dct_matrix, double *out,
              int64_t out_rows);
+
+/* ----------------------------------------------------------------- voice-activity detector (row f6: the second half of the front-end)
+ * AudioProcessing.VAD.mfcc (StatisticalModel/AudioProcessing.py:538-543) = mel_distance (:462-478) -> osf (:480-507) -> detect (:509-536)
+ * for U utterances at once, float64, on the device (csrc/vad.hip).  It is what AcousticModel.__load_audio (AcousticModel.py:463-477) and
+ * Decoder (Decoder.py:55-60) put between MFCC.mfcc and the hot path.  The reference's conventions, kept exactly (golden G19):
+ *   V1 (:467-472)  noise = (1/s) * (sum of the first s = simple_size rows), then for i = 0..s-1: noise = alpha*noise + (1-alpha)*x_i
+ *   V2 (:475-477)  dist_t = sqrt(sum_d (noise_d - x_td)^2) over all D columns (deltas included), summed over d in ascending order
+ *   V3 (:500-507)  for s <= i < T - s: the window is d[i-s : i+s] -- 2s values, not the 2s+1 the comment speaks of --, sorted ascending
+ *                  (NaN last), h = int(beta*(2s+1)), osf_i = (1-beta)*w[h] + beta*w[h+1]; every other frame keeps its distance
+ *   V4 (:516-536)  thr = osf[int(s/2)] * (max - min) / max over the utterance (the sorted sample of :516-517 is never used: no median);
+ *                  frame t is kept iff osf_t - thr > 0, IEEE semantics: a non-finite distance makes thr NaN and nothing is kept
+ *   V5             T_u < s: the reference raises IndexError (:472) -> PCL_ERR_INVALID naming the utterance; s <= T_u <= 2s: no frame is filtered
+ * Every step is one correctly rounded float64 operation at a time (nothing contracted into an fma), the selection is exact, nothing is
+ * summed with atomics: from equal distances, osf / thr / the kept set are those of a NumPy restatement bit for bit (tests/_vad_twin.py).
+ * mfcc: (row_off[U], D) row-major features, utterance u = rows [row_off[u], row_off[u+1]), row_off[0] = 0; D <= 64 as pcl_frames_upload.
+ * Outputs (NULL pointers are skipped; a stage none of whose results is asked for does not run): dist / dist_osf (rows,), thr (U,),
+ * kept_len (U,), kept_idx (rows,) int32: utterance u's kept rows, counted from ITS first row, ascending, at kept_idx[row_off[u] ..
+ * row_off[u] + kept_len[u]), -1 behind them.  flags: PCL_VAD_DIST_IN = `dist` is the caller's (V1-V2 skipped, mfcc may be NULL),
+ * PCL_VAD_OSF_IN = `dist_osf` is the caller's (V1-V3 skipped): the reference's three methods one at a time.
+ * h + 1 >= 2s is PCL_ERR_INVALID when V3 runs and some utterance has T > 2s (the reference indexes out of range as soon as a frame is
+ * filtered; with every T <= 2s it never looks at h, and neither does this).  1 <= s <= 1024, U <= 65535.
+ * Synchronous. */
+#define PCL_VAD_DIST_IN 1
+#define PCL_VAD_OSF_IN 2
+int pcl_vad(pcl_ctx *ctx, int U, const double *mfcc, const int64_t *row_off, int D, int simple_size, double alpha, double beta, int flags,
+            int32_t *kept_len, int32_t *kept_idx, double *dist, double *dist_osf, double *thr);
+/* PCM -> resident frames: pcl_mfcc's kernels, then V1-V5 above on their device result, then the survivors gathered into the context's
+ * frame matrix -- what AcousticModel.__load_audio (AcousticModel.py:463-477) does per file, for U signals, without the features leaving the
+ * device.  signal .. dct_matrix are pcl_mfcc's arguments (mfcc_flags = its flags).  On return the survivors ARE the current frame matrix,
+ * exactly as pcl_frames_upload would have left them: float32, rows padded with zeros to the device dimension, rounded to nearest; with
+ * PCL_FRONTEND_KEEP_F64 the float64 copy parity mode (PCL_F64) reads is kept too (otherwise it is derived from the float32 rows on first use,
+ * as after a float32 upload).  T_out (U,) int32 / frame_begin_out (U,) int64 are what pcl_batch_create(_labels) takes: batches follow with
+ * no feature upload.  An utterance that keeps no frame has T_out = 0 (leave it out of the batch).  PCL_FRONTEND_NO_VAD: every MFCC row is
+ * kept (MFCC straight to resident frames).  out_host: NULL, or out_rows x D float64 (out_rows = total MFCC frames, as pcl_mfcc) whose
+ * first sum(T_out) rows receive the survivors.  Every check -- V5 from the signal lengths, the order statistics, D > 64 -- runs before
+ * the first launch: a failed call leaves the previous frame matrix in place.  When no frame of ANY utterance survives the call succeeds
+ * like any other: every T_out is 0 and the current frame matrix is empty (0 rows: no batch can be created on it).  Synchronous. */
+#define PCL_FRONTEND_NO_VAD 1
+#define PCL_FRONTEND_KEEP_F64 2
+int pcl_frontend(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap, int nfft,
+                 int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin, const double *mel_response,
+                 const double *dct_matrix, int simple_size, double alpha, double beta, int flags, int32_t *T_out, int64_t *frame_begin_out,
+                 double *out_host, int64_t out_rows);
 
 /* ----------------------------------------------------------------- multi-GPU (RCCL over xGMI)
  * Replaces the reference's file-based accumulator merge (LHMM.py:256-290, Clustering.py:314-367).

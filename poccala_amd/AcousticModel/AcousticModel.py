@@ -5,8 +5,9 @@ Mirrored (starred): `embedded` :957-1014, `viterbi` :101
 per-utterance E-step or alignment can be written exactly as the reference's workers write it
 (`multi_embedded_training_1` :884-916, `multi_process_data` :723-768).  Batched equivalents that keep
 everything on the GPU are `estep_batch` / `align_batch`, and `train_segments_batch` / `train_segments_data` for training
-scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state).  Orchestration (Pool fan-out, file walking,
-flat start, audio) is out of scope.
+scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state).  `load_audio` is `__load_audio` (:463-477: wav -> MFCC ->
+VAD); `load_audio_batch` does it for many files in one call and leaves the frames resident.  Orchestration (Pool fan-out, file
+walking, flat start, recording) is out of scope.
 """
 import os
 
@@ -29,6 +30,7 @@ class AcousticModel(DataInitialization):
         self.__state_num = state_num
         self.__mix_level = mix_level
         self.__vector_size = dct_num * (3 if delta_2 else 2 if delta_1 else 1)     # AcousticModel.py:84-88
+        self.__dct_num, self.__delta_1, self.__delta_2 = dct_num, delta_1, delta_2
         self.__address = parameters_path or os.environ.get('parameters_file_path', '.')
         self.__loaded_units = []
         self.processes = processes or 1
@@ -44,6 +46,43 @@ class AcousticModel(DataInitialization):
 
     loaded_units = property(lambda self: self.__loaded_units)
     statenum = property(lambda self: self.__state_num)
+
+    def load_audio(self, audiopath):
+        """__load_audio (AcousticModel.py:463-477): the wav file's MFCC with this object's dct_num / delta_1 / delta_2 at nfft = 512,
+        then the voice-activity detector's survivors, (T', D) float64."""
+        from ..StatisticalModel.AudioProcessing import AudioProcessing
+        mfcc = AudioProcessing.MFCC(self.__dct_num)
+        mfcc.init_audio(path=audiopath)
+        m = mfcc.mfcc(nfft=512, d1=self.__delta_1, d2=self.__delta_2)
+        mfcc.wav.close()                                           # (the samples have been read; the reference leaves the file open)
+        vad = AudioProcessing.VAD()
+        vad.init_mfcc(m)
+        return vad.mfcc()
+
+    def load_audio_batch(self, paths, engine=None, fetch=True):
+        """load_audio for many files through Engine.frontend: one MFCC + VAD + compaction on the device, the survivors left resident as
+        the engine's frame matrix.  Returns (lens, begin, data_list): data_list[u] = what load_audio(paths[u]) returns (fetch=False:
+        None, nothing comes back to the host); an utterance that kept no frame has lens[u] = 0 and a (0, D) entry, which estep_batch /
+        align_batch / segment_batch / regroup_batch / train_segments_batch skip.  Those helpers take data_list and upload it again: the
+        route WITHOUT a feature upload is engine.label_batch / all_state_batch on (lens, begin) of the non-empty utterances, as
+        INTEGRATION.md shows.  The files must share one sampling rate."""
+        from ..StatisticalModel.AudioProcessing import AudioProcessing
+        eng = engine or default_engine()
+        sigs, rate = [], None
+        for p in paths:
+            m = AudioProcessing.MFCC(self.__dct_num)
+            m.init_audio(path=p)
+            if rate is not None and m.params[2] != rate:
+                raise ValueError('load_audio_batch: %s is sampled at %d Hz, the files before it at %d' % (p, m.params[2], rate))
+            rate = m.params[2]
+            sigs.append(m.data)
+            m.wav.close()
+        d2 = bool(self.__delta_1 and self.__delta_2)               # MFCC.mfcc computes the second deltas only inside d1 (:440-447)
+        res = eng.frontend(sigs, rate, vec_num=self.__dct_num, nfft=512, d1=bool(self.__delta_1), d2=d2, fetch=fetch)
+        if not fetch:
+            return res[0], res[1], None
+        lens, begin, rows = res
+        return lens, begin, [rows[b:b + n] for b, n in zip(begin, lens)]
 
     def load_unit(self, unit_type=None, unit_file=None):
         """AcousticModel.load_unit (AcousticModel.py:134-161): the inventory is the file `$unit_file_path/<unit_type>` (unit_type given:
@@ -170,6 +209,17 @@ class AcousticModel(DataInitialization):
         trans = [np.asarray(unit_hmms[u].transmat, dtype=np.float64) for u in units]
         return units, idx, (np.stack([a[0] for a in arrs]), np.stack([a[1] for a in arrs]), np.stack([a[2] for a in arrs])), trans
 
+    @staticmethod
+    def _nonempty(data_list):
+        """Indices of the utterances that have frames.  The voice-activity detector may keep no frame of an utterance (load_audio /
+        load_audio_batch then give a (0, D) array): the batch helpers below leave such an utterance out of the device batch -- a
+        sentence HMM over zero frames has no alignment and adds nothing to any accumulator -- and keep their results aligned with
+        the input lists."""
+        keep = [u for u, d in enumerate(data_list) if len(d) > 0]
+        if not keep:
+            raise ValueError('every utterance of the batch is empty (no frame survived the voice-activity detector)')
+        return keep
+
     def _sentence_batch(self, labels, data_list, unit_hmms, engine):
         units, idx, (mean, var, w), trans = self._model_arrays(unit_hmms)
         engine.load_model(mean, var, w)
@@ -183,8 +233,16 @@ class AcousticModel(DataInitialization):
 
     def align_batch(self, labels, data_list, unit_hmms, precision=PCL_F64, engine=None):
         """Forced alignment of many utterances at once (call stack C, AcousticModel.py:723-768):
-        returns [(point, unit-name sequence)] like AcousticModel.viterbi does per utterance."""
+        returns [(point, unit-name sequence)] like AcousticModel.viterbi does per utterance.  An utterance without frames is
+        skipped: (nan, empty sequence) in its place."""
         engine = engine or default_engine()
+        keep = self._nonempty(data_list)
+        if len(keep) < len(data_list):          # an empty utterance: (nan, no names) in its place
+            res = self.align_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, precision, engine)
+            out = [(float('nan'), np.array([], dtype=str))] * len(data_list)
+            for u, r in zip(keep, res):
+                out[u] = r
+            return out
         b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
         b.score(precision)
         b.viterbi()
@@ -204,8 +262,15 @@ class AcousticModel(DataInitialization):
         gamma_acc (S-2,)) log-domain, merged over every occurrence as LHMM.add_acc does (LHMM.py:149-161,
         473-500).  Everything per utterance x label position runs in the library: the sentence HMMs are built
         from the labels there (pcl_batch_create_labels) and the per-unit merge is a kernel
-        (pcl_batch_accumulate_hmm); nothing here loops over utterances."""
+        (pcl_batch_accumulate_hmm); nothing here loops over utterances.  An utterance without frames is skipped (logp = nan)."""
         engine = engine or default_engine()
+        keep = self._nonempty(data_list)
+        if len(keep) < len(data_list):          # empty utterances add nothing to the statistics: logp = nan in their place
+            stats, hmm_acc, lp = self.estep_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, fix_code, precision,
+                                                  engine)
+            logp = np.full(len(data_list), np.nan)
+            logp[keep] = lp
+            return stats, hmm_acc, logp
         b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
         b.score(precision)
         b.forward_backward(fix_pi=bool(fix_code & 1))
@@ -287,6 +352,10 @@ class AcousticModel(DataInitialization):
         (AcousticModel.py:758-764, 629-644).  Returns ({unit: [S-2 arrays (n_k, D)]}, dropped): for each unit the frames
         of its GMM states, in utterance then time order; an utterance whose path misses a label unit is dropped
         (:754-757)."""
+        keep = self._nonempty(data_list)
+        if len(keep) < len(data_list):          # empty utterances are dropped like the ones whose path misses a unit
+            out, dropped = self.regroup_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, precision, engine)
+            return out, sorted((set(range(len(data_list))) - set(keep)) | {keep[u] for u in dropped})
         b, units, idx, row_unit, fu, fk, dropped = self._align_regroup(labels, data_list, unit_hmms, precision, engine)
         b.close()
         s = self.__state_num
@@ -345,6 +414,12 @@ class AcousticModel(DataInitialization):
         (Clustering.ClusterInitialization)."""
         self._no_smem(smem)
         engine = engine or default_engine()
+        keep = self._nonempty(data_list)
+        if len(keep) < len(data_list):          # empty utterances are dropped like the ones whose path misses a unit
+            out = self.train_segments_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, init, mix_level, smem,
+                                            c_covariance, seed, precision, engine)
+            self.last_dropped = sorted((set(range(len(data_list))) - set(keep)) | {keep[u] for u in self.last_dropped})
+            return out
         b, units, idx, row_unit, fu, fk, self.last_dropped = self._align_regroup(labels, data_list, unit_hmms, precision, engine)
         try:
             seg = b.segments(row_unit, self.__state_num - 2, dropped=self.last_dropped, regrouped=(fu, fk))

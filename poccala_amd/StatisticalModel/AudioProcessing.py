@@ -1,9 +1,11 @@
 """Drop-in for the feature-extraction part of StatisticalModel/AudioProcessing.py: `AudioProcessing.MFCC`
-(wav -> (T, 13/26/39) float64 MFCC matrix), computed on the GPU (csrc/mfcc.hip) through `pcl_mfcc`.
+(wav -> (T, 13/26/39) float64 MFCC matrix), computed on the GPU (csrc/mfcc.hip) through `pcl_mfcc`, and `AudioProcessing.VAD`
+(MFCC matrix -> the rows its voice-activity detector keeps), computed on the GPU (csrc/vad.hip) through `pcl_vad`.
 
-This is SURVEY.md section 8(f) row 4, the step BEFORE the hot path.  Mirrored: MFCC(vec_num), init_audio,
-data, params, mfcc(sampletime, overlap, nfft, cal_energy, d1, d2) (AudioProcessing.py:100-448); added:
-`mfcc_batch` for many signals in one launch.  Recording / playback (pyaudio) and the VAD are out of scope.
+This is SURVEY.md section 8(f) rows 4 and 6, the steps BEFORE the hot path.  Mirrored: MFCC(vec_num), init_audio,
+data, params, mfcc(sampletime, overlap, nfft, cal_energy, d1, d2) (AudioProcessing.py:100-448); VAD(simple_size), init_mfcc,
+mel_distance, osf, detect, mfcc (:450-543; plotting is not supported).  Added: `mfcc_batch` / `vad_batch` for many utterances in one
+launch; `Engine.frontend` runs both and leaves the survivors resident on the device.  Recording / playback (pyaudio) are out of scope.
 The reference's conventions are kept exactly (they are pinned by tests/golden/G10_mfcc.npz):
 the "Hamming window" is one factor per frame, the spectrum is the rFFT magnitude, every mel filter is two
 rising ramps, the DCT kernel is cos(pi (2k-1) j / 2N) * 2/sqrt(N), c0 is ln(sum of magnitudes).
@@ -14,7 +16,7 @@ import wave
 
 import numpy as np
 
-from .._lib import as_c, ptr
+from .._lib import PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, as_c, ptr
 from ..runtime import default_engine
 
 
@@ -71,6 +73,52 @@ def mfcc_batch(signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nf
     return np.split(out, cuts)
 
 
+def mfcc_tables(framerate, vec_num=13, nfft=512, filterbanks=26):
+    """The float64 tables pcl_mfcc / pcl_frontend take: twiddle cos / sin (nfft,), mel response, DCT basis."""
+    n = np.arange(nfft)
+    return (as_c(np.cos(2 * np.pi * n / nfft), np.float64), as_c(-np.sin(2 * np.pi * n / nfft), np.float64),
+            as_c(mel_filter_matrix(framerate, nfft, filterbanks), np.float64), as_c(dct_basis(filterbanks, vec_num), np.float64))
+
+
+def _vad_call(eng, mats, simple_size, alpha, beta, flags, want, dist=None, osf=None):
+    """One pcl_vad call over a ragged list.  mats: feature matrices (or None with PCL_VAD_DIST_IN / _OSF_IN, then `dist` / `osf` are
+    lists of the caller's vectors); want: subset of {'dist', 'osf', 'kept'}.  Returns dict of flat arrays + row_off."""
+    src = mats if mats is not None else (dist if flags & PCL_VAD_DIST_IN else osf)
+    lens = [len(m) for m in src]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    rows, U = int(off[-1]), len(lens)
+    x, D = None, 0
+    if mats is not None:
+        mats = [np.asarray(m, dtype=np.float64) for m in mats]
+        D = mats[0].shape[1]
+        if any(m.ndim != 2 or m.shape[1] != D for m in mats):
+            raise ValueError('vad: every utterance must be a (T, %d) matrix' % D)
+        x = as_c(np.concatenate(mats), np.float64)
+    d = as_c(np.concatenate(dist), np.float64).copy() if flags & PCL_VAD_DIST_IN else (np.empty(rows) if 'dist' in want else None)
+    o = as_c(np.concatenate(osf), np.float64).copy() if flags & PCL_VAD_OSF_IN else (np.empty(rows) if 'osf' in want else None)
+    kl = ki = thr = None
+    if 'kept' in want:
+        kl, ki, thr = np.empty(U, dtype=np.int32), np.empty(rows, dtype=np.int32), np.empty(U)
+    eng._check(eng._lib.pcl_vad(eng._ctx, U, ptr(x), ptr(off), int(D), int(simple_size), float(alpha), float(beta), int(flags),
+                                ptr(kl), ptr(ki), ptr(d), ptr(o), ptr(thr)))
+    return dict(row_off=off, dist=d, osf=o, kept_len=kl, kept_idx=ki, thr=thr)
+
+
+def vad_batch(mfcc_list, simple_size=16, alpha=0.5, beta=0.93, details=False, engine=None):
+    """VAD.mfcc() of many utterances in one call: list of the kept rows (T'_u, D) float64 -- an utterance that keeps no frame
+    gives a (0, D) array.  details=True: (rows, info) with info = dict(kept=[indices], dist=[...], osf=[...], thr=(U,))."""
+    eng = engine or default_engine()
+    mats = [np.asarray(m, dtype=np.float64) for m in mfcc_list]
+    r = _vad_call(eng, mats, simple_size, alpha, beta, 0, ('dist', 'osf', 'kept') if details else ('kept',))
+    off = r['row_off']
+    kept = [r['kept_idx'][off[u]:off[u] + r['kept_len'][u]].astype(np.int64) for u in range(len(mats))]
+    rows = [m[k] for m, k in zip(mats, kept)]
+    if not details:
+        return rows
+    cut = off[1:-1]
+    return rows, dict(kept=kept, dist=np.split(r['dist'], cut), osf=np.split(r['osf'], cut), thr=r['thr'])
+
+
 class AudioProcessing(object):
     class MFCC(object):
         def __init__(self, vec_num=13):
@@ -112,3 +160,50 @@ class AudioProcessing(object):
         def mfcc(self, sampletime=0.025, overlap=0.5, nfft=512, cal_energy=True, d1=False, d2=False):
             return mfcc_batch([self.__wdata], self.params[2], self.__vec_num, sampletime, overlap, nfft, 26, cal_energy,
                               d1, d2)[0]
+
+    class VAD(object):
+        """AudioProcessing.VAD (AudioProcessing.py:450-543) on the device: noise estimate from the first `simple_size` frames, distance
+        of every frame to it, order-statistics filter, threshold.  The reference's conventions are kept exactly (golden G19; they are
+        listed as V1-V5 in include/poccala_hip.h)."""
+
+        def __init__(self, simple_size=16):
+            self.__mfcc = None
+            self.__simple_size = simple_size
+
+        def init_mfcc(self, mfcc):
+            self.__mfcc = mfcc
+
+        def __features(self):
+            m = np.asarray(self.__mfcc, dtype=np.float64)
+            if len(m) < self.__simple_size:                       # the reference's own failure (:472)
+                raise IndexError('index %d is out of bounds for axis 0 with size %d' % (len(m), len(m)))
+            return m
+
+        def mel_distance(self, alpha=0.5):
+            """Distance of every frame to the noise vector (:462-478)."""
+            return _vad_call(default_engine(), [self.__features()], self.__simple_size, alpha, 0.93, 0, ('dist',))['dist']
+
+        def osf(self, mel_distance, beta=0.93):
+            """Order-statistics filter over the distances (:480-507)."""
+            d = np.asarray(mel_distance, dtype=np.float64)
+            if len(d) != len(self.__mfcc):
+                raise ValueError('osf: %d distances for %d frames' % (len(d), len(self.__mfcc)))
+            if len(d) <= 2 * self.__simple_size:                  # no frame has a full window: the reference's loop does not run
+                return d.copy()
+            return _vad_call(default_engine(), None, self.__simple_size, 0.5, beta, PCL_VAD_DIST_IN, ('osf',), dist=[d])['osf']
+
+        def detect(self, mel_distance, show_pic=False):
+            """Rows whose (smoothed) distance lies above the threshold (:509-536)."""
+            if show_pic:
+                raise NotImplementedError('VAD.detect(show_pic=True): plotting is not supported')
+            d = np.asarray(mel_distance, dtype=np.float64)
+            if len(d) != len(self.__mfcc):
+                raise ValueError('detect: %d distances for %d frames' % (len(d), len(self.__mfcc)))
+            r = _vad_call(default_engine(), None, self.__simple_size, 0.5, 0.93, PCL_VAD_OSF_IN, ('kept',), osf=[d])
+            return np.asarray(self.__mfcc)[r['kept_idx'][:r['kept_len'][0]]]
+
+        def mfcc(self, show_pic=False):
+            """The frames that survive the detector (:538-543)."""
+            if show_pic:
+                raise NotImplementedError('VAD.mfcc(show_pic=True): plotting is not supported')
+            return vad_batch([self.__features()], self.__simple_size)[0]

@@ -15,6 +15,8 @@ PCL_F32, PCL_F64 = 0, 1
 PCL_MODEL_Q1_SUMVAR, PCL_MODEL_LOGDET = 0, 1
 PCL_ROW_ENTRY, PCL_ROW_EXIT = -1, -2
 PCL_MAX_PASS = 16
+PCL_VAD_DIST_IN, PCL_VAD_OSF_IN = 1, 2
+PCL_FRONTEND_NO_VAD, PCL_FRONTEND_KEEP_F64 = 1, 2
 SEG_GET = dict(counts=0, order=1, assign=2, seeds=3)
 GET = dict(B=0, alpha=1, beta=2, lgamma=3, ksai=4, gamma=5, pi=6, logp=7, npass=8, qtrace=9, path=10, point=11, ksai_nz=12)
 
@@ -66,6 +68,8 @@ PROTOTYPES = {
     'pcl_score_occupancy': (_i, [_vp, _i]),
     'pcl_batch_regroup': (_i, [_vp, _vp, _i, _vp, _vp]),
     'pcl_mfcc': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
+    'pcl_vad': (_i, [_vp, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pcl_frontend': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),
     'pcl_timing_enable': (_i, [_vp, _i]),
     'pcl_device_count': (_i, [C.POINTER(_i)]),
     'pcl_units_upload': (_i, [_vp, _i, _i, _vp, _vp]),

@@ -398,6 +398,19 @@ static int device_dim(int D) {
     return -1;
 }
 
+int pcl_device_dim(int D) { return device_dim(D); }
+
+// The front-end (vad.hip) built the frame matrix on the device: make it the current one, as pcl_frames_upload does with a host matrix.
+void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D) {
+    release_frames32(ctx);
+    dev_free(ctx->frames64);
+    ctx->frames32 = f32;
+    ctx->frames64 = f64;
+    ctx->F = F;
+    ctx->FD = device_dim(D);
+    ctx->FDhost = D;
+}
+
 int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, const double *var, const double *weight,
                      int flags) {
     if (!ctx) return PCL_ERR_INVALID;

@@ -567,3 +567,12 @@ void pcl_comm_release(pcl_ctx *ctx);
 void pcl_lexicon_release(pcl_ctx *ctx);
 void pcl_batch_decode_release(pcl_batch *b);
 int pcl_launch_pack(pcl_ctx *ctx, const double *src, int inner, double *dst);
+extern "C" {   // defined inside pcl_api.hip's extern "C" block; hidden like every symbol the public header does not declare
+int pcl_device_dim(int D);                                   // the padded feature dimension the kernels have an instance for (-1: D > 64)
+void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D);   // device-built (F, pcl_device_dim(D)) matrices become the current frames
+}
+// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (hipMalloc: the caller hipFree's it), complete on
+// return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.
+int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime,
+                    double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos, const double *twiddle_sin,
+                    const double *mel_response, const double *dct_matrix, int64_t out_rows, double **d_out, std::vector<long long> *row_off);

@@ -156,6 +156,35 @@ class Engine(object):
         self.F, self.FD = f.shape[0], f.shape[1]
         self._frames_key = key
 
+    def frontend(self, signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nfft=512, filterbanks=26, cal_energy=True,
+                 d1=True, d2=True, vad=True, simple_size=16, alpha=0.5, beta=0.93, keep_f64=False, fetch=False):
+        """PCM -> resident frames: MFCC (AudioProcessing.MFCC.mfcc), the voice-activity detector (AudioProcessing.VAD.mfcc) and the
+        compaction of its survivors in one call, without the features leaving the device -- AcousticModel.__load_audio
+        (AcousticModel.py:463-477) for a list of signals.  Afterwards the survivors are the current frame matrix, exactly as
+        load_frames(np.float32(rows)) would have left them; returns (lens (U,) int32, begin (U,) int64) for label_batch / batch /
+        all_state_batch -- an utterance that kept no frame has length 0 and must be left out of the lists handed to them (lens > 0:
+        a batch takes utterances of at least one frame; AcousticModel's batch helpers, which take host arrays, skip empty ones
+        themselves).  If no frame of any utterance survives, every length is 0 and the frame matrix is empty.  vad=False: every MFCC row is kept.  keep_f64: the float64 copy parity mode reads is kept too instead of being derived
+        from the float32 rows.  fetch=True: (lens, begin, rows) with rows the (sum lens, D) float64 survivors, for inspection."""
+        from .StatisticalModel.AudioProcessing import frame_count, mfcc_tables
+        sigs = [np.asarray(s, dtype=np.float64).reshape(-1) for s in signals]
+        off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+        rows = int(sum(frame_count(len(s), framerate, sampletime, overlap) for s in sigs))
+        dim = vec_num * (3 if (d1 and d2) else 2 if d1 else 1)
+        twc, tws, resp, dct = mfcc_tables(framerate, vec_num, nfft, filterbanks)
+        flat = as_c(np.concatenate(sigs), np.float64)
+        mflags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
+        flags = (0 if vad else _lib.PCL_FRONTEND_NO_VAD) | (_lib.PCL_FRONTEND_KEEP_F64 if keep_f64 else 0)
+        lens, begin = np.empty(len(sigs), dtype=np.int32), np.empty(len(sigs), dtype=np.int64)
+        out = np.empty((max(rows, 1), dim)) if fetch else None
+        self._check(self._lib.pcl_frontend(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
+                                           int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
+                                           int(simple_size), float(alpha), float(beta), flags, ptr(lens), ptr(begin), ptr(out),
+                                           C.c_int64(rows)))
+        self.F, self.FD = int(lens.sum()), dim
+        self._frames_key = None
+        return (lens, begin, out[:self.F].copy()) if fetch else (lens, begin)
+
     # ------------------------------------------------------------------ streaming (BASELINE config 5: a corpus fed chunk by chunk)
     def stage_frames(self, frames):
         """Queue the H2D copy of the NEXT chunk's (F,D) float32 rows on the copy stream, into the frame slot that is not
