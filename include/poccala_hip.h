@@ -100,7 +100,8 @@ int pcl_sync(pcl_ctx *ctx);
 int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_bytes);
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
- * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather".
+ * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
+ * pcl_model_upload / pcl_model_flat_start).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -347,6 +348,56 @@ int pcl_seg_centres(pcl_seg *seg, double *centres /* (J,K,D) of the last pcl_seg
  * pcl_batch_accumulate had summed there before is gone, and afterwards the block holds the call's last E-step.  Synchronous. */
 int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_iters, int precision, int32_t *iters, double *q,
                double *q_trace);
+
+/* ----------------------------------------------------------------- starting from nothing (row f7: the step before either training scheme)
+ * Both training schemes of the reference begin with a step that needs no model; csrc/bootstrap.hip runs them on the resident frames.
+ *
+ * pcl_frames_moments: what AcousticModel.__flat_start (AcousticModel.py:479-517) does with p_data.  The sample is data[::step] PER
+ * UTTERANCE, concatenated, over the first n_utts utterances (n_utts = int(file_count * proportion), :492, taken by the caller): the rows
+ * frame_begin[u] + step * i, i = 0 .. ceil(T[u] / step) - 1, of the current frame matrix; an utterance of length 0 adds nothing.
+ * mean_out / var_out (D,) = what ClusterInitialization(p_data, 1, D).kmeans(algorithm=1, cov_matrix=True) returns for k = 1 (:499-501):
+ * the arithmetic mean; the mean squared deviation ABOUT THAT MEAN divided by n (not n - 1), floored at 1e-4 (cal_variance,
+ * Clustering.py:807-832), then sqrt and squared again, as cov_matrix=True does.  *n_rows_out = rows in the sample (may be NULL).
+ * Float64 throughout, two passes (mean, then deviations); the float64 frame copy is read when the context holds one (float64 upload,
+ * PCL_FRONTEND_KEEP_F64), otherwise the float32 rows are widened.  No floating-point atomics; the summation order is fixed: sample
+ * row g belongs to workgroup g / 1024; inside a workgroup, row lane r (of 256 / 64 = 4) adds its rows r, r + 4, ... in ascending order
+ * and the four lanes are added 0, 1, 2, 3; one workgroup then adds the workgroups' partial sums in ascending index order.  Two runs
+ * give the same bits.  U is the length of T / frame_begin (frame_begin NULL: utterances back to back from row 0); n_utts < 1 or > U,
+ * step < 1, an utterance outside the frame matrix, no frames loaded, or an empty sample (the reference indexes an empty list there):
+ * PCL_ERR_INVALID.  Synchronous. */
+int pcl_frames_moments(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, int n_utts, int step, double *mean_out /* D */,
+                       double *var_out /* D */, int64_t *n_rows_out);
+/* The flat-start model, made where it will live (AcousticModel.py:504-516): for every state j and mixture m
+ *   mean[j,m,d] = mean[d] + coeff[m] * var[d]     (the coefficient multiplies the VARIANCE -- covariance_diagonal, :514 --, one rounded
+ *                                                  product and one rounded sum, as NumPy evaluates it)
+ *   var[j,m,d]  = var[d],   weight[j,m] = 1 / M   (the GMM constructor's default, Clustering.py:87-88)
+ * written straight into the context's float64 master copy; then everything pcl_model_upload runs after its copy (derived layouts,
+ * conditioning, split lists, a zeroed statistics block): pcl_model_download and every scoring path see the model an upload of the same
+ * (J, M, D) arrays would give.  coeff (M,): the caller's draw, (np.random.random((M, 1)) - np.random.random((M, 1))) * coefficient --
+ * drawn ONCE and shared by every unit and state (:508-516); NULL = differentiation=False (all zero).  flags: pcl_model_upload's.
+ * A variance that is not positive and finite, a non-finite mean or coefficient, or D other than the dimension of the frame matrix the
+ * context holds (none loaded: any D): PCL_ERR_INVALID, the model in place stays.  Synchronous. */
+int pcl_model_flat_start(pcl_ctx *ctx, int J, int M, int D, const double *mean /* D */, const double *var /* D */,
+                         const double *coeff /* M or NULL */, int flags);
+/* The two calls above chained, the moments never visiting the host on their way into the model (D = the frame matrix's); mean_out /
+ * var_out / n_rows_out (NULLs are skipped) report them.  Same results as pcl_frames_moments + pcl_model_flat_start, bit for bit. */
+int pcl_flat_start(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, int n_utts, int step, int J, int M,
+                   const double *coeff /* M or NULL */, int flags, double *mean_out, double *var_out, int64_t *n_rows_out);
+/* Uniform segmentation: the first round of training scheme 1, multi_process_data(init=True) (AcousticModel.py:734-735) =
+ * __eq_segment(data, label, mode='e') (:605-612), followed per unit by __get_gmmdata (:629-644, mode 'g' :613-625) in multi_training
+ * (:834).  Label arguments as pcl_batch_create_labels (labels = concatenated unit ids, label_len[u] of them per utterance), but neither
+ * a model nor an uploaded unit inventory is needed: J = number of GMM states, a multiple of gmm_num (= S - 2); unit i owns the states
+ * i * gmm_num ...  For utterance u with L labels: chunk = T / L (integer); label position i owns the frames [i chunk, (i + 1) chunk); the
+ * T - L chunk frames left over are NOT used (mode 'e' drops them).  Inside a chunk: c2 = chunk / gmm_num; state k < gmm_num - 1 takes
+ * [k c2, (k + 1) c2), the last state the rest.  So T < L uses nothing, and chunk < gmm_num gives everything to the last state.
+ * frame_state_out (rows of the frame matrix,) int32 or NULL: unit * gmm_num + k, -1 for unused frames and for rows outside the batch --
+ * pcl_seg_create's input.  out or NULL: the pcl_seg of that map, built from it ON THE DEVICE by pcl_seg_create's counting sort and
+ * gather (a unit named several times collects all of it, in row order).  At least one of the two must be given.  Not in the reference's
+ * signature: the utterances must not overlap in the frame matrix (a frame has ONE owner; PCL_ERR_INVALID), and an utterance may have
+ * T = 0 or no label (nothing is used).  A label id outside [0, J / gmm_num), J not a multiple of gmm_num, an utterance outside the frame
+ * matrix, no frames loaded: PCL_ERR_INVALID.  Integer arithmetic only.  Synchronous. */
+int pcl_uniform_segments(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T, const int64_t *frame_begin,
+                         int gmm_num, int J, int32_t *frame_state_out, pcl_seg **out);
 
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /

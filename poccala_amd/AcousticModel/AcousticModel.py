@@ -5,9 +5,10 @@ Mirrored (starred): `embedded` :957-1014, `viterbi` :101
 per-utterance E-step or alignment can be written exactly as the reference's workers write it
 (`multi_embedded_training_1` :884-916, `multi_process_data` :723-768).  Batched equivalents that keep
 everything on the GPU are `estep_batch` / `align_batch`, and `train_segments_batch` / `train_segments_data` for training
-scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state).  `load_audio` is `__load_audio` (:463-477: wav -> MFCC ->
+scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state), and `flat_start_batch` (`__flat_start` :479-517) /
+`init_segments_batch` (`multi_process_data(init=True)` :734-735) for the model-free step either scheme begins with.  `load_audio` is `__load_audio` (:463-477: wav -> MFCC ->
 VAD); `load_audio_batch` does it for many files in one call and leaves the frames resident.  Orchestration (Pool fan-out, file
-walking, flat start, recording) is out of scope.
+walking, recording) is out of scope.
 """
 import os
 
@@ -426,6 +427,62 @@ class AcousticModel(DataInitialization):
         finally:
             b.close()
         return self._train_segments(engine, seg, units, unit_hmms, init, mix_level, smem, c_covariance, seed, precision)
+
+    # ------------------------------------------------------------------ starting from nothing: what either scheme begins with
+    def flat_start_batch(self, data, unit_hmms, proportion=0.25, step=1, differentiation=True, coefficient=1., seed=None, engine=None):
+        """AcousticModel.__flat_start (AcousticModel.py:479-517) on the device.  `data` is a list of (T_u, D) arrays (uploaded here), or
+        the (lens, begin) of frames already resident (Engine.frontend / load_audio_batch(fetch=False)): the global mean and variance
+        of data[::step] of the first int(len * proportion) utterances, then every mixture of every GMM state of every unit in
+        `unit_hmms` set to mean + diff[m] * variance / variance / weight 1 / mix_level, with ONE draw diff = (random((M, 1)) -
+        random((M, 1))) * coefficient shared by all of them (differentiation=False: zero).  seed=None draws from NumPy's global
+        generator as the reference does; a seed draws the same numbers np.random.seed(seed) would have given.  The model is left
+        resident in the engine (states unit-major over sorted(unit_hmms), as every batch helper lays them out) AND written into
+        the units' GMM objects, so save_parameter works afterwards.  Returns (mean (D,), var (D,), coeff (M,))."""
+        engine = engine or default_engine()
+        if isinstance(data, tuple) and len(data) == 2 and np.ndim(data[0]) == 1:
+            lens, begin = np.asarray(data[0], dtype=np.int32), np.asarray(data[1], dtype=np.int64)
+        else:
+            lens = np.array([len(d) for d in data], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d).reshape(-1, self.__vector_size) for d in data], axis=0))
+        m = self.__mix_level
+        diff = np.zeros((m, 1))
+        if differentiation:
+            assert 0 <= coefficient <= 1, 'coefficient must lie in [0, 1]'
+            rs = np.random if seed is None else np.random.RandomState(seed)
+            diff = (rs.random_sample((m, 1)) - rs.random_sample((m, 1))) * coefficient
+        units = sorted(unit_hmms)
+        e = self.__state_num - 2
+        mean, var, _ = engine.flat_start(lens, begin, len(units) * e, m, n_utts=int(len(lens) * proportion), step=step,
+                                         coeff=diff[:, 0] if differentiation else None)
+        g_mean = mean[None, :].repeat(m, axis=0) + diff * var          # :514, the arithmetic the device repeats per state
+        g_var = var[None, :].repeat(m, axis=0)
+        for unit in units:
+            for k in range(e):
+                unit_hmms[unit].profunction[1 + k].set_model(g_mean, g_var, np.ones(m) / m)
+        return mean, var, diff[:, 0].copy()
+
+    def init_segments_batch(self, labels, data_list, unit_hmms, mix_level=None, c_covariance=1e-3, seed=0, precision=PCL_F64, engine=None):
+        """The first round of training scheme 1, which needs no model: uniform segmentation (multi_process_data(init=True),
+        AcousticModel.py:734-735: every utterance cut into equal chunks, one per label unit; __get_gmmdata :629-644: every chunk into
+        S-2 slices) on the device, then clustering + stand-alone EM of every GMM state as train_segments_batch(init=True) runs them
+        -- but WITHOUT its forced alignment, which would need a model.  mix_level defaults to this object's.  Returns what
+        train_segments_batch returns, {unit: (iters (S-2,), q (S-2,), skipped (S-2,) bool)}; the units' GMM objects receive the new
+        parameters and the engine holds the model.  An utterance without frames adds nothing.  The reference also runs the SMEM split /
+        merge on this round (smem=init, :835): outside the hot path here, as for train_segments_batch."""
+        engine = engine or default_engine()
+        keep = self._nonempty(data_list)
+        labels, data_list = [labels[u] for u in keep], [data_list[u] for u in keep]
+        units = sorted(unit_hmms)
+        idx = {u: i for i, u in enumerate(units)}
+        e = self.__state_num - 2
+        lens = np.array([len(d) for d in data_list], dtype=np.int32)
+        begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+        engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
+        unit_ids = [np.array([idx[u] for u in lab], dtype=np.int32) for lab in labels]
+        seg = engine.uniform_segments(unit_ids, lens, begin, e, len(units) * e)
+        k = int(mix_level) if mix_level is not None else self.__mix_level
+        return self._train_segments(engine, seg, units, unit_hmms, True, k, False, c_covariance, seed, precision)
 
     def train_segments_data(self, unit_data, unit_hmms, init=False, mix_level=None, smem=False, c_covariance=1e-3, seed=0,
                             precision=PCL_F64, engine=None):

@@ -479,6 +479,28 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
         if (frame_state[t] < -1 || frame_state[t] >= J)
             PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: frame_state[%lld] = %d is neither -1 nor a state in [0,%d)", (long long)t, frame_state[t], J);
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    int *d_state = nullptr;
+    TRY(dev_alloc(ctx, &d_state, (size_t)n_frames_total));
+    int rc = PCL_OK;
+    if (pcl_h2d(ctx, d_state, frame_state, (size_t)n_frames_total * sizeof(int)) != hipSuccess) {
+        pcl_set_error(ctx, "pcl_seg_create: copy of the owner array failed");
+        rc = PCL_ERR_HIP;
+    }
+    if (rc == PCL_OK) rc = pcl_seg_create_device(ctx, n_frames_total, J, d_state, out);
+    dev_free(d_state);
+    return rc;
+}
+
+}  // extern "C"
+
+// The owner array is on the device already (pcl_seg_create above; pcl_uniform_segments, bootstrap.hip): counting sort + gather.
+int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_state, pcl_seg **out) {
+    *out = nullptr;
+    if (J <= 0 || J > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: bad arguments (J=%d, at most 65535 states)", J);
+    if (!ctx->frames32 || ctx->F == 0) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_seg_create: no frames uploaded");
+    if (n_frames_total != ctx->F || n_frames_total > 0x7fffffffLL)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: %lld owner entries for a frame matrix of %lld rows", (long long)n_frames_total, (long long)ctx->F);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long F = n_frames_total;
     pcl_seg *s = new pcl_seg();
     s->ctx = ctx;
@@ -490,18 +512,14 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
     const long long per_tile = std::max<long long>(std::max<long long>(2048, (F + 4095) / 4096), (F * (long long)J + (1LL << 26) - 1) >> 26);
     const int tile = (int)((per_tile + SEG_T - 1) / SEG_T * SEG_T);
     const int n_tiles = (int)((F + tile - 1) / tile);
-    int *d_state = nullptr, *d_tilecnt = nullptr;
+    int *d_tilecnt = nullptr;
     Latch A(ctx);
     Latch &H = A;
     int &rc = A.rc;
-    A(dev_alloc(ctx, &d_state, (size_t)F));
     A(dev_alloc(ctx, &d_tilecnt, (size_t)n_tiles * J));
     A(dev_alloc(ctx, &s->d_counts, (size_t)J));
     A(dev_alloc(ctx, &s->d_off, (size_t)J + 1));
-    if (rc == PCL_OK) {
-        H(hipMemcpyAsync(d_state, frame_state, (size_t)F * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        H(hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
-    }
+    if (rc == PCL_OK) H(hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
     if (rc == PCL_OK) {
         hipLaunchKernelGGL(seg_hist_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt);
         hipLaunchKernelGGL(seg_colscan_kernel, dim3((J + 255) / 256), dim3(256), 0, ctx->stream, d_tilecnt, n_tiles, J, s->d_counts);
@@ -527,7 +545,6 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
         H(hipGetLastError());
     }
     if (rc == PCL_OK) H(hipStreamSynchronize(ctx->stream));
-    dev_free(d_state);
     dev_free(d_tilecnt);
     if (rc != PCL_OK) {
         seg_free(s);
@@ -536,6 +553,8 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
     *out = s;
     return PCL_OK;
 }
+
+extern "C" {
 
 int pcl_seg_destroy(pcl_seg *seg) {
     if (!seg) return PCL_ERR_INVALID;

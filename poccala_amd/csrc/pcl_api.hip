@@ -411,32 +411,20 @@ void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D) {
     ctx->FDhost = D;
 }
 
-int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, const double *var, const double *weight,
-                     int flags) {
-    if (!ctx) return PCL_ERR_INVALID;
-    if (J <= 0 || M <= 0 || D <= 0 || !mean || !var || !weight) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: bad shape J=%d M=%d D=%d", J, M, D);
+// The first half of pcl_model_upload (also bootstrap.hip: a model made on the device): the old model goes, the master copy and every derived
+// buffer of a (J, M, D) model are allocated, the shape fields set.  The master copy's contents are the caller's to write.
+int pcl_model_alloc(pcl_ctx *ctx, int J, int M, int D, int flags, const char *who) {
+    if (J <= 0 || M <= 0 || D <= 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: bad shape J=%d M=%d D=%d", who, J, M, D);
     const int Dd = device_dim(D);
-    if (Dd < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: feature dimension %d > 64 is not supported", D);
+    if (Dd < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: feature dimension %d > 64 is not supported", who, D);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     free_model(ctx);
     const int Mpad = (M + 3) / 4 * 4;
     const int row = (2 * Dd + 1 + 3) / 4 * 4;
     const int Mp32 = (M + 31) / 32 * 32, KS4 = (Dd + 1 + 3) / 4;
-    const size_t np = (size_t)J * Mpad * row, nm = (size_t)J * Mpad * Dd, nw = (size_t)J * Mpad;
+    const size_t nm = (size_t)J * Mpad * Dd, nw = (size_t)J * Mpad;
     const size_t npm = (size_t)J * (Mp32 / 32) * KS4 * 64 * 4;
-    // float64 master copy in the padded device layout; every derived layout is built on the device
-    std::vector<double> m64(nm, 0.0), v64(nm, 1.0), w64(nw, 0.0);
-    for (int j = 0; j < J; ++j)
-        for (int m = 0; m < M; ++m) {
-            w64[(size_t)j * Mpad + m] = weight[(size_t)j * M + m];
-            for (int d = 0; d < D; ++d) {
-                const double vr = var[((size_t)j * M + m) * D + d];
-                if (!(vr > 0.0)) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: variance[%d,%d,%d] = %g is not positive", j, m, d, vr);
-                m64[((size_t)j * Mpad + m) * Dd + d] = mean[((size_t)j * M + m) * D + d];
-                v64[((size_t)j * Mpad + m) * Dd + d] = vr;
-            }
-        }
-    (void)np;                                                     // (params32 / params64 / mean32: allocated when first derived, model_derive.hip)
+    // (params32 / params64 / mean32: allocated when first derived, model_derive.hip)
     TRY(dev_alloc(ctx, &ctx->mean64, nm));
     TRY(dev_alloc(ctx, &ctx->var64, nm));
     TRY(dev_alloc(ctx, &ctx->w64, nw));
@@ -460,9 +448,6 @@ int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, cons
     // the limits 0.95, 0.99, 0.998: 274 / 256 / 275, 206 / 260 / 306 and 160 / 276 / 362 ms (profiles/r06_coarse_rework.txt).  PCL_SPLIT_MAX overrides both limits; the accumulate pass keeps the round 4-5 half
     ctx->acc_split_max = (int)((ctx->split_frac_set ? ctx->split_frac : 0.5f) * (float)M);
     ctx->split_max = (int)(((ctx->split_frac_set || !pcl_coarse_enabled_for(ctx, Dd)) ? ctx->split_frac : ctx->coarse_split_frac) * (float)M);
-    HIPCHK(ctx, hipMemcpy(ctx->mean64, m64.data(), nm * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->var64, v64.data(), nm * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->w64, w64.data(), nw * sizeof(double), hipMemcpyHostToDevice));
     ctx->J = J;
     ctx->M = M;
     ctx->Mpad = Mpad;
@@ -471,7 +456,17 @@ int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, cons
     ctx->Dhost = D;
     ctx->row = row;
     ctx->model_flags = flags;
-    TRY(pcl_launch_derive(ctx));
+    return PCL_OK;
+}
+
+// The second half: from the master copy on the device to a model every scoring path can use.
+int pcl_model_finish(pcl_ctx *ctx) {
+    const int J = ctx->J, Mpad = ctx->Mpad;
+    const size_t nm = (size_t)J * Mpad * ctx->D;
+    pcl_timer_begin(ctx, "derive");
+    const int rc_derive = pcl_launch_derive(ctx);
+    pcl_timer_end(ctx, "derive");
+    TRY(rc_derive);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // statistics: [acc J*Mpad | alpha J | mean J*Mpad*Dd | cov J*Mpad*Dd]
     ctx->stats_len = (size_t)J * Mpad + J + 2 * nm;
@@ -482,6 +477,35 @@ int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, cons
     ctx->st_cov = ctx->st_mean + nm;
     HIPCHK(ctx, hipMemset(ctx->stats, 0, ctx->stats_len * sizeof(double)));
     return PCL_OK;
+}
+
+int pcl_model_upload(pcl_ctx *ctx, int J, int M, int D, const double *mean, const double *var, const double *weight,
+                     int flags) {
+    if (!ctx) return PCL_ERR_INVALID;
+    if (J <= 0 || M <= 0 || D <= 0 || !mean || !var || !weight) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: bad shape J=%d M=%d D=%d", J, M, D);
+    const int Dd = device_dim(D);
+    if (Dd < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: feature dimension %d > 64 is not supported", D);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    free_model(ctx);                                              // (as always: a rejected variance below leaves the context without a model)
+    const int Mpad = (M + 3) / 4 * 4;
+    const size_t nm = (size_t)J * Mpad * Dd, nw = (size_t)J * Mpad;
+    // float64 master copy in the padded device layout; every derived layout is built on the device
+    std::vector<double> m64(nm, 0.0), v64(nm, 1.0), w64(nw, 0.0);
+    for (int j = 0; j < J; ++j)
+        for (int m = 0; m < M; ++m) {
+            w64[(size_t)j * Mpad + m] = weight[(size_t)j * M + m];
+            for (int d = 0; d < D; ++d) {
+                const double vr = var[((size_t)j * M + m) * D + d];
+                if (!(vr > 0.0)) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_model_upload: variance[%d,%d,%d] = %g is not positive", j, m, d, vr);
+                m64[((size_t)j * Mpad + m) * Dd + d] = mean[((size_t)j * M + m) * D + d];
+                v64[((size_t)j * Mpad + m) * Dd + d] = vr;
+            }
+        }
+    TRY(pcl_model_alloc(ctx, J, M, D, flags, "pcl_model_upload"));
+    HIPCHK(ctx, hipMemcpy(ctx->mean64, m64.data(), nm * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->var64, v64.data(), nm * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->w64, w64.data(), nw * sizeof(double), hipMemcpyHostToDevice));
+    return pcl_model_finish(ctx);
 }
 
 // ================================================================ frames

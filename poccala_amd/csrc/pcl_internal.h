@@ -570,7 +570,16 @@ int pcl_launch_pack(pcl_ctx *ctx, const double *src, int inner, double *dst);
 extern "C" {   // defined inside pcl_api.hip's extern "C" block; hidden like every symbol the public header does not declare
 int pcl_device_dim(int D);                                   // the padded feature dimension the kernels have an instance for (-1: D > 64)
 void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D);   // device-built (F, pcl_device_dim(D)) matrices become the current frames
+// pcl_model_upload in two halves, for a model that is MADE on the device (bootstrap.hip): pcl_model_alloc drops the old model, allocates the
+// float64 master copy (mean64 / var64 / w64, padded device layout, contents undefined) and every derived buffer, and sets the shape fields;
+// the caller fills the master copy on ctx->stream; pcl_model_finish derives the layouts, conditioning and split lists and makes the
+// statistics block -- exactly what pcl_model_upload runs after its copy.
+int pcl_model_alloc(pcl_ctx *ctx, int J, int M, int D, int flags, const char *who);
+int pcl_model_finish(pcl_ctx *ctx);
 }
+// pcl_seg_create from an owner array that is already on the device (F = ctx->F entries, every one -1 or in [0, J): the CALLER guarantees it,
+// nothing is validated here); the array is only read and stays the caller's.  gmm_segment.hip.
+int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_frame_state, pcl_seg **out);
 // pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (hipMalloc: the caller hipFree's it), complete on
 // return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.
 int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime,

@@ -265,6 +265,82 @@ class Engine(object):
         state that owns frame t, or -1 (unused).  J defaults to the loaded model's."""
         return Segments(self, frame_state, self.J if J is None else J)
 
+    # ------------------------------------------------------------------ starting from nothing: flat start, uniform segmentation
+    def _utt_ranges(self, T, frame_begin):
+        T = as_c(T, np.int32).reshape(-1)
+        fb = None if frame_begin is None else as_c(frame_begin, np.int64).reshape(-1)
+        if T.size == 0 or (fb is not None and fb.shape != T.shape):
+            raise ValueError('T and frame_begin must be equal-length, non-empty')
+        return T, fb
+
+    def frames_moments(self, T, frame_begin=None, n_utts=None, step=1):
+        """Global mean and variance of data[::step] of the first n_utts utterances of the resident frames (default: all), as
+        AcousticModel.__flat_start takes them (AcousticModel.py:492-501): (mean (D,), var (D,), n_rows).  The variance is about that
+        mean, divided by n, floored at 1e-4.  frame_begin=None: the utterances lie back to back from row 0."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        mean, var = np.empty(max(self.FD, 1)), np.empty(max(self.FD, 1))
+        n = np.zeros(1, dtype=np.int64)
+        self._check(self._lib.pcl_frames_moments(self._ctx, T.size, ptr(T), ptr(fb), int(T.size if n_utts is None else n_utts), int(step),
+                                                 ptr(mean), ptr(var), ptr(n)))
+        return mean[:self.FD], var[:self.FD], int(n[0])
+
+    def flat_start_model(self, J, M, mean, var, coeff=None, logdet=False):
+        """The flat-start model made on the device (AcousticModel.py:504-516): every mixture m of every one of the J states gets
+        mean + coeff[m] * var, var and weight 1 / M; coeff (M,) or None (differentiation=False).  Afterwards the engine holds the
+        model exactly as load_model of those (J, M, D) arrays would have left it."""
+        mean, var = as_c(mean, np.float64).reshape(-1), as_c(var, np.float64).reshape(-1)
+        if mean.shape != var.shape:
+            raise ValueError('mean %s and var %s must be (D,)' % (mean.shape, var.shape))
+        c = None
+        if coeff is not None:
+            c = as_c(coeff, np.float64).reshape(-1)
+            if c.shape != (int(M),):
+                raise ValueError('coeff must hold M = %d values, got %s' % (M, c.shape))
+        self._check(self._lib.pcl_model_flat_start(self._ctx, int(J), int(M), mean.size, ptr(mean), ptr(var), ptr(c), 1 if logdet else 0))
+        self.J, self.M, self.D = int(J), int(M), int(mean.size)
+        self._model_key = None
+
+    def flat_start(self, T, frame_begin, J, M, n_utts=None, step=1, coeff=None, logdet=False):
+        """frames_moments + flat_start_model in one call, the moments going from the frames into the model on the device.
+        Returns (mean, var, n_rows)."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        c = None
+        if coeff is not None:
+            c = as_c(coeff, np.float64).reshape(-1)
+            if c.shape != (int(M),):
+                raise ValueError('coeff must hold M = %d values, got %s' % (M, c.shape))
+        mean, var = np.empty(max(self.FD, 1)), np.empty(max(self.FD, 1))
+        n = np.zeros(1, dtype=np.int64)
+        self._check(self._lib.pcl_flat_start(self._ctx, T.size, ptr(T), ptr(fb), int(T.size if n_utts is None else n_utts), int(step), int(J),
+                                             int(M), ptr(c), 1 if logdet else 0, ptr(mean), ptr(var), ptr(n)))
+        self.J, self.M, self.D = int(J), int(M), self.FD
+        self._model_key = None
+        return mean[:self.FD], var[:self.FD], int(n[0])
+
+    def uniform_segments(self, unit_ids, T, frame_begin, gmm_num, J, want_map=False):
+        """Uniform segmentation of labelled utterances (multi_process_data(init=True): __eq_segment mode 'e', then __get_gmmdata,
+        AcousticModel.py:605-644): every utterance is cut into equal chunks, one per label unit, every chunk into gmm_num slices.
+        unit_ids as label_batch takes them; J = n_units * gmm_num.  Needs neither a model nor a unit inventory.  Returns the
+        Segments of that map, built without it leaving the device (want_map=True: (Segments, frame_state (F,) int32))."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        if isinstance(unit_ids, np.ndarray) and unit_ids.ndim == 2:
+            lens = np.full(unit_ids.shape[0], unit_ids.shape[1], dtype=np.int32)
+            flat = np.ascontiguousarray(unit_ids, dtype=np.int32).reshape(-1)
+        else:
+            lens = np.array([len(l) for l in unit_ids], dtype=np.int32)
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).reshape(-1) for l in unit_ids] + [np.zeros(0, np.int32)]),
+                                        dtype=np.int32)
+        if lens.shape != T.shape:
+            raise ValueError('labels and T must be equal-length')
+        if flat.size == 0:
+            flat = np.zeros(1, dtype=np.int32)
+        state = np.empty(max(self.F, 1), dtype=np.int32) if want_map else None
+        h = C.c_void_p()
+        self._check(self._lib.pcl_uniform_segments(self._ctx, T.size, ptr(lens), ptr(flat), ptr(T), ptr(fb), int(gmm_num), int(J), ptr(state),
+                                                   C.byref(h)))
+        seg = Segments(self, None, int(J), handle=h)
+        return (seg, state[:self.F]) if want_map else seg
+
     # ------------------------------------------------------------------ unit inventory, label-built batches
     def load_units(self, unit_trans):
         """unit_trans: (n_units, S, S) transition matrices (LHMM.transmat of every unit HMM, AcousticModel.py:174-181).
@@ -763,13 +839,16 @@ class Segments(object):
     `kmeans` then `em` make the engine's model from them, all states at once.  States with fewer frames than mixtures are left
     untouched and reported as -1, as the reference skips them (:549-551)."""
 
-    def __init__(self, engine, frame_state, J):
+    def __init__(self, engine, frame_state, J, handle=None):
         self.eng = engine
         self._lib = engine._lib
-        self._s = C.c_void_p()
-        st = as_c(frame_state, np.int32).reshape(-1)
         self.J = int(J)
-        engine._check(self._lib.pcl_seg_create(engine._ctx, st.shape[0], self.J, ptr(st), C.byref(self._s)))
+        if handle is not None:                        # a pcl_seg the library built itself (Engine.uniform_segments)
+            self._s = handle
+        else:
+            self._s = C.c_void_p()
+            st = as_c(frame_state, np.int32).reshape(-1)
+            engine._check(self._lib.pcl_seg_create(engine._ctx, st.shape[0], self.J, ptr(st), C.byref(self._s)))
         engine._segments.add(self)
         self.counts = self._get('counts', self.J)
         self.K = 0
