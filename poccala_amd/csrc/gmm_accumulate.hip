@@ -24,10 +24,6 @@
 //      in chunks and read back as broadcasts.  Per (frame, mixture, dim): y = x s + c; q += y^2
 //      (2 FMA), then z = g y; S1 += z; S2 += z y (3 ops).  Centred, scaled moments avoid the
 //      cancellation of raw moments: (o - mu) = y / s, (o - mu)^2 = y^2 / s^2.
-#include <stdlib.h>
-
-#include <algorithm>
-
 #include "pcl_internal.h"
 
 namespace {
@@ -610,130 +606,89 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
 }
 
 template <int D, typename real, int MINW>
-void launch_acc_t(pcl_ctx *ctx, pcl_batch *b, const real *frames, const real *params, const real *means, int first, int count,
+void launch_acc_t(pcl_ctx *ctx, const real *frames, const real *params, const real *means, int first, int count,
                   const int *tile_off = nullptr, const unsigned int *tile_mask = nullptr, const int *state_flag = nullptr) {
     if (count == 0) return;
+    const AccScratch &a = ctx->acc;
     dim3 grid((ctx->Mpad + WG - 1) / WG, (unsigned)count);
     if (tile_mask && sizeof(real) == 4) {                              // the masked fix-up: rows from the master copy
         const AccMaster mm{ctx->mean64, ctx->var64, ctx->w64, ctx->M, ctx->Dhost, ctx->model_flags, ctx->d_bad, nullptr, nullptr};
         hipLaunchKernelGGL((gmm_accumulate_kernel<D, float, MINW, true>), grid, dim3(WG), 0, ctx->stream, (const float *)frames, (const float *)nullptr,
-                           (const float *)nullptr, ctx->Mpad, b->ctx->acc.d_work_states + first, b->ctx->acc.d_seg_lo + first, b->ctx->acc.d_seg_hi + first, b->ctx->acc.acc_off, b->ctx->acc.acc_list, 100.0,
+                           (const float *)nullptr, ctx->Mpad, a.work_states.p + first, a.seg_lo.p + first, a.seg_hi.p + first, a.off.p, a.list.p, 100.0,
                            ctx->st_acc, ctx->st_alpha, ctx->st_mean, ctx->st_cov, tile_off, tile_mask, state_flag, mm);
         return;
     }
     hipLaunchKernelGGL((gmm_accumulate_kernel<D, real, MINW>), grid, dim3(WG), 0, ctx->stream, frames, params, means,
-                       ctx->Mpad, b->ctx->acc.d_work_states + first, b->ctx->acc.d_seg_lo + first, b->ctx->acc.d_seg_hi + first, b->ctx->acc.acc_off, b->ctx->acc.acc_list, 100.0, ctx->st_acc,
+                       ctx->Mpad, a.work_states.p + first, a.seg_lo.p + first, a.seg_hi.p + first, a.off.p, a.list.p, 100.0, ctx->st_acc,
                        ctx->st_alpha, ctx->st_mean, ctx->st_cov, tile_off, tile_mask, state_flag, AccMaster{});
 }
 
 // split states among [first, first + count) of the accumulate order (split_flag marks them): their off-pipe mixtures over all their frames
 template <int D, int MINW>
-void launch_acc_subset_t(pcl_ctx *ctx, pcl_batch *b, int first, int count, const int *split_flag) {
+void launch_acc_subset_t(pcl_ctx *ctx, pcl_batch *b, int first, int count) {
+    const AccScratch &a = ctx->acc;
     int most = 1;                                                         // slices for the state with the most off-pipe mixtures in this range
     for (int k = first; k < first + count; ++k)
         if (b->acc_split[k]) most = std::max(most, ctx->nbad[b->acc_ws[k]]);
     dim3 grid((unsigned)count, (most + WG - 1) / WG);                     // (states, slices): see the kernel
     const AccMaster mm{ctx->mean64, ctx->var64, ctx->w64, ctx->M, ctx->Dhost, ctx->model_flags, ctx->d_bad, ctx->d_bad_idx, ctx->d_nbad};
     hipLaunchKernelGGL((gmm_accumulate_kernel<D, float, MINW, true>), grid, dim3(WG), 0, ctx->stream, ctx->frames32, (const float *)nullptr,
-                       (const float *)nullptr, ctx->Mpad, b->ctx->acc.d_work_states + first, b->ctx->acc.d_seg_lo + first, b->ctx->acc.d_seg_hi + first, b->ctx->acc.acc_off, b->ctx->acc.acc_list, 100.0,
-                       ctx->st_acc, ctx->st_alpha, ctx->st_mean, ctx->st_cov, (const int *)nullptr, (const unsigned int *)nullptr, split_flag + first, mm);
+                       (const float *)nullptr, ctx->Mpad, a.work_states.p + first, a.seg_lo.p + first, a.seg_hi.p + first, a.off.p, a.list.p, 100.0,
+                       ctx->st_acc, ctx->st_alpha, ctx->st_mean, ctx->st_cov, (const int *)nullptr, (const unsigned int *)nullptr, a.split_flag.p + first, mm);
 }
-void launch_acc_subset(pcl_ctx *ctx, pcl_batch *b, int first, int count, const int *split_flag) {
+void launch_acc_subset(pcl_ctx *ctx, pcl_batch *b, int first, int count) {
     if (count == 0) return;
     switch (ctx->D) {
-        case 13: launch_acc_subset_t<13, 2>(ctx, b, first, count, split_flag); break;
-        case 26: launch_acc_subset_t<26, 2>(ctx, b, first, count, split_flag); break;
-        case 39: launch_acc_subset_t<39, 2>(ctx, b, first, count, split_flag); break;
-        case 47: launch_acc_subset_t<47, 2>(ctx, b, first, count, split_flag); break;
+#define CASE(DD) case DD: launch_acc_subset_t<DD, 2>(ctx, b, first, count); break;
+        PCL_MFMA_DIMS(CASE)
+#undef CASE
         default: break;
     }
 }
 
-// f32, states [first, first + count) of the accumulate order (optionally only the frames a tile mask marks)
-void launch_acc_f32(pcl_ctx *ctx, pcl_batch *b, int first, int count, const int *tile_off = nullptr, const unsigned int *tile_mask = nullptr,
+// the dimensions the direct-form kernel has an instance for
+#define ACC_DIRECT_DIMS(X) X(13) X(26) X(39) X(47) X(48) X(64)
+// f32, states [first, first + count) of the accumulate order (optionally only the frames a tile mask marks); false: no instance for this D
+bool launch_acc_f32(pcl_ctx *ctx, int first, int count, const int *tile_off = nullptr, const unsigned int *tile_mask = nullptr,
                     const int *state_flag = nullptr) {
-    switch (ctx->D) {
-#define CASE32(DD) case DD: launch_acc_t<DD, float, 2>(ctx, b, ctx->frames32, ctx->params32, ctx->mean32, first, count, tile_off, tile_mask, state_flag); break;
-        CASE32(13) CASE32(26) CASE32(39) CASE32(47)
+    switch (ctx->D) {                                                  // (launch bounds: two workgroups per CU up to D = 47, one above)
+#define CASE32(DD) case DD: launch_acc_t<DD, float, (DD < 48 ? 2 : 1)>(ctx, ctx->frames32, ctx->params32, ctx->mean32, first, count, tile_off, tile_mask, state_flag); break;
+        ACC_DIRECT_DIMS(CASE32)
 #undef CASE32
-#define CASE32W(DD) case DD: launch_acc_t<DD, float, 1>(ctx, b, ctx->frames32, ctx->params32, ctx->mean32, first, count, tile_off, tile_mask, state_flag); break;
-        CASE32W(48) CASE32W(64)
-#undef CASE32W
-        default: break;
+        default: return false;
     }
+    return true;
 }
 
-bool device_dim_supported(int D) { return D == 13 || D == 26 || D == 39 || D == 47 || D == 48 || D == 64; }
+// ---------------------------------------------------------------- the steps of a pass, in the order they happen
+// What they hand on: the accumulate order of the batch's states (b->acc_ws / acc_lo / acc_hi / acc_split) has the n_good states of the matrix
+// pipe in front (n_split of them split states) and the n_bad whole states of the direct form behind (a direct-form pass has no "bad").
+struct AccPass {
+    int n_good = 0, n_split = 0, n_bad = 0;
+    std::vector<int> gfirst, gcount, gtiles;   // f16 route: the state groups (first, states, tiles) whose tile images fit one buffer set
+};
 
-}  // namespace
-
-void pcl_accumulate_release(pcl_ctx *ctx) {
-    struct { pcl_ctx *ctx; } bb{ctx}, *b = &bb;              // (the body below names the members through b->ctx->acc)
-    dev_free(b->ctx->acc.acc_cnt);
-    dev_free(b->ctx->acc.acc_off);
-    dev_free(b->ctx->acc.acc_list);
-    dev_free(b->ctx->acc.d_work_states);
-    dev_free(b->ctx->acc.d_seg_lo);
-    dev_free(b->ctx->acc.d_seg_hi);
-    dev_free(b->ctx->acc.d_split_flag);
-    for (int k = 0; k < 2; ++k) {
-        dev_free(b->ctx->acc.acc16_images[k]);
-        dev_free(b->ctx->acc.acc16_tile_off[k]);
-        dev_free(b->ctx->acc.acc16_tile_mask[k]);
-        dev_free(b->ctx->acc.acc16_state_flag[k]);
-        if (b->ctx->acc.acc16_ev_prod[k]) (void)hipEventDestroy(b->ctx->acc.acc16_ev_prod[k]);
-        if (b->ctx->acc.acc16_ev_cons[k]) (void)hipEventDestroy(b->ctx->acc.acc16_ev_cons[k]);
-        b->ctx->acc.acc16_images[k] = nullptr; b->ctx->acc.acc16_tile_off[k] = nullptr; b->ctx->acc.acc16_tile_mask[k] = nullptr; b->ctx->acc.acc16_state_flag[k] = nullptr;
-        b->ctx->acc.acc16_ev_prod[k] = b->ctx->acc.acc16_ev_cons[k] = nullptr;
-    }
-    if (b->ctx->acc.acc16_ev_start) (void)hipEventDestroy(b->ctx->acc.acc16_ev_start);
-    b->ctx->acc.acc16_ev_start = nullptr;
-    b->ctx->acc.acc16_cap_tiles = b->ctx->acc.acc16_cap_states = 0;
-    b->ctx->acc.acc_cnt = nullptr; b->ctx->acc.acc_off = nullptr; b->ctx->acc.acc_list = nullptr;
-    b->ctx->acc.d_work_states = b->ctx->acc.d_seg_lo = b->ctx->acc.d_seg_hi = b->ctx->acc.d_split_flag = nullptr;
-    b->ctx->acc.acc_cap_list = b->ctx->acc.acc_cap_segs = b->ctx->acc.acc_cap_states = 0;
-}
-
-int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision) {
-    if (b->n_segs == 0) return PCL_OK;
-    size_t cap = 0;
-    for (size_t k = 0; k < b->work_states.size(); ++k) {
+// room for this batch: every list at its worst case (every frame of every state survives)
+int reserve_scratch(pcl_ctx *ctx, const pcl_batch *b) {
+    AccScratch &a = ctx->acc;
+    const size_t nseg = (size_t)b->n_segs + 1, ns = b->work_states.size();
+    size_t frames = 0;
+    for (size_t k = 0; k < ns; ++k) {
         const ScoreSeg &last = b->segs[b->state_seg_hi[k] - 1];
-        cap += (size_t)last.vstart + last.len;
+        frames += (size_t)last.vstart + last.len;
     }
-    if (b->ctx->acc.acc_cap_segs < (size_t)b->n_segs + 1) {
-        dev_free(b->ctx->acc.acc_cnt);
-        dev_free(b->ctx->acc.acc_off);
-        b->ctx->acc.acc_cnt = nullptr; b->ctx->acc.acc_off = nullptr;
-        TRY(dev_alloc(ctx, &b->ctx->acc.acc_cnt, (size_t)(((size_t)b->n_segs + 1))));
-        TRY(dev_alloc(ctx, &b->ctx->acc.acc_off, (size_t)b->n_segs + 1));
-        b->ctx->acc.acc_cap_segs = (size_t)b->n_segs + 1;
-    }
-    if (b->ctx->acc.acc_cap_list < cap) {
-        dev_free(b->ctx->acc.acc_list);
-        b->ctx->acc.acc_list = nullptr;
-        TRY(dev_alloc(ctx, &b->ctx->acc.acc_list, (size_t)(cap)));
-        b->ctx->acc.acc_cap_list = cap;
-    }
+    TRY(a.cnt.reserve(ctx, nseg));
+    TRY(a.off.reserve(ctx, nseg));
+    TRY(a.list.reserve(ctx, frames));
+    for (GrowBuf<int> *v : {&a.split_flag, &a.work_states, &a.seg_lo, &a.seg_hi}) TRY(v->reserve(ctx, ns));
+    return PCL_OK;
+}
+
+// MFMA mode: well-conditioned states first (MFMA kernel), then the ill-conditioned ones (direct-form VALU kernel)
+int order_states(pcl_ctx *ctx, pcl_batch *b, bool mfma, AccPass &p) {
+    AccScratch &a = ctx->acc;
     const size_t ns = b->work_states.size();
-    if (b->ctx->acc.acc_cap_states < ns) {
-        dev_free(b->ctx->acc.d_work_states);
-        dev_free(b->ctx->acc.d_seg_lo);
-        dev_free(b->ctx->acc.d_seg_hi);
-        dev_free(b->ctx->acc.d_split_flag);
-        b->ctx->acc.d_work_states = b->ctx->acc.d_seg_lo = b->ctx->acc.d_seg_hi = b->ctx->acc.d_split_flag = nullptr;
-        TRY(dev_alloc(ctx, &b->ctx->acc.d_split_flag, (size_t)(ns)));
-        TRY(dev_alloc(ctx, &b->ctx->acc.d_work_states, (size_t)(ns)));
-        TRY(dev_alloc(ctx, &b->ctx->acc.d_seg_lo, (size_t)(ns)));
-        TRY(dev_alloc(ctx, &b->ctx->acc.d_seg_hi, (size_t)(ns)));
-        b->ctx->acc.acc_cap_states = ns;
-    }
-    // MFMA mode: well-conditioned states first (MFMA kernel), then the ill-conditioned ones (direct-form VALU kernel)
-    const int D = ctx->D;
-    const bool mfma = precision == PCL_F32 && ctx->score_variant >= 3 && (D == 47 || D == 39 || D == 26 || D == 13);
-    b->acc_ws.clear(); b->acc_lo.clear(); b->acc_hi.clear();
-    int n_good = 0, n_split = 0;
-    b->acc_split.clear();
+    b->acc_ws.clear(); b->acc_lo.clear(); b->acc_hi.clear(); b->acc_split.clear();
     for (int pass = 0; pass < 2; ++pass)
         for (size_t k = 0; k < ns; ++k) {
             const bool bad = mfma && pcl_state_acc_uses_valu(ctx, b->work_states[k]);
@@ -743,166 +698,190 @@ int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision) {
             b->acc_hi.push_back(b->state_seg_hi[k]);
             const int sp = (mfma && pass == 0 && pcl_state_acc_is_split(ctx, b->work_states[k])) ? 1 : 0;
             b->acc_split.push_back(sp);
-            n_split += sp;
-            n_good += pass == 0;
+            p.n_split += sp;
+            p.n_good += pass == 0;
         }
-    const int n_bad = (int)ns - n_good;
+    p.n_bad = (int)ns - p.n_good;
     // the staging vectors live in the batch: the copies below are asynchronous from pageable memory only until the
     // call returns on this runtime, but keeping them alive costs nothing
-    HIPCHK(ctx, hipMemcpyAsync(b->ctx->acc.d_work_states, b->acc_ws.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->ctx->acc.d_seg_lo, b->acc_lo.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(b->ctx->acc.d_seg_hi, b->acc_hi.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (n_split) HIPCHK(ctx, hipMemcpyAsync(b->ctx->acc.d_split_flag, b->acc_split.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.work_states.p, b->acc_ws.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.seg_lo.p, b->acc_lo.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(a.seg_hi.p, b->acc_hi.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (p.n_split) HIPCHK(ctx, hipMemcpyAsync(a.split_flag.p, b->acc_split.data(), ns * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    return PCL_OK;
+}
 
-    // a frame survives unless every gamma_t(j,m) <= gamma_t(j) underflows to exactly 0 in the
-    // kernel's arithmetic (f32: 2^-149, f64: 2^-1074)
+// count -> scan -> ordered fill.  A frame survives unless every gamma_t(j,m) <= gamma_t(j) underflows to exactly 0 in the
+// kernel's arithmetic (f32: 2^-149, f64: 2^-1074)
+void build_active_lists(pcl_ctx *ctx, pcl_batch *b, int precision) {
+    AccScratch &a = ctx->acc;
     const double LN2 = 0.693147180559945309417232121458;
     const double thr = std::max(precision == PCL_F64 ? -1076.0 : -150.0, ctx->acc_prune_log2) * LN2;
-    pcl_timer_begin(ctx, "accumulate");
     const int wpb = 4;
     dim3 gseg((b->n_segs + wpb - 1) / wpb);
     static const bool rows_on = !(getenv("PCL_ACC_ROWS") && atoi(getenv("PCL_ACC_ROWS")) == 0);      // 0: a wave per segment (rounds 1-3), A/B
     const bool by_rows = rows_on && b->U <= 65535 && b->d_seg_of_row;                                // (grid.y = utterances)
     const dim3 grows((b->max_N + 8 * ROWS_WPB - 1) / (8 * ROWS_WPB), (unsigned)b->U);
-    if (by_rows) hipLaunchKernelGGL(acc_count_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, thr, b->ctx->acc.acc_cnt);
-    else hipLaunchKernelGGL(acc_count_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, thr, b->ctx->acc.acc_cnt);
-    hipLaunchKernelGGL(acc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, b->ctx->acc.acc_cnt, b->n_segs, b->ctx->acc.acc_off);
-    if (by_rows) hipLaunchKernelGGL(acc_fill_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, b->Bt, thr,
-                                    b->ctx->acc.acc_off, b->ctx->acc.acc_list);
-    else hipLaunchKernelGGL(acc_fill_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, b->Bt, thr,
-                            b->ctx->acc.acc_off, b->ctx->acc.acc_list);
-    if (mfma && n_good > 0 && ctx->score_variant == 7) {
-        // producer / consumer on the f16 + bf16 matrix pipes (gmm_accumulate_f16.hip), in groups of states whose tile
-        // images fit the image buffer (worst case: every frame of the state survives)
-        const size_t budget = (size_t)(getenv("PCL_ACC_IMAGE_MB") ? std::max(1L, atol(getenv("PCL_ACC_IMAGE_MB"))) : 2048) << 20;   // per buffer set, two sets; read per call (tests lower it to force many groups)
-        const size_t ib = pcl_acc16_image_bytes(D);
-        // group by the ACTUAL tile counts: the scan result comes back (n_segs + 1 offsets, one short copy behind the scan
-        // kernel) -- on peaked posteriors a tenth of the frames survive, and sizing the groups for the worst case made
-        // eight half-empty launches, each with its parameter prologue and statistics flush, out of one
-        std::vector<long long> off_h((size_t)b->n_segs + 1);
-        HIPCHK(ctx, hipMemcpyAsync(off_h.data(), b->ctx->acc.acc_off, off_h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<int> wtiles(n_good);
-        size_t worst = 0, biggest = 0;
-        for (int k = 0; k < n_good; ++k) {
-            wtiles[k] = (int)((off_h[b->acc_hi[k]] - off_h[b->acc_lo[k]] + 31) / 32);
-            worst += wtiles[k];
-            biggest = std::max(biggest, (size_t)wtiles[k]);
+    if (by_rows) hipLaunchKernelGGL(acc_count_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, thr, a.cnt.p);
+    else hipLaunchKernelGGL(acc_count_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, thr, a.cnt.p);
+    hipLaunchKernelGGL(acc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, a.cnt.p, b->n_segs, a.off.p);
+    if (by_rows) hipLaunchKernelGGL(acc_fill_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, b->Bt, thr, a.off.p, a.list.p);
+    else hipLaunchKernelGGL(acc_fill_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, b->Bt, thr, a.off.p, a.list.p);
+}
+
+// f16 route, 1: the two image buffer sets, and the groups of states whose tile images fit one.  Grouped by the ACTUAL tile counts: the scan
+// result comes back (n_segs + 1 offsets, one short copy behind the scan kernel) -- on peaked posteriors a tenth of the frames survive, and
+// sizing the groups for the worst case made eight half-empty launches, each with its parameter prologue and statistics flush, out of one
+int size_groups(pcl_ctx *ctx, const pcl_batch *b, AccPass &p) {
+    AccScratch &a = ctx->acc;
+    std::vector<long long> off_h((size_t)b->n_segs + 1);
+    HIPCHK(ctx, hipMemcpyAsync(off_h.data(), a.off.p, off_h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int> wtiles(p.n_good);
+    size_t worst = 0, biggest = 0;
+    for (int k = 0; k < p.n_good; ++k) {
+        wtiles[k] = (int)((off_h[b->acc_hi[k]] - off_h[b->acc_lo[k]] + 31) / 32);
+        worst += wtiles[k];
+        biggest = std::max(biggest, (size_t)wtiles[k]);
+    }
+    if (getenv("PCL_DEBUG_ACC")) {                       // distribution of the active-frame lists over the states (diagnostic)
+        std::vector<int> sorted(wtiles);
+        std::sort(sorted.begin(), sorted.end());
+        fprintf(stderr, "[pcl] accumulate: %d states, active 32-frame tiles per state: min %d median %d p90 %d p99 %d max %d, total %zu\n", p.n_good,
+                sorted.front(), sorted[sorted.size() / 2], sorted[sorted.size() * 9 / 10], sorted[sorted.size() * 99 / 100], sorted.back(), worst);
+    }
+    const size_t budget = (size_t)(getenv("PCL_ACC_IMAGE_MB") ? std::max(1L, atol(getenv("PCL_ACC_IMAGE_MB"))) : 2048) << 20;   // per buffer set, two sets; read per call (tests lower it to force many groups)
+    const size_t ib = pcl_acc16_image_bytes(ctx->D), by_budget = std::max<size_t>(budget / ib, 1), have = a.tile_mask[0].cap;   // (have: a mask word per tile)
+    size_t cap_tiles = std::max(biggest, std::min(worst, by_budget));
+    if (have >= cap_tiles) cap_tiles = have;                                                                   // never shrink: the counts move from call to call
+    else cap_tiles = std::max(cap_tiles, std::min(cap_tiles + cap_tiles / 4, std::max(by_budget, biggest)));   // grow with headroom
+    for (int k = 0; k < 2; ++k) {
+        TRY(a.images[k].reserve(ctx, cap_tiles * ib));
+        TRY(a.tile_mask[k].reserve(ctx, cap_tiles));
+        TRY(a.tile_off[k].reserve(ctx, (size_t)p.n_good + 1));
+        TRY(a.state_flag[k].reserve(ctx, (size_t)p.n_good + 1));
+    }
+    // the FIRST group is small: its producer is the only one nothing runs beside (1.25 ms of a flat pass when the groups are equal)
+    static const int first_div = getenv("PCL_ACC_FIRST_DIV") ? atoi(getenv("PCL_ACC_FIRST_DIV")) : 12;
+    for (int first = 0; first < p.n_good;) {
+        size_t t = 0;
+        int last = first;
+        const size_t cap_g = (first == 0 && first_div > 1) ? std::max(biggest, std::min(cap_tiles, worst / (size_t)first_div)) : cap_tiles;
+        while (last < p.n_good && t + wtiles[last] <= cap_g) t += wtiles[last++];
+        p.gfirst.push_back(first); p.gcount.push_back(last - first); p.gtiles.push_back((int)t);
+        first = last;
+    }
+    return PCL_OK;
+}
+
+// the producer of group g into buffer set g & 1, on stream ps
+int produce_group(pcl_ctx *ctx, const AccPass &p, int g, bool overlap, hipStream_t ps) {
+    const int buf = g & 1;
+    if (overlap && g >= 2) HIPCHK(ctx, hipStreamWaitEvent(ps, ctx->acc.ev_cons[buf], 0));      // the buffer set is free again
+    TRY(pcl_launch_acc16_produce(ctx, p.gfirst[g], p.gcount[g], p.gtiles[g], buf, ps));
+    if (overlap) HIPCHK(ctx, hipEventRecord(ctx->acc.ev_prod[buf], ps));
+    return PCL_OK;
+}
+
+// f16 route, 2: producer / consumer on the f16 + bf16 matrix pipes (gmm_accumulate_f16.hip).  The producer of group g + 1 runs on the
+// auxiliary stream beside the consumer of group g (it is HBM-write bound, the consumer matrix-pipe bound, and a consumer workgroup
+// leaves registers for one small wave per SIMD)
+int run_groups(pcl_ctx *ctx, pcl_batch *b, const AccPass &p) {
+    AccScratch &a = ctx->acc;
+    if (!a.ev_start)                                                 // (ev_start last: it stands for the whole set)
+        for (hipEvent_t *e : {&a.ev_prod[0], &a.ev_cons[0], &a.ev_prod[1], &a.ev_cons[1], &a.ev_start}) HIPCHK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    static const bool overlap = !(getenv("PCL_ACC_OVERLAP") && atoi(getenv("PCL_ACC_OVERLAP")) == 0);
+    hipStream_t ps = overlap ? ctx->stream_aux : ctx->stream;
+    HIPCHK(ctx, hipEventRecord(a.ev_start, ctx->stream));            // the active-frame lists are complete
+    if (overlap) HIPCHK(ctx, hipStreamWaitEvent(ps, a.ev_start, 0));
+    const int G = (int)p.gfirst.size();
+    bool ascending = true;
+    for (int k = 1; k < p.n_good; ++k) ascending = ascending && b->acc_ws[k - 1] < b->acc_ws[k];
+    if (G > 0) TRY(produce_group(ctx, p, 0, overlap, ps));
+    for (int g = 0; g < G; ++g) {
+        const int buf = g & 1, first = p.gfirst[g], count = p.gcount[g];
+        if (overlap && g + 1 < G) TRY(produce_group(ctx, p, g + 1, overlap, ps));
+        if (overlap) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, a.ev_prod[buf], 0));
+        pcl_timer_begin(ctx, "acc_consume");                                 // one entry per state group (timing mode only)
+        const int rc = pcl_launch_acc16_consume(ctx, first, count, buf, ctx->stats_fresh, ctx->stream);
+        pcl_timer_end(ctx, "acc_consume");
+        TRY(rc);
+        launch_acc_f32(ctx, first, count, a.tile_off[buf].p, a.tile_mask[buf].p, a.state_flag[buf].p);   // the frames the images left out
+        if (p.n_split) {                                                                              // the mixtures the pipe left out (split states)
+            pcl_timer_begin(ctx, "acc_subset");
+            launch_acc_subset(ctx, b, first, count);
+            pcl_timer_end(ctx, "acc_subset");
         }
-        if (getenv("PCL_DEBUG_ACC")) {                       // distribution of the active-frame lists over the states (diagnostic)
-            std::vector<int> sorted(wtiles);
-            std::sort(sorted.begin(), sorted.end());
-            if (!sorted.empty())
-                fprintf(stderr, "[pcl] accumulate: %d states, active 32-frame tiles per state: min %d median %d p90 %d p99 %d max %d, total %zu\n", n_good,
-                        sorted.front(), sorted[sorted.size() / 2], sorted[sorted.size() * 9 / 10], sorted[sorted.size() * 99 / 100], sorted.back(), worst);
-        }
-        const size_t by_budget = std::max<size_t>(budget / ib, 1);
-        size_t cap_tiles = std::max(biggest, std::min(worst, by_budget));
-        if (b->ctx->acc.acc16_cap_tiles >= cap_tiles) cap_tiles = b->ctx->acc.acc16_cap_tiles;                 // never shrink: the counts move from call to call
-        else cap_tiles = std::max(cap_tiles, std::min(cap_tiles + cap_tiles / 4, std::max(by_budget, biggest)));   // grow with headroom
-        if (b->ctx->acc.acc16_cap_tiles < cap_tiles) {
-            for (int k = 0; k < 2; ++k) {
-                dev_free(b->ctx->acc.acc16_images[k]);
-                dev_free(b->ctx->acc.acc16_tile_mask[k]);
-                b->ctx->acc.acc16_images[k] = nullptr; b->ctx->acc.acc16_tile_mask[k] = nullptr;
-                b->ctx->acc.acc16_images[k] = pcl_pool_alloc(ctx->device, cap_tiles * ib);
-                if (!b->ctx->acc.acc16_images[k]) PCL_FAIL(ctx, PCL_ERR_NOMEM, "device memory: %zu bytes of tile images", cap_tiles * ib);
-                TRY(dev_alloc(ctx, &b->ctx->acc.acc16_tile_mask[k], cap_tiles));
-            }
-            b->ctx->acc.acc16_cap_tiles = cap_tiles;
-        }
-        if (b->ctx->acc.acc16_cap_states < (size_t)n_good + 1) {
-            for (int k = 0; k < 2; ++k) {
-                dev_free(b->ctx->acc.acc16_tile_off[k]);
-                dev_free(b->ctx->acc.acc16_state_flag[k]);
-                b->ctx->acc.acc16_tile_off[k] = b->ctx->acc.acc16_state_flag[k] = nullptr;
-                TRY(dev_alloc(ctx, &b->ctx->acc.acc16_tile_off[k], (size_t)(((size_t)n_good + 1))));
-                TRY(dev_alloc(ctx, &b->ctx->acc.acc16_state_flag[k], (size_t)(((size_t)n_good + 1))));
-            }
-            b->ctx->acc.acc16_cap_states = (size_t)n_good + 1;
-        }
-        if (!b->ctx->acc.acc16_ev_start) {
-            HIPCHK(ctx, hipEventCreateWithFlags(&b->ctx->acc.acc16_ev_start, hipEventDisableTiming));
-            for (int k = 0; k < 2; ++k) {
-                HIPCHK(ctx, hipEventCreateWithFlags(&b->ctx->acc.acc16_ev_prod[k], hipEventDisableTiming));
-                HIPCHK(ctx, hipEventCreateWithFlags(&b->ctx->acc.acc16_ev_cons[k], hipEventDisableTiming));
-            }
-        }
-        // groups of states: (first, count, worst-case tiles)
-        // the FIRST group is small: its producer is the only one nothing runs beside (1.25 ms of a flat pass when the groups are equal)
-        static const int first_div = getenv("PCL_ACC_FIRST_DIV") ? atoi(getenv("PCL_ACC_FIRST_DIV")) : 12;
-        std::vector<int> gfirst, gcount, gtiles;
-        for (int first = 0; first < n_good;) {
-            size_t t = 0;
-            int last = first;
-            const size_t cap_g = (first == 0 && first_div > 1) ? std::max(biggest, std::min(cap_tiles, worst / (size_t)first_div)) : cap_tiles;
-            while (last < n_good && t + wtiles[last] <= cap_g) t += wtiles[last++];
-            gfirst.push_back(first); gcount.push_back(last - first); gtiles.push_back((int)t);
-            first = last;
-        }
-        // the producer of group g + 1 runs on the auxiliary stream beside the consumer of group g (it is HBM-write
-        // bound, the consumer matrix-pipe bound, and a consumer workgroup leaves registers for one small wave per SIMD)
-        static const bool overlap = !(getenv("PCL_ACC_OVERLAP") && atoi(getenv("PCL_ACC_OVERLAP")) == 0);
-        hipStream_t ps = overlap ? ctx->stream_aux : ctx->stream;
-        HIPCHK(ctx, hipEventRecord(b->ctx->acc.acc16_ev_start, ctx->stream));            // the active-frame lists are complete
-        if (overlap) HIPCHK(ctx, hipStreamWaitEvent(ps, b->ctx->acc.acc16_ev_start, 0));
-        const int G = (int)gfirst.size();
-        bool ascending = true;
-        for (int k = 1; k < n_good; ++k) ascending = ascending && b->acc_ws[k - 1] < b->acc_ws[k];
-        auto produce = [&](int g) -> int {
-            const int buf = g & 1;
-            if (overlap && g >= 2) HIPCHK(ctx, hipStreamWaitEvent(ps, b->ctx->acc.acc16_ev_cons[buf], 0));      // the buffer set is free again
-            const int rc = pcl_launch_acc16_produce(ctx, b, gfirst[g], gcount[g], gtiles[g], buf, ps);
-            if (rc != PCL_OK) return rc;
-            if (overlap) HIPCHK(ctx, hipEventRecord(b->ctx->acc.acc16_ev_prod[buf], ps));
-            return PCL_OK;
-        };
-        if (G > 0) { const int rc = produce(0); if (rc != PCL_OK) return rc; }
-        for (int g = 0; g < G; ++g) {
-            const int buf = g & 1;
-            if (overlap && g + 1 < G) { const int rc = produce(g + 1); if (rc != PCL_OK) return rc; }
-            if (overlap) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ctx->acc.acc16_ev_prod[buf], 0));
-            pcl_timer_begin(ctx, "acc_consume");                                 // one entry per state group (timing mode only)
-            int rc = pcl_launch_acc16_consume(ctx, b, gfirst[g], gcount[g], buf, ctx->stats_fresh, ctx->stream);
-            pcl_timer_end(ctx, "acc_consume");
-            if (rc != PCL_OK) return rc;
-            launch_acc_f32(ctx, b, gfirst[g], gcount[g], b->ctx->acc.acc16_tile_off[buf], b->ctx->acc.acc16_tile_mask[buf], b->ctx->acc.acc16_state_flag[buf]);   // the frames the images left out
-            if (n_split) {                                                                                    // the mixtures the pipe left out (split states)
-                pcl_timer_begin(ctx, "acc_subset");
-                launch_acc_subset(ctx, b, gfirst[g], gcount[g], b->ctx->acc.d_split_flag);
-                pcl_timer_end(ctx, "acc_subset");
-            }
-            if (overlap) HIPCHK(ctx, hipEventRecord(b->ctx->acc.acc16_ev_cons[buf], ctx->stream));
-            if (!overlap && g + 1 < G) { rc = produce(g + 1); if (rc != PCL_OK) return rc; }
-            // a pipelined exchange is open (pcl_batch_accumulate_exchange): every state below the next group's first one has its
-            // final statistics behind what is queued now -- its chunks may leave (states come in ascending order; states of the
-            // direct-form kernel, if any, are accumulated at the end, so nothing is final before that)
-            if (ctx->pipe_active && ascending && n_bad == 0) TRY(pcl_pipe_progress(ctx, g + 1 < G ? b->acc_ws[gfirst[g + 1]] : ctx->J));
-        }
-    } else if (mfma && n_good > 0) {
-        const int nmt = ctx->Mpad32 / 32, nslice = (nmt + AW - 1) / AW, ns = n_good;
-        const int nblocks = (nslice == 8) ? ((ns + 7) / 8) * 64 : ns * nslice;
-#define LAUNCH_MFMA(DD)                                                                                                   \
-    hipLaunchKernelGGL((gmm_accumulate_mfma_kernel<DD, PCL_ACC_T16 != 0>), dim3(nblocks), dim3(AW * 64), 0, ctx->stream, ctx->frames32, ctx->pm32, \
-                       ctx->centers32, ctx->mean64, ctx->M, ctx->Mpad, nmt, ns, b->ctx->acc.d_work_states, b->ctx->acc.d_seg_lo, b->ctx->acc.d_seg_hi,   \
-                       b->ctx->acc.acc_off, b->ctx->acc.acc_list, 100.0, ctx->st_acc, ctx->st_alpha, ctx->st_mean, ctx->st_cov)
-        if (D == 47) LAUNCH_MFMA(47); else if (D == 39) LAUNCH_MFMA(39); else if (D == 26) LAUNCH_MFMA(26); else LAUNCH_MFMA(13);
+        if (overlap) HIPCHK(ctx, hipEventRecord(a.ev_cons[buf], ctx->stream));
+        if (!overlap && g + 1 < G) TRY(produce_group(ctx, p, g + 1, overlap, ps));
+        // a pipelined exchange is open (pcl_batch_accumulate_exchange): every state below the next group's first one has its
+        // final statistics behind what is queued now -- its chunks may leave (states come in ascending order; states of the
+        // direct-form kernel, if any, are accumulated at the end, so nothing is final before that)
+        if (ctx->pipe_active && ascending && p.n_bad == 0) TRY(pcl_pipe_progress(ctx, g + 1 < G ? b->acc_ws[p.gfirst[g + 1]] : ctx->J));
+    }
+    return PCL_OK;
+}
+
+// the strict-f32 route: the matrix-pipe states in one launch of the f32-input MFMA kernel
+void run_mfma32(pcl_ctx *ctx, pcl_batch *b, const AccPass &p) {
+    const AccScratch &a = ctx->acc;
+    const int nmt = ctx->Mpad32 / 32, nslice = (nmt + AW - 1) / AW, ns = p.n_good;
+    const int nblocks = (nslice == 8) ? ((ns + 7) / 8) * 64 : ns * nslice;
+    switch (ctx->D) {
+#define LAUNCH_MFMA(DD)                                                                                                                                                  \
+    case DD: hipLaunchKernelGGL((gmm_accumulate_mfma_kernel<DD, PCL_ACC_T16 != 0>), dim3(nblocks), dim3(AW * 64), 0, ctx->stream, ctx->frames32, ctx->pm32,              \
+                                ctx->centers32, ctx->mean64, ctx->M, ctx->Mpad, nmt, ns, a.work_states.p, a.seg_lo.p, a.seg_hi.p, a.off.p, a.list.p, 100.0, ctx->st_acc, \
+                                ctx->st_alpha, ctx->st_mean, ctx->st_cov); break;
+        PCL_MFMA_DIMS(LAUNCH_MFMA)
 #undef LAUNCH_MFMA
-        if (n_split) launch_acc_subset(ctx, b, 0, n_good, b->ctx->acc.d_split_flag);
+        default: break;
     }
+    if (p.n_split) launch_acc_subset(ctx, b, 0, p.n_good);
+}
+
+// whole states in direct form: [first, first + count) of the accumulate order
+int run_direct(pcl_ctx *ctx, int precision, int first, int count) {
     if (precision == PCL_F32) {
-        const int first = mfma ? n_good : 0, count = mfma ? n_bad : (int)ns;
         if (count > 0) TRY(pcl_ensure_layouts(ctx, PCL_LAYOUT_P32));   // whole states on the direct-form kernel: its layouts, derived on first use
-        if (device_dim_supported(D)) launch_acc_f32(ctx, b, first, count);
-        else PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f32 accumulate kernel for padded D=%d", D);
-    } else {
-        switch (D) {
-#define CASE64(DD) case DD: launch_acc_t<DD, double, 1>(ctx, b, ctx->frames64, ctx->params64, ctx->mean64, 0, (int)ns); break;
-            CASE64(13) CASE64(26) CASE64(39) CASE64(47) CASE64(48) CASE64(64)
-#undef CASE64
-            default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f64 accumulate kernel for padded D=%d", D);
-        }
+        if (!launch_acc_f32(ctx, first, count)) PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f32 accumulate kernel for padded D=%d", ctx->D);
+        return PCL_OK;
     }
+    switch (ctx->D) {
+#define CASE64(DD) case DD: launch_acc_t<DD, double, 1>(ctx, ctx->frames64, ctx->params64, ctx->mean64, first, count); break;
+        ACC_DIRECT_DIMS(CASE64)
+#undef CASE64
+        default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f64 accumulate kernel for padded D=%d", ctx->D);
+    }
+    return PCL_OK;
+}
+
+}  // namespace
+
+void pcl_accumulate_release(pcl_ctx *ctx) {
+    AccScratch &a = ctx->acc;
+    a.cnt.release(); a.off.release(); a.list.release();
+    a.work_states.release(); a.seg_lo.release(); a.seg_hi.release(); a.split_flag.release();
+    for (int k = 0; k < 2; ++k) { a.images[k].release(); a.tile_off[k].release(); a.tile_mask[k].release(); a.state_flag[k].release(); }
+    for (hipEvent_t *e : {&a.ev_prod[0], &a.ev_cons[0], &a.ev_prod[1], &a.ev_cons[1], &a.ev_start}) {
+        if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+}
+
+int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision) {
+    if (b->n_segs == 0) return PCL_OK;
+    const int route = pcl_route(ctx, precision, ctx->D), ns = (int)b->work_states.size();
+    AccPass p;
+    TRY(reserve_scratch(ctx, b));
+    TRY(order_states(ctx, b, route != PCL_ROUTE_DIRECT, p));
+    pcl_timer_begin(ctx, "accumulate");
+    build_active_lists(ctx, b, precision);
+    if (route == PCL_ROUTE_SPLIT16 && p.n_good > 0) {
+        TRY(size_groups(ctx, b, p));
+        TRY(run_groups(ctx, b, p));
+    } else if (route == PCL_ROUTE_MFMA32 && p.n_good > 0) run_mfma32(ctx, b, p);
+    const int first = route != PCL_ROUTE_DIRECT ? p.n_good : 0;      // behind the matrix-pipe states; a direct-form pass: all of them
+    TRY(run_direct(ctx, precision, first, ns - first));
     pcl_timer_end(ctx, "accumulate");
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;

@@ -523,63 +523,54 @@ __global__ __launch_bounds__(AW * 64, AW == 8 ? 1 : 2) void acc16_consumer_kerne
 
 size_t pcl_acc16_image_bytes(int D) {
     switch (D) {
-        case 47: return (size_t)Img<47>::NB * 1024;
-        case 39: return (size_t)Img<39>::NB * 1024;
-        case 26: return (size_t)Img<26>::NB * 1024;
-        case 13: return (size_t)Img<13>::NB * 1024;
+#define CASE(DD) case DD: return (size_t)Img<DD>::NB * 1024;
+        PCL_MFMA_DIMS(CASE)
+#undef CASE
         default: return 0;
     }
 }
 
 // states [first, first + ns) of the batch's accumulate order, whose tiles fit one image buffer: the tile bookkeeping and
 // the producer (into buffer set `buf`) ...
-int pcl_launch_acc16_produce(pcl_ctx *ctx, pcl_batch *b, int first, int ns, int max_tiles, int buf, hipStream_t stream) {
+int pcl_launch_acc16_produce(pcl_ctx *ctx, int first, int ns, int max_tiles, int buf, hipStream_t stream) {
     if (ns == 0) return PCL_OK;
-    const int *ws = b->ctx->acc.d_work_states + first, *lo = b->ctx->acc.d_seg_lo + first, *hi = b->ctx->acc.d_seg_hi + first;
-    hipLaunchKernelGGL(acc16_tiles_kernel, dim3(1), dim3(1024), 0, stream, lo, hi, b->ctx->acc.acc_off, ns, b->ctx->acc.acc16_tile_off[buf], b->ctx->acc.acc16_state_flag[buf]);
+    AccScratch &a = ctx->acc;
+    const int *ws = a.work_states.p + first, *lo = a.seg_lo.p + first, *hi = a.seg_hi.p + first;
+    hipLaunchKernelGGL(acc16_tiles_kernel, dim3(1), dim3(1024), 0, stream, lo, hi, a.off.p, ns, a.tile_off[buf].p, a.state_flag[buf].p);
     // (max_tiles = 0: no frame of the group's states survived -- a batch scored by a collapsed model can have such groups; a grid of 0 is an
     //  invalid launch, tools/sweep_fuzz.py seed 514 -- one workgroup then finds nothing to do)
     const int pgrid = std::max(1, std::min(max_tiles, std::max(ctx->cus, 1) * 16));
-#define PRODUCE16(DD)                                                                                                         \
-    hipLaunchKernelGGL((acc16_producer_kernel<DD>), dim3(pgrid), dim3(256), 0, stream, ctx->frames32, ctx->centers32, ctx->fscale, \
-                       ctx->kzero, ns, ws, lo, hi, b->ctx->acc.acc_off, b->ctx->acc.acc_list, b->ctx->acc.acc16_tile_off[buf], 0, reinterpret_cast<uint4 *>(b->ctx->acc.acc16_images[buf]),  \
-                       b->ctx->acc.acc16_tile_mask[buf], b->ctx->acc.acc16_state_flag[buf])
     switch (ctx->D) {
-        case 47: PRODUCE16(47); break;
-        case 39: PRODUCE16(39); break;
-        case 26: PRODUCE16(26); break;
-        case 13: PRODUCE16(13); break;
+#define PRODUCE16(DD)                                                                                                                              \
+    case DD: hipLaunchKernelGGL((acc16_producer_kernel<DD>), dim3(pgrid), dim3(256), 0, stream, ctx->frames32, ctx->centers32, ctx->fscale,        \
+                                ctx->kzero, ns, ws, lo, hi, a.off.p, a.list.p, a.tile_off[buf].p, 0, reinterpret_cast<uint4 *>(a.images[buf].p),   \
+                                a.tile_mask[buf].p, a.state_flag[buf].p); break;
+        PCL_MFMA_DIMS(PRODUCE16)
+#undef PRODUCE16
         default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f16 accumulate kernel for D=%d", ctx->D);
     }
-#undef PRODUCE16
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }
 
 // ... and the consumer of the same group
-int pcl_launch_acc16_consume(pcl_ctx *ctx, pcl_batch *b, int first, int ns, int buf, bool fresh, hipStream_t stream) {
+int pcl_launch_acc16_consume(pcl_ctx *ctx, int first, int ns, int buf, bool fresh, hipStream_t stream) {
     if (ns == 0) return PCL_OK;
+    AccScratch &a = ctx->acc;
     const int nmt = ctx->Mpad32 / 32, nslice = (nmt + AW - 1) / AW;
     const int nblocks = ((ns + 7) / 8) * 8 * nslice;
-    const int *ws = b->ctx->acc.d_work_states + first;
+    const int *ws = a.work_states.p + first;
 #define CONSUME16F(DD, FR)                                                                                                    \
     hipLaunchKernelGGL((acc16_consumer_kernel<DD, FR>), dim3(nblocks), dim3(AW * 64), 0, stream,                              \
-                       reinterpret_cast<const uint4 *>(b->ctx->acc.acc16_images[buf]), reinterpret_cast<const uint4 *>(ctx->pm16f), ctx->centers32, ctx->fscale, \
-                       ctx->mean64, ctx->M, ctx->Mpad, nmt, ns, ws, b->ctx->acc.acc16_tile_off[buf], 0, 100.0, ctx->st_acc, ctx->st_alpha,      \
+                       reinterpret_cast<const uint4 *>(a.images[buf].p), reinterpret_cast<const uint4 *>(ctx->pm16f), ctx->centers32, ctx->fscale, \
+                       ctx->mean64, ctx->M, ctx->Mpad, nmt, ns, ws, a.tile_off[buf].p, 0, 100.0, ctx->st_acc, ctx->st_alpha,      \
                        ctx->st_mean, ctx->st_cov, ctx->d_npt, ctx->d_nbad, (ctx->compact_main && ctx->D <= 48) ? ctx->d_good_idx : (const int *)nullptr)
-#define CONSUME16(DD)                     \
-    do {                                  \
-        if (fresh) CONSUME16F(DD, true);  \
-        else CONSUME16F(DD, false);       \
-    } while (0)
     switch (ctx->D) {
-        case 47: CONSUME16(47); break;
-        case 39: CONSUME16(39); break;
-        case 26: CONSUME16(26); break;
-        case 13: CONSUME16(13); break;
+#define CONSUME16(DD) case DD: if (fresh) CONSUME16F(DD, true); else CONSUME16F(DD, false); break;
+        PCL_MFMA_DIMS(CONSUME16)
+#undef CONSUME16
         default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no f16 accumulate kernel for D=%d", ctx->D);
     }
-#undef CONSUME16
 #undef CONSUME16F
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;

@@ -841,7 +841,7 @@ void launch_coarse_t(pcl_ctx *ctx, pcl_batch *b, const CoarseExact &ex, unsigned
 }  // namespace
 
 bool pcl_coarse_enabled_for(const pcl_ctx *ctx, int D) {
-    return ctx->coarse_on && ctx->score_variant == 7 && (D == 13 || D == 26 || D == 39 || D == 47);
+    return ctx->coarse_on && pcl_route(ctx, PCL_F32, D) == PCL_ROUTE_SPLIT16;
 }
 bool pcl_coarse_enabled(const pcl_ctx *ctx) { return pcl_coarse_enabled_for(ctx, ctx->D); }
 
@@ -893,10 +893,9 @@ int pcl_launch_score_coarse(pcl_ctx *ctx, pcl_batch *b) {
     unsigned long long *counters = ctx->coarse_stats ? ctx->d_coarse_counter : nullptr;
     pcl_timer_begin(ctx, "score_coarse");
     switch (ctx->D) {
-        case 47: launch_coarse_t<47>(ctx, b, ex, counters); break;
-        case 39: launch_coarse_t<39>(ctx, b, ex, counters); break;
-        case 26: launch_coarse_t<26>(ctx, b, ex, counters); break;
-        case 13: launch_coarse_t<13>(ctx, b, ex, counters); break;
+#define CASE(DD) case DD: launch_coarse_t<DD>(ctx, b, ex, counters); break;
+        PCL_MFMA_DIMS(CASE)
+#undef CASE
         default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no coarse scoring kernel for D=%d", ctx->D);
     }
     pcl_timer_end(ctx, "score_coarse");

@@ -321,10 +321,9 @@ int pcl_launch_score_split16(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles,
     if (n_tiles == 0) return PCL_OK;
     pcl_timer_begin(ctx, "score");
     switch (ctx->D) {
-        case 47: launch16_t<47>(ctx, b, tiles, n_tiles); break;
-        case 39: launch16_t<39>(ctx, b, tiles, n_tiles); break;
-        case 26: launch16_t<26>(ctx, b, tiles, n_tiles); break;
-        case 13: launch16_t<13>(ctx, b, tiles, n_tiles); break;
+#define CASE(DD) case DD: launch16_t<DD>(ctx, b, tiles, n_tiles); break;
+        PCL_MFMA_DIMS(CASE)
+#undef CASE
         default: PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: no split-f16 scoring kernel for D=%d", ctx->D);
     }
     pcl_timer_end(ctx, "score");

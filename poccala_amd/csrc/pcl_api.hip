@@ -1056,9 +1056,10 @@ static std::vector<ScoreTile> make_tiles(const pcl_batch *b, const std::vector<s
 
 static int build_tiles(pcl_batch *b, int precision) {
     pcl_ctx *ctx = b->ctx;
-    const bool mfma = precision == PCL_F32 && ctx->score_variant >= 3 && pcl_score_mfma_supported(ctx->D);
-    const int tf = mfma ? (ctx->score_variant == 7 ? pcl_score_split16_tile_frames() : pcl_score_mfma_tile_frames())
-                        : pcl_score_tile_frames(ctx->D, precision);
+    const int route = pcl_route(ctx, precision, ctx->D);
+    const bool mfma = route != PCL_ROUTE_DIRECT;
+    const int tf = route == PCL_ROUTE_SPLIT16 ? pcl_score_split16_tile_frames()
+                 : route == PCL_ROUTE_MFMA32 ? pcl_score_mfma_tile_frames() : pcl_score_tile_frames(ctx->D, precision);
     if (b->d_tiles && b->tile_frames == tf && b->tile_gen == ctx->model_gen) return PCL_OK;
     // MFMA mode: states whose centred expansion is ill conditioned go to the direct-form VALU kernel
     std::vector<size_t> good, bad;
@@ -1071,7 +1072,7 @@ static int build_tiles(pcl_batch *b, int precision) {
         for (size_t k : good)
             if (pcl_state_is_split(ctx, b->work_states[k])) split.push_back(k);
     // ... at the direct-form tile size (the subset launch, rounds 4-5) or, with the coarse pass, at the matrix pipe's
-    const bool coarse = mfma && ctx->score_variant == 7 && pcl_coarse_enabled(ctx);
+    const bool coarse = route == PCL_ROUTE_SPLIT16 && pcl_coarse_enabled(ctx);
     const std::vector<ScoreTile> tiles_s = (split.empty() || coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_score_subset_tile_frames(ctx->D));
     const std::vector<ScoreTile> tiles_c = (split.empty() || !coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_coarse_tile_frames());
     dev_free(b->d_tiles);
@@ -1129,8 +1130,9 @@ int pcl_batch_score(pcl_batch *b, int precision) {
         TRY(pcl_launch_fill_virtual_rows(ctx, b));                // written once per row map, not once per scoring pass
         b->virt_rows_filled = true;
     }
-    if (precision == PCL_F32 && ctx->score_variant >= 3 && pcl_score_mfma_supported(ctx->D)) {
-        if (ctx->score_variant == 7) {
+    const int route = pcl_route(ctx, precision, ctx->D);
+    if (route != PCL_ROUTE_DIRECT) {
+        if (route == PCL_ROUTE_SPLIT16) {
             TRY(pcl_launch_score_split16(ctx, b, b->d_tiles, b->n_tiles));
 #ifndef PCL_DIAG_NOFIXUP
             TRY(pcl_launch_score_fixup(ctx, b, b->d_tiles, b->n_tiles, b->d_tile_flags));   // tiles with out-of-range features

@@ -62,25 +62,31 @@ struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
 };
 
+// A grow-only device array: a pointer, a capacity (elements) and two functions, defined beside dev_alloc / dev_free below.
+struct pcl_ctx;
+template <typename T>
+struct GrowBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    int reserve(pcl_ctx *ctx, size_t n);   // room for n elements; nothing is copied: the contents are undefined after a growth
+    void release();
+};
+
 // Scratch of the accumulate pass (gmm_accumulate.hip, gmm_accumulate_f16.hip): everything here is rebuilt by every pass and dead when the
 // pass's last kernel has run, and the passes of a context are serialised on its main stream (the auxiliary stream's producers are
-// joined by the consumers) -- so it belongs to the CONTEXT, grow-only, not to the batch: rounds 2-4 gave every batch its own (4 GB of
-// tile images + up to 442 MB of active-frame lists: 35 GB for the 8 resident batches of config 4, and a corpus sweep that makes a
-// batch per step allocated them per step).
+// joined by the consumers) -- so it belongs to the CONTEXT, not to the batch: rounds 2-4 gave every batch its own (4 GB of tile images +
+// up to 442 MB of active-frame lists: 35 GB for the 8 resident batches of config 4, and a corpus sweep that makes a batch per step
+// allocated them per step).  Every array has its own capacity: a pass reserves what it needs, pcl_accumulate_release gives all of it back.
 struct AccScratch {
     // work lists: per-segment counts / offsets, per-state active-frame lists, the accumulate order of the states
-    int *acc_cnt = nullptr;
-    long long *acc_off = nullptr;
-    ActiveFrame *acc_list = nullptr;
-    int *d_work_states = nullptr, *d_seg_lo = nullptr, *d_seg_hi = nullptr, *d_split_flag = nullptr;   // (split_flag: 1 = a split state, in accumulate order)
-    size_t acc_cap_list = 0, acc_cap_segs = 0, acc_cap_states = 0;
+    GrowBuf<int> cnt; GrowBuf<long long> off; GrowBuf<ActiveFrame> list;
+    GrowBuf<int> work_states, seg_lo, seg_hi, split_flag;   // (split_flag: 1 = a split state, in accumulate order)
     // producer / consumer: tile images in LDS order, per-state tile offsets, outlier masks; two sets: the producer of state group g + 1
     // runs on the auxiliary stream beside the consumer of group g
-    void *acc16_images[2] = {nullptr, nullptr};
-    int *acc16_tile_off[2] = {nullptr, nullptr}, *acc16_state_flag[2] = {nullptr, nullptr};
-    unsigned int *acc16_tile_mask[2] = {nullptr, nullptr};
-    hipEvent_t acc16_ev_prod[2] = {nullptr, nullptr}, acc16_ev_cons[2] = {nullptr, nullptr}, acc16_ev_start = nullptr;
-    size_t acc16_cap_tiles = 0, acc16_cap_states = 0;
+    GrowBuf<unsigned char> images[2];
+    GrowBuf<int> tile_off[2], state_flag[2];
+    GrowBuf<unsigned int> tile_mask[2];                     // one word per tile: its capacity is the sets' capacity in tiles
+    hipEvent_t ev_prod[2] = {nullptr, nullptr}, ev_cons[2] = {nullptr, nullptr}, ev_start = nullptr;
 };
 
 struct pcl_ctx {
@@ -288,7 +294,7 @@ struct pcl_batch {
     std::vector<int> seg_of_row;              // (utterance, row) -> its segment (-1: not a GMM row); d_seg_of_row: the device copy (sumN ints)
     int *d_seg_of_row = nullptr;
     int max_N = 0;                            // rows of the largest sentence HMM of the batch
-    // (the accumulate pass's device work lists and tile images are the CONTEXT's scratch since round 5: pcl_ctx::acc)
+    // (the accumulate pass's device work lists and tile images are the CONTEXT's scratch, pcl_ctx::acc; the host staging of its state order is acc_ws ... above)
     // decoder state (hmm_decode.hip): token buffers, node -> token map, scratch, results
     double *dec_f64 = nullptr;
     int *dec_slot = nullptr, *dec_work = nullptr, *dec_int = nullptr;
@@ -363,6 +369,16 @@ static inline void dev_free(T *&p) {
     if (p) pcl_pool_free((void *)p);
     p = nullptr;
 }
+template <typename T>
+int GrowBuf<T>::reserve(pcl_ctx *ctx, size_t n) {
+    if (n <= cap) return PCL_OK;
+    release();
+    const int rc = dev_alloc(ctx, &p, n);
+    if (rc == PCL_OK) cap = n;
+    return rc;
+}
+template <typename T>
+void GrowBuf<T>::release() { dev_free(p); cap = 0; }
 // Host -> device copy on the context's main stream, complete on return: unlike hipMemcpy (legacy null stream) it does not
 // wait for the work of the other streams (a decoder running on the second stream while the next chunk's batch is built).
 static inline hipError_t pcl_h2d(pcl_ctx *ctx, void *dst, const void *src, size_t bytes);
@@ -511,8 +527,8 @@ void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);
-int pcl_launch_acc16_produce(pcl_ctx *ctx, pcl_batch *b, int first, int ns, int max_tiles, int buf, hipStream_t stream);
-int pcl_launch_acc16_consume(pcl_ctx *ctx, pcl_batch *b, int first, int ns, int buf, bool fresh, hipStream_t stream);
+int pcl_launch_acc16_produce(pcl_ctx *ctx, int first, int ns, int max_tiles, int buf, hipStream_t stream);
+int pcl_launch_acc16_consume(pcl_ctx *ctx, int first, int ns, int buf, bool fresh, hipStream_t stream);
 size_t pcl_acc16_image_bytes(int D);
 int pcl_launch_score_split16(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);
 int pcl_score_split16_tile_frames();
@@ -520,7 +536,21 @@ int pcl_launch_score_fixup(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, i
 int pcl_launch_score_subset(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);
 int pcl_score_subset_tile_frames(int D);
 int pcl_score_mfma_tile_frames();
-bool pcl_score_mfma_supported(int D);
+// The (padded) feature dimensions the matrix-pipe kernels have an instance for: the ONE list behind pcl_score_mfma_supported and every
+// per-D switch of those kernels' launchers (largest first, the order those switches always had: it is the order of the kernels in the code objects).
+#define PCL_MFMA_DIMS(X) X(47) X(39) X(26) X(13)
+inline bool pcl_score_mfma_supported(int D) {
+#define PCL_IS_DIM(DD) || D == DD
+    return false PCL_MFMA_DIMS(PCL_IS_DIM);
+#undef PCL_IS_DIM
+}
+// Which kernel family scores / accumulates at this precision for a model of (padded) dimension D, numbered like score_variant: the direct
+// form on the VALU (also: every f64 pass, every dimension without a matrix-pipe instance), the f32-input MFMA kernels, the split-f16 ones.
+enum { PCL_ROUTE_DIRECT = 1, PCL_ROUTE_MFMA32 = 3, PCL_ROUTE_SPLIT16 = 7 };
+inline int pcl_route(const pcl_ctx *ctx, int precision, int D) {
+    if (precision != PCL_F32 || ctx->score_variant < 3 || !pcl_score_mfma_supported(D)) return PCL_ROUTE_DIRECT;
+    return ctx->score_variant == 7 ? PCL_ROUTE_SPLIT16 : PCL_ROUTE_MFMA32;
+}
 int pcl_launch_dup_rows(pcl_ctx *ctx, pcl_batch *b);
 int pcl_launch_derive(pcl_ctx *ctx);
 int pcl_launch_derive_range(pcl_ctx *ctx, int j_lo, int j_hi);   // no wait, no generation bump: pcl_derive_finish closes
