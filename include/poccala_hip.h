@@ -44,6 +44,7 @@ extern "C" {
 
 typedef struct pcl_ctx pcl_ctx;
 typedef struct pcl_batch pcl_batch;
+typedef struct pcl_seg pcl_seg;     /* segmental GMM training, below */
 
 typedef enum {
     PCL_OK = 0,
@@ -183,6 +184,22 @@ int pcl_batch_viterbi(pcl_batch *b, int end_state_back);
  * (:614-625) and __get_gmmdata (:629-644) do.  Needs pcl_batch_viterbi first.  Synchronous. */
 int pcl_batch_regroup(pcl_batch *b, const int32_t *row_unit, int gmm_num, int32_t *frame_unit, int32_t *frame_k);
 
+/* Row f8: realignment, the hop every round of training scheme 1 after the first goes through -- multi_process_data(init=False)
+ * (AcousticModel.py:736-764): forced alignment, the drop rule (:751-757), then discriminate (:937-955) and __get_gmmdata's mode 'g'
+ * (:614-644) -- from the Viterbi paths of a batch made by pcl_batch_create_labels to the owner map pcl_seg_create sorts by, on the
+ * device.  The row -> unit map comes from the batch's own labels (row 0 -> label position 0, rows 1 .. gmm_num L -> position
+ * (row - 1) / gmm_num, the exit row -> position L - 1; gmm_num = S - 2); runs and slices exactly as pcl_batch_regroup cuts them.  An
+ * utterance whose path visits fewer distinct units than its label names is dropped (a label unit nobody visited).
+ * frame_state_out (rows of the frame matrix,) int32 or NULL: unit * gmm_num + k for the frames of the kept utterances, -1 for the
+ * dropped ones and for every row outside the batch -- pcl_seg_create's input.  dropped_out (U,) int32 or NULL: 1 = dropped.  out or
+ * NULL: the pcl_seg of that map, built from it ON THE DEVICE by pcl_seg_create's counting sort and gather; the map travels to the host
+ * only when frame_state_out is given.  At least one of frame_state_out and out must be given.  PCL_ERR_STATE: the batch was not made
+ * from labels, or pcl_batch_viterbi has not run.  PCL_ERR_INVALID: the utterances overlap in the frame matrix (a frame has ONE owner),
+ * the batch no longer fits the current frame matrix, the model's J is not n_units * (S - 2) or the inventory changed since the batch
+ * was made, 2 T + 2 L of an utterance beyond 16384.  Integer arithmetic only.  Synchronous. */
+int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out /* (rows of the frame matrix,) or NULL */,
+                             int32_t *dropped_out /* (U,) or NULL */, pcl_seg **out /* or NULL */);
+
 /* ----------------------------------------------------------------- unit inventory and label-built batches
  * The reference builds, PER UTTERANCE, one LHMM per label unit (AcousticModel.init_unit / init_parameter,
  * AcousticModel.py:164-240: transmat (S,S), S-2 GMM states between an entry and an exit VirtualState) and glues them
@@ -304,7 +321,6 @@ int pcl_model_download(pcl_ctx *ctx, double *mean, double *var, double *weight);
  * -1 = the frame is not used (dropped utterances).  Builds on the device the per-state frame lists (counting sort, stable in frame
  * order) and a copy of the frames in that order; the object does not refer to the context's frame matrix afterwards.  From the two
  * arrays pcl_batch_regroup writes: frame_state = frame_unit * gmm_num + frame_k.  At most 65535 states.  Synchronous. */
-typedef struct pcl_seg pcl_seg;
 int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *frame_state, pcl_seg **out);
 int pcl_seg_destroy(pcl_seg *seg);
 /* pcl_seg_get selectors */

@@ -216,18 +216,42 @@ class AcousticModel(DataInitialization):
         load_audio_batch then give a (0, D) array): the batch helpers below leave such an utterance out of the device batch -- a
         sentence HMM over zero frames has no alignment and adds nothing to any accumulator -- and keep their results aligned with
         the input lists."""
-        keep = [u for u, d in enumerate(data_list) if len(d) > 0]
+        res = AcousticModel._resident(data_list)
+        keep = [u for u, d in enumerate(data_list) if len(d) > 0] if res is None else np.flatnonzero(res[0] > 0).tolist()
         if not keep:
             raise ValueError('every utterance of the batch is empty (no frame survived the voice-activity detector)')
         return keep
+
+    @staticmethod
+    def _resident(data_list):
+        """The batch helpers take a list of (T_u, D) arrays, which they upload, or the (lens, begin) of frames already resident
+        (Engine.frontend / load_audio_batch(fetch=False)), the form flat_start_batch accepts: (lens int32, begin int64) for the
+        second form, None for the first."""
+        if isinstance(data_list, tuple) and len(data_list) == 2 and np.ndim(data_list[0]) == 1:
+            return np.asarray(data_list[0], dtype=np.int32), np.asarray(data_list[1], dtype=np.int64)
+        return None
+
+    @staticmethod
+    def _utt_count(data_list):
+        res = AcousticModel._resident(data_list)
+        return len(data_list) if res is None else len(res[0])
+
+    @staticmethod
+    def _utt_subset(data_list, keep):
+        res = AcousticModel._resident(data_list)
+        return [data_list[u] for u in keep] if res is None else (res[0][keep], res[1][keep])
 
     def _sentence_batch(self, labels, data_list, unit_hmms, engine):
         units, idx, (mean, var, w), trans = self._model_arrays(unit_hmms)
         engine.load_model(mean, var, w)
         engine.load_units(np.stack(trans))
-        lens = np.array([len(d) for d in data_list], dtype=np.int32)
-        begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
-        engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
+        res = self._resident(data_list)
+        if res is not None:                                  # frames already resident: nothing is uploaded
+            lens, begin = res
+        else:
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
         unit_ids = [np.array([idx[u] for u in lab], dtype=np.int32) for lab in labels]
         b = engine.label_batch(unit_ids, lens, begin)        # AcousticModel.embedded for every utterance, in the library
         return b, b.N, units, idx
@@ -238,9 +262,9 @@ class AcousticModel(DataInitialization):
         skipped: (nan, empty sequence) in its place."""
         engine = engine or default_engine()
         keep = self._nonempty(data_list)
-        if len(keep) < len(data_list):          # an empty utterance: (nan, no names) in its place
-            res = self.align_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, precision, engine)
-            out = [(float('nan'), np.array([], dtype=str))] * len(data_list)
+        if len(keep) < self._utt_count(data_list):          # an empty utterance: (nan, no names) in its place
+            res = self.align_batch([labels[u] for u in keep], self._utt_subset(data_list, keep), unit_hmms, precision, engine)
+            out = [(float('nan'), np.array([], dtype=str))] * self._utt_count(data_list)
             for u, r in zip(keep, res):
                 out[u] = r
             return out
@@ -266,10 +290,10 @@ class AcousticModel(DataInitialization):
         (pcl_batch_accumulate_hmm); nothing here loops over utterances.  An utterance without frames is skipped (logp = nan)."""
         engine = engine or default_engine()
         keep = self._nonempty(data_list)
-        if len(keep) < len(data_list):          # empty utterances add nothing to the statistics: logp = nan in their place
-            stats, hmm_acc, lp = self.estep_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, fix_code, precision,
+        if len(keep) < self._utt_count(data_list):          # empty utterances add nothing to the statistics: logp = nan in their place
+            stats, hmm_acc, lp = self.estep_batch([labels[u] for u in keep], self._utt_subset(data_list, keep), unit_hmms, fix_code, precision,
                                                   engine)
-            logp = np.full(len(data_list), np.nan)
+            logp = np.full(self._utt_count(data_list), np.nan)
             logp[keep] = lp
             return stats, hmm_acc, logp
         b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
@@ -406,24 +430,30 @@ class AcousticModel(DataInitialization):
 
     def train_segments_batch(self, labels, data_list, unit_hmms, init=False, mix_level=None, smem=False, c_covariance=1e-3, seed=0,
                              precision=PCL_F64, engine=None):
-        """Training scheme 1 for many utterances at once: forced alignment and regrouping as `regroup_batch` does them, then --
-        without the frames leaving the device -- clustering (init=True, or mix_level differs from the model's) and the stand-alone
+        """Training scheme 1 for many utterances at once: forced alignment, then regrouping, the drop rule and the per-state frame
+        lists in one device call (Batch.align_segments; the same result as `regroup_batch`'s route), then -- without the frames or the
+        owner map leaving the device -- clustering (init=True, or mix_level differs from the model's) and the stand-alone
         EM of every GMM state of every unit in one batch of launches (AcousticModel.__cal_gmm, AcousticModel.py:532-561, for every
         unit of multi_training :771-840).  The units' GMM objects receive the new parameters.  Returns {unit: (iters (S-2,),
         q (S-2,), skipped (S-2,) bool)}; utterances whose path misses a label unit are dropped (:754-757) and listed in
-        `self.last_dropped`.  The clustering is textbook k-means++ / Lloyd, not the reference routine's arithmetic
+        `self.last_dropped`.  `data_list` is a list of (T_u, D) arrays (uploaded here) or the (lens, begin) of frames already resident
+        (Engine.frontend / load_audio_batch(fetch=False)), of which nothing is uploaded; utterances of length 0 are left out and
+        listed in `last_dropped`.  The clustering is textbook k-means++ / Lloyd, not the reference routine's arithmetic
         (Clustering.ClusterInitialization)."""
         self._no_smem(smem)
         engine = engine or default_engine()
         keep = self._nonempty(data_list)
-        if len(keep) < len(data_list):          # empty utterances are dropped like the ones whose path misses a unit
-            out = self.train_segments_batch([labels[u] for u in keep], [data_list[u] for u in keep], unit_hmms, init, mix_level, smem,
+        n_utts = self._utt_count(data_list)
+        if len(keep) < n_utts:                  # empty utterances are dropped like the ones whose path misses a unit
+            out = self.train_segments_batch([labels[u] for u in keep], self._utt_subset(data_list, keep), unit_hmms, init, mix_level, smem,
                                             c_covariance, seed, precision, engine)
-            self.last_dropped = sorted((set(range(len(data_list))) - set(keep)) | {keep[u] for u in self.last_dropped})
+            self.last_dropped = sorted((set(range(n_utts)) - set(keep)) | {keep[u] for u in self.last_dropped})
             return out
-        b, units, idx, row_unit, fu, fk, self.last_dropped = self._align_regroup(labels, data_list, unit_hmms, precision, engine)
+        b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
         try:
-            seg = b.segments(row_unit, self.__state_num - 2, dropped=self.last_dropped, regrouped=(fu, fk))
+            b.score(precision)
+            b.viterbi()
+            seg, self.last_dropped = b.align_segments()      # regrouping, drop rule and owner map: one kernel, nothing per utterance here
         finally:
             b.close()
         return self._train_segments(engine, seg, units, unit_hmms, init, mix_level, smem, c_covariance, seed, precision)
@@ -468,17 +498,22 @@ class AcousticModel(DataInitialization):
         S-2 slices) on the device, then clustering + stand-alone EM of every GMM state as train_segments_batch(init=True) runs them
         -- but WITHOUT its forced alignment, which would need a model.  mix_level defaults to this object's.  Returns what
         train_segments_batch returns, {unit: (iters (S-2,), q (S-2,), skipped (S-2,) bool)}; the units' GMM objects receive the new
-        parameters and the engine holds the model.  An utterance without frames adds nothing.  The reference also runs the SMEM split /
+        parameters and the engine holds the model.  `data_list` as for train_segments_batch: host arrays, or (lens, begin) of resident
+        frames.  An utterance without frames adds nothing.  The reference also runs the SMEM split /
         merge on this round (smem=init, :835): outside the hot path here, as for train_segments_batch."""
         engine = engine or default_engine()
         keep = self._nonempty(data_list)
-        labels, data_list = [labels[u] for u in keep], [data_list[u] for u in keep]
+        labels, data_list = [labels[u] for u in keep], self._utt_subset(data_list, keep)
         units = sorted(unit_hmms)
         idx = {u: i for i, u in enumerate(units)}
         e = self.__state_num - 2
-        lens = np.array([len(d) for d in data_list], dtype=np.int32)
-        begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
-        engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
+        res = self._resident(data_list)
+        if res is not None:                                  # frames already resident: nothing is uploaded
+            lens, begin = res
+        else:
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
         unit_ids = [np.array([idx[u] for u in lab], dtype=np.int32) for lab in labels]
         seg = engine.uniform_segments(unit_ids, lens, begin, e, len(units) * e)
         k = int(mix_level) if mix_level is not None else self.__mix_level

@@ -71,6 +71,7 @@ PROTOTYPES = {
     'pcl_coarse_counters': (_i, [_vp, _vp, _vp, _i]),
     'pcl_score_occupancy': (_i, [_vp, _i]),
     'pcl_batch_regroup': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'pcl_batch_align_segments': (_i, [_vp, _vp, _vp, C.POINTER(_vp)]),
     'pcl_mfcc': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
     'pcl_vad': (_i, [_vp, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     'pcl_frontend': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),

@@ -493,7 +493,8 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
 
 }  // extern "C"
 
-// The owner array is on the device already (pcl_seg_create above; pcl_uniform_segments, bootstrap.hip): counting sort + gather.
+// The owner array is on the device already (pcl_seg_create above; pcl_uniform_segments, bootstrap.hip; pcl_batch_align_segments, pcl_api.hip):
+// counting sort (timer "seg_count") + scatter and gather (timer "seg_gather").
 int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_state, pcl_seg **out) {
     *out = nullptr;
     if (J <= 0 || J > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: bad arguments (J=%d, at most 65535 states)", J);
@@ -521,8 +522,10 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
     A(dev_alloc(ctx, &s->d_off, (size_t)J + 1));
     if (rc == PCL_OK) H(hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
     if (rc == PCL_OK) {
+        pcl_timer_begin(ctx, "seg_count");
         hipLaunchKernelGGL(seg_hist_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt);
         hipLaunchKernelGGL(seg_colscan_kernel, dim3((J + 255) / 256), dim3(256), 0, ctx->stream, d_tilecnt, n_tiles, J, s->d_counts);
+        pcl_timer_end(ctx, "seg_count");
         H(hipGetLastError());
         s->counts.resize(J);
         H(hipMemcpyAsync(s->counts.data(), s->d_counts, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -538,10 +541,12 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
         if (rc == PCL_OK && ctx->frames64) A(dev_alloc(ctx, &s->G64, (size_t)s->Ntot * s->FD));
     }
     if (rc == PCL_OK && s->Ntot > 0) {
+        pcl_timer_begin(ctx, "seg_gather");
         hipLaunchKernelGGL(seg_scatter_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt, s->d_off, s->d_order);
         const unsigned gb = (unsigned)std::min<long long>(8192, (s->Ntot * s->FD + 255) / 256);
         hipLaunchKernelGGL(seg_gather_kernel<float>, dim3(gb), dim3(256), 0, ctx->stream, ctx->frames32, s->d_order, s->Ntot, s->FD, s->G32);
         if (s->G64) hipLaunchKernelGGL(seg_gather_kernel<double>, dim3(gb), dim3(256), 0, ctx->stream, ctx->frames64, s->d_order, s->Ntot, s->FD, s->G64);
+        pcl_timer_end(ctx, "seg_gather");
         H(hipGetLastError());
     }
     if (rc == PCL_OK) H(hipStreamSynchronize(ctx->stream));

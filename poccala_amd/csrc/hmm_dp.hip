@@ -1026,15 +1026,8 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
 // frames is cut into gmm_num slices, the first gmm_num-1 of n / gmm_num frames, the last takes the rest
 // (__eq_segment mode 'g', :614-625); k[t] = the slice of frame t.  One wave per utterance: run starts by a forward
 // max-scan over boundary flags, run ends by a backward min-scan, both through LDS.
-__global__ void hmm_regroup_kernel(const UttDesc *__restrict__ utts, const int32_t *__restrict__ path,
-                                   const int32_t *__restrict__ row_unit, int gmm_num, int32_t *__restrict__ frame_unit,
-                                   int32_t *__restrict__ frame_k) {
-    extern __shared__ int rg[];                       // [Tmax] units, [Tmax] run starts
-    const UttDesc d = utts[blockIdx.x];
-    const int T = d.T, lane = threadIdx.x;
-    int *un = rg, *st = rg + T;
-    for (int t = lane; t < T; t += 64) un[t] = row_unit[d.vec_off + path[d.path_off + t]];
-    __syncthreads();
+template <typename Emit>
+__device__ __forceinline__ void regroup_slices(const int *un, int *st, int T, int lane, int gmm_num, Emit emit) {
     // forward: start of the run of t
     int carry = 0;
     for (int t0 = 0; t0 < T; t0 += 64) {
@@ -1065,11 +1058,64 @@ __global__ void hmm_regroup_kernel(const UttDesc *__restrict__ utts, const int32
         e = min(e, carry_e);
         if (t < T) {
             const int n = e - st[t], chunk = n / gmm_num, pos = t - st[t];
-            frame_unit[d.path_off + t] = un[t];
-            frame_k[d.path_off + t] = (chunk == 0) ? gmm_num - 1 : min(pos / chunk, gmm_num - 1);
+            emit(t, un[t], (chunk == 0) ? gmm_num - 1 : min(pos / chunk, gmm_num - 1));
         }
         carry_e = __shfl(e, 0, 64);
     }
+}
+
+__global__ void hmm_regroup_kernel(const UttDesc *__restrict__ utts, const int32_t *__restrict__ path,
+                                   const int32_t *__restrict__ row_unit, int gmm_num, int32_t *__restrict__ frame_unit,
+                                   int32_t *__restrict__ frame_k) {
+    extern __shared__ int rg[];                       // [Tmax] units, [Tmax] run starts
+    const UttDesc d = utts[blockIdx.x];
+    const int T = d.T, lane = threadIdx.x;
+    int *un = rg, *st = rg + T;
+    for (int t = lane; t < T; t += 64) un[t] = row_unit[d.vec_off + path[d.path_off + t]];
+    __syncthreads();
+    regroup_slices(un, st, T, lane, gmm_num, [&](int t, int unit, int k) {
+        frame_unit[d.path_off + t] = unit;
+        frame_k[d.path_off + t] = k;
+    });
+}
+
+// Row f8: the same runs and slices straight from the batch's labels, the drop rule of multi_process_data(init=False)
+// (AcousticModel.py:751-757: an utterance whose path visits fewer distinct units than its label names is not used) and the
+// owner map pcl_seg_create sorts by, in one pass.  Row -> label position: row 0 (entry) -> 0, rows 1 .. gmm_num L -> (row - 1) /
+// gmm_num, row N - 1 (exit) -> L - 1; unit = labels[position].  Path units are a subset of label units, so "fewer distinct
+// units" means a label unit nobody visited: a flag per label position, and a unit is seen when any position that names it is.
+// Integer work only.  frame_state was filled with -1 before; a dropped utterance writes nothing.
+__global__ void hmm_align_segments_kernel(const UttDesc *__restrict__ utts, const int32_t *__restrict__ path,
+                                          const int32_t *__restrict__ labels, const int *__restrict__ label_off, int gmm_num,
+                                          int32_t *__restrict__ frame_state, int32_t *__restrict__ dropped) {
+    extern __shared__ int rg[];                       // [T] units, [T] run starts, [L] label, [L] visited
+    const UttDesc d = utts[blockIdx.x];
+    const int T = d.T, lane = threadIdx.x;
+    const int lo = label_off[blockIdx.x], L = label_off[blockIdx.x + 1] - lo;
+    int *un = rg, *st = rg + T, *lab = rg + 2 * T, *vis = lab + L;
+    for (int p = lane; p < L; p += 64) {
+        lab[p] = labels[lo + p];
+        vis[p] = 0;
+    }
+    __syncthreads();
+    for (int t = lane; t < T; t += 64) {
+        const int row = path[d.path_off + t];
+        const int p = row <= 0 ? 0 : min((row - 1) / gmm_num, L - 1);
+        un[t] = lab[p];
+        vis[p] = 1;                                   // (every writer stores the same value)
+    }
+    __syncthreads();
+    int missed = 0;
+    for (int p = lane; p < L; p += 64) {
+        int seen = 0;
+        for (int q = 0; q < L; ++q) seen |= (lab[q] == lab[p]) & vis[q];
+        missed |= seen ^ 1;
+    }
+    const int drop = __any(missed) ? 1 : 0;
+    if (lane == 0) dropped[blockIdx.x] = drop;
+    if (drop) return;                                 // (the whole wave)
+    int32_t *dst = frame_state + d.frame0;
+    regroup_slices(un, st, T, lane, gmm_num, [&](int t, int unit, int k) { dst[t] = unit * gmm_num + k; });
 }
 
 int pcl_launch_regroup(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_row_unit, int gmm_num, int32_t *d_frame_unit, int32_t *d_frame_k) {
@@ -1079,6 +1125,19 @@ int pcl_launch_regroup(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_row_unit, in
     hipLaunchKernelGGL(hmm_regroup_kernel, dim3(b->U), dim3(64), shm, ctx->stream, b->d_utt, b->path, d_row_unit, gmm_num, d_frame_unit,
                        d_frame_k);
     pcl_timer_end(ctx, "regroup");
+    HIPCHK(ctx, hipGetLastError());
+    return PCL_OK;
+}
+
+int pcl_launch_align_segments(pcl_ctx *ctx, pcl_batch *b, int Lmax, int gmm_num, int32_t *d_frame_state, int32_t *d_dropped) {
+    const size_t shm = ((size_t)2 * b->Tmax + (size_t)2 * Lmax) * sizeof(int);
+    if (shm > 64 * 1024)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_align_segments: utterances of %d frames and %d label units exceed the 8192-frame limit (2 T + 2 L <= 16384)",
+                 b->Tmax, Lmax);
+    pcl_timer_begin(ctx, "align_segments");
+    hipLaunchKernelGGL(hmm_align_segments_kernel, dim3(b->U), dim3(64), shm, ctx->stream, b->d_utt, b->path, b->d_labels, b->d_label_off, gmm_num,
+                       d_frame_state, d_dropped);
+    pcl_timer_end(ctx, "align_segments");
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }

@@ -130,6 +130,8 @@ void pcl_batch_units_release(pcl_batch *b) {
     dev_free(b->occ_ptr);
     dev_free(b->occ_utt);
     dev_free(b->occ_row0);
+    dev_free(b->d_labels);
+    dev_free(b->d_label_off);
 }
 
 static size_t hmm_acc_len(const pcl_ctx *ctx) { return (size_t)ctx->n_units * (ctx->S - 2) * (ctx->S + 1); }
@@ -298,6 +300,8 @@ int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const
     b->from_labels = true;
     b->label_len.assign(label_len, label_len + U);
     b->labels.assign(labels, labels + tot);
+    b->label_max = *std::max_element(labels, labels + tot);
+    b->label_len_max = *std::max_element(label_len, label_len + U);
     b->logpi_u.resize(U);
     for (int u = 0; u < U; ++u) b->logpi_u[u] = logpi ? logpi[u] : log(1.0 / N[u]);
     // row -> GMM state (embedded_prob, AcousticModel.py:990-1001) and unit -> occurrences

@@ -1259,6 +1259,76 @@ int pcl_batch_regroup(pcl_batch *b, const int32_t *row_unit, int gmm_num, int32_
     return rc;
 }
 
+int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dropped_out, pcl_seg **out) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    const char *who = "pcl_batch_align_segments";
+    if (out) *out = nullptr;
+    if (!frame_state_out && !out) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: neither frame_state_out nor out is given", who);
+    if (!b->from_labels) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch was not created from labels (pcl_batch_create_labels)", who);
+    if (!b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: run pcl_batch_viterbi first", who);
+    const int e = ctx->S - 2;
+    if (ctx->n_units < 1 || e < 1 || ctx->J != ctx->n_units * e)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the model has %d GMM states, %d units x %d emitting states need %d", who, ctx->J, ctx->n_units, e, ctx->n_units * e);
+    if (b->label_max >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch names unit %d, the inventory now has %d units", who, b->label_max, ctx->n_units);
+    for (int u = 0; u < b->U; ++u)
+        if (b->utt[u].N != e * b->label_len[u] + 2)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has %d rows for %d label units, the inventory now has %d emitting states per unit", who, u,
+                     b->utt[u].N, b->label_len[u], e);
+    if (!ctx->frames32 || ctx->F == 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: no frames uploaded", who);
+    if (b->max_frame_end > ctx->F)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch refers to frame rows up to %lld but the frame matrix now has %lld rows (re-uploaded after the batch was created)",
+                 who, b->max_frame_end, (long long)ctx->F);
+    if (ctx->F > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame matrix of %lld rows", who, (long long)ctx->F);
+    {   // a frame has one owner: the utterances' row ranges are disjoint
+        std::vector<int> by(b->U);
+        for (int u = 0; u < b->U; ++u) by[u] = u;
+        std::sort(by.begin(), by.end(), [&](int x, int y) { return b->utt[x].frame0 != b->utt[y].frame0 ? b->utt[x].frame0 < b->utt[y].frame0 : x < y; });
+        long long end = 0;
+        int prev = -1;
+        for (int u : by) {
+            if (b->utt[u].frame0 < end) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterances %d and %d overlap in the frame matrix", who, prev, u);
+            end = b->utt[u].frame0 + b->utt[u].T;
+            prev = u;
+        }
+    }
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long F = ctx->F;
+    if (!b->d_labels) {                                             // once per batch
+        std::vector<int> loff((size_t)b->U + 1, 0);
+        for (int u = 0; u < b->U; ++u) loff[u + 1] = loff[u] + b->label_len[u];
+        dev_free(b->d_label_off);                                   // (left by a call whose second allocation failed)
+        TRY(dev_alloc(ctx, &b->d_label_off, loff.size()));
+        TRY(dev_alloc(ctx, &b->d_labels, b->labels.size()));
+        HIPCHK(ctx, pcl_h2d(ctx, b->d_label_off, loff.data(), loff.size() * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->labels.data(), b->labels.size() * sizeof(int32_t)));
+    }
+    int32_t *d_state = nullptr, *d_drop = nullptr;
+    int rc = dev_alloc(ctx, &d_state, (size_t)F);
+    if (rc == PCL_OK) rc = dev_alloc(ctx, &d_drop, (size_t)b->U);
+    bool hip_ok = true;
+    if (rc == PCL_OK) hip_ok = hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream) == hipSuccess;
+    if (rc == PCL_OK && hip_ok) rc = pcl_launch_align_segments(ctx, b, b->label_len_max, e, d_state, d_drop);
+    if (rc == PCL_OK && hip_ok && frame_state_out)
+        hip_ok = hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (rc == PCL_OK && hip_ok && dropped_out)
+        hip_ok = hipMemcpyAsync(dropped_out, d_drop, (size_t)b->U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    if (rc == PCL_OK && hip_ok) hip_ok = pcl_batch_mark(b) == hipSuccess;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) hip_ok = false;
+    if (rc == PCL_OK && !hip_ok) {
+        pcl_set_error(ctx, "pcl_batch_align_segments: HIP error");
+        rc = PCL_ERR_HIP;
+    }
+    if (rc == PCL_OK && out) rc = pcl_seg_create_device(ctx, F, ctx->J, d_state, out);
+    {
+        pcl_free_synced_scope done;                                 // the stream these two were used on has been waited for
+        dev_free(d_state);
+        dev_free(d_drop);
+    }
+    return rc;
+}
+
 int pcl_batch_get(pcl_batch *b, int what, void *host) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;

@@ -307,6 +307,9 @@ struct pcl_batch {
     std::vector<double> logpi_u;             // ln pi of every state of utterance u (uniform 1/N, AcousticModel.py:1003-1006)
     int n_occ = 0;
     int *occ_ptr = nullptr, *occ_utt = nullptr, *occ_row0 = nullptr;   // unit -> [occ_ptr[u], occ_ptr[u+1]) -> (utterance, first emitting row)
+    int32_t *d_labels = nullptr;             // the labels on the device and the U + 1 offsets into them: uploaded by the first
+    int *d_label_off = nullptr;              // pcl_batch_align_segments of the batch, kept for the next
+    int label_max = 0, label_len_max = 0;    // largest unit id / longest label of the batch
 };
 
 // ---------------------------------------------------------------- scaled linear-domain forward-backward (hmm_fb_linear.hip)
@@ -520,6 +523,7 @@ int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshol
 int pcl_launch_fb_linear_post(pcl_ctx *ctx, pcl_batch *b);
 int pcl_launch_fb_to_log(pcl_ctx *ctx, pcl_batch *b, const double *m, const int *e, double *out);
 int pcl_launch_regroup(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_row_unit, int gmm_num, int32_t *d_frame_unit, int32_t *d_frame_k);
+int pcl_launch_align_segments(pcl_ctx *ctx, pcl_batch *b, int Lmax, int gmm_num, int32_t *d_frame_state, int32_t *d_dropped);
 int pcl_launch_ksai_gather(pcl_ctx *ctx, pcl_batch *b, double *dst);
 int pcl_launch_clock_probe(pcl_ctx *ctx, int spin_us, unsigned long long *d_out);
 int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision);

@@ -791,6 +791,20 @@ class Batch(object):
                 state[begin[u]:begin[u] + self.T[u]] = frame_state_of(fu[u], fk[u], gmm_num)
         return Segments(self.eng, state, self.eng.J)
 
+    def align_segments(self, want_map=False):
+        """viterbi() handed on to segmental training on the device, for a label-built batch (multi_process_data(init=False),
+        AcousticModel.py:736-764): the row -> unit map comes from the batch's labels, runs and slices are regroup()'s, an utterance
+        whose path misses a label unit is dropped (:751-757), and the Segments are built from the owner map without it leaving the
+        device.  Returns (Segments, dropped) with dropped the sorted list of dropped utterance indices; want_map=True:
+        (Segments, dropped, frame_state (F,) int32), the map segments() would have uploaded."""
+        state = np.empty(max(self.eng.F, 1), dtype=np.int32) if want_map else None
+        flags = np.empty(self.U, dtype=np.int32)
+        h = C.c_void_p()
+        self._check(self._lib.pcl_batch_align_segments(self._b, ptr(state), ptr(flags), C.byref(h)))
+        seg = Segments(self.eng, None, self.eng.J, handle=h)
+        dropped = np.flatnonzero(flags).tolist()
+        return (seg, dropped, state[:self.eng.F]) if want_map else (seg, dropped)
+
     def get(self, what):
         """List of per-utterance arrays (or a (U,...) array for per-utterance scalars)."""
         code = GET[what]
@@ -843,7 +857,7 @@ class Segments(object):
         self.eng = engine
         self._lib = engine._lib
         self.J = int(J)
-        if handle is not None:                        # a pcl_seg the library built itself (Engine.uniform_segments)
+        if handle is not None:                        # a pcl_seg the library built itself (Engine.uniform_segments, Batch.align_segments)
             self._s = handle
         else:
             self._s = C.c_void_p()
