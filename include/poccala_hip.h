@@ -102,7 +102,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start).
+ * pcl_model_upload / pcl_model_flat_start) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -468,6 +468,22 @@ int pcl_mfcc(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, 
              double overlap, int nfft, int filterbanks, int rank, int flags, const double *twiddle_cos,
              const double *twiddle_sin, const double *mel_response, const double *dct_matrix, double *out,
              int64_t out_rows);
+/* pcl_mfcc on int16 PCM, the samples as a wav file holds them (AudioProcessing.py:128-176 reads np.short): a quarter of the bytes of
+ * the float64 form on the wire.  The arguments are pcl_mfcc's with int16_t samples (sig_off still counts SAMPLES); a sample becomes a
+ * double at the kernel's load and every operation after it is pcl_mfcc's, so the result is bit-identical to pcl_mfcc on
+ * (double)sample.  Checks, error codes and texts (prefixed pcl_mfcc_pcm16) are pcl_mfcc's.
+ * The samples travel through two page-locked staging buffers owned by the context: the library copies chunk k+1 into one while the
+ * asynchronous H2D copy of chunk k runs from the other on a stream of its own; the kernels start behind the last chunk.  Samples per
+ * chunk: env PCL_PCM_CHUNK, read on EVERY call (default 2097152 = 4 MiB per buffer: the per-chunk queueing cost stays below 5 % of the
+ * chunk's host memcpy, which is the longer of the two overlapping legs, and the context pins 8 MiB); the buffers grow when a call asks
+ * for a larger chunk.  Device buffers come from the library's pool, and the four tables stay on the device with the context: they are
+ * uploaded again only when their geometry or their BYTES differ from the last call's (both for pcl_mfcc / pcl_frontend too).
+ * pcl_kernel_time groups, while timing is on: "pcm_stage" = host milliseconds spent copying into the staging buffers, "pcm_h2d" = the
+ * chunks' copies on the staging stream (for the float64 entry points: the host time of their one blocking copy).  Synchronous. */
+int pcl_mfcc_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t *sig_off, int framerate, double sampletime,
+                   double overlap, int nfft, int filterbanks, int rank, int flags, const double *twiddle_cos,
+                   const double *twiddle_sin, const double *mel_response, const double *dct_matrix, double *out,
+                   int64_t out_rows);
 
 /* ----------------------------------------------------------------- voice-activity detector (row f6: the second half of the front-end)
  * AudioProcessing.VAD.mfcc (StatisticalModel/AudioProcessing.py:538-543) = mel_distance (:462-478) -> osf (:480-507) -> detect (:509-536)
@@ -511,6 +527,14 @@ int pcl_frontend(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_o
                  int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin, const double *mel_response,
                  const double *dct_matrix, int simple_size, double alpha, double beta, int flags, int32_t *T_out, int64_t *frame_begin_out,
                  double *out_host, int64_t out_rows);
+/* pcl_frontend on int16 PCM: its arguments with int16_t samples, pcl_mfcc_pcm16's transfer (staging, PCL_PCM_CHUNK, pooled buffers,
+ * cached tables) in front of the same kernels.  T_out, frame_begin_out, the resident float32 (and float64) frames and out_host are
+ * bit-identical to pcl_frontend on (double)sample; every check runs before the first copy or launch, and a failed call leaves the
+ * previous frame matrix in place (error texts prefixed pcl_frontend_pcm16).  Synchronous. */
+int pcl_frontend_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
+                       int nfft, int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin,
+                       const double *mel_response, const double *dct_matrix, int simple_size, double alpha, double beta, int flags,
+                       int32_t *T_out, int64_t *frame_begin_out, double *out_host, int64_t out_rows);
 
 /* ----------------------------------------------------------------- multi-GPU (RCCL over xGMI)
  * Replaces the reference's file-based accumulator merge (LHMM.py:256-290, Clustering.py:314-367).

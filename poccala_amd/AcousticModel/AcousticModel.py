@@ -66,7 +66,8 @@ class AcousticModel(DataInitialization):
         None, nothing comes back to the host); an utterance that kept no frame has lens[u] = 0 and a (0, D) entry, which estep_batch /
         align_batch / segment_batch / regroup_batch / train_segments_batch skip.  Those helpers take data_list and upload it again: the
         route WITHOUT a feature upload is engine.label_batch / all_state_batch on (lens, begin) of the non-empty utterances, as
-        INTEGRATION.md shows.  The files must share one sampling rate."""
+        INTEGRATION.md shows.  The files must share one sampling rate.  init_audio reads the samples as np.int16 and they are handed on
+        as they are: the call takes Engine.frontend's int16 route (int16 on the wire, converted in the MFCC kernel), same bits."""
         from ..StatisticalModel.AudioProcessing import AudioProcessing
         eng = engine or default_engine()
         sigs, rate = [], None

@@ -49,9 +49,24 @@ def _report(res, tree):
 
 
 def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096):
-    """data_list: MFCC matrices (T_u, D).  Scores every GMM state for every frame (the decoder has no label) and runs the
-    token passing.  Returns per utterance (words, score, detail)."""
+    """data_list: MFCC matrices (T_u, D), which are uploaded -- or the (lens, begin) of frames already resident (Engine.frontend /
+    load_audio_batch(fetch=False)), the form AcousticModel's batch helpers take: nothing is uploaded, PCM goes to words without a host
+    round trip.  Scores every GMM state for every frame (the decoder has no label) and runs the token passing.  Returns per utterance
+    (words, score, detail); on the resident route an utterance of length 0 (the detector kept no frame) is left out of the batch and
+    reported as ([], -inf, None)."""
     engine = engine or default_engine()
+    if isinstance(data_list, tuple) and len(data_list) == 2 and np.ndim(data_list[0]) == 1:       # AcousticModel._resident's test
+        lens, begin = np.asarray(data_list[0], dtype=np.int32), np.asarray(data_list[1], dtype=np.int64)
+        keep = np.flatnonzero(lens > 0)
+        out = [([], -np.inf, None)] * len(lens)
+        if len(keep):
+            b = engine.all_state_batch(lens[keep], begin[keep])
+            b.score(precision)
+            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens)
+            b.close()
+            for u, r in zip(keep, _report(res, tree)):
+                out[u] = r
+        return out
     lens = np.array([len(d) for d in data_list], dtype=np.int32)
     begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
     engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))

@@ -16,7 +16,7 @@ import wave
 
 import numpy as np
 
-from .._lib import PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, as_c, ptr
+from .._lib import PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, all_int16, as_c, ptr
 from ..runtime import default_engine
 
 
@@ -52,9 +52,13 @@ def dct_basis(filterbanks, rank):
 
 def mfcc_batch(signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nfft=512, filterbanks=26, cal_energy=True,
                d1=False, d2=False, engine=None):
-    """MFCC matrices of many signals in one launch: list of (T_u, vec_num * {1,2,3}) float64 arrays."""
+    """MFCC matrices of many signals in one launch: list of (T_u, vec_num * {1,2,3}) float64 arrays.  When every signal is an np.int16
+    array the samples travel as int16 (pcl_mfcc_pcm16) and give the same bits; anything else is sent as float64 (Engine.frontend's rule)."""
     eng = engine or default_engine()
-    sigs = [np.asarray(s, dtype=np.float64).reshape(-1) for s in signals]
+    signals = list(signals)
+    pcm16 = all_int16(signals)
+    wire = np.int16 if pcm16 else np.float64
+    sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
     off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
     frames = [frame_count(len(s), framerate, sampletime, overlap) for s in sigs]
     rows = int(sum(frames))
@@ -63,12 +67,13 @@ def mfcc_batch(signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nf
     twc, tws = as_c(np.cos(2 * np.pi * n / nfft), np.float64), as_c(-np.sin(2 * np.pi * n / nfft), np.float64)
     resp = as_c(mel_filter_matrix(framerate, nfft, filterbanks), np.float64)
     dct = as_c(dct_basis(filterbanks, vec_num), np.float64)
-    flat = as_c(np.concatenate(sigs), np.float64)
+    flat = as_c(np.concatenate(sigs), wire)
     out = np.empty((rows, dim))
     flags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
-    eng._check(eng._lib.pcl_mfcc(eng._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
-                                 int(nfft), int(filterbanks), int(vec_num), flags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
-                                 ptr(out), C.c_int64(rows)))
+    call = eng._lib.pcl_mfcc_pcm16 if pcm16 else eng._lib.pcl_mfcc
+    eng._check(call(eng._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
+                    int(nfft), int(filterbanks), int(vec_num), flags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
+                    ptr(out), C.c_int64(rows)))
     cuts = np.cumsum(frames)[:-1]
     return np.split(out, cuts)
 

@@ -73,8 +73,10 @@ PROTOTYPES = {
     'pcl_batch_regroup': (_i, [_vp, _vp, _i, _vp, _vp]),
     'pcl_batch_align_segments': (_i, [_vp, _vp, _vp, C.POINTER(_vp)]),
     'pcl_mfcc': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
+    'pcl_mfcc_pcm16': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64]),
     'pcl_vad': (_i, [_vp, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     'pcl_frontend': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),
+    'pcl_frontend_pcm16': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),
     'pcl_timing_enable': (_i, [_vp, _i]),
     'pcl_device_count': (_i, [C.POINTER(_i)]),
     'pcl_units_upload': (_i, [_vp, _i, _i, _vp, _vp]),
@@ -134,7 +136,8 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise ImportError('%s is missing: run `python -c "import __graft_entry__ as g; g.build()"` '
                           '(or make -C poccala_amd/csrc).  There is no CPU fallback.' % LIB_PATH)
-    # A context owns five HIP streams (main, dynamic programming, producer / frame staging, descriptors, downloads).  The runtime
+    # A context owns five HIP streams (main, dynamic programming, producer / frame staging, descriptors, downloads; the first int16
+    # front-end call adds one for its PCM chunks, busy only inside that call while the main stream waits for it).  The runtime
     # multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default: two of the five then share a queue, and a command
     # that waits for an event (the download of step k waits for its forward-backward) holds up whatever sits behind it in that
     # queue (the scoring kernel of step k + 1).  Read when the HIP runtime starts: set before the library (and with it
@@ -168,3 +171,11 @@ def ptr(a):
 
 def as_c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def all_int16(signals):
+    """The front-end's route: True when `signals` is a non-empty sequence of np.int16 arrays and nothing else -- they travel as int16
+    (pcl_mfcc_pcm16 / pcl_frontend_pcm16).  Everything else (float arrays, whatever their values; other integer widths; lists; a mixed
+    sequence; no signal at all) takes the float64 entry points, as before there was a choice."""
+    signals = list(signals) if not isinstance(signals, (list, tuple)) else signals
+    return len(signals) > 0 and all(isinstance(s, np.ndarray) and s.dtype == np.int16 for s in signals)

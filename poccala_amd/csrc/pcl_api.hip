@@ -37,8 +37,17 @@ void pcl_timer_end(pcl_ctx *ctx, const char *which) {
     if (!t.ev.empty()) hipEventRecord(t.ev.back().second, ctx->stream);
 }
 
+void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms) {
+    if (!ctx->timing) return;
+    auto &t = ctx->timers[which];
+    t.host_ms += ms;
+    ++t.host_n;
+}
+
 static void drop_timers(pcl_ctx *ctx) {
     for (auto &kv : ctx->timers) {
+        kv.second.host_ms = 0.0;
+        kv.second.host_n = 0;
         for (auto &p : kv.second.ev) {
             hipEventDestroy(p.first);
             hipEventDestroy(p.second);
@@ -279,7 +288,7 @@ int pcl_destroy(pcl_ctx *ctx) {
     // is there for the reader), THEN the communicator (collectives and the pipelined exchange run on these streams and stream_comm;
     // rounds 1-5 destroyed it first), the buried batches, events, memory, streams.
     for (int round = 0; round < 2; ++round) {
-        hipStream_t all[] = {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_d2h, ctx->stream_desc, ctx->stream_comm};
+        hipStream_t all[] = {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_d2h, ctx->stream_desc, ctx->stream_comm, ctx->pcm.stream};
         for (hipStream_t s : all)
             if (s) hipStreamSynchronize(s);
     }
@@ -294,7 +303,8 @@ int pcl_destroy(pcl_ctx *ctx) {
     ctx->ev_zero = ctx->ev_zero_src = nullptr;
     if (ctx->desc_pin) hipHostFree(ctx->desc_pin);
     ctx->desc_pin = nullptr;
-    drop_timers(ctx);
+    drop_timers(ctx);                                            // (the per-chunk events of the staging stream's "pcm_h2d" group among them)
+    pcl_mfcc_release(ctx);                                       // drained above: no copy reads the staging buffers, no event is waited for
     free_model(ctx);
     pcl_units_release(ctx);
     release_frames32(ctx);
@@ -377,6 +387,10 @@ int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launc
             hipEventDestroy(p.second);
         }
         it->second.ev.clear();
+        tot += (float)it->second.host_ms;
+        n += it->second.host_n;
+        it->second.host_ms = 0.0;
+        it->second.host_n = 0;
     }
     if (total_ms) *total_ms = tot;
     if (launches) *launches = n;

@@ -60,6 +60,26 @@ struct ActiveFrame {
 // ---------------------------------------------------------------- host-side objects
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    double host_ms = 0.0;   // groups measured on the host clock ("pcm_stage", the float64 route's blocking "pcm_h2d"): added to the events' sum
+    int host_n = 0;
+};
+
+// The int16 PCM route of the front-end (mfcc.hip): two page-locked staging buffers of one chunk each and the stream their H2D copies run
+// on, beside the host's memcpy of the next chunk.  Made on the first int16 call, kept with the context, released by pcl_destroy after it
+// has drained `stream`.  ev[s] = the last copy that read pin[s] is done.
+struct PcmStage {
+    hipStream_t stream = nullptr;
+    int16_t *pin[2] = {nullptr, nullptr};
+    size_t cap = 0;                          // samples per buffer
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+// The four host-built MFCC tables (twiddle cos | sin | mel response | DCT basis) in ONE device block, kept with the context: `host` is the
+// copy the next call's tables are compared with byte for byte (the caller builds them: equal geometry does not mean equal contents).
+struct MfccTables {
+    double *d = nullptr;
+    size_t cap = 0;                          // doubles
+    int nfft = 0, nfilt = 0, rank = 0;       // nfft = 0: nothing valid on the device
+    std::vector<double> host;
 };
 
 // A grow-only device array: a pointer, a capacity (elements) and two functions, defined beside dev_alloc / dev_free below.
@@ -227,6 +247,8 @@ struct pcl_ctx {
     void *desc_dst[24];          // the staged entries of the open group (PCL_DESC_MAX)
     unsigned long long desc_off[24], desc_bytes[24];
     int desc_n = 0;
+    PcmStage pcm;
+    MfccTables mfcc_tab;
 };
 
 struct pcl_batch {
@@ -614,8 +636,12 @@ int pcl_model_finish(pcl_ctx *ctx);
 // pcl_seg_create from an owner array that is already on the device (F = ctx->F entries, every one -1 or in [0, J): the CALLER guarantees it,
 // nothing is validated here); the array is only read and stays the caller's.  gmm_segment.hip.
 int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_frame_state, pcl_seg **out);
-// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (hipMalloc: the caller hipFree's it), complete on
-// return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.
-int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime,
-                    double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos, const double *twiddle_sin,
-                    const double *mel_response, const double *dct_matrix, int64_t out_rows, double **d_out, std::vector<long long> *row_off);
+// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (from the pool: the caller dev_free's it),
+// complete on return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.  pcm16: `signal` is int16_t
+// samples, which travel through the context's page-locked staging; otherwise double, copied from the caller's memory as it is.
+int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const void *signal, bool pcm16, const int64_t *sig_off, int framerate,
+                    double sampletime, double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos,
+                    const double *twiddle_sin, const double *mel_response, const double *dct_matrix, int64_t out_rows, double **d_out,
+                    std::vector<long long> *row_off);
+void pcl_mfcc_release(pcl_ctx *ctx);          // the staging buffers, their events and stream, the cached tables (pcl_destroy, streams drained)
+void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms);   // a host-clock entry of a timer group (only while timing is on)

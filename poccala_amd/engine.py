@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import GET, SEG_GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, as_c, ptr
+from ._lib import GET, SEG_GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, all_int16, as_c, ptr
 
 
 def device_count():
@@ -165,22 +165,29 @@ class Engine(object):
         all_state_batch -- an utterance that kept no frame has length 0 and must be left out of the lists handed to them (lens > 0:
         a batch takes utterances of at least one frame; AcousticModel's batch helpers, which take host arrays, skip empty ones
         themselves).  If no frame of any utterance survives, every length is 0 and the frame matrix is empty.  vad=False: every MFCC row is kept.  keep_f64: the float64 copy parity mode reads is kept too instead of being derived
-        from the float32 rows.  fetch=True: (lens, begin, rows) with rows the (sum lens, D) float64 survivors, for inspection."""
+        from the float32 rows.  fetch=True: (lens, begin, rows) with rows the (sum lens, D) float64 survivors, for inspection.
+        When EVERY signal is an np.int16 array (what a wav file holds, and what AudioProcessing.MFCC.init_audio reads) the samples are
+        concatenated and sent as int16 (pcl_frontend_pcm16: a quarter of the bytes, page-locked staging, no float64 copy on the host)
+        and become float64 in the kernel -- the same bits as the float64 route, which anything else takes (float arrays that hold
+        integers, mixed lists, Python lists): nothing is rounded silently."""
         from .StatisticalModel.AudioProcessing import frame_count, mfcc_tables
-        sigs = [np.asarray(s, dtype=np.float64).reshape(-1) for s in signals]
+        signals = list(signals)
+        pcm16 = all_int16(signals)
+        wire = np.int16 if pcm16 else np.float64
+        sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
         off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
         rows = int(sum(frame_count(len(s), framerate, sampletime, overlap) for s in sigs))
         dim = vec_num * (3 if (d1 and d2) else 2 if d1 else 1)
         twc, tws, resp, dct = mfcc_tables(framerate, vec_num, nfft, filterbanks)
-        flat = as_c(np.concatenate(sigs), np.float64)
+        flat = as_c(np.concatenate(sigs), wire)
         mflags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
         flags = (0 if vad else _lib.PCL_FRONTEND_NO_VAD) | (_lib.PCL_FRONTEND_KEEP_F64 if keep_f64 else 0)
         lens, begin = np.empty(len(sigs), dtype=np.int32), np.empty(len(sigs), dtype=np.int64)
         out = np.empty((max(rows, 1), dim)) if fetch else None
-        self._check(self._lib.pcl_frontend(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
-                                           int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
-                                           int(simple_size), float(alpha), float(beta), flags, ptr(lens), ptr(begin), ptr(out),
-                                           C.c_int64(rows)))
+        call = self._lib.pcl_frontend_pcm16 if pcm16 else self._lib.pcl_frontend
+        self._check(call(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
+                         int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
+                         int(simple_size), float(alpha), float(beta), flags, ptr(lens), ptr(begin), ptr(out), C.c_int64(rows)))
         self.F, self.FD = int(lens.sum()), dim
         self._frames_key = None
         return (lens, begin, out[:self.F].copy()) if fetch else (lens, begin)
