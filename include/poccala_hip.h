@@ -93,8 +93,14 @@ int pcl_init(int device, pcl_ctx **out);
  * streams.  Batches the caller never destroyed are NOT walked: their device blocks stay in the process-wide pool's books (a
  * leak, not a fault) -- destroy batches first.  Page-locked host memory from pcl_host_alloc belongs to the caller: free it
  * with pcl_host_free BEFORE pcl_destroy (pcl_host_free itself waits for every stream of the context, because hipHostFree does
- * not wait for copies still using the block).  tools/lifecycle_stress.py exercises all of this. */
+ * not wait for copies still using the block).  tools/lifecycle_stress.py exercises all of this.
+ * Inside the library every device array and event belongs to one owning member of the context, the batch or the segment set, or to a
+ * local of the call that made it: destroying the handle (or leaving the call, on any path) gives them back; pcl_pool_stats counts. */
 int pcl_destroy(pcl_ctx *ctx);
+/* The process-wide device memory pool's books (any argument may be NULL): blocks / bytes handed out and not yet given back (0 / 0 once
+ * every handle of the process is destroyed), bytes cached for reuse, successful hipMalloc calls so far, and the device-wide waits
+ * (hipDeviceSynchronize) its frees have made so far. */
+int pcl_pool_stats(size_t *handed_out_blocks, size_t *handed_out_bytes, size_t *cached_bytes, uint64_t *device_allocs, uint64_t *device_waits);
 const char *pcl_last_error(pcl_ctx *ctx); /* ctx may be NULL: error of a failed pcl_init */
 int pcl_sync(pcl_ctx *ctx);
 /* name (cap bytes), compute units, HBM bytes */

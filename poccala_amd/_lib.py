@@ -27,6 +27,7 @@ PROTOTYPES = {
     'pcl_destroy': (_i, [_vp]),
     'pcl_last_error': (C.c_char_p, [_vp]),
     'pcl_sync': (_i, [_vp]),
+    'pcl_pool_stats': (_i, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     'pcl_device_info': (_i, [_vp, C.c_char_p, _i, C.POINTER(_i), C.POINTER(C.c_size_t)]),
     'pcl_kernel_time': (_i, [_vp, C.c_char_p, C.POINTER(C.c_float), C.POINTER(_i)]),
     'pcl_model_upload': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),

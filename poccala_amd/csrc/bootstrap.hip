@@ -124,18 +124,6 @@ __global__ __launch_bounds__(256) void uniform_map_kernel(const int *__restrict_
     }
 }
 
-struct DevBuf {                                          // a pool block released when the call returns
-    void *p = nullptr;
-    ~DevBuf() { if (p) pcl_pool_free(p); }
-    template <typename T>
-    T *as() const { return static_cast<T *>(p); }
-};
-int buf_alloc(pcl_ctx *ctx, DevBuf &b, size_t bytes) {
-    b.p = pcl_pool_alloc(ctx->device, bytes ? bytes : 1);
-    if (!b.p) PCL_FAIL(ctx, PCL_ERR_NOMEM, "device memory: %zu bytes", bytes);
-    return PCL_OK;
-}
-
 // utterance ranges against the current frame matrix; begin_out = frame_begin, or the utterances back to back
 int check_ranges(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, std::vector<long long> &begin_out) {
     begin_out.resize(U);
@@ -168,25 +156,26 @@ int moments_device(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const
     if (n_blocks_ll > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: sample of %lld rows is too large", who, n);
     const int n_blocks = (int)n_blocks_ll;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevBuf d_roff, d_begin, d_partial;
-    TRY(buf_alloc(ctx, d_roff, roff.size() * sizeof(long long)));
-    TRY(buf_alloc(ctx, d_begin, begin.size() * sizeof(long long)));
-    TRY(buf_alloc(ctx, d_partial, (size_t)n_blocks * 64 * sizeof(double)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_roff.p, roff.data(), roff.size() * sizeof(long long)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin.p, begin.data(), begin.size() * sizeof(long long)));
+    DevBuf<long long> d_roff, d_begin;
+    DevBuf<double> d_partial;
+    TRY(d_roff.alloc(ctx, roff.size()));
+    TRY(d_begin.alloc(ctx, begin.size()));
+    TRY(d_partial.alloc(ctx, (size_t)n_blocks * 64));
+    HIPCHK(ctx, pcl_h2d(ctx, d_roff, roff.data(), roff.size() * sizeof(long long)));
+    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), begin.size() * sizeof(long long)));
     const int FD = ctx->FD, Dh = ctx->FDhost;
     hipStream_t st = ctx->stream;
 #define MOM_PARTIAL(TY, SQ, FR)                                                                                                                     \
-    hipLaunchKernelGGL((moments_partial_kernel<TY, SQ>), dim3(n_blocks), dim3(MOM_T), 0, st, FR, FD, Dh, d_roff.as<long long>(), d_begin.as<long long>(), \
-                       n_utts, n, step, d_mean, d_partial.as<double>())
+    hipLaunchKernelGGL((moments_partial_kernel<TY, SQ>), dim3(n_blocks), dim3(MOM_T), 0, st, FR, FD, Dh, d_roff, d_begin, \
+                       n_utts, n, step, d_mean, d_partial)
     const bool f64 = ctx->frames64 != nullptr;
     pcl_timer_begin(ctx, "moments");
     if (f64) MOM_PARTIAL(double, false, ctx->frames64);
     else MOM_PARTIAL(float, false, ctx->frames32);
-    hipLaunchKernelGGL(moments_final_kernel<false>, dim3(1), dim3(64), 0, st, d_partial.as<double>(), n_blocks, n, Dh, d_mean);
+    hipLaunchKernelGGL(moments_final_kernel<false>, dim3(1), dim3(64), 0, st, d_partial, n_blocks, n, Dh, d_mean);
     if (f64) MOM_PARTIAL(double, true, ctx->frames64);
     else MOM_PARTIAL(float, true, ctx->frames32);
-    hipLaunchKernelGGL(moments_final_kernel<true>, dim3(1), dim3(64), 0, st, d_partial.as<double>(), n_blocks, n, Dh, d_var);
+    hipLaunchKernelGGL(moments_final_kernel<true>, dim3(1), dim3(64), 0, st, d_partial, n_blocks, n, Dh, d_var);
 #undef MOM_PARTIAL
     pcl_timer_end(ctx, "moments");
     HIPCHK(ctx, hipGetLastError());
@@ -241,11 +230,11 @@ int pcl_frames_moments(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *fra
     if (!ctx) return PCL_ERR_INVALID;
     if (!mean_out || !var_out) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_frames_moments: NULL destination");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevBuf d_mv;
-    TRY(buf_alloc(ctx, d_mv, 128 * sizeof(double)));
+    DevBuf<double> d_mv;
+    TRY(d_mv.alloc(ctx, 128));
     long long n = 0;
-    TRY(moments_device(ctx, "pcl_frames_moments", U, T, frame_begin, n_utts, step, d_mv.as<double>(), d_mv.as<double>() + 64, &n));
-    TRY(moments_to_host(ctx, d_mv.as<double>(), d_mv.as<double>() + 64, mean_out, var_out));
+    TRY(moments_device(ctx, "pcl_frames_moments", U, T, frame_begin, n_utts, step, d_mv, d_mv + 64, &n));
+    TRY(moments_to_host(ctx, d_mv, d_mv + 64, mean_out, var_out));
     if (n_rows_out) *n_rows_out = n;
     return PCL_OK;
 }
@@ -263,9 +252,9 @@ int pcl_model_flat_start(pcl_ctx *ctx, int J, int M, int D, const double *mean, 
     if (ctx->frames32 && ctx->F > 0 && ctx->FDhost != D)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: D = %d, the frame matrix in place has %d features", who, D, ctx->FDhost);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevBuf d_in;
-    TRY(buf_alloc(ctx, d_in, (size_t)(2 * D + M) * sizeof(double)));
-    double *d_mean = d_in.as<double>(), *d_var = d_mean + D, *d_coeff = coeff ? d_var + D : nullptr;
+    DevBuf<double> d_in;
+    TRY(d_in.alloc(ctx, (size_t)(2 * D + M)));
+    double *d_mean = d_in, *d_var = d_mean + D, *d_coeff = coeff ? d_var + D : nullptr;
     HIPCHK(ctx, pcl_h2d(ctx, d_mean, mean, (size_t)D * sizeof(double)));
     HIPCHK(ctx, pcl_h2d(ctx, d_var, var, (size_t)D * sizeof(double)));
     if (coeff) HIPCHK(ctx, pcl_h2d(ctx, d_coeff, coeff, (size_t)M * sizeof(double)));
@@ -281,19 +270,19 @@ int pcl_flat_start(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_b
     TRY(check_shape(ctx, who, J, M, D));
     TRY(check_coeff(ctx, who, M, coeff));
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    DevBuf d_mv, d_c;
-    TRY(buf_alloc(ctx, d_mv, 128 * sizeof(double)));
-    TRY(buf_alloc(ctx, d_c, (size_t)M * sizeof(double)));
+    DevBuf<double> d_mv, d_c;
+    TRY(d_mv.alloc(ctx, 128));
+    TRY(d_c.alloc(ctx, (size_t)M));
     long long n = 0;
-    TRY(moments_device(ctx, who, U, T, frame_begin, n_utts, step, d_mv.as<double>(), d_mv.as<double>() + 64, &n));
+    TRY(moments_device(ctx, who, U, T, frame_begin, n_utts, step, d_mv, d_mv + 64, &n));
     // (a non-finite frame makes the moments NaN: they are read back before the model in place is given up)
     std::vector<double> mv(2 * (size_t)D);
-    TRY(moments_to_host(ctx, d_mv.as<double>(), d_mv.as<double>() + 64, mv.data(), mv.data() + D));
+    TRY(moments_to_host(ctx, d_mv, d_mv + 64, mv.data(), mv.data() + D));
     for (int d = 0; d < D; ++d)
         if (!std::isfinite(mv[d]) || !std::isfinite(mv[D + d]))
             PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: feature %d of the sample has mean %g, variance %g (non-finite frames)", who, d, mv[d], mv[D + d]);
-    if (coeff) HIPCHK(ctx, pcl_h2d(ctx, d_c.p, coeff, (size_t)M * sizeof(double)));
-    TRY(flat_start_device(ctx, who, J, M, D, d_mv.as<double>(), d_mv.as<double>() + 64, coeff ? d_c.as<double>() : nullptr, flags));
+    if (coeff) HIPCHK(ctx, pcl_h2d(ctx, d_c, coeff, (size_t)M * sizeof(double)));
+    TRY(flat_start_device(ctx, who, J, M, D, d_mv, d_mv + 64, coeff ? d_c : nullptr, flags));
     if (mean_out) memcpy(mean_out, mv.data(), (size_t)D * sizeof(double));
     if (var_out) memcpy(var_out, mv.data() + D, (size_t)D * sizeof(double));
     if (n_rows_out) *n_rows_out = n;
@@ -336,27 +325,28 @@ int pcl_uniform_segments(pcl_ctx *ctx, int U, const int32_t *label_len, const in
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long F = ctx->F;
-    DevBuf d_state, d_ll, d_lo, d_lab, d_T, d_begin;
-    TRY(buf_alloc(ctx, d_state, (size_t)F * sizeof(int)));
-    TRY(buf_alloc(ctx, d_ll, (size_t)U * sizeof(int)));
-    TRY(buf_alloc(ctx, d_lo, (size_t)(U + 1) * sizeof(long long)));
-    TRY(buf_alloc(ctx, d_lab, (size_t)std::max<long long>(1, loff[U]) * sizeof(int)));
-    TRY(buf_alloc(ctx, d_T, (size_t)U * sizeof(int)));
-    TRY(buf_alloc(ctx, d_begin, (size_t)U * sizeof(long long)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_ll.p, label_len, (size_t)U * sizeof(int)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_lo.p, loff.data(), (size_t)(U + 1) * sizeof(long long)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_lab.p, labels, (size_t)loff[U] * sizeof(int)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_T.p, T, (size_t)U * sizeof(int)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin.p, begin.data(), (size_t)U * sizeof(long long)));
-    HIPCHK(ctx, hipMemsetAsync(d_state.p, 0xff, (size_t)F * sizeof(int), ctx->stream));
+    DevBuf<int> d_state, d_ll, d_lab, d_T;
+    DevBuf<long long> d_lo, d_begin;
+    TRY(d_state.alloc(ctx, (size_t)F));
+    TRY(d_ll.alloc(ctx, (size_t)U));
+    TRY(d_lo.alloc(ctx, (size_t)(U + 1)));
+    TRY(d_lab.alloc(ctx, (size_t)std::max<long long>(1, loff[U])));
+    TRY(d_T.alloc(ctx, (size_t)U));
+    TRY(d_begin.alloc(ctx, (size_t)U));
+    HIPCHK(ctx, pcl_h2d(ctx, d_ll, label_len, (size_t)U * sizeof(int)));
+    HIPCHK(ctx, pcl_h2d(ctx, d_lo, loff.data(), (size_t)(U + 1) * sizeof(long long)));
+    HIPCHK(ctx, pcl_h2d(ctx, d_lab, labels, (size_t)loff[U] * sizeof(int)));
+    HIPCHK(ctx, pcl_h2d(ctx, d_T, T, (size_t)U * sizeof(int)));
+    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), (size_t)U * sizeof(long long)));
+    HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int), ctx->stream));
     int Tmax = 1;
     for (int u = 0; u < U; ++u) Tmax = std::max(Tmax, (int)T[u]);
-    hipLaunchKernelGGL(uniform_map_kernel, dim3(std::min(64, (Tmax + 255) / 256), U), dim3(256), 0, ctx->stream, d_ll.as<int>(), d_lo.as<long long>(), d_lab.as<int>(),
-                       d_T.as<int>(), d_begin.as<long long>(), gmm_num, d_state.as<int>());
+    hipLaunchKernelGGL(uniform_map_kernel, dim3(std::min(64, (Tmax + 255) / 256), U), dim3(256), 0, ctx->stream, d_ll, d_lo, d_lab,
+                       d_T, d_begin, gmm_num, d_state);
     HIPCHK(ctx, hipGetLastError());
-    if (frame_state_out) HIPCHK(ctx, hipMemcpyAsync(frame_state_out, d_state.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (frame_state_out) HIPCHK(ctx, hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (out) TRY(pcl_seg_create_device(ctx, F, J, d_state.as<int>(), out));
+    if (out) TRY(pcl_seg_create_device(ctx, F, J, d_state, out));
     return PCL_OK;
 }
 

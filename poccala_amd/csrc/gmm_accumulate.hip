@@ -680,7 +680,7 @@ int reserve_scratch(pcl_ctx *ctx, const pcl_batch *b) {
     TRY(a.cnt.reserve(ctx, nseg));
     TRY(a.off.reserve(ctx, nseg));
     TRY(a.list.reserve(ctx, frames));
-    for (GrowBuf<int> *v : {&a.split_flag, &a.work_states, &a.seg_lo, &a.seg_hi}) TRY(v->reserve(ctx, ns));
+    for (DevBuf<int> *v : {&a.split_flag, &a.work_states, &a.seg_lo, &a.seg_hi}) TRY(v->reserve(ctx, ns));
     return PCL_OK;
 }
 
@@ -789,7 +789,7 @@ int produce_group(pcl_ctx *ctx, const AccPass &p, int g, bool overlap, hipStream
 int run_groups(pcl_ctx *ctx, pcl_batch *b, const AccPass &p) {
     AccScratch &a = ctx->acc;
     if (!a.ev_start)                                                 // (ev_start last: it stands for the whole set)
-        for (hipEvent_t *e : {&a.ev_prod[0], &a.ev_cons[0], &a.ev_prod[1], &a.ev_cons[1], &a.ev_start}) HIPCHK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (LazyEvent *e : {&a.ev_prod[0], &a.ev_cons[0], &a.ev_prod[1], &a.ev_cons[1], &a.ev_start}) HIPCHK(ctx, e->make());
     static const bool overlap = !(getenv("PCL_ACC_OVERLAP") && atoi(getenv("PCL_ACC_OVERLAP")) == 0);
     hipStream_t ps = overlap ? ctx->stream_aux : ctx->stream;
     HIPCHK(ctx, hipEventRecord(a.ev_start, ctx->stream));            // the active-frame lists are complete
@@ -857,16 +857,7 @@ int run_direct(pcl_ctx *ctx, int precision, int first, int count) {
 
 }  // namespace
 
-void pcl_accumulate_release(pcl_ctx *ctx) {
-    AccScratch &a = ctx->acc;
-    a.cnt.release(); a.off.release(); a.list.release();
-    a.work_states.release(); a.seg_lo.release(); a.seg_hi.release(); a.split_flag.release();
-    for (int k = 0; k < 2; ++k) { a.images[k].release(); a.tile_off[k].release(); a.tile_mask[k].release(); a.state_flag[k].release(); }
-    for (hipEvent_t *e : {&a.ev_prod[0], &a.ev_cons[0], &a.ev_prod[1], &a.ev_cons[1], &a.ev_start}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-}
+void pcl_accumulate_release(pcl_ctx *ctx) { ctx->acc = {}; }
 
 int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision) {
     if (b->n_segs == 0) return PCL_OK;

@@ -562,7 +562,7 @@ int pcl_launch_acc16_consume(pcl_ctx *ctx, int first, int ns, int buf, bool fres
     const int *ws = a.work_states.p + first;
 #define CONSUME16F(DD, FR)                                                                                                    \
     hipLaunchKernelGGL((acc16_consumer_kernel<DD, FR>), dim3(nblocks), dim3(AW * 64), 0, stream,                              \
-                       reinterpret_cast<const uint4 *>(a.images[buf].p), reinterpret_cast<const uint4 *>(ctx->pm16f), ctx->centers32, ctx->fscale, \
+                       reinterpret_cast<const uint4 *>(a.images[buf].p), reinterpret_cast<const uint4 *>(ctx->pm16f.p), ctx->centers32, ctx->fscale, \
                        ctx->mean64, ctx->M, ctx->Mpad, nmt, ns, ws, a.tile_off[buf].p, 0, 100.0, ctx->st_acc, ctx->st_alpha,      \
                        ctx->st_mean, ctx->st_cov, ctx->d_npt, ctx->d_nbad, (ctx->compact_main && ctx->D <= 48) ? ctx->d_good_idx : (const int *)nullptr)
     switch (ctx->D) {

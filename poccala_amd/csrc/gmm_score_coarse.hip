@@ -829,7 +829,7 @@ __global__ __launch_bounds__(256) void compact_main_kernel(const double *__restr
 template <int D, int NP>
 void launch_coarse_p(pcl_ctx *ctx, pcl_batch *b, const CoarseExact &ex, unsigned long long *counters) {
     hipLaunchKernelGGL((gmm_score_coarse_kernel<D, PCL_COARSE_NT, NP>), dim3(b->n_tiles_c), dim3(WG), 0, ctx->stream, ctx->frames32,
-                       reinterpret_cast<const uint4 *>(ctx->pmc), ctx->fscale_c, ctx->centers32, ctx->Mpad32 / 32, ctx->d_nct, b->d_tiles_c, b->d_segs,
+                       reinterpret_cast<const uint4 *>(ctx->pmc.p), ctx->fscale_c, ctx->centers32, ctx->Mpad32 / 32, ctx->d_nct, b->d_tiles_c, b->d_segs,
                        b->Bt, b->d_tile_flags_c, ctx->kzero_c, ctx->kgap_c, ex, counters);
 }
 template <int D>
@@ -848,14 +848,7 @@ bool pcl_coarse_enabled(const pcl_ctx *ctx) { return pcl_coarse_enabled_for(ctx,
 int pcl_coarse_tile_frames() { return WG / 64 * PCL_COARSE_NT * 32; }
 
 void pcl_coarse_release(pcl_ctx *ctx) {
-    dev_free(ctx->pmc);
-    dev_free(ctx->fscale_c);
-    dev_free(ctx->kzero_c);
-    dev_free(ctx->kgap_c);
-    dev_free(ctx->rows_c);
-    dev_free(ctx->k2c);
-    dev_free(ctx->d_nct);
-    dev_free(ctx->d_coarse_counter);
+    static_cast<CoarseDev &>(*ctx) = {};
     ctx->coarse_gen = -1;
 }
 
@@ -864,21 +857,21 @@ int pcl_ensure_coarse(pcl_ctx *ctx) {
     if (ctx->coarse_gen == ctx->model_gen && ctx->pmc) return PCL_OK;
     const int KS8 = (ctx->D + 7) / 8, nmt = ctx->Mpad32 / 32;
     if (!ctx->pmc) {
-        TRY(dev_alloc(ctx, &ctx->pmc, (size_t)ctx->J * nmt * (2 * KS8 * 64) * 8));      // unsigned short elements: 8 per uint4
-        TRY(dev_alloc(ctx, &ctx->fscale_c, (size_t)ctx->J * 2 * KS8 * 8));
-        TRY(dev_alloc(ctx, &ctx->kzero_c, (size_t)ctx->J));
-        TRY(dev_alloc(ctx, &ctx->kgap_c, (size_t)ctx->J));
-        TRY(dev_alloc(ctx, &ctx->rows_c, (size_t)ctx->J * ctx->Mpad * ctx->D * 2));
-        TRY(dev_alloc(ctx, &ctx->k2c, (size_t)ctx->J * ctx->Mpad));
-        TRY(dev_alloc(ctx, &ctx->d_nct, (size_t)ctx->J));
-        TRY(dev_alloc(ctx, &ctx->d_coarse_counter, (size_t)2));              // [pairs evaluated in direct form, tiles given up]
+        TRY(ctx->pmc.alloc(ctx, (size_t)ctx->J * nmt * (2 * KS8 * 64) * 8));      // unsigned short elements: 8 per uint4
+        TRY(ctx->fscale_c.alloc(ctx, (size_t)ctx->J * 2 * KS8 * 8));
+        TRY(ctx->kzero_c.alloc(ctx, (size_t)ctx->J));
+        TRY(ctx->kgap_c.alloc(ctx, (size_t)ctx->J));
+        TRY(ctx->rows_c.alloc(ctx, (size_t)ctx->J * ctx->Mpad * ctx->D * 2));
+        TRY(ctx->k2c.alloc(ctx, (size_t)ctx->J * ctx->Mpad));
+        TRY(ctx->d_nct.alloc(ctx, (size_t)ctx->J));
+        TRY(ctx->d_coarse_counter.alloc(ctx, (size_t)2));              // [pairs evaluated in direct form, tiles given up]
         HIPCHK(ctx, hipMemsetAsync(ctx->d_coarse_counter, 0, 2 * sizeof(unsigned long long), ctx->stream));
     }
     pcl_timer_begin(ctx, "derive_coarse");
     if (ctx->D > 48) PCL_FAIL(ctx, PCL_ERR_INVALID, "internal: coarse layout for D=%d", ctx->D);
     hipLaunchKernelGGL((coarse_derive_kernel<48>), dim3(ctx->J), dim3(256), 0, ctx->stream, ctx->mean64, ctx->var64, ctx->w64, ctx->centers32, ctx->M,
-                       ctx->Mpad, ctx->Mpad32, ctx->D, ctx->Dhost, ctx->model_flags, ctx->d_bad_idx, ctx->d_nbad, reinterpret_cast<uint4 *>(ctx->pmc),
-                       ctx->fscale_c, ctx->kzero_c, ctx->k2c, ctx->d_nct, ctx->coarse_np, ctx->kgap_c, reinterpret_cast<float2 *>(ctx->rows_c));
+                       ctx->Mpad, ctx->Mpad32, ctx->D, ctx->Dhost, ctx->model_flags, ctx->d_bad_idx, ctx->d_nbad, reinterpret_cast<uint4 *>(ctx->pmc.p),
+                       ctx->fscale_c, ctx->kzero_c, ctx->k2c, ctx->d_nct, ctx->coarse_np, ctx->kgap_c, reinterpret_cast<float2 *>(ctx->rows_c.p));
     pcl_timer_end(ctx, "derive_coarse");
     HIPCHK(ctx, hipGetLastError());
     ctx->coarse_gen = ctx->model_gen;
@@ -889,7 +882,7 @@ int pcl_ensure_coarse(pcl_ctx *ctx) {
 int pcl_launch_score_coarse(pcl_ctx *ctx, pcl_batch *b) {
     if (b->n_tiles_c == 0) return PCL_OK;
     TRY(pcl_ensure_coarse(ctx));
-    const CoarseExact ex{reinterpret_cast<const float2 *>(ctx->rows_c), ctx->k2c, ctx->d_nbad, ctx->Mpad, ctx->Dhost};
+    const CoarseExact ex{reinterpret_cast<const float2 *>(ctx->rows_c.p), ctx->k2c, ctx->d_nbad, ctx->Mpad, ctx->Dhost};
     unsigned long long *counters = ctx->coarse_stats ? ctx->d_coarse_counter : nullptr;
     pcl_timer_begin(ctx, "score_coarse");
     switch (ctx->D) {
@@ -913,7 +906,7 @@ int pcl_launch_compact_main(pcl_ctx *ctx, int j_lo, int j_hi) {
     }
     hipLaunchKernelGGL((compact_main_kernel<48>), dim3(j_hi - j_lo), dim3(256), 0, ctx->stream, ctx->mean64, ctx->var64, ctx->w64, ctx->centers32, ctx->M,
                        ctx->Mpad, ctx->Mpad32, ctx->D, ctx->Dhost, ctx->model_flags, j_lo, ctx->d_good_idx, ctx->d_nbad, ctx->fscale, ctx->kzero,
-                       reinterpret_cast<uint4 *>(ctx->pm16f));
+                       reinterpret_cast<uint4 *>(ctx->pm16f.p));
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }

@@ -309,7 +309,7 @@ void launch16_t(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles)
     constexpr size_t static_lds = 2 * (size_t)(2 * ((D + 7) / 8)) * 64 * 16;
     const size_t pad = (ctx->score_wgs_per_cu == 2 && static_lds < (56u << 10)) ? (56u << 10) - static_lds : 0;
     hipLaunchKernelGGL((gmm_score_split16_kernel<D, PCL_SPLIT16_NT>), dim3(n_tiles), dim3(WG), pad, ctx->stream, ctx->frames32,
-                       reinterpret_cast<const uint4 *>(ctx->pm16f), ctx->fscale, ctx->centers32, ctx->Mpad32 / 32, tiles, b->d_segs,
+                       reinterpret_cast<const uint4 *>(ctx->pm16f.p), ctx->fscale, ctx->centers32, ctx->Mpad32 / 32, tiles, b->d_segs,
                        b->Bt, b->d_tile_flags, ctx->kzero, ctx->d_non, ctx->d_npt);
 }
 

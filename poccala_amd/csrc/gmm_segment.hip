@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include <limits>
+#include <memory>
 
 #include "pcl_internal.h"
 
@@ -22,12 +23,12 @@ struct pcl_seg {
     int J = 0, FD = 0, FDhost = 0;
     long long F = 0, Ntot = 0;
     std::vector<int> counts, off;      // off: J + 1 entries
-    int *d_counts = nullptr, *d_off = nullptr, *d_order = nullptr;   // order[off[j] + i] = frame row of the i-th frame of state j
-    float *G32 = nullptr;              // (Ntot, FD) frames in segment order
-    double *G64 = nullptr;             // ... float64 (made when first needed)
+    DevBuf<int> d_counts, d_off, d_order;   // order[off[j] + i] = frame row of the i-th frame of state j
+    DevBuf<float> G32;                 // (Ntot, FD) frames in segment order
+    DevBuf<double> G64;                // ... float64 (made when first needed)
     int K = 0;                         // of the last pcl_seg_kmeans
-    int *d_assign = nullptr, *d_corder = nullptr, *d_coff = nullptr, *d_seed = nullptr;
-    double *d_centres = nullptr;       // (J, K, FD)
+    DevBuf<int> d_assign, d_corder, d_coff, d_seed;
+    DevBuf<double> d_centres;          // (J, K, FD)
 };
 
 namespace {
@@ -400,44 +401,33 @@ int launch_assign(pcl_seg *s, const T *G, const int2 *tiles, int n_tiles, const 
     return PCL_OK;
 }
 
-void seg_free(pcl_seg *s) {
-    dev_free(s->d_counts);
-    dev_free(s->d_off);
-    dev_free(s->d_order);
-    dev_free(s->G32);
-    dev_free(s->G64);
-    dev_free(s->d_assign);
-    dev_free(s->d_corder);
-    dev_free(s->d_coff);
-    dev_free(s->d_seed);
-    dev_free(s->d_centres);
-    delete s;
-}
-
 int seg_ensure_g64(pcl_seg *s) {
     if (s->G64) return PCL_OK;
     const size_t n = (size_t)s->Ntot * s->FD;
-    TRY(dev_alloc(s->ctx, &s->G64, n));
+    TRY(s->G64.alloc(s->ctx, n));
     return pcl_launch_cast(s->ctx, nullptr, s->G32, s->G64, n);          // float -> double is exact
 }
 
-// While a segment call runs the library's scoring / accumulate pass, the context's frame matrix IS the gathered copy.
+// While a segment call runs the library's scoring / accumulate pass, the context's frame matrix IS the gathered copy: the f32 view points
+// at it, the f64 matrices change hands for the duration (so one the pass derives meanwhile is the segment set's to keep).
 struct FrameSwap {
     pcl_ctx *ctx;
+    pcl_seg *seg;
     float *f32;
-    double *f64;
+    DevBuf<double> f64;
     int64_t F;
     int FD, FDhost;
-    FrameSwap(pcl_ctx *c, pcl_seg *s) : ctx(c), f32(c->frames32), f64(c->frames64), F(c->F), FD(c->FD), FDhost(c->FDhost) {
+    FrameSwap(pcl_ctx *c, pcl_seg *s) : ctx(c), seg(s), f32(c->frames32), f64(std::move(c->frames64)), F(c->F), FD(c->FD), FDhost(c->FDhost) {
         c->frames32 = s->G32;
-        c->frames64 = s->G64;
+        c->frames64 = std::move(s->G64);
         c->F = s->Ntot;
         c->FD = s->FD;
         c->FDhost = s->FDhost;
     }
     ~FrameSwap() {
         ctx->frames32 = f32;
-        ctx->frames64 = f64;
+        seg->G64 = std::move(ctx->frames64);
+        ctx->frames64 = std::move(f64);
         ctx->F = F;
         ctx->FD = FD;
         ctx->FDhost = FDhost;
@@ -448,21 +438,6 @@ int upload_flags(pcl_ctx *ctx, int *d, const std::vector<int> &h) {
     HIPCHK(ctx, pcl_h2d(ctx, d, h.data(), h.size() * sizeof(int)));
     return PCL_OK;
 }
-
-// first error of a sequence of calls: later steps are skipped, the clean-up at the end still runs
-struct Latch {
-    pcl_ctx *ctx;
-    int rc = PCL_OK;
-    explicit Latch(pcl_ctx *c) : ctx(c) {}
-    bool ok() const { return rc == PCL_OK; }
-    void operator()(int r) { if (rc == PCL_OK) rc = r; }
-    void operator()(hipError_t e) {
-        if (rc == PCL_OK && e != hipSuccess) {
-            pcl_set_error(ctx, hipGetErrorString(e));
-            rc = PCL_ERR_HIP;
-        }
-    }
-};
 
 }  // namespace
 
@@ -479,16 +454,10 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
         if (frame_state[t] < -1 || frame_state[t] >= J)
             PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: frame_state[%lld] = %d is neither -1 nor a state in [0,%d)", (long long)t, frame_state[t], J);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int *d_state = nullptr;
-    TRY(dev_alloc(ctx, &d_state, (size_t)n_frames_total));
-    int rc = PCL_OK;
-    if (pcl_h2d(ctx, d_state, frame_state, (size_t)n_frames_total * sizeof(int)) != hipSuccess) {
-        pcl_set_error(ctx, "pcl_seg_create: copy of the owner array failed");
-        rc = PCL_ERR_HIP;
-    }
-    if (rc == PCL_OK) rc = pcl_seg_create_device(ctx, n_frames_total, J, d_state, out);
-    dev_free(d_state);
-    return rc;
+    DevBuf<int> d_state;
+    TRY(d_state.alloc(ctx, (size_t)n_frames_total));
+    HIPCHK(ctx, pcl_h2d(ctx, d_state, frame_state, (size_t)n_frames_total * sizeof(int)));
+    return pcl_seg_create_device(ctx, n_frames_total, J, d_state, out);
 }
 
 }  // extern "C"
@@ -503,7 +472,7 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
         PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_seg_create: %lld owner entries for a frame matrix of %lld rows", (long long)n_frames_total, (long long)ctx->F);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const long long F = n_frames_total;
-    pcl_seg *s = new pcl_seg();
+    std::unique_ptr<pcl_seg> s(new pcl_seg());                   // (a failure below gives back whatever the set holds by then)
     s->ctx = ctx;
     s->J = J;
     s->F = F;
@@ -513,49 +482,37 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
     const long long per_tile = std::max<long long>(std::max<long long>(2048, (F + 4095) / 4096), (F * (long long)J + (1LL << 26) - 1) >> 26);
     const int tile = (int)((per_tile + SEG_T - 1) / SEG_T * SEG_T);
     const int n_tiles = (int)((F + tile - 1) / tile);
-    int *d_tilecnt = nullptr;
-    Latch A(ctx);
-    Latch &H = A;
-    int &rc = A.rc;
-    A(dev_alloc(ctx, &d_tilecnt, (size_t)n_tiles * J));
-    A(dev_alloc(ctx, &s->d_counts, (size_t)J));
-    A(dev_alloc(ctx, &s->d_off, (size_t)J + 1));
-    if (rc == PCL_OK) H(hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
-    if (rc == PCL_OK) {
-        pcl_timer_begin(ctx, "seg_count");
-        hipLaunchKernelGGL(seg_hist_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt);
-        hipLaunchKernelGGL(seg_colscan_kernel, dim3((J + 255) / 256), dim3(256), 0, ctx->stream, d_tilecnt, n_tiles, J, s->d_counts);
-        pcl_timer_end(ctx, "seg_count");
-        H(hipGetLastError());
-        s->counts.resize(J);
-        H(hipMemcpyAsync(s->counts.data(), s->d_counts, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        H(hipStreamSynchronize(ctx->stream));
-    }
-    if (rc == PCL_OK) {
-        s->off.assign(J + 1, 0);
-        for (int j = 0; j < J; ++j) s->off[j + 1] = s->off[j] + s->counts[j];
-        s->Ntot = s->off[J];
-        H(pcl_h2d(ctx, s->d_off, s->off.data(), (size_t)(J + 1) * sizeof(int)));
-        A(dev_alloc(ctx, &s->d_order, (size_t)s->Ntot));
-        A(dev_alloc(ctx, &s->G32, (size_t)s->Ntot * s->FD));
-        if (rc == PCL_OK && ctx->frames64) A(dev_alloc(ctx, &s->G64, (size_t)s->Ntot * s->FD));
-    }
-    if (rc == PCL_OK && s->Ntot > 0) {
+    DevBuf<int> d_tilecnt;
+    TRY(d_tilecnt.alloc(ctx, (size_t)n_tiles * J));
+    TRY(s->d_counts.alloc(ctx, (size_t)J));
+    TRY(s->d_off.alloc(ctx, (size_t)J + 1));
+    HIPCHK(ctx, hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
+    pcl_timer_begin(ctx, "seg_count");
+    hipLaunchKernelGGL(seg_hist_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt);
+    hipLaunchKernelGGL(seg_colscan_kernel, dim3((J + 255) / 256), dim3(256), 0, ctx->stream, d_tilecnt, n_tiles, J, s->d_counts);
+    pcl_timer_end(ctx, "seg_count");
+    HIPCHK(ctx, hipGetLastError());
+    s->counts.resize(J);
+    HIPCHK(ctx, hipMemcpyAsync(s->counts.data(), s->d_counts, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    s->off.assign(J + 1, 0);
+    for (int j = 0; j < J; ++j) s->off[j + 1] = s->off[j] + s->counts[j];
+    s->Ntot = s->off[J];
+    HIPCHK(ctx, pcl_h2d(ctx, s->d_off, s->off.data(), (size_t)(J + 1) * sizeof(int)));
+    TRY(s->d_order.alloc(ctx, (size_t)s->Ntot));
+    TRY(s->G32.alloc(ctx, (size_t)s->Ntot * s->FD));
+    if (ctx->frames64) TRY(s->G64.alloc(ctx, (size_t)s->Ntot * s->FD));
+    if (s->Ntot > 0) {
         pcl_timer_begin(ctx, "seg_gather");
         hipLaunchKernelGGL(seg_scatter_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_state, F, J, tile, d_tilecnt, s->d_off, s->d_order);
         const unsigned gb = (unsigned)std::min<long long>(8192, (s->Ntot * s->FD + 255) / 256);
         hipLaunchKernelGGL(seg_gather_kernel<float>, dim3(gb), dim3(256), 0, ctx->stream, ctx->frames32, s->d_order, s->Ntot, s->FD, s->G32);
         if (s->G64) hipLaunchKernelGGL(seg_gather_kernel<double>, dim3(gb), dim3(256), 0, ctx->stream, ctx->frames64, s->d_order, s->Ntot, s->FD, s->G64);
         pcl_timer_end(ctx, "seg_gather");
-        H(hipGetLastError());
+        HIPCHK(ctx, hipGetLastError());
     }
-    if (rc == PCL_OK) H(hipStreamSynchronize(ctx->stream));
-    dev_free(d_tilecnt);
-    if (rc != PCL_OK) {
-        seg_free(s);
-        return rc;
-    }
-    *out = s;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *out = s.release();
     return PCL_OK;
 }
 
@@ -564,7 +521,7 @@ extern "C" {
 int pcl_seg_destroy(pcl_seg *seg) {
     if (!seg) return PCL_ERR_INVALID;
     (void)hipSetDevice(seg->ctx->device);
-    seg_free(seg);
+    delete seg;                                                  // (every block with its device-wide wait: nothing says the GPU is done with them)
     return PCL_OK;
 }
 
@@ -609,17 +566,17 @@ int pcl_seg_kmeans(pcl_seg *seg, int K, uint64_t seed, int max_sweeps, int preci
     if (ctx->D != DD) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_seg_kmeans: model and frames disagree on the device feature dimension");
     if (precision == PCL_F64) TRY(seg_ensure_g64(seg));
     // per-call buffers (K may differ from the last call)
-    dev_free(seg->d_assign);
-    dev_free(seg->d_corder);
-    dev_free(seg->d_coff);
-    dev_free(seg->d_seed);
-    dev_free(seg->d_centres);
+    seg->d_assign.release();
+    seg->d_corder.release();
+    seg->d_coff.release();
+    seg->d_seed.release();
+    seg->d_centres.release();
     seg->K = K;
-    TRY(dev_alloc(ctx, &seg->d_assign, (size_t)seg->Ntot));
-    TRY(dev_alloc(ctx, &seg->d_corder, (size_t)seg->Ntot));
-    TRY(dev_alloc(ctx, &seg->d_coff, (size_t)J * (K + 1)));
-    TRY(dev_alloc(ctx, &seg->d_seed, (size_t)J * K));
-    TRY(dev_alloc(ctx, &seg->d_centres, (size_t)J * K * DD));
+    TRY(seg->d_assign.alloc(ctx, (size_t)seg->Ntot));
+    TRY(seg->d_corder.alloc(ctx, (size_t)seg->Ntot));
+    TRY(seg->d_coff.alloc(ctx, (size_t)J * (K + 1)));
+    TRY(seg->d_seed.alloc(ctx, (size_t)J * K));
+    TRY(seg->d_centres.alloc(ctx, (size_t)J * K * DD));
     HIPCHK(ctx, hipMemsetAsync(seg->d_assign, 0xff, (size_t)seg->Ntot * sizeof(int), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(seg->d_seed, 0xff, (size_t)J * K * sizeof(int), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(seg->d_centres, 0, (size_t)J * K * DD * sizeof(double), ctx->stream));
@@ -635,40 +592,34 @@ int pcl_seg_kmeans(pcl_seg *seg, int K, uint64_t seed, int max_sweeps, int preci
             for (int t0 = 0; t0 < seg->counts[j]; t0 += SEG_T) tiles.push_back(make_int2(j, t0));
     }
     if (n_train == 0) return PCL_OK;
-    int *d_train = nullptr, *d_active = nullptr, *d_changed = nullptr;
-    int2 *d_tiles = nullptr;
-    double *d_mind2 = nullptr;
-    Latch A(ctx);
-    Latch &H = A;
-    int &rc = A.rc;
-    A(dev_alloc(ctx, &d_train, (size_t)J));
-    A(dev_alloc(ctx, &d_active, (size_t)J));
-    A(dev_alloc(ctx, &d_changed, (size_t)J));
-    A(dev_alloc(ctx, &d_tiles, tiles.size()));
-    if (rc == PCL_OK) {
-        A(upload_flags(ctx, d_train, train));
-        H(pcl_h2d(ctx, d_tiles, tiles.data(), tiles.size() * sizeof(int2)));
-    }
+    DevBuf<int> d_train, d_active, d_changed;                    // (call-scoped: released, each with its device-wide wait, on every way out)
+    DevBuf<int2> d_tiles;
+    DevBuf<double> d_mind2;
+    auto run = [&]() -> int {
+    TRY(d_train.alloc(ctx, (size_t)J));
+    TRY(d_active.alloc(ctx, (size_t)J));
+    TRY(d_changed.alloc(ctx, (size_t)J));
+    TRY(d_tiles.alloc(ctx, tiles.size()));
+    TRY(upload_flags(ctx, d_train, train));
+    HIPCHK(ctx, pcl_h2d(ctx, d_tiles, tiles.data(), tiles.size() * sizeof(int2)));
     const bool f64 = precision == PCL_F64;
     // ---- seeds
-    if (rc == PCL_OK && init_centres) {
+    if (init_centres) {
         std::vector<double> c((size_t)J * K * DD, 0.0);
         for (size_t jk = 0; jk < (size_t)J * K; ++jk)
             for (int d = 0; d < Dh; ++d) c[jk * DD + d] = init_centres[jk * Dh + d];
-        H(pcl_h2d(ctx, seg->d_centres, c.data(), c.size() * sizeof(double)));
-    } else if (rc == PCL_OK) {
-        A(dev_alloc(ctx, &d_mind2, (size_t)seg->Ntot));
-        if (rc == PCL_OK) {
-            if (f64) hipLaunchKernelGGL(seg_seed_kernel<double>, dim3(J), dim3(SEG_T), 0, ctx->stream, seg->G64, DD, seg->d_off, seg->d_counts, d_train, K,
-                                        (unsigned long long)seed, d_mind2, seg->d_centres, seg->d_seed);
-            else hipLaunchKernelGGL(seg_seed_kernel<float>, dim3(J), dim3(SEG_T), 0, ctx->stream, seg->G32, DD, seg->d_off, seg->d_counts, d_train, K,
+        HIPCHK(ctx, pcl_h2d(ctx, seg->d_centres, c.data(), c.size() * sizeof(double)));
+    } else {
+        TRY(d_mind2.alloc(ctx, (size_t)seg->Ntot));
+        if (f64) hipLaunchKernelGGL(seg_seed_kernel<double>, dim3(J), dim3(SEG_T), 0, ctx->stream, seg->G64, DD, seg->d_off, seg->d_counts, d_train, K,
                                     (unsigned long long)seed, d_mind2, seg->d_centres, seg->d_seed);
-            H(hipGetLastError());
-        }
+        else hipLaunchKernelGGL(seg_seed_kernel<float>, dim3(J), dim3(SEG_T), 0, ctx->stream, seg->G32, DD, seg->d_off, seg->d_counts, d_train, K,
+                                (unsigned long long)seed, d_mind2, seg->d_centres, seg->d_seed);
+        HIPCHK(ctx, hipGetLastError());
     }
     // ---- Lloyd sweeps: a state leaves the loop when none of its frames changed cluster
     const size_t sort_shm = (size_t)(K + SEG_T) * sizeof(int);
-    auto sort_and_centres = [&](const int *d_flags, bool final) {
+    auto sort_and_centres = [&](const int *d_flags, bool final) -> int {
         hipLaunchKernelGGL(seg_cluster_sort_kernel, dim3(J), dim3(SEG_T), sort_shm, ctx->stream, seg->d_off, seg->d_counts, d_flags, seg->d_assign, K,
                            seg->d_corder, seg->d_coff);
 #define SEG_CENTRE(T, G, FIN)                                                                                                                         \
@@ -682,19 +633,18 @@ int pcl_seg_kmeans(pcl_seg *seg, int K, uint64_t seed, int max_sweeps, int preci
             else SEG_CENTRE(float, seg->G32, false);
         }
 #undef SEG_CENTRE
-        H(hipGetLastError());
+        HIPCHK(ctx, hipGetLastError());
+        return PCL_OK;
     };
     active = train;
     int n_active = n_train;
-    for (int sweep = 0; sweep < max_sweeps && n_active > 0 && rc == PCL_OK; ++sweep) {
-        A(upload_flags(ctx, d_active, active));
-        H(hipMemsetAsync(d_changed, 0, (size_t)J * sizeof(int), ctx->stream));
-        if (rc != PCL_OK) break;
-        A(f64 ? launch_assign<double>(seg, seg->G64, d_tiles, (int)tiles.size(), d_active, d_changed)
+    for (int sweep = 0; sweep < max_sweeps && n_active > 0; ++sweep) {
+        TRY(upload_flags(ctx, d_active, active));
+        HIPCHK(ctx, hipMemsetAsync(d_changed, 0, (size_t)J * sizeof(int), ctx->stream));
+        TRY(f64 ? launch_assign<double>(seg, seg->G64, d_tiles, (int)tiles.size(), d_active, d_changed)
               : launch_assign<float>(seg, seg->G32, d_tiles, (int)tiles.size(), d_active, d_changed));
-        H(hipMemcpyAsync(changed.data(), d_changed, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        H(hipStreamSynchronize(ctx->stream));
-        if (rc != PCL_OK) break;
+        HIPCHK(ctx, hipMemcpyAsync(changed.data(), d_changed, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         n_active = 0;
         for (int j = 0; j < J; ++j)
             if (active[j]) {
@@ -703,19 +653,17 @@ int pcl_seg_kmeans(pcl_seg *seg, int K, uint64_t seed, int max_sweeps, int preci
                 n_active += active[j];
             }
         if (n_active > 0) {
-            A(upload_flags(ctx, d_active, active));
-            if (rc == PCL_OK) sort_and_centres(d_active, false);
+            TRY(upload_flags(ctx, d_active, active));
+            TRY(sort_and_centres(d_active, false));
         }
     }
     // ---- the model: cluster mean, floored mean squared deviation, n_jk / n_j; then every scoring layout, as pcl_mstep does
-    if (rc == PCL_OK) sort_and_centres(d_train, true);
-    if (rc == PCL_OK) A(pcl_launch_derive(ctx));
-    H(hipStreamSynchronize(ctx->stream));
-    dev_free(d_train);
-    dev_free(d_active);
-    dev_free(d_changed);
-    dev_free(d_tiles);
-    dev_free(d_mind2);
+    TRY(sort_and_centres(d_train, true));
+    TRY(pcl_launch_derive(ctx));
+    return PCL_OK;
+    };
+    int rc = run();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) PCL_FAIL(ctx, PCL_ERR_HIP, "pcl_seg_kmeans: HIP error");
     return rc;
 }
 
@@ -758,19 +706,17 @@ int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_it
         for (size_t i = 0; i < (size_t)J * max_iters; ++i) q_trace[i] = NAN;
     if (n_active == 0) return PCL_OK;
     FrameSwap swap(ctx, seg);
-    int *d_active = nullptr;
-    double *d_q = nullptr;
+    DevBuf<int> d_active;                                        // (call-scoped: released, each with its device-wide wait, on every way out)
+    DevBuf<double> d_q;
     pcl_batch *b = nullptr;
-    Latch A(ctx);
-    Latch &H = A;
-    int &rc = A.rc;
-    A(dev_alloc(ctx, &d_active, (size_t)J));
-    A(dev_alloc(ctx, &d_q, (size_t)J));
+    auto run = [&]() -> int {
+    TRY(d_active.alloc(ctx, (size_t)J));
+    TRY(d_q.alloc(ctx, (size_t)J));
     bool rebuild = true;
-    for (int it = 0; it < max_iters && n_active > 0 && rc == PCL_OK; ++it) {
+    for (int it = 0; it < max_iters && n_active > 0; ++it) {
         if (rebuild) {
             // the running states as three-row utterances over the gathered frames; a converged state is not scored again
-            if (b) A(pcl_batch_destroy(b));
+            if (b) TRY(pcl_batch_destroy(b));
             b = nullptr;
             std::vector<int32_t> N, T, rows;
             std::vector<int64_t> begin;
@@ -783,30 +729,27 @@ int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_it
                     rows.push_back(j);
                     rows.push_back(PCL_ROW_EXIT);
                 }
-            A(pcl_batch_create(ctx, (int)N.size(), N.data(), T.data(), begin.data(), &b));
-            if (rc == PCL_OK) A(pcl_batch_set_states(b, rows.data()));
-            if (rc == PCL_OK) A(dev_alloc(ctx, &b->lgam, (size_t)b->sumNT));
-            if (rc == PCL_OK) {
+            TRY(pcl_batch_create(ctx, (int)N.size(), N.data(), T.data(), begin.data(), &b));
+            TRY(pcl_batch_set_states(b, rows.data()));
+            TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
+            {
                 hipLaunchKernelGGL(seg_posterior_kernel, dim3((unsigned)std::min<long long>(4096, (b->sumNT + 255) / 256)), dim3(256), 0, ctx->stream, b->lgam,
                                    b->sumNT);
-                H(hipGetLastError());
+                HIPCHK(ctx, hipGetLastError());
                 b->have_post = true;
             }
-            A(upload_flags(ctx, d_active, active));
+            TRY(upload_flags(ctx, d_active, active));
             rebuild = false;
         }
-        if (rc != PCL_OK) break;
-        A(pcl_batch_score(b, precision));                         // GMM.expectation: the per-frame normaliser ln b_j(o_t) ...
-        if (rc == PCL_OK) A(pcl_stats_zero(ctx));
-        if (rc == PCL_OK) A(pcl_batch_accumulate(b, precision));  // ... and the responsibilities summed into Gamma, sum gamma (x + bias), sum gamma (x - c)^2
-        if (rc != PCL_OK) break;
-        H(pcl_stats_join(ctx));
+        TRY(pcl_batch_score(b, precision));                         // GMM.expectation: the per-frame normaliser ln b_j(o_t) ...
+        TRY(pcl_stats_zero(ctx));
+        TRY(pcl_batch_accumulate(b, precision));  // ... and the responsibilities summed into Gamma, sum gamma (x + bias), sum gamma (x - c)^2
+        HIPCHK(ctx, pcl_stats_join(ctx));
         hipLaunchKernelGGL(seg_mstep_q_kernel, dim3(J), dim3(SEG_T), 0, ctx->stream, ctx->st_acc, ctx->st_mean, ctx->st_cov, seg->d_counts, d_active, M, ctx->Mpad,
                            ctx->D, ctx->Dhost, 100.0, c_covariance, ctx->model_flags & PCL_MODEL_LOGDET, ctx->mean64, ctx->var64, ctx->w64, d_q);
-        H(hipGetLastError());
-        H(hipMemcpyAsync(q_new.data(), d_q, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (rc == PCL_OK) A(pcl_launch_derive(ctx));              // (waits for the stream: q_new has landed)
-        if (rc != PCL_OK) break;
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(q_new.data(), d_q, (size_t)J * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        TRY(pcl_launch_derive(ctx));              // (waits for the stream: q_new has landed)
         for (int j = 0; j < J; ++j) {
             if (!active[j]) continue;
             ++iters[j];
@@ -821,10 +764,11 @@ int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_it
             }
         }
     }
-    if (b) A(pcl_batch_destroy(b));
-    H(hipStreamSynchronize(ctx->stream));
-    dev_free(d_active);
-    dev_free(d_q);
+    return PCL_OK;
+    };
+    int rc = run();
+    if (b) (void)pcl_batch_destroy(b);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) PCL_FAIL(ctx, PCL_ERR_HIP, "pcl_seg_em: HIP error");
     return rc;
 }
 

@@ -715,24 +715,8 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
 }  // namespace
 
 void pcl_lexicon_release(pcl_ctx *ctx) {
-    dev_free(ctx->lex_units);
-    dev_free(ctx->lex_nunits);
-    dev_free(ctx->lex_child_ptr);
-    dev_free(ctx->lex_child_idx);
-    dev_free(ctx->lex_word);
-    dev_free(ctx->lex_roots);
-    dev_free(ctx->lex_info);
-    dev_free(ctx->d_unit_logtrans);
+    static_cast<LexiconDev &>(*ctx) = {};
     ctx->lex_nodes = ctx->lex_nroots = 0;
-}
-
-void pcl_batch_decode_release(pcl_batch *b) {
-    dev_free(b->dec_f64);
-    dev_free(b->dec_slot);
-    dev_free(b->dec_work);
-    dev_free(b->dec_int);
-    dev_free(b->dec_score);
-    b->dec_cap = b->dec_cand = 0;
 }
 
 extern "C" {
@@ -768,13 +752,13 @@ int pcl_lexicon_upload(pcl_ctx *ctx, int n_nodes, const int32_t *node_units, con
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pcl_lexicon_release(ctx);
-    TRY(dev_alloc(ctx, &ctx->lex_units, (size_t)2 * n_nodes));
-    TRY(dev_alloc(ctx, &ctx->lex_nunits, (size_t)n_nodes));
-    TRY(dev_alloc(ctx, &ctx->lex_child_ptr, (size_t)n_nodes + 1));
-    TRY(dev_alloc(ctx, &ctx->lex_child_idx, (size_t)std::max(nc, 1)));
-    TRY(dev_alloc(ctx, &ctx->lex_word, (size_t)n_nodes));
-    TRY(dev_alloc(ctx, &ctx->lex_roots, (size_t)n_roots));
-    TRY(dev_alloc(ctx, &ctx->lex_info, (size_t)n_nodes));
+    TRY(ctx->lex_units.alloc(ctx, (size_t)2 * n_nodes));
+    TRY(ctx->lex_nunits.alloc(ctx, (size_t)n_nodes));
+    TRY(ctx->lex_child_ptr.alloc(ctx, (size_t)n_nodes + 1));
+    TRY(ctx->lex_child_idx.alloc(ctx, (size_t)std::max(nc, 1)));
+    TRY(ctx->lex_word.alloc(ctx, (size_t)n_nodes));
+    TRY(ctx->lex_roots.alloc(ctx, (size_t)n_roots));
+    TRY(ctx->lex_info.alloc(ctx, (size_t)n_nodes));
     {   // (first child, children, words end here, unit pair) of a node in one 16-byte record
         std::vector<int4> info(n_nodes);
         for (int i = 0; i < n_nodes; ++i) {
@@ -783,7 +767,7 @@ int pcl_lexicon_upload(pcl_ctx *ctx, int n_nodes, const int32_t *node_units, con
         }
         HIPCHK(ctx, hipMemcpy(ctx->lex_info, info.data(), (size_t)n_nodes * sizeof(int4), hipMemcpyHostToDevice));
     }
-    TRY(dev_alloc(ctx, &ctx->d_unit_logtrans, ctx->unit_logtrans.size()));
+    TRY(ctx->d_unit_logtrans.alloc(ctx, ctx->unit_logtrans.size()));
     HIPCHK(ctx, hipMemcpy(ctx->lex_units, node_units, (size_t)2 * n_nodes * 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->lex_nunits, node_nunits, (size_t)n_nodes * 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(ctx->lex_child_ptr, child_ptr, ((size_t)n_nodes + 1) * 4, hipMemcpyHostToDevice));
@@ -819,32 +803,22 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
     }
     // Like the forward-backward recursion, the decoder does no matrix work and is latency / bandwidth bound: it runs on
     // the second stream, beside the scoring of the next chunk on the main one (every later call on this batch joins it).
-    hipStream_t main_stream = ctx->stream;
-    if (ctx->dp_async) {
-        if (!b->ev_dp) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_dp, hipEventDisableTiming));
-        HIPCHK(ctx, pcl_dp_follows_main(b));
-    }
-    struct StreamSwap {                                                        // the launches below and their timer use ctx->stream
-        pcl_ctx *c;
-        hipStream_t keep;
-        ~StreamSwap() { c->stream = keep; }
-    } swap_back{ctx, main_stream};
-    if (ctx->dp_async) ctx->stream = ctx->stream_dp;
+    auto launch = [&]() -> int {                                               // (on ctx->stream: the second stream when dp_async)
     const int cap = max_tokens, U = b->U, Tm = b->Tmax;
     // left-to-right units (every model the reference builds): one lane per token, hmm_decode_lr.hip; PCL_DEC_GENERAL=1 keeps
     // the general kernel (the parity tests run both against the restatement)
     const char *force_general = getenv("PCL_DEC_GENERAL");
     const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, J + 2, cap, Tm);
     if (b->dec_cap != cap || b->dec_cand != candidate || b->dec_nodes != ctx->lex_nodes) {
-        pcl_batch_decode_release(b);
+        static_cast<BatchDecodeDev &>(*b) = {};
         // doubles per utterance: score 2 cap | p 2 cap NS | seg_score cap + 2;  ints: node, hist, upair 2 cap each | flag, dst cap each |
         // seg_ofs, seg_cptr, seg_hist cap + 2 each (general kernel); the left-to-right kernel lays meta 8 cap | src 2 cap over the same words
-        TRY(dev_alloc(ctx, &b->dec_f64, (size_t)U * (2 * (size_t)cap * (1 + NS) + cap + 2)));
-        TRY(dev_alloc(ctx, &b->dec_work, (size_t)U * (10 * (size_t)cap + 3 * ((size_t)cap + 2))));
-        TRY(dev_alloc(ctx, &b->dec_slot, (size_t)U * ctx->lex_nodes));
+        TRY(b->dec_f64.alloc(ctx, (size_t)U * (2 * (size_t)cap * (1 + NS) + cap + 2)));
+        TRY(b->dec_work.alloc(ctx, (size_t)U * (10 * (size_t)cap + 3 * ((size_t)cap + 2))));
+        TRY(b->dec_slot.alloc(ctx, (size_t)U * ctx->lex_nodes));
         // ints: out_n U | out_node U*cand | out_hist U*cand | hist_n U | hist_prev U*Tm | hist_node U*Tm | trace U*Tm | overflow U
-        TRY(dev_alloc(ctx, &b->dec_int, (size_t)U * (3 + 2 * candidate + 3 * Tm)));
-        TRY(dev_alloc(ctx, &b->dec_score, (size_t)U * candidate));
+        TRY(b->dec_int.alloc(ctx, (size_t)U * (3 + 2 * candidate + 3 * Tm)));
+        TRY(b->dec_score.alloc(ctx, (size_t)U * candidate));
         b->dec_cap = cap;
         b->dec_cand = candidate;
         b->dec_nodes = ctx->lex_nodes;
@@ -894,8 +868,8 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
     a.out_score = b->dec_score;
     a.stamps = nullptr;
 #ifdef PCL_DEC_STAMPS
-    long long *d_stamps = nullptr;
-    TRY(dev_alloc(ctx, &d_stamps, (size_t)N_STAMP));
+    DevBuf<long long> d_stamps;
+    TRY(d_stamps.alloc(ctx, (size_t)N_STAMP));
     HIPCHK(ctx, hipMemsetAsync(d_stamps, 0, N_STAMP * sizeof(long long), ctx->stream));
     a.stamps = d_stamps;
 #endif
@@ -930,13 +904,15 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
         HIPCHK(ctx, hipMemcpyAsync(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         fprintf(stderr, "decode stamps (utterance 0, 100 MHz ticks): step %lld donors %lld pairs %lld first|keys %lld prune %lld compact %lld select %lld\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-        dev_free(d_stamps);
+        d_stamps.release();
     }
 #endif
+    return PCL_OK;
+    };
     if (ctx->dp_async) {
-        HIPCHK(ctx, hipEventRecord(b->ev_dp, ctx->stream_dp));
-        b->dp_pending = true;
+        TRY(pcl_run_on_dp_stream(b, false, launch));
     } else {
+        TRY(launch());
         HIPCHK(ctx, pcl_batch_mark(b));
     }
     b->have_dec = true;

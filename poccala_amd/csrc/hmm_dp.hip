@@ -884,11 +884,11 @@ bool pcl_fb_linear_enabled() {
 
 int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshold) {
     if (!b->Bp) {
-        TRY(dev_alloc(ctx, &b->Bp, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->alpha_e, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->beta_e, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->fb_kmax, (size_t)PCL_FB_KREC * b->U));
-        TRY(dev_alloc(ctx, &b->fb_dump, (size_t)128));                  // where the posterior kernel's lanes beyond N "store"
+        TRY(b->Bp.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->alpha_e.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->beta_e.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->fb_kmax.alloc(ctx, (size_t)PCL_FB_KREC * b->U));
+        TRY(b->fb_dump.alloc(ctx, (size_t)128));                  // where the posterior kernel's lanes beyond N "store"
     }
     hipLaunchKernelGGL(hmm_emis_pack_kernel, dim3(PACK_BLOCKS, b->U), dim3(256), 0, ctx->stream, b->d_utt, b->Bt, b->Bp, b->fb_kmax, b->row_ptr, b->csr_val,
                        b->logpi);
@@ -904,7 +904,7 @@ int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshol
     }
     hipLaunchKernelGGL(hmm_fbl_kernel, dim3(b->U), dim3(128), 0, ctx->stream, b->d_utt, b->Bp, b->fb_kmax, b->row_ptr, b->col_idx, b->csr_val,
                        b->logpi, b->alpha, b->alpha_e, b->beta, b->beta_e, b->pi_out, b->logp, b->qtrace, b->npass, fix_pi, threshold, b->Bt, b->col_ptr,
-                       b->row_idx, b->csc_val, reinterpret_cast<const double2 *>(ctx->d_softplus), b->fb_dump);
+                       b->row_idx, b->csc_val, reinterpret_cast<const double2 *>(ctx->d_softplus.p), b->fb_dump);
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }
@@ -912,8 +912,8 @@ int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshol
 int pcl_launch_fb_linear_post(pcl_ctx *ctx, pcl_batch *b) {
     const int NPp = (b->Nmax + 63) / 64 * 64;
     if (!b->fb_part_m) {
-        TRY(dev_alloc(ctx, &b->fb_part_m, (size_t)b->U * 3 * POSTL_W * NPp));
-        TRY(dev_alloc(ctx, &b->fb_part_e, (size_t)b->U * 3 * POSTL_W * NPp));
+        TRY(b->fb_part_m.alloc(ctx, (size_t)b->U * 3 * POSTL_W * NPp));
+        TRY(b->fb_part_e.alloc(ctx, (size_t)b->U * 3 * POSTL_W * NPp));
     }
     if (NPp > 64) {                                                  // more than one wave of states: hmm_fb_linear_mw.inc
 #define LAUNCH_PM(W)                                                                                                                              \
@@ -972,7 +972,7 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
             tab[2 * k] = log1p(exp(-d));
             tab[2 * k + 1] = 1.0 / (1.0 + exp(d));
         }
-        TRY(dev_alloc(ctx, &ctx->d_softplus, tab.size()));
+        TRY(ctx->d_softplus.alloc(ctx, tab.size()));
         HIPCHK(ctx, hipMemcpyAsync(ctx->d_softplus, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -990,7 +990,7 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
         } else {
             hipLaunchKernelGGL(hmm_fb2_kernel, dim3(b->U), dim3(128), 0, ctx->stream, b->d_utt, b->Bt, b->row_ptr, b->col_idx,
                                b->csr_val, b->col_ptr, b->row_idx, b->csc_val, b->logpi, b->alpha, b->beta, b->pi_out, b->logp, b->qtrace, b->npass,
-                               fix_pi, threshold, reinterpret_cast<const double2 *>(ctx->d_softplus));
+                               fix_pi, threshold, reinterpret_cast<const double2 *>(ctx->d_softplus.p));
             hipLaunchKernelGGL(hmm_post_kernel, dim3(b->U), dim3(64 * POST_W), 0, ctx->stream, b->d_utt, b->Bt, b->row_ptr, b->col_idx, b->csr_val,
                                b->alpha, b->beta, b->lgam, b->ksai, b->gamma_out, b->logp);
         }

@@ -109,8 +109,7 @@ static int lexicon_refresh_logtrans(pcl_ctx *ctx) {
 }
 
 static void units_free(pcl_ctx *ctx) {
-    dev_free(ctx->d_unit_trans);
-    dev_free(ctx->hmm_ksai);
+    static_cast<UnitsDev &>(*ctx) = {};
     ctx->hmm_gamma = nullptr;                        // inside the hmm_ksai allocation
     ctx->unit_trans.clear();
     ctx->unit_logtrans.clear();
@@ -118,20 +117,8 @@ static void units_free(pcl_ctx *ctx) {
 
 void pcl_units_release(pcl_ctx *ctx) {
     pcl_lexicon_release(ctx);                        // the tree names units of this inventory: upload it again after a DIFFERENT inventory
-    dev_free(ctx->d_unit_trans);
-    dev_free(ctx->hmm_ksai);
-    ctx->hmm_gamma = nullptr;                        // inside the hmm_ksai allocation
-    ctx->unit_trans.clear();
-    ctx->unit_logtrans.clear();
+    units_free(ctx);
     ctx->n_units = ctx->S = 0;
-}
-
-void pcl_batch_units_release(pcl_batch *b) {
-    dev_free(b->occ_ptr);
-    dev_free(b->occ_utt);
-    dev_free(b->occ_row0);
-    dev_free(b->d_labels);
-    dev_free(b->d_label_off);
 }
 
 static size_t hmm_acc_len(const pcl_ctx *ctx) { return (size_t)ctx->n_units * (ctx->S - 2) * (ctx->S + 1); }
@@ -255,10 +242,10 @@ int pcl_units_upload(pcl_ctx *ctx, int n_units, int S, const double *trans, cons
     }
     ctx->n_units = n_units;
     ctx->S = S;
-    TRY(dev_alloc(ctx, &ctx->d_unit_trans, n));
+    TRY(ctx->d_unit_trans.alloc(ctx, n));
     HIPCHK(ctx, hipMemcpy(ctx->d_unit_trans, trans, n * sizeof(double), hipMemcpyHostToDevice));
     // ksai_acc then gamma_acc in ONE allocation, so that the cross-rank merge is one pair of all-reduces
-    TRY(dev_alloc(ctx, &ctx->hmm_ksai, hmm_acc_len(ctx)));
+    TRY(ctx->hmm_ksai.alloc(ctx, hmm_acc_len(ctx)));
     ctx->hmm_gamma = ctx->hmm_ksai + (size_t)n_units * (S - 2) * S;
     TRY(hmm_acc_reset(ctx));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -324,35 +311,30 @@ int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const
         }
         lo += label_len[u];
     }
-    int rc = pcl_batch_set_states_impl(b, row_state.data());
-    if (rc == PCL_OK) rc = build_sentences(b);
     b->n_occ = (int)tot;
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &b->occ_ptr, occ_ptr.size());
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &b->occ_utt, tot);
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &b->occ_row0, tot);
-    if (rc == PCL_OK && (pcl_h2d_fresh(ctx, b->occ_ptr, occ_ptr.data(), occ_ptr.size() * sizeof(int)) != hipSuccess ||
-                         pcl_h2d_fresh(ctx, b->occ_utt, occ_utt.data(), tot * sizeof(int)) != hipSuccess ||
-                         pcl_h2d_fresh(ctx, b->occ_row0, occ_row0.data(), tot * sizeof(int)) != hipSuccess)) {
-        pcl_set_error(ctx, "pcl_batch_create_labels: copy failed");
-        rc = PCL_ERR_HIP;
-    }
-    if (rc == PCL_OK && uploads.finish() != hipSuccess) {
-        pcl_set_error(ctx, "pcl_batch_create_labels: copy failed");
-        rc = PCL_ERR_HIP;
-    }
-    if (rc == PCL_OK && ctx->stream_desc && pcl_fewer_markers()) {
-        // the constant entry / exit rows of the emission matrix (AcousticModel.py:218-219), here instead of in front of the batch's first
-        // scoring launch: on the descriptor stream, beside whatever the main stream is doing (the buffer is fresh, nobody reads it yet)
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->stream_desc;
-        rc = pcl_launch_fill_virtual_rows(ctx, b);
-        ctx->stream = main_stream;
-        if (rc == PCL_OK && hipStreamSynchronize(ctx->stream_desc) != hipSuccess) {
-            pcl_set_error(ctx, "pcl_batch_create_labels: fill failed");
-            rc = PCL_ERR_HIP;
+    auto fill = [&]() -> int {                                     // (the batch is the caller's only once all of it has worked)
+        TRY(pcl_batch_set_states_impl(b, row_state.data()));
+        TRY(build_sentences(b));
+        TRY(b->occ_ptr.alloc(ctx, occ_ptr.size()));
+        TRY(b->occ_utt.alloc(ctx, tot));
+        TRY(b->occ_row0.alloc(ctx, tot));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_ptr, occ_ptr.data(), occ_ptr.size() * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_utt, occ_utt.data(), tot * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_row0, occ_row0.data(), tot * sizeof(int)));
+        HIPCHK(ctx, uploads.finish());
+        if (ctx->stream_desc && pcl_fewer_markers()) {
+            // the constant entry / exit rows of the emission matrix (AcousticModel.py:218-219), here instead of in front of the batch's first
+            // scoring launch: on the descriptor stream, beside whatever the main stream is doing (the buffer is fresh, nobody reads it yet)
+            {
+                pcl_stream_scope on_desc(ctx, ctx->stream_desc);
+                TRY(pcl_launch_fill_virtual_rows(ctx, b));
+            }
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream_desc));
+            b->virt_rows_filled = true;
         }
-        if (rc == PCL_OK) b->virt_rows_filled = true;
-    }
+        return PCL_OK;
+    };
+    const int rc = fill();
     if (rc != PCL_OK) {
         const std::string keep = ctx->err;
         (void)uploads.finish();

@@ -442,10 +442,10 @@ static int eager_layouts(const pcl_ctx *ctx) {
 static int alloc_for(pcl_ctx *ctx, int what) {                 // the buffers of the lazily derived layouts
     const size_t np = (size_t)ctx->J * ctx->Mpad * ctx->row, nm = (size_t)ctx->J * ctx->Mpad * ctx->D;
     if ((what & PCL_LAYOUT_P32) && !ctx->params32) {
-        TRY(dev_alloc(ctx, &ctx->params32, np));
-        TRY(dev_alloc(ctx, &ctx->mean32, nm));
+        TRY(ctx->params32.alloc(ctx, np));
+        TRY(ctx->mean32.alloc(ctx, nm));
     }
-    if ((what & PCL_LAYOUT_P64) && !ctx->params64) TRY(dev_alloc(ctx, &ctx->params64, np));
+    if ((what & PCL_LAYOUT_P64) && !ctx->params64) TRY(ctx->params64.alloc(ctx, np));
     return PCL_OK;
 }
 
@@ -455,7 +455,7 @@ static int launch_derive_kernel(pcl_ctx *ctx, int what, int j_lo, int j_hi) {
     if (j_hi <= j_lo) return PCL_OK;
     hipLaunchKernelGGL(derive_kernel, dim3((unsigned)((j_hi - j_lo) * (ctx->Mpad32 / 32))), dim3(256), shm, ctx->stream, ctx->mean64, ctx->var64,
                        ctx->w64, ctx->centers32, ctx->M, ctx->Mpad, ctx->Mpad32, ctx->D, ctx->Dhost, ctx->row, ctx->model_flags,
-                       ctx->params32, ctx->params64, ctx->mean32, ctx->pm32, reinterpret_cast<uint4 *>(ctx->pm16f),
+                       ctx->params32, ctx->params64, ctx->mean32, ctx->pm32, reinterpret_cast<uint4 *>(ctx->pm16f.p),
                        ctx->kzero, ctx->fscale, ctx->d_cond, what, j_lo, ctx->d_bad);
     HIPCHK(ctx, hipGetLastError());
     // split states: their on-pipe mixtures compacted to the front of the state's tiles (gmm_score_coarse.hip), so that the matrix-pipe

@@ -68,6 +68,7 @@ std::mutex g_pool_mu;
 std::unordered_map<void *, PoolBlock> g_pool_live;                 // every block handed out or cached
 std::multimap<std::pair<int, size_t>, void *> g_pool_free;           // (device, class bytes) -> cached block
 size_t g_pool_cached = 0;
+uint64_t g_pool_device_allocs = 0, g_pool_device_waits = 0;         // successful hipMalloc calls / device-wide waits of pcl_pool_free (pcl_pool_stats)
 size_t pool_class(size_t n) {
     if (n <= 256) return 256;
     size_t p2 = 256;
@@ -116,14 +117,17 @@ void *pcl_pool_alloc(int device, size_t bytes) {
             return nullptr;
         }
     }
+    ++g_pool_device_allocs;
     g_pool_live[p] = PoolBlock{cls, device};                        // (overwrites a stale entry, should a block ever have left the pool by a raw hipFree)
     return p;
 }
 
 void pcl_pool_free(void *p) {
     if (!p) return;
-    if (pcl_tls_free_synced <= 0) (void)hipDeviceSynchronize();     // what hipFree did: nobody on the device still uses the block
+    const bool wait = pcl_tls_free_synced <= 0;
+    if (wait) (void)hipDeviceSynchronize();                         // what hipFree did: nobody on the device still uses the block
     std::lock_guard<std::mutex> lock(g_pool_mu);
+    if (wait) ++g_pool_device_waits;
     auto it = g_pool_live.find(p);
     if (it == g_pool_live.end()) {                                   // not ours (never happens): the runtime's problem
         (void)hipFree(p);
@@ -132,6 +136,18 @@ void pcl_pool_free(void *p) {
     g_pool_free.emplace(std::make_pair(it->second.device, it->second.bytes), p);
     g_pool_cached += it->second.bytes;
     if (g_pool_cached > pool_limit()) pool_release_locked(pool_limit() / 2);
+}
+
+extern "C" int pcl_pool_stats(size_t *handed_out_blocks, size_t *handed_out_bytes, size_t *cached_bytes, uint64_t *device_allocs, uint64_t *device_waits) {
+    std::lock_guard<std::mutex> lock(g_pool_mu);
+    size_t live_bytes = 0;
+    for (const auto &kv : g_pool_live) live_bytes += kv.second.bytes;
+    if (handed_out_blocks) *handed_out_blocks = g_pool_live.size() - g_pool_free.size();
+    if (handed_out_bytes) *handed_out_bytes = live_bytes - g_pool_cached;
+    if (cached_bytes) *cached_bytes = g_pool_cached;
+    if (device_allocs) *device_allocs = g_pool_device_allocs;
+    if (device_waits) *device_waits = g_pool_device_waits;
+    return PCL_OK;
 }
 
 // ---------------------------------------------------------------- descriptor uploads (pcl_desc_group, pcl_internal.h)
@@ -176,6 +192,87 @@ static int pcl_batch_reap(pcl_ctx *ctx, bool wait);   // frees the destroyed bat
 extern "C" {
 
 // ================================================================ context
+static void free_model(pcl_ctx *ctx) {
+    pcl_accumulate_release(ctx);                                 // (sized for the model's states and mixtures)
+    pcl_coarse_release(ctx);
+    ctx->nbad.clear();
+    if (ctx->zero_pending && ctx->ev_zero) (void)hipEventSynchronize(ctx->ev_zero);
+    ctx->zero_pending = false;
+    static_cast<ModelDev &>(*ctx) = {};                          // the master copy, every derived layout, the statistics block
+    ctx->st_acc = ctx->st_alpha = ctx->st_mean = ctx->st_cov = nullptr;
+    ctx->J = ctx->M = ctx->Mpad = 0;
+}
+
+// frames32 is a view of either the plain upload (which goes) or a streaming slot (which stays)
+static void release_frames32(pcl_ctx *ctx) {
+    if (ctx->frames_front < 0) ctx->frames_up.release();
+    ctx->frames32 = nullptr;
+    ctx->frames_front = -1;
+}
+
+// The streams and the environment's knobs of a fresh context.  On a failure the caller unwinds through ctx_teardown.
+static int ctx_setup(pcl_ctx *ctx) {
+    HIPCHK(nullptr, hipSetDevice(ctx->device));
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->cus = prop.multiProcessorCount;
+    // (compute units set aside for the second stream with hipExtStreamCreateWithCUMask were tried in round 4: 8 of 256 cost the scoring
+    //  kernel 20 %, 16 cost 70 %, and the posterior kernel's in-loop span did not move -- it waits for registers, not for CUs)
+    HIPCHK(nullptr, hipStreamCreate(&ctx->stream));
+    HIPCHK(nullptr, hipStreamCreateWithPriority(&ctx->stream_dp, hipStreamDefault, -1));      // (priority 0 measured: no difference)
+    HIPCHK(nullptr, hipStreamCreate(&ctx->stream_aux));
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->stream_desc, hipStreamNonBlocking));
+    HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->stream_d2h, hipStreamNonBlocking));
+    // PCL_SCORE_VARIANT: 7 (default) = f32-class contraction on the f16 matrix pipe, 3 = strict f32 on the f32-input MFMA,
+    // 1 = direct form on the VALU (the kernels states leave the matrix pipe for: fix-up, ill-conditioned models)
+    const char *var = getenv("PCL_SCORE_VARIANT");
+    ctx->score_variant = var ? atoi(var) : 7;
+    if (ctx->score_variant != 1 && ctx->score_variant != 3 && ctx->score_variant != 7)
+        PCL_FAIL(nullptr, PCL_ERR_INVALID, "pcl_init: PCL_SCORE_VARIANT must be 1, 3 or 7");
+    if (const char *cm = getenv("PCL_MFMA_COND_MAX")) ctx->cond_max = (float)atof(cm);
+    if (const char *sm = getenv("PCL_SPLIT_MAX")) {
+        ctx->split_frac = std::min(1.0f, std::max(0.0f, (float)atof(sm)));
+        ctx->split_frac_set = true;
+    }
+    if (const char *ds = getenv("PCL_DP_STREAM")) ctx->dp_async = atoi(ds) != 0;
+    if (const char *co = getenv("PCL_COARSE")) ctx->coarse_on = atoi(co) != 0;
+    if (const char *cm2 = getenv("PCL_COMPACT_MAIN")) ctx->compact_main = atoi(cm2) != 0;
+    if (const char *cs = getenv("PCL_COARSE_STATS")) ctx->coarse_stats = atoi(cs) != 0;
+    if (const char *cp = getenv("PCL_COARSE_PASSES")) ctx->coarse_np = atoi(cp) == 3 ? 3 : 1;
+    if (const char *cm_ = getenv("PCL_COARSE_SPLIT_MAX")) ctx->coarse_split_frac = std::min(1.0f, std::max(0.0f, (float)atof(cm_)));   // (scoring only: A/B, tests)
+    if (const char *tm = getenv("PCL_TIMERS")) ctx->timing = atoi(tm) != 0;
+    return PCL_OK;
+}
+
+// Everything a context holds goes, in this order: the communicator (collectives and the pipelined exchange run on the context's streams and
+// stream_comm; rounds 1-5 destroyed it first), the buried batches, events, memory, streams.  The caller has DRAINED the streams (pcl_destroy);
+// a context pcl_init gives up on has queued nothing.  Every handle may be null.
+static void ctx_teardown(pcl_ctx *ctx) {
+    pcl_comm_destroy(ctx);
+    pcl_batch_reap(ctx, true);
+    // (round 6, tools/lifecycle_stress.py: a context destroyed with an asynchronous pcl_stats_zero still un-joined -- zero_pending --
+    //  had ev_zero destroyed HERE and then synchronised on by free_model below: a use of a dead event, SIGSEGV inside the runtime.
+    //  The streams are drained: nothing is pending any more, and the handles are cleared as they go.)
+    ctx->zero_pending = false;
+    ctx->ev_zero.destroy();
+    ctx->ev_zero_src.destroy();
+    if (ctx->desc_pin) hipHostFree(ctx->desc_pin);
+    ctx->desc_pin = nullptr;
+    drop_timers(ctx);                                            // (the per-chunk events of the staging stream's "pcm_h2d" group among them)
+    pcl_mfcc_release(ctx);                                       // drained: no copy reads the staging buffers, no event is waited for
+    free_model(ctx);
+    pcl_units_release(ctx);
+    release_frames32(ctx);
+    ctx->frames64.release();
+    ctx->d_softplus.release();
+    ctx->frames_slot[0].release();
+    ctx->frames_slot[1].release();
+    ctx->ev_stage.destroy();
+    ctx->ev_slot_free.destroy();
+    for (hipStream_t s : {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_desc, ctx->stream_d2h})
+        if (s) hipStreamDestroy(s);
+    delete ctx;                                                  // (nothing is left for the members' destructors to give back)
+}
+
 int pcl_init(int device, pcl_ctx **out) {
     if (!out) PCL_FAIL(nullptr, PCL_ERR_INVALID, "pcl_init: out is NULL");
     *out = nullptr;
@@ -189,95 +286,13 @@ int pcl_init(int device, pcl_ctx **out) {
     if (device < 0 || device >= n) PCL_FAIL(nullptr, PCL_ERR_INVALID, "pcl_init: device %d out of range [0,%d)", device, n);
     pcl_ctx *ctx = new pcl_ctx();
     ctx->device = device;
-    if ((e = hipSetDevice(device)) != hipSuccess) {
-        g_init_error = std::string("pcl_init: ") + hipGetErrorString(e);
-        delete ctx;
-        return PCL_ERR_HIP;
+    const int rc = ctx_setup(ctx);
+    if (rc != PCL_OK) {
+        ctx_teardown(ctx);                                       // (the message is pcl_last_error(NULL)'s)
+        return rc;
     }
-    {
-        hipDeviceProp_t prop0;
-        if (hipGetDeviceProperties(&prop0, device) == hipSuccess) ctx->cus = prop0.multiProcessorCount;
-    }
-    // (compute units set aside for the second stream with hipExtStreamCreateWithCUMask were tried in round 4: 8 of 256 cost the scoring
-    //  kernel 20 %, 16 cost 70 %, and the posterior kernel's in-loop span did not move -- it waits for registers, not for CUs)
-    if ((e = hipStreamCreate(&ctx->stream)) != hipSuccess ||
-        (e = hipStreamCreateWithPriority(&ctx->stream_dp, hipStreamDefault, -1)) != hipSuccess) {      // (priority 0 measured: no difference)
-        g_init_error = std::string("pcl_init: ") + hipGetErrorString(e);
-        delete ctx;
-        return PCL_ERR_HIP;
-    }
-    if ((e = hipStreamCreate(&ctx->stream_aux)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&ctx->stream_desc, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipStreamCreateWithFlags(&ctx->stream_d2h, hipStreamNonBlocking)) != hipSuccess) {
-        g_init_error = std::string("pcl_init: ") + hipGetErrorString(e);
-        delete ctx;
-        return PCL_ERR_HIP;
-    }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cus = prop.multiProcessorCount;
-    // PCL_SCORE_VARIANT: 7 (default) = f32-class contraction on the f16 matrix pipe, 3 = strict f32 on the f32-input MFMA,
-    // 1 = direct form on the VALU (the kernels states leave the matrix pipe for: fix-up, ill-conditioned models)
-    const char *var = getenv("PCL_SCORE_VARIANT");
-    ctx->score_variant = var ? atoi(var) : 7;
-    if (ctx->score_variant != 1 && ctx->score_variant != 3 && ctx->score_variant != 7) {
-        g_init_error = "pcl_init: PCL_SCORE_VARIANT must be 1, 3 or 7";
-        hipStreamDestroy(ctx->stream); hipStreamDestroy(ctx->stream_dp); hipStreamDestroy(ctx->stream_aux); hipStreamDestroy(ctx->stream_desc);
-        delete ctx;
-        return PCL_ERR_INVALID;
-    }
-    if (const char *cm = getenv("PCL_MFMA_COND_MAX")) ctx->cond_max = (float)atof(cm);
-    if (const char *sm = getenv("PCL_SPLIT_MAX")) {
-        ctx->split_frac = std::min(1.0f, std::max(0.0f, (float)atof(sm)));
-        ctx->split_frac_set = true;
-    }
-    if (const char *ds = getenv("PCL_DP_STREAM")) ctx->dp_async = atoi(ds) != 0;
-    if (const char *co = getenv("PCL_COARSE")) ctx->coarse_on = atoi(co) != 0;
-    if (const char *cm2 = getenv("PCL_COMPACT_MAIN")) ctx->compact_main = atoi(cm2) != 0;
-    if (const char *cs = getenv("PCL_COARSE_STATS")) ctx->coarse_stats = atoi(cs) != 0;
-    if (const char *cp = getenv("PCL_COARSE_PASSES")) ctx->coarse_np = atoi(cp) == 3 ? 3 : 1;
-    if (const char *cm_ = getenv("PCL_COARSE_SPLIT_MAX")) ctx->coarse_split_frac = std::min(1.0f, std::max(0.0f, (float)atof(cm_)));   // (scoring only: A/B, tests)
-    if (const char *tm = getenv("PCL_TIMERS")) ctx->timing = atoi(tm) != 0;
     *out = ctx;
     return PCL_OK;
-}
-
-static void free_model(pcl_ctx *ctx) {
-    pcl_accumulate_release(ctx);                                 // (sized for the model's states and mixtures)
-    pcl_coarse_release(ctx);
-    dev_free(ctx->params32);
-    dev_free(ctx->params64);
-    dev_free(ctx->mean32);
-    dev_free(ctx->mean64);
-    dev_free(ctx->var64);
-    dev_free(ctx->w64);
-    dev_free(ctx->pm32);
-    dev_free(ctx->pm16f);
-    dev_free(ctx->kzero);
-    dev_free(ctx->fscale);
-    dev_free(ctx->centers32);
-    dev_free(ctx->d_cond);
-    dev_free(ctx->d_bad);
-    dev_free(ctx->d_bad_idx);
-    dev_free(ctx->d_nbad);
-    dev_free(ctx->d_non);
-    dev_free(ctx->d_good_idx);
-    dev_free(ctx->d_npt);
-    ctx->nbad.clear();
-    if (ctx->zero_pending && ctx->ev_zero) (void)hipEventSynchronize(ctx->ev_zero);
-    ctx->zero_pending = false;
-    dev_free(ctx->stats);
-    ctx->st_acc = ctx->st_alpha = ctx->st_mean = ctx->st_cov = nullptr;
-    ctx->J = ctx->M = ctx->Mpad = 0;
-}
-
-// frames32 is either a plain upload (owned) or a view of a streaming slot
-static void release_frames32(pcl_ctx *ctx) {
-    if (ctx->frames_front >= 0) {
-        ctx->frames32 = nullptr;
-        ctx->frames_front = -1;
-    } else {
-        dev_free(ctx->frames32);
-    }
 }
 
 int pcl_destroy(pcl_ctx *ctx) {
@@ -285,41 +300,13 @@ int pcl_destroy(pcl_ctx *ctx) {
     hipSetDevice(ctx->device);
     // Drain first, release second: every stream of the context (twice -- a stream drained early may have been handed work by an event
     // of one drained later only in the sense that its wait completes; nothing new is queued, so the second round returns at once and
-    // is there for the reader), THEN the communicator (collectives and the pipelined exchange run on these streams and stream_comm;
-    // rounds 1-5 destroyed it first), the buried batches, events, memory, streams.
+    // is there for the reader), THEN ctx_teardown.  No member of the context gives anything back before this point.
     for (int round = 0; round < 2; ++round) {
         hipStream_t all[] = {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_d2h, ctx->stream_desc, ctx->stream_comm, ctx->pcm.stream};
         for (hipStream_t s : all)
             if (s) hipStreamSynchronize(s);
     }
-    pcl_comm_destroy(ctx);
-    pcl_batch_reap(ctx, true);
-    // (round 6, tools/lifecycle_stress.py: a context destroyed with an asynchronous pcl_stats_zero still un-joined -- zero_pending --
-    //  had ev_zero destroyed HERE and then synchronised on by free_model below: a use of a dead event, SIGSEGV inside the runtime.
-    //  The streams are drained: nothing is pending any more, and the handles are cleared as they go.)
-    ctx->zero_pending = false;
-    if (ctx->ev_zero) hipEventDestroy(ctx->ev_zero);
-    if (ctx->ev_zero_src) hipEventDestroy(ctx->ev_zero_src);
-    ctx->ev_zero = ctx->ev_zero_src = nullptr;
-    if (ctx->desc_pin) hipHostFree(ctx->desc_pin);
-    ctx->desc_pin = nullptr;
-    drop_timers(ctx);                                            // (the per-chunk events of the staging stream's "pcm_h2d" group among them)
-    pcl_mfcc_release(ctx);                                       // drained above: no copy reads the staging buffers, no event is waited for
-    free_model(ctx);
-    pcl_units_release(ctx);
-    release_frames32(ctx);
-    dev_free(ctx->frames64);
-    dev_free(ctx->d_softplus);
-    dev_free(ctx->frames_slot[0]);
-    dev_free(ctx->frames_slot[1]);
-    if (ctx->ev_stage) hipEventDestroy(ctx->ev_stage);
-    if (ctx->ev_slot_free) hipEventDestroy(ctx->ev_slot_free);
-    hipStreamDestroy(ctx->stream);
-    hipStreamDestroy(ctx->stream_dp);
-    hipStreamDestroy(ctx->stream_aux);
-    if (ctx->stream_desc) hipStreamDestroy(ctx->stream_desc);
-    if (ctx->stream_d2h) hipStreamDestroy(ctx->stream_d2h);
-    delete ctx;
+    ctx_teardown(ctx);
     return PCL_OK;
 }
 
@@ -415,11 +402,12 @@ static int device_dim(int D) {
 int pcl_device_dim(int D) { return device_dim(D); }
 
 // The front-end (vad.hip) built the frame matrix on the device: make it the current one, as pcl_frames_upload does with a host matrix.
-void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D) {
+void pcl_frames_adopt(pcl_ctx *ctx, DevBuf<float> &&f32, DevBuf<double> &&f64, int64_t F, int D) {
     release_frames32(ctx);
-    dev_free(ctx->frames64);
-    ctx->frames32 = f32;
-    ctx->frames64 = f64;
+    ctx->frames64.release();
+    ctx->frames_up = std::move(f32);
+    ctx->frames32 = ctx->frames_up;
+    ctx->frames64 = std::move(f64);
     ctx->F = F;
     ctx->FD = device_dim(D);
     ctx->FDhost = D;
@@ -439,21 +427,21 @@ int pcl_model_alloc(pcl_ctx *ctx, int J, int M, int D, int flags, const char *wh
     const size_t nm = (size_t)J * Mpad * Dd, nw = (size_t)J * Mpad;
     const size_t npm = (size_t)J * (Mp32 / 32) * KS4 * 64 * 4;
     // (params32 / params64 / mean32: allocated when first derived, model_derive.hip)
-    TRY(dev_alloc(ctx, &ctx->mean64, nm));
-    TRY(dev_alloc(ctx, &ctx->var64, nm));
-    TRY(dev_alloc(ctx, &ctx->w64, nw));
-    TRY(dev_alloc(ctx, &ctx->pm32, npm));
-    TRY(dev_alloc(ctx, &ctx->pm16f, (size_t)J * (Mp32 / 32) * 2 * ((Dd + 7) / 8) * 64 * 8));
-    TRY(dev_alloc(ctx, &ctx->kzero, (size_t)J));
-    TRY(dev_alloc(ctx, &ctx->fscale, (size_t)J * 2 * ((Dd + 7) / 8) * 8));
-    TRY(dev_alloc(ctx, &ctx->centers32, (size_t)J * Dd));
-    TRY(dev_alloc(ctx, &ctx->d_cond, (size_t)J));
-    TRY(dev_alloc(ctx, &ctx->d_bad, (size_t)J * Mpad));
-    TRY(dev_alloc(ctx, &ctx->d_bad_idx, (size_t)J * Mpad));
-    TRY(dev_alloc(ctx, &ctx->d_nbad, (size_t)J));
-    TRY(dev_alloc(ctx, &ctx->d_non, (size_t)J));
-    TRY(dev_alloc(ctx, &ctx->d_good_idx, (size_t)J * Mpad));
-    TRY(dev_alloc(ctx, &ctx->d_npt, (size_t)J));
+    TRY(ctx->mean64.alloc(ctx, nm));
+    TRY(ctx->var64.alloc(ctx, nm));
+    TRY(ctx->w64.alloc(ctx, nw));
+    TRY(ctx->pm32.alloc(ctx, npm));
+    TRY(ctx->pm16f.alloc(ctx, (size_t)J * (Mp32 / 32) * 2 * ((Dd + 7) / 8) * 64 * 8));
+    TRY(ctx->kzero.alloc(ctx, (size_t)J));
+    TRY(ctx->fscale.alloc(ctx, (size_t)J * 2 * ((Dd + 7) / 8) * 8));
+    TRY(ctx->centers32.alloc(ctx, (size_t)J * Dd));
+    TRY(ctx->d_cond.alloc(ctx, (size_t)J));
+    TRY(ctx->d_bad.alloc(ctx, (size_t)J * Mpad));
+    TRY(ctx->d_bad_idx.alloc(ctx, (size_t)J * Mpad));
+    TRY(ctx->d_nbad.alloc(ctx, (size_t)J));
+    TRY(ctx->d_non.alloc(ctx, (size_t)J));
+    TRY(ctx->d_good_idx.alloc(ctx, (size_t)J * Mpad));
+    TRY(ctx->d_npt.alloc(ctx, (size_t)J));
     // with the coarse pass (gmm_score_coarse.hip) a state's off-pipe mixtures cost the scoring about what they would cost on the pipe, so
     // states stay split for scoring up to coarse_split_frac (0.99) of their mixtures.  Beyond it the route stops paying: tens of pairs per
     // frame and state pass the bound (many of a state's broader mixtures have by then crossed cond_max themselves and sit, off-pipe,
@@ -484,7 +472,7 @@ int pcl_model_finish(pcl_ctx *ctx) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // statistics: [acc J*Mpad | alpha J | mean J*Mpad*Dd | cov J*Mpad*Dd]
     ctx->stats_len = (size_t)J * Mpad + J + 2 * nm;
-    TRY(dev_alloc(ctx, &ctx->stats, ctx->stats_len));
+    TRY(ctx->stats.alloc(ctx, ctx->stats_len));
     ctx->st_acc = ctx->stats;
     ctx->st_alpha = ctx->st_acc + (size_t)J * Mpad;
     ctx->st_mean = ctx->st_alpha + J;
@@ -530,7 +518,7 @@ int pcl_frames_upload(pcl_ctx *ctx, int64_t F, int D, const void *frames, int dt
     if (Dd < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_frames_upload: feature dimension %d > 64 is not supported", D);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     release_frames32(ctx);
-    dev_free(ctx->frames64);
+    ctx->frames64.release();
     const size_t n = (size_t)F * Dd;
     // Direct PCIe copy in the host element type (padded on the host only when D has no exact kernel);
     // the other precision is derived on the device: f32 now (every mode reads it), f64 lazily (parity mode).
@@ -542,9 +530,10 @@ int pcl_frames_upload(pcl_ctx *ctx, int64_t F, int D, const void *frames, int dt
         for (int64_t f = 0; f < F; ++f) memcpy(&padded[(size_t)f * Dd * esz], (const char *)frames + (size_t)f * D * esz, (size_t)D * esz);
         src = padded.data();
     }
-    TRY(dev_alloc(ctx, &ctx->frames32, n));
+    TRY(ctx->frames_up.alloc(ctx, n));
+    ctx->frames32 = ctx->frames_up;
     if (dtype == PCL_F64) {
-        TRY(dev_alloc(ctx, &ctx->frames64, n));
+        TRY(ctx->frames64.alloc(ctx, n));
         HIPCHK(ctx, hipMemcpy(ctx->frames64, src, n * esz, hipMemcpyHostToDevice));
         TRY(pcl_launch_cast(ctx, ctx->frames64, ctx->frames32, nullptr, n));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -567,13 +556,8 @@ int pcl_frames_stage(pcl_ctx *ctx, int64_t F, int D, const float *frames) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int back = ctx->frames_front == 0 ? 1 : 0;
     const size_t n = (size_t)F * Dd;
-    if (n > ctx->frames_slot_cap[back]) {                          // (grows only: a steady stream of equal chunks allocates twice)
-        dev_free(ctx->frames_slot[back]);
-        ctx->frames_slot_cap[back] = 0;
-        TRY(dev_alloc(ctx, &ctx->frames_slot[back], n));
-        ctx->frames_slot_cap[back] = n;
-    }
-    if (!ctx->ev_stage) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
+    TRY(ctx->frames_slot[back].reserve(ctx, n));                   // (grows only: a steady stream of equal chunks allocates twice)
+    HIPCHK(ctx, ctx->ev_stage.make());
     if (ctx->have_slot_free) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_slot_free, 0));   // its last readers
     if (Dd == D) {
         HIPCHK(ctx, hipMemcpyAsync(ctx->frames_slot[back], frames, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream_aux));
@@ -597,8 +581,8 @@ int pcl_frames_swap(pcl_ctx *ctx) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipEventSynchronize(ctx->ev_stage));               // the copy is done: the caller's buffer is free again
     release_frames32(ctx);
-    dev_free(ctx->frames64);
-    if (!ctx->ev_slot_free) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_slot_free, hipEventDisableTiming));
+    ctx->frames64.release();
+    HIPCHK(ctx, ctx->ev_slot_free.make());
     HIPCHK(ctx, hipEventRecord(ctx->ev_slot_free, ctx->stream));   // everything queued so far read the old slot
     ctx->have_slot_free = true;
     ctx->frames_front = ctx->staged_slot;
@@ -684,12 +668,14 @@ int pcl_batch_create(pcl_ctx *ctx, int U, const int32_t *N, const int32_t *T, co
         delete b;
         PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: batch too large");
     }
-    int r = PCL_OK;
-    auto A = [&](int rr) { if (r == PCL_OK) r = rr; };
-    A(dev_alloc(ctx, &b->d_utt, (size_t)U));
-    A(dev_alloc(ctx, &b->Bt, (size_t)bo));
-    A(dev_alloc(ctx, &b->logpi, (size_t)vo));
-    A(dev_alloc(ctx, &b->d_row_state, (size_t)vo));
+    auto alloc = [&]() -> int {
+        TRY(b->d_utt.alloc(ctx, (size_t)U));
+        TRY(b->Bt.alloc(ctx, (size_t)bo));
+        TRY(b->logpi.alloc(ctx, (size_t)vo));
+        TRY(b->d_row_state.alloc(ctx, (size_t)vo));
+        return PCL_OK;
+    };
+    const int r = alloc();
     if (r != PCL_OK) {
         pcl_batch_destroy(b);
         return r;
@@ -700,23 +686,7 @@ int pcl_batch_create(pcl_ctx *ctx, int U, const int32_t *N, const int32_t *T, co
 
 // Everything a batch owns goes back to the pool.  The caller has made sure the GPU is done with the batch.
 static void batch_free_now(pcl_batch *b) {
-    pcl_free_synced_scope done;                              // the frees below skip their device-wide wait
-    if (b->ev_fetch) hipEventDestroy(b->ev_fetch);
-    if (b->ev_fetch_src) hipEventDestroy(b->ev_fetch_src);
-    if (b->ev_dp) hipEventDestroy(b->ev_dp);
-    if (b->ev_main) hipEventDestroy(b->ev_main);
-    if (b->ev_mark) hipEventDestroy(b->ev_mark);
-    pcl_batch_units_release(b);
-    pcl_batch_decode_release(b);
-    dev_free(b->d_utt); dev_free(b->Bt); dev_free(b->alpha); dev_free(b->beta); dev_free(b->lgam);
-    dev_free(b->logpi); dev_free(b->pi_out); dev_free(b->gamma_out); dev_free(b->ksai);
-    dev_free(b->logp); dev_free(b->qtrace); dev_free(b->point); dev_free(b->npass); dev_free(b->path);
-    dev_free(b->row_ptr); dev_free(b->col_idx); dev_free(b->csr_val);
-    dev_free(b->col_ptr); dev_free(b->row_idx); dev_free(b->csc_val);
-    dev_free(b->xi_m); dev_free(b->xi_s); dev_free(b->bp); dev_free(b->d_row_state);
-    dev_free(b->Bp); dev_free(b->alpha_e); dev_free(b->beta_e); dev_free(b->fb_kmax); dev_free(b->fb_dump); dev_free(b->fb_part_m); dev_free(b->fb_part_e);
-    dev_free(b->d_dups);
-    dev_free(b->d_segs); dev_free(b->d_seg_of_row); dev_free(b->d_tiles); dev_free(b->d_tiles_v); dev_free(b->d_tiles_s); dev_free(b->d_tiles_c); dev_free(b->d_tile_flags_c); dev_free(b->d_tile_flags); dev_free(b->tmp); dev_free(b->nz_tmp);
+    pcl_free_synced_scope done;                              // the members' frees skip their device-wide wait
     delete b;
 }
 
@@ -783,18 +753,18 @@ int pcl_batch_upload_sparse(pcl_batch *b, const std::vector<int> &row_ptr, const
                 }
             }
     }
-    dev_free(b->row_ptr); dev_free(b->col_idx); dev_free(b->csr_val);
-    dev_free(b->col_ptr); dev_free(b->row_idx); dev_free(b->csc_val);
-    dev_free(b->xi_m); dev_free(b->xi_s); dev_free(b->nz_tmp);
+    b->row_ptr.release(); b->col_idx.release(); b->csr_val.release();
+    b->col_ptr.release(); b->row_idx.release(); b->csc_val.release();
+    b->xi_m.release(); b->xi_s.release(); b->nz_tmp.release();
     const size_t nz = (size_t)b->nnz, np = row_ptr.size();
-    TRY(dev_alloc(ctx, &b->row_ptr, np));
-    TRY(dev_alloc(ctx, &b->col_ptr, np));
-    TRY(dev_alloc(ctx, &b->col_idx, nz));
-    TRY(dev_alloc(ctx, &b->row_idx, nz));
-    TRY(dev_alloc(ctx, &b->csr_val, nz));
-    TRY(dev_alloc(ctx, &b->csc_val, nz));
-    TRY(dev_alloc(ctx, &b->xi_m, nz));
-    TRY(dev_alloc(ctx, &b->xi_s, nz));
+    TRY(b->row_ptr.alloc(ctx, np));
+    TRY(b->col_ptr.alloc(ctx, np));
+    TRY(b->col_idx.alloc(ctx, nz));
+    TRY(b->row_idx.alloc(ctx, nz));
+    TRY(b->csr_val.alloc(ctx, nz));
+    TRY(b->csc_val.alloc(ctx, nz));
+    TRY(b->xi_m.alloc(ctx, nz));
+    TRY(b->xi_s.alloc(ctx, nz));
     // (a batch that has launched nothing: its buffers are fresh, the copies need not queue behind the main stream's kernels)
     auto up = b->launched ? pcl_h2d : pcl_h2d_fresh;
     HIPCHK(ctx, up(ctx, b->row_ptr, row_ptr.data(), np * sizeof(int)));
@@ -950,23 +920,23 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
             b->state_seg_hi.push_back(start[j + 1]);
             b->state_seg_hip.push_back(start[j] + nprim[j]);
         }
-    dev_free(b->d_dups);
+    b->d_dups.release();
     if (!b->dups.empty()) {
-        TRY(dev_alloc(ctx, &b->d_dups, b->dups.size()));
+        TRY(b->d_dups.alloc(ctx, b->dups.size()));
         HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_dups, b->dups.data(), b->dups.size() * sizeof(DupRow)));
     }
-    dev_free(b->d_segs);
-    dev_free(b->d_tiles);
-    dev_free(b->d_tiles_v);
-    dev_free(b->d_tiles_s);
-    dev_free(b->d_tiles_c);
-    dev_free(b->d_tile_flags_c);
+    b->d_segs.release();
+    b->d_tiles.release();
+    b->d_tiles_v.release();
+    b->d_tiles_s.release();
+    b->d_tiles_c.release();
+    b->d_tile_flags_c.release();
     b->n_tiles_s = b->n_tiles_c = 0;
     b->tile_frames = 0;
-    TRY(dev_alloc(ctx, &b->d_segs, (size_t)b->n_segs));
+    TRY(b->d_segs.alloc(ctx, (size_t)b->n_segs));
     if (b->n_segs) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_segs, b->segs.data(), (size_t)b->n_segs * sizeof(ScoreSeg)));
-    dev_free(b->d_seg_of_row);
-    TRY(dev_alloc(ctx, &b->d_seg_of_row, (size_t)b->sumN));
+    b->d_seg_of_row.release();
+    TRY(b->d_seg_of_row.alloc(ctx, (size_t)b->sumN));
     if (b->sumN) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_seg_of_row, b->seg_of_row.data(), (size_t)b->sumN * sizeof(int)));
     auto up = b->launched ? pcl_h2d : pcl_h2d_fresh;             // (batch-lifetime buffers: fresh only while nothing was launched)
     HIPCHK(ctx, up(ctx, b->d_row_state, row_state, (size_t)b->sumN * sizeof(int32_t)));
@@ -993,7 +963,7 @@ static int batch_revalidate(pcl_batch *b, const char *who) {
 }
 
 static int ensure_tmp(pcl_batch *b) {
-    if (!b->tmp) TRY(dev_alloc(b->ctx, &b->tmp, (size_t)b->sumNT));
+    if (!b->tmp) TRY(b->tmp.alloc(b->ctx, (size_t)b->sumNT));
     return PCL_OK;
 }
 
@@ -1022,7 +992,7 @@ int pcl_batch_set_posteriors(pcl_batch *b, const double *lgamma) {
     if (!lgamma) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_posteriors: NULL argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TRY(ensure_tmp(b));
-    if (!b->lgam) TRY(dev_alloc(ctx, &b->lgam, (size_t)b->sumNT));
+    if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
     HIPCHK(ctx, pcl_h2d(ctx, b->d_utt, b->utt.data(), (size_t)b->U * sizeof(UttDesc)));
     HIPCHK(ctx, hipMemcpyAsync(b->tmp, lgamma, (size_t)b->sumNT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TRY(pcl_launch_transpose(ctx, b, b->tmp, b->lgam, 1));
@@ -1034,7 +1004,7 @@ int pcl_batch_set_posteriors(pcl_batch *b, const double *lgamma) {
 static int ensure_frames64(pcl_ctx *ctx) {
     if (ctx->frames64 || !ctx->frames32) return PCL_OK;
     const size_t n = (size_t)ctx->F * ctx->FD;
-    TRY(dev_alloc(ctx, &ctx->frames64, n));
+    TRY(ctx->frames64.alloc(ctx, n));
     return pcl_launch_cast(ctx, nullptr, ctx->frames32, ctx->frames64, n);   // float -> double is exact
 }
 
@@ -1089,33 +1059,33 @@ static int build_tiles(pcl_batch *b, int precision) {
     const bool coarse = route == PCL_ROUTE_SPLIT16 && pcl_coarse_enabled(ctx);
     const std::vector<ScoreTile> tiles_s = (split.empty() || coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_score_subset_tile_frames(ctx->D));
     const std::vector<ScoreTile> tiles_c = (split.empty() || !coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_coarse_tile_frames());
-    dev_free(b->d_tiles);
-    dev_free(b->d_tiles_v);
-    dev_free(b->d_tiles_s);
-    dev_free(b->d_tiles_c);
-    dev_free(b->d_tile_flags_c);
+    b->d_tiles.release();
+    b->d_tiles_v.release();
+    b->d_tiles_s.release();
+    b->d_tiles_c.release();
+    b->d_tile_flags_c.release();
     pcl_desc_group uploads(ctx);                                   // the tile lists: staged, one wait at the end
     b->n_tiles_s = (int)tiles_s.size();
     if (!tiles_s.empty()) {
-        TRY(dev_alloc(ctx, &b->d_tiles_s, tiles_s.size()));
+        TRY(b->d_tiles_s.alloc(ctx, tiles_s.size()));
         HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_tiles_s, tiles_s.data(), tiles_s.size() * sizeof(ScoreTile)));
     }
     b->n_tiles_c = (int)tiles_c.size();
     if (!tiles_c.empty()) {
-        TRY(dev_alloc(ctx, &b->d_tiles_c, tiles_c.size()));
-        TRY(dev_alloc(ctx, &b->d_tile_flags_c, tiles_c.size()));
+        TRY(b->d_tiles_c.alloc(ctx, tiles_c.size()));
+        TRY(b->d_tile_flags_c.alloc(ctx, tiles_c.size()));
         HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_tiles_c, tiles_c.data(), tiles_c.size() * sizeof(ScoreTile)));
     }
-    dev_free(b->d_tile_flags);
-    TRY(dev_alloc(ctx, &b->d_tile_flags, tiles.size()));
+    b->d_tile_flags.release();
+    TRY(b->d_tile_flags.alloc(ctx, tiles.size()));
     b->n_tiles = (int)tiles.size();
     b->n_tiles_v = (int)tiles_v.size();
     b->tile_frames = tf;
     b->tile_gen = ctx->model_gen;
-    TRY(dev_alloc(ctx, &b->d_tiles, tiles.size()));
+    TRY(b->d_tiles.alloc(ctx, tiles.size()));
     if (!tiles.empty()) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_tiles, tiles.data(), tiles.size() * sizeof(ScoreTile)));
     if (!tiles_v.empty()) {
-        TRY(dev_alloc(ctx, &b->d_tiles_v, tiles_v.size()));
+        TRY(b->d_tiles_v.alloc(ctx, tiles_v.size()));
         HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_tiles_v, tiles_v.data(), tiles_v.size() * sizeof(ScoreTile)));
     }
     HIPCHK(ctx, uploads.finish());
@@ -1181,28 +1151,20 @@ int pcl_batch_forward_backward(pcl_batch *b, int fix_pi, double threshold) {
         b->fetch_pending = false;
     }
     if (!b->alpha) {
-        TRY(dev_alloc(ctx, &b->alpha, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->beta, (size_t)b->sumNT));
-        if (!b->lgam) TRY(dev_alloc(ctx, &b->lgam, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->pi_out, (size_t)b->sumN));
-        TRY(dev_alloc(ctx, &b->gamma_out, (size_t)b->sumN));
-        TRY(dev_alloc(ctx, &b->ksai, (size_t)b->sumNN));
-        TRY(dev_alloc(ctx, &b->logp, (size_t)b->U));
-        TRY(dev_alloc(ctx, &b->qtrace, (size_t)b->U * PCL_MAX_PASS));
-        TRY(dev_alloc(ctx, &b->npass, (size_t)b->U));
+        TRY(b->alpha.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->beta.alloc(ctx, (size_t)b->sumNT));
+        if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->pi_out.alloc(ctx, (size_t)b->sumN));
+        TRY(b->gamma_out.alloc(ctx, (size_t)b->sumN));
+        TRY(b->ksai.alloc(ctx, (size_t)b->sumNN));
+        TRY(b->logp.alloc(ctx, (size_t)b->U));
+        TRY(b->qtrace.alloc(ctx, (size_t)b->U * PCL_MAX_PASS));
+        TRY(b->npass.alloc(ctx, (size_t)b->U));
     }
     if (ctx->dp_async) {
         // stream_dp waits for everything queued on the main stream so far (the scoring of this batch), runs the
         // recursion, and leaves an event for whoever touches the batch next
-        if (!b->ev_dp) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_dp, hipEventDisableTiming));
-        HIPCHK(ctx, pcl_dp_follows_main(b, after_fetch));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->stream_dp;                      // the launcher and its timer use ctx->stream
-        const int rc = pcl_launch_forward_backward(ctx, b, fix_pi ? 1 : 0, threshold);
-        ctx->stream = main_stream;
-        if (rc != PCL_OK) return rc;
-        HIPCHK(ctx, hipEventRecord(b->ev_dp, ctx->stream_dp));
-        b->dp_pending = true;
+        TRY(pcl_run_on_dp_stream(b, after_fetch, [&] { return pcl_launch_forward_backward(ctx, b, fix_pi ? 1 : 0, threshold); }));
     } else {
         TRY(pcl_launch_forward_backward(ctx, b, fix_pi ? 1 : 0, threshold));
         HIPCHK(ctx, pcl_batch_mark(b));
@@ -1225,23 +1187,15 @@ int pcl_batch_viterbi(pcl_batch *b, int end_state_back) {
         b->fetch_pending = false;
     }
     if (!b->bp) {
-        TRY(dev_alloc(ctx, &b->bp, (size_t)b->sumNT));
-        TRY(dev_alloc(ctx, &b->path, (size_t)b->sumT));
-        TRY(dev_alloc(ctx, &b->point, (size_t)b->U));
+        TRY(b->bp.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->path.alloc(ctx, (size_t)b->sumT));
+        TRY(b->point.alloc(ctx, (size_t)b->U));
     }
     if (ctx->dp_async) {
         // like the forward-backward: on the second stream, behind everything the main stream has queued (this batch's scoring), beside
         // the NEXT batch's scoring; in order with a forward-backward of the same batch already queued there (round 4: on the main
         // stream the 0.35 ms recursion sat between two scoring kernels -- config 3's step is score + Viterbi)
-        if (!b->ev_dp) HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_dp, hipEventDisableTiming));
-        HIPCHK(ctx, pcl_dp_follows_main(b, after_fetch));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->stream_dp;                      // the launcher and its timer use ctx->stream
-        const int rc = pcl_launch_viterbi(ctx, b, end_state_back ? 1 : 0);
-        ctx->stream = main_stream;
-        if (rc != PCL_OK) return rc;
-        HIPCHK(ctx, hipEventRecord(b->ev_dp, ctx->stream_dp));
-        b->dp_pending = true;
+        TRY(pcl_run_on_dp_stream(b, after_fetch, [&] { return pcl_launch_viterbi(ctx, b, end_state_back ? 1 : 0); }));
     } else {
         TRY(batch_join(b));
         TRY(pcl_launch_viterbi(ctx, b, end_state_back ? 1 : 0));
@@ -1259,18 +1213,16 @@ int pcl_batch_regroup(pcl_batch *b, const int32_t *row_unit, int gmm_num, int32_
     if (!row_unit || !frame_unit || !frame_k || gmm_num < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_regroup: bad arguments");
     if (!b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_regroup: run pcl_batch_viterbi first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int32_t *d_ru = nullptr, *d_fu = nullptr, *d_fk = nullptr;
-    int rc = dev_alloc(ctx, &d_ru, (size_t)b->sumN);
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &d_fu, (size_t)b->sumT);
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &d_fk, (size_t)b->sumT);
-    if (rc == PCL_OK && hipMemcpyAsync(d_ru, row_unit, (size_t)b->sumN * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = PCL_ERR_HIP;
-    if (rc == PCL_OK) rc = pcl_launch_regroup(ctx, b, d_ru, gmm_num, d_fu, d_fk);
-    if (rc == PCL_OK && hipMemcpyAsync(frame_unit, d_fu, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = PCL_ERR_HIP;
-    if (rc == PCL_OK && hipMemcpyAsync(frame_k, d_fk, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = PCL_ERR_HIP;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) rc = PCL_ERR_HIP;
-    dev_free(d_ru); dev_free(d_fu); dev_free(d_fk);
-    if (rc == PCL_ERR_HIP) PCL_FAIL(ctx, PCL_ERR_HIP, "pcl_batch_regroup: HIP error");
-    return rc;
+    DevBuf<int32_t> d_ru, d_fu, d_fk;                       // (released with the device-wide wait, as ever, on every path)
+    TRY(d_ru.alloc(ctx, (size_t)b->sumN));
+    TRY(d_fu.alloc(ctx, (size_t)b->sumT));
+    TRY(d_fk.alloc(ctx, (size_t)b->sumT));
+    HIPCHK(ctx, hipMemcpyAsync(d_ru, row_unit, (size_t)b->sumN * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(pcl_launch_regroup(ctx, b, d_ru, gmm_num, d_fu, d_fk));
+    HIPCHK(ctx, hipMemcpyAsync(frame_unit, d_fu, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(frame_k, d_fk, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PCL_OK;
 }
 
 int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dropped_out, pcl_seg **out) {
@@ -1312,34 +1264,32 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
     if (!b->d_labels) {                                             // once per batch
         std::vector<int> loff((size_t)b->U + 1, 0);
         for (int u = 0; u < b->U; ++u) loff[u + 1] = loff[u] + b->label_len[u];
-        dev_free(b->d_label_off);                                   // (left by a call whose second allocation failed)
-        TRY(dev_alloc(ctx, &b->d_label_off, loff.size()));
-        TRY(dev_alloc(ctx, &b->d_labels, b->labels.size()));
+        b->d_label_off.release();                                   // (left by a call whose second allocation failed)
+        TRY(b->d_label_off.alloc(ctx, loff.size()));
+        TRY(b->d_labels.alloc(ctx, b->labels.size()));
         HIPCHK(ctx, pcl_h2d(ctx, b->d_label_off, loff.data(), loff.size() * sizeof(int)));
         HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->labels.data(), b->labels.size() * sizeof(int32_t)));
     }
-    int32_t *d_state = nullptr, *d_drop = nullptr;
-    int rc = dev_alloc(ctx, &d_state, (size_t)F);
-    if (rc == PCL_OK) rc = dev_alloc(ctx, &d_drop, (size_t)b->U);
-    bool hip_ok = true;
-    if (rc == PCL_OK) hip_ok = hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream) == hipSuccess;
-    if (rc == PCL_OK && hip_ok) rc = pcl_launch_align_segments(ctx, b, b->label_len_max, e, d_state, d_drop);
-    if (rc == PCL_OK && hip_ok && frame_state_out)
-        hip_ok = hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (rc == PCL_OK && hip_ok && dropped_out)
-        hip_ok = hipMemcpyAsync(dropped_out, d_drop, (size_t)b->U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-    if (rc == PCL_OK && hip_ok) hip_ok = pcl_batch_mark(b) == hipSuccess;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) hip_ok = false;
-    if (rc == PCL_OK && !hip_ok) {
+    DevBuf<int32_t> d_state, d_drop;
+    auto align = [&]() -> int {
+        TRY(d_state.alloc(ctx, (size_t)F));
+        TRY(d_drop.alloc(ctx, (size_t)b->U));
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
+        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, e, d_state, d_drop));
+        if (frame_state_out) HIPCHK(ctx, hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (dropped_out) HIPCHK(ctx, hipMemcpyAsync(dropped_out, d_drop, (size_t)b->U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, pcl_batch_mark(b));
+        return PCL_OK;
+    };
+    int rc = align();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) {      // (on every path: the frees below rely on it)
         pcl_set_error(ctx, "pcl_batch_align_segments: HIP error");
         rc = PCL_ERR_HIP;
     }
     if (rc == PCL_OK && out) rc = pcl_seg_create_device(ctx, F, ctx->J, d_state, out);
-    {
-        pcl_free_synced_scope done;                                 // the stream these two were used on has been waited for
-        dev_free(d_state);
-        dev_free(d_drop);
-    }
+    pcl_free_synced_scope done;                                     // the stream these two were used on has been waited for
+    d_state.release();
+    d_drop.release();
     return rc;
 }
 
@@ -1364,22 +1314,18 @@ int pcl_batch_get(pcl_batch *b, int what, void *host) {
     if ((what == PCL_GET_PATH || what == PCL_GET_POINT) && !b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_get: run pcl_batch_viterbi first");
     if (mat) {
         TRY(ensure_tmp(b));
-        double *logs = nullptr;
+        DevBuf<double> logs;
         if ((what == PCL_GET_ALPHA || what == PCL_GET_BETA) && b->fb_linear) {
             // the scaled forward-backward keeps (mantissa, exponent) pairs; the logarithms the reference holds are made here, on demand
-            TRY(dev_alloc(ctx, &logs, (size_t)b->sumNT));
-            const int rc = pcl_launch_fb_to_log(ctx, b, mat, what == PCL_GET_ALPHA ? b->alpha_e : b->beta_e, logs);
-            if (rc != PCL_OK) {
-                dev_free(logs);
-                return rc;
-            }
+            TRY(logs.alloc(ctx, (size_t)b->sumNT));
+            TRY(pcl_launch_fb_to_log(ctx, b, mat, what == PCL_GET_ALPHA ? b->alpha_e : b->beta_e, logs));
             mat = logs;
         }
         const int rt = pcl_launch_transpose(ctx, b, mat, b->tmp, 0);
         if (logs) {
             hipStreamSynchronize(ctx->stream);
             pcl_free_synced_scope done;
-            dev_free(logs);
+            logs.release();
         }
         TRY(rt);
         HIPCHK(ctx, hipMemcpyAsync(host, b->tmp, (size_t)b->sumNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1391,7 +1337,7 @@ int pcl_batch_get(pcl_batch *b, int what, void *host) {
     switch (what) {
         case PCL_GET_KSAI: src = b->ksai; bytes = (size_t)b->sumNN * 8; break;
         case PCL_GET_KSAI_NZ:
-            if (!b->nz_tmp) TRY(dev_alloc(ctx, &b->nz_tmp, (size_t)b->nnz));
+            if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->nnz));
             TRY(pcl_launch_ksai_gather(ctx, b, b->nz_tmp));
             src = b->nz_tmp; bytes = (size_t)b->nnz * 8;
             break;
@@ -1424,10 +1370,8 @@ int pcl_batch_fetch_async(pcl_batch *b, double *logp, double *lgamma_tm, double 
     if ((logp || lgamma_tm || ksai_nz) && !b->have_fb) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_fetch_async: run pcl_batch_forward_backward first");
     if ((path || point) && !b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_fetch_async: run pcl_batch_viterbi first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (!b->ev_fetch) {
-        HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fetch, hipEventDisableTiming));
-        HIPCHK(ctx, hipEventCreateWithFlags(&b->ev_fetch_src, hipEventDisableTiming));
-    }
+    HIPCHK(ctx, b->ev_fetch.make());
+    HIPCHK(ctx, b->ev_fetch_src.make());
     hipStream_t ds = ctx->stream_d2h;
     // behind what the batch has queued: the second stream's recursion (which itself waited for the batch's scoring) when one is
     // pending -- no packet on the main stream then --, else the main stream as of now
@@ -1439,12 +1383,11 @@ int pcl_batch_fetch_async(pcl_batch *b, double *logp, double *lgamma_tm, double 
         if (b->dp_pending) HIPCHK(ctx, hipStreamWaitEvent(ds, b->ev_dp, 0));
     }
     if (ksai_nz) {
-        if (!b->nz_tmp) TRY(dev_alloc(ctx, &b->nz_tmp, (size_t)b->nnz));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ds;                                     // (the launcher uses ctx->stream)
-        const int rc = pcl_launch_ksai_gather(ctx, b, b->nz_tmp);
-        ctx->stream = main_stream;
-        if (rc != PCL_OK) return rc;
+        if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->nnz));
+        {
+            pcl_stream_scope on_d2h(ctx, ds);
+            TRY(pcl_launch_ksai_gather(ctx, b, b->nz_tmp));
+        }
         HIPCHK(ctx, hipMemcpyAsync(ksai_nz, b->nz_tmp, (size_t)b->nnz * 8, hipMemcpyDeviceToHost, ds));
     }
     if (logp) HIPCHK(ctx, hipMemcpyAsync(logp, b->logp, (size_t)b->U * 8, hipMemcpyDeviceToHost, ds));
@@ -1467,14 +1410,15 @@ int pcl_batch_fetch_wait(pcl_batch *b) {
 int pcl_clock_probe(pcl_ctx *ctx, int spin_us, double *shader_mhz) {
     if (!ctx || !shader_mhz || spin_us < 1 || spin_us > 1000000) return PCL_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    unsigned long long *d = nullptr, h[4] = {0, 0, 0, 0};
-    TRY(dev_alloc(ctx, &d, (size_t)4));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    DevBuf<unsigned long long> d;
+    TRY(d.alloc(ctx, (size_t)4));
     int rc = pcl_launch_clock_probe(ctx, spin_us, d);
     if (rc == PCL_OK && hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream_aux) != hipSuccess) rc = PCL_ERR_HIP;
     if (rc == PCL_OK && hipStreamSynchronize(ctx->stream_aux) != hipSuccess) rc = PCL_ERR_HIP;
     {
         pcl_free_synced_scope done;                           // (the probe is the only user of d and it has finished)
-        dev_free(d);
+        d.release();
     }
     if (rc != PCL_OK) PCL_FAIL(ctx, rc, "pcl_clock_probe: HIP error");
     const double cyc = (double)(h[1] - h[0]), ref = (double)(h[3] - h[2]);
@@ -1493,10 +1437,8 @@ int pcl_stats_zero(pcl_ctx *ctx) {
     if (zero_async && ctx->stream_aux && ctx->stats_len * sizeof(double) >= ((size_t)64 << 20)) {
         // beside whatever the main stream does next (an E-step starts with the scoring of its first batch, which does not touch the block):
         // behind everything queued so far (the block's last readers), on the auxiliary stream
-        if (!ctx->ev_zero) {
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_zero, hipEventDisableTiming));
-            HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_zero_src, hipEventDisableTiming));
-        }
+        HIPCHK(ctx, ctx->ev_zero.make());
+        HIPCHK(ctx, ctx->ev_zero_src.make());
         HIPCHK(ctx, hipEventRecord(ctx->ev_zero_src, ctx->stream));
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_zero_src, 0));
         HIPCHK(ctx, hipMemsetAsync(ctx->stats, 0, ctx->stats_len * sizeof(double), ctx->stream_aux));
@@ -1613,21 +1555,18 @@ int pcl_model_download(pcl_ctx *ctx, double *mean, double *var, double *weight) 
     if (!ctx->mean64) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_model_download: no model uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)ctx->J * ctx->M * ctx->Dhost;
-    double *tmp = nullptr;
-    TRY(dev_alloc(ctx, &tmp, n));
-    int r = PCL_OK;
+    DevBuf<double> tmp;                                      // (released with the device-wide wait, on every path)
+    TRY(tmp.alloc(ctx, n));
     const double *srcs[3] = {ctx->mean64, ctx->var64, ctx->w64};
     double *dsts[3] = {mean, var, weight};
-    for (int k = 0; k < 3 && r == PCL_OK; ++k) {
+    for (int k = 0; k < 3; ++k) {
         if (!dsts[k]) continue;
         const int inner = (k == 2) ? 1 : ctx->Dhost;
-        r = pcl_launch_pack(ctx, srcs[k], inner, tmp);
-        if (r == PCL_OK && hipMemcpyAsync(dsts[k], tmp, (size_t)ctx->J * ctx->M * inner * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) r = PCL_ERR_HIP;
-        if (r == PCL_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = PCL_ERR_HIP;
+        TRY(pcl_launch_pack(ctx, srcs[k], inner, tmp));
+        HIPCHK(ctx, hipMemcpyAsync(dsts[k], tmp, (size_t)ctx->J * ctx->M * inner * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
-    dev_free(tmp);
-    if (r != PCL_OK && ctx->err.empty()) pcl_set_error(ctx, "pcl_model_download: copy failed");
-    return r;
+    return PCL_OK;
 }
 
 int pcl_accumulate_prune(pcl_ctx *ctx, double log2_threshold) {

@@ -227,25 +227,19 @@ int all_gather_parts(pcl_ctx *ctx, T *const *bases, const size_t *per_state, int
 int merge_hmm_acc(pcl_ctx *ctx) {
     if (!ctx->hmm_ksai || ctx->nranks == 1) return PCL_OK;
     const size_t n = (size_t)ctx->n_units * (ctx->S - 2) * (ctx->S + 1);
-    double *top = nullptr;
-    TRY(dev_alloc(ctx, &top, n));
-    int rc = pcl_launch_hmm_acc_merge_prepare(ctx, top);
-    if (rc == PCL_OK) rc = allreduce(ctx, top, n, true);
-    if (rc == PCL_OK) rc = pcl_launch_hmm_acc_merge_scale(ctx, top);
-    if (rc == PCL_OK) rc = allreduce(ctx, ctx->hmm_ksai, n, false);
-    if (rc == PCL_OK) rc = pcl_launch_hmm_acc_merge_finish(ctx, top);
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) rc = PCL_ERR_HIP;
-    dev_free(top);
-    return rc;
+    DevBuf<double> top;                              // (released with the device-wide wait, on every path)
+    TRY(top.alloc(ctx, n));
+    TRY(pcl_launch_hmm_acc_merge_prepare(ctx, top));
+    TRY(allreduce(ctx, top.p, n, true));
+    TRY(pcl_launch_hmm_acc_merge_scale(ctx, top));
+    TRY(allreduce(ctx, ctx->hmm_ksai.p, n, false));
+    TRY(pcl_launch_hmm_acc_merge_finish(ctx, top));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PCL_OK;
 }
 
 int ensure_payload32(pcl_ctx *ctx, size_t n) {
-    if (ctx->payload32_len >= n) return PCL_OK;
-    dev_free(ctx->payload32);                        // back to the pool it came from (a raw hipFree left a stale pool entry)
-    ctx->payload32_len = 0;
-    TRY(dev_alloc(ctx, &ctx->payload32, n));
-    ctx->payload32_len = n;
-    return PCL_OK;
+    return ctx->payload32.reserve(ctx, n);
 }
 
 
@@ -319,8 +313,7 @@ int exchange_all_gather(pcl_ctx *ctx, int payload, int j0, int len) {
 
 void pcl_comm_release(pcl_ctx *ctx) {
     pcl_pipe_release(ctx);
-    dev_free(ctx->payload32);
-    ctx->payload32_len = 0;
+    ctx->payload32.release();
 }
 
 extern "C" {
@@ -406,7 +399,7 @@ int pcl_stats_allreduce(pcl_ctx *ctx) {
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pcl_timer_begin(ctx, "allreduce");
-    int rc = allreduce(ctx, ctx->stats, ctx->stats_len, false);
+    int rc = allreduce(ctx, ctx->stats.p, ctx->stats_len, false);
     pcl_timer_end(ctx, "allreduce");
     if (rc != PCL_OK) return rc;
     TRY(merge_hmm_acc(ctx));
@@ -464,13 +457,6 @@ int pcl_em_exchange(pcl_ctx *ctx, double c_covariance, int payload, int update_t
 // later groups.  One rank: M-step + derive of finished chunks beside the rest of the pass.  Same sums, same M-step arithmetic
 // as pcl_em_exchange; only WHO re-estimates a state differs (the r-th slice of every chunk instead of one range).
 namespace {
-struct StreamSwap {                                                // the launchers and their timers use ctx->stream
-    pcl_ctx *c;
-    hipStream_t keep;
-    StreamSwap(pcl_ctx *ctx, hipStream_t s) : c(ctx), keep(ctx->stream) { ctx->stream = s; }
-    ~StreamSwap() { c->stream = keep; }
-};
-
 // mode 1 (default): only the chunk's REDUCE-SCATTER leaves early -- it costs the GPU little beside the accumulate pass, and it
 // is half of the bytes on the wire; M-step, all-gather and derive follow in pcl_pipe_finish.  mode 0 (PCL_PIPE_MODE=0): the
 // chunk's whole chain leaves early (measured on one GPU: the M-step and derive kernels beside the power-limited accumulate pass
@@ -509,7 +495,7 @@ int pipe_issue_chunk(pcl_ctx *ctx, int c) {
     const bool solo = ctx->transport == 0;
     if (solo && ctx->pipe_mode != 0) return PCL_OK;                // one GPU, nothing to send: everything waits for pcl_pipe_finish
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream_comm, ctx->pipe_ev[c], 0));
-    StreamSwap sw(ctx, ctx->stream_comm);
+    pcl_stream_scope sw(ctx, ctx->stream_comm);
     int lo = a, hi = b, rc = PCL_OK;
     if (!solo) {
         pcl_timer_begin(ctx, "reduce_scatter");
@@ -527,9 +513,9 @@ int pcl_pipe_begin(pcl_ctx *ctx, double c_covariance, int payload, int n_chunks)
     if (!ctx->stream_comm) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream_comm, hipStreamNonBlocking));
     const int K = std::max(1, std::min(n_chunks, std::min(ctx->J, 64)));
     while ((int)ctx->pipe_ev.size() < K) {
-        hipEvent_t e;
-        HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ctx->pipe_ev.push_back(e);
+        LazyEvent e;
+        HIPCHK(ctx, e.make());
+        ctx->pipe_ev.push_back(std::move(e));
     }
     if (payload == PCL_F32 && ctx->transport != 0)
         TRY(ensure_payload32(ctx, std::max(ctx->stats_len, (size_t)ctx->J * (2 * (size_t)ctx->Mpad * ctx->D + ctx->Mpad))));
@@ -560,7 +546,7 @@ int pcl_pipe_finish(pcl_ctx *ctx, int update_transitions) {
     int rc = pcl_pipe_progress(ctx, ctx->J);                       // whatever the pass did not release itself
     ctx->pipe_active = false;
     if (rc != PCL_OK) return rc;
-    if (!ctx->pipe_done) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pipe_done, hipEventDisableTiming));
+    HIPCHK(ctx, ctx->pipe_done.make());
     HIPCHK(ctx, hipEventRecord(ctx->pipe_done, ctx->stream_comm));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->pipe_done, 0));
     if (ctx->pipe_mode != 0) {                                     // the chunks' M-steps and all-gathers, then every layout at once
@@ -587,10 +573,8 @@ int pcl_pipe_finish(pcl_ctx *ctx, int update_transitions) {
 }
 
 void pcl_pipe_release(pcl_ctx *ctx) {
-    for (hipEvent_t e : ctx->pipe_ev) hipEventDestroy(e);
     ctx->pipe_ev.clear();
-    if (ctx->pipe_done) hipEventDestroy(ctx->pipe_done);
-    ctx->pipe_done = nullptr;
+    ctx->pipe_done.destroy();
     if (ctx->stream_comm) {
         hipStreamSynchronize(ctx->stream_comm);
         hipStreamDestroy(ctx->stream_comm);

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/poccala_hip.h"
+#include "pcl_own.h"
 
 // ---------------------------------------------------------------- device-side descriptors
 // One scoring segment = one (utterance, emitting row): `len` consecutive frames starting at frame
@@ -71,25 +72,14 @@ struct PcmStage {
     hipStream_t stream = nullptr;
     int16_t *pin[2] = {nullptr, nullptr};
     size_t cap = 0;                          // samples per buffer
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    LazyEvent ev[2];
 };
 // The four host-built MFCC tables (twiddle cos | sin | mel response | DCT basis) in ONE device block, kept with the context: `host` is the
 // copy the next call's tables are compared with byte for byte (the caller builds them: equal geometry does not mean equal contents).
 struct MfccTables {
-    double *d = nullptr;
-    size_t cap = 0;                          // doubles
+    DevBuf<double> d;
     int nfft = 0, nfilt = 0, rank = 0;       // nfft = 0: nothing valid on the device
     std::vector<double> host;
-};
-
-// A grow-only device array: a pointer, a capacity (elements) and two functions, defined beside dev_alloc / dev_free below.
-struct pcl_ctx;
-template <typename T>
-struct GrowBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int reserve(pcl_ctx *ctx, size_t n);   // room for n elements; nothing is copied: the contents are undefined after a growth
-    void release();
 };
 
 // Scratch of the accumulate pass (gmm_accumulate.hip, gmm_accumulate_f16.hip): everything here is rebuilt by every pass and dead when the
@@ -99,17 +89,64 @@ struct GrowBuf {
 // allocated them per step).  Every array has its own capacity: a pass reserves what it needs, pcl_accumulate_release gives all of it back.
 struct AccScratch {
     // work lists: per-segment counts / offsets, per-state active-frame lists, the accumulate order of the states
-    GrowBuf<int> cnt; GrowBuf<long long> off; GrowBuf<ActiveFrame> list;
-    GrowBuf<int> work_states, seg_lo, seg_hi, split_flag;   // (split_flag: 1 = a split state, in accumulate order)
+    DevBuf<int> cnt; DevBuf<long long> off; DevBuf<ActiveFrame> list;
+    DevBuf<int> work_states, seg_lo, seg_hi, split_flag;   // (split_flag: 1 = a split state, in accumulate order)
     // producer / consumer: tile images in LDS order, per-state tile offsets, outlier masks; two sets: the producer of state group g + 1
     // runs on the auxiliary stream beside the consumer of group g
-    GrowBuf<unsigned char> images[2];
-    GrowBuf<int> tile_off[2], state_flag[2];
-    GrowBuf<unsigned int> tile_mask[2];                     // one word per tile: its capacity is the sets' capacity in tiles
-    hipEvent_t ev_prod[2] = {nullptr, nullptr}, ev_cons[2] = {nullptr, nullptr}, ev_start = nullptr;
+    DevBuf<unsigned char> images[2];
+    DevBuf<int> tile_off[2], state_flag[2];
+    DevBuf<unsigned int> tile_mask[2];                     // one word per tile: its capacity is the sets' capacity in tiles
+    LazyEvent ev_prod[2], ev_cons[2], ev_start;
 };
 
-struct pcl_ctx {
+// What a context owns on the device, in the groups that live and die together: pcl_ctx inherits them, so a member reads ctx->pm32 as before,
+// and a group is dropped by assigning it an empty one (every DevBuf releases its block).
+// The model: float64 master copy and the layouts derived from it (model_derive.hip).
+struct ModelDev {
+    DevBuf<float> params32;      // J * Mpad * row : [s_0 c_0 s_1 c_1 ... const2]  (log2 domain)
+    DevBuf<double> params64;     // same layout, float64
+    DevBuf<float> pm32;          // MFMA scoring layout: [J][Mpad32/32][KS4][64 lanes][4], see gmm_score_mfma.hip
+    DevBuf<float> centers32;     // J * D per-state expansion centres c_j
+    DevBuf<unsigned short> pm16f;     // split-f16 layout with the constants folded into the spare K slot: [J][Mpad32/32][2][KS8f][64 lanes][8], see gmm_score_split.hip
+    DevBuf<double> kzero;             // [J] K0_j = max_m k'_m of that layout
+    DevBuf<float> fscale;             // [J][2][KS8f*8] power-of-two feature scales of that layout
+    DevBuf<float> d_cond;             // [J] conditioning of the centred expansion (pcl_ctx::cond is the host copy)
+    DevBuf<unsigned char> d_bad;      // [J][Mpad] 1 = the mixture is off the matrix pipe
+    DevBuf<int> d_bad_idx;            // [J][Mpad] the state's off-pipe mixtures in ascending order (first nbad[j] entries)
+    DevBuf<int> d_nbad;               // [J]
+    DevBuf<int> d_non;                // [J] mixtures on the pipe (M - nbad)
+    DevBuf<int> d_good_idx;           // [J][Mpad] the state's ON-pipe mixtures in ascending order (first M - nbad[j] entries): row r of a split state's matrix-pipe layout is mixture good_idx[r]
+    DevBuf<int> d_npt;                // [J] 32-mixture tiles of the matrix-pipe layout in use: ceil((M - nbad) / 32)
+    DevBuf<float> mean32;        // J * Mpad * D raw means (accumulate kernel)
+    DevBuf<double> mean64;       // float64 master copy of the model: mean, var (J*Mpad*D), weight (J*Mpad)
+    DevBuf<double> var64, w64;
+    DevBuf<double> stats;        // E-step statistics (float64, linear domain), one allocation: [acc J*Mpad | alpha J | mean J*Mpad*D | cov J*Mpad*D]
+};
+// Coarse layout of the off-pipe mixtures (gmm_score_coarse.hip): their bound v_up on the matrix pipe, exact evaluation of what it
+// cannot rule out.  Derived on first use after the model changed (coarse_gen != model_gen).
+struct CoarseDev {
+    DevBuf<unsigned short> pmc;       // [J][Mpad32/32][2][KS8f][64 lanes][8]: the state's bad_idx list, 32 per tile
+    DevBuf<float> fscale_c;           // [J][2][KS8f*8]
+    DevBuf<double> kzero_c;           // [J]
+    DevBuf<float> rows_c;             // [J][Mpad][D][2]: the tight mixtures' direct-form rows (s_d, c_d) in bad_idx order, for the pairs the coarse pass cannot rule out
+    DevBuf<float> kgap_c;             // [J]: (the state's largest tight k2) - K0, rounded up (the one-product pass: see EPS1 in gmm_score_coarse.hip)
+    DevBuf<double> k2c;               // [J][Mpad] exact log2-domain constant of the idx-th off-pipe mixture
+    DevBuf<int> d_nct;                // [J] coarse tiles in use
+    DevBuf<unsigned long long> d_coarse_counter;   // PCL_COARSE_STATS=1: pairs evaluated exactly
+};
+// Unit inventory (hmm_units.hip)
+struct UnitsDev {
+    DevBuf<double> d_unit_trans;                  // device copy of unit_trans (the transition M-step writes it)
+    DevBuf<double> hmm_ksai;                      // per-unit accumulators, LOG domain: [n_units][S-2][S] and, behind them (hmm_gamma), [n_units][S-2]
+};
+// Pronunciation tree for the decoder (hmm_decode.hip)
+struct LexiconDev {
+    DevBuf<int> lex_units, lex_nunits, lex_child_ptr, lex_child_idx, lex_word, lex_roots;
+    DevBuf<int4> lex_info;                        // per node (first child, children, words end here, unit pair)
+    DevBuf<double> d_unit_logtrans;
+};
+
+struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     int device = 0;
     AccScratch acc;
     hipStream_t stream = nullptr;
@@ -118,13 +155,6 @@ struct pcl_ctx {
     // model (device)
     int J = 0, M = 0, Mpad = 0, D = 0, Dhost = 0, row = 0;  // D = device (padded) feature dimension
     int model_flags = 0;
-    float *params32 = nullptr;   // J * Mpad * row : [s_0 c_0 s_1 c_1 ... const2]  (log2 domain)
-    double *params64 = nullptr;  // same layout, float64
-    float *pm32 = nullptr;       // MFMA scoring layout: [J][Mpad32/32][KS4][64 lanes][4], see gmm_score_mfma.hip
-    float *centers32 = nullptr;  // J * D per-state expansion centres c_j
-    unsigned short *pm16f = nullptr;  // split-f16 layout with the constants folded into the spare K slot: [J][Mpad32/32][2][KS8f][64 lanes][8], see gmm_score_split.hip
-    double *kzero = nullptr;          // [J] K0_j = max_m k'_m of that layout
-    float *fscale = nullptr;          // [J][2][KS8f*8] power-of-two feature scales of that layout
     int Mpad32 = 0;              // M rounded up to a multiple of 32
     int layouts_valid = 0;             // PCL_LAYOUT_* derived for the current model (the f64 rows are derived on first use)
     hipStream_t stream_dp = nullptr;   // forward-backward runs here, beside the next batch's scoring on `stream`
@@ -137,37 +167,21 @@ struct pcl_ctx {
     // conditioning of the centred expansion the MFMA kernels use: cond[j] = max_m log2e sum_d (mu - c_j)^2 / (2 var),
     // the magnitude of the terms that cancel in it.  States above cond_max are scored / accumulated by the
     // direct-form VALU kernels instead (f32 error of the expansion ~ 5e-7 * cond nats).
-    float *d_cond = nullptr;
-    std::vector<float> cond;
+    std::vector<float> cond;             // (host copy of d_cond)
     float cond_max = 96.f;
     // Split states.  The limit is a property of single MIXTURES (one tight mixture far from the state's centre), and after an M-step most states
     // have a few of them (tools/cond_probe.py: 7 % of the mixtures, every state).  A mixture with cond_m > cond_max is therefore taken OUT of
     // the matrix-pipe layouts (written like a zero-weight mixture, left out of the state's feature scales, K0 and cond) and evaluated by the
     // direct-form kernels over the state's compacted list of such mixtures, merged by a log-add (scoring) / added to the statistics
     // (accumulate).  A state goes to the direct-form kernels as a whole only when more than split_max of its mixtures are out.
-    unsigned char *d_bad = nullptr;    // [J][Mpad] 1 = the mixture is off the matrix pipe
-    int *d_bad_idx = nullptr;          // [J][Mpad] the state's off-pipe mixtures in ascending order (first nbad[j] entries)
-    int *d_nbad = nullptr;             // [J]
-    int *d_non = nullptr;              // [J] mixtures on the pipe (M - nbad)
-    int *d_good_idx = nullptr;         // [J][Mpad] the state's ON-pipe mixtures in ascending order (first M - nbad[j] entries): row r of a split state's matrix-pipe layout is mixture good_idx[r]
     bool compact_main = true;          // env PCL_COMPACT_MAIN=0 (read when the context is made): every state keeps derive_kernel's tiles in mixture order, all of them walked (A/B)
-    int *d_npt = nullptr;              // [J] 32-mixture tiles of the matrix-pipe layout in use: ceil((M - nbad) / 32)
     std::vector<int> nbad;
     float split_frac = 0.5f;           // env PCL_SPLIT_MAX: the share of a state's mixtures that may be off the pipe (0 = no splitting)
     bool split_frac_set = false;       // PCL_SPLIT_MAX was given (otherwise: 1.0 for scoring when the coarse pass is available, 0.5 for the accumulate pass)
     int split_max = 0;                 // = split_frac * M: mixtures per state that may be off the pipe (0: no splitting -- whole states, as before round 4)
     int model_gen = 0;           // bumped whenever the layouts (and cond) are re-derived
-    // Coarse layout of the off-pipe mixtures (gmm_score_coarse.hip): their bound v_up on the matrix pipe, exact evaluation of what it
-    // cannot rule out.  Derived on first use after the model changed (coarse_gen != model_gen).
-    unsigned short *pmc = nullptr;     // [J][Mpad32/32][2][KS8f][64 lanes][8]: the state's bad_idx list, 32 per tile
-    float *fscale_c = nullptr;         // [J][2][KS8f*8]
-    double *kzero_c = nullptr;         // [J]
-    float *rows_c = nullptr;           // [J][Mpad][D][2]: the tight mixtures' direct-form rows (s_d, c_d) in bad_idx order, for the pairs the coarse pass cannot rule out
-    float *kgap_c = nullptr;           // [J]: (the state's largest tight k2) - K0, rounded up (the one-product pass: see EPS1 in gmm_score_coarse.hip)
+    // the coarse layout (CoarseDev)
     int coarse_np = 1;                 // env PCL_COARSE_PASSES (read when the context is made): 1 = one f16 product per term, 3 = the two-piece operands' three
-    double *k2c = nullptr;             // [J][Mpad] exact log2-domain constant of the idx-th off-pipe mixture
-    int *d_nct = nullptr;              // [J] coarse tiles in use
-    unsigned long long *d_coarse_counter = nullptr;   // PCL_COARSE_STATS=1: pairs evaluated exactly
     int coarse_gen = -1;
     float coarse_split_frac = 0.99f;   // env PCL_COARSE_SPLIT_MAX: the share of a state's mixtures that may be off the pipe with the coarse pass (see pcl_model_upload)
     bool coarse_stats = false;         // env PCL_COARSE_STATS=1 (read when the context is made): count the pairs evaluated exactly (pcl_coarse_counter)
@@ -175,42 +189,34 @@ struct pcl_ctx {
     // the accumulate pass keeps the round 4-5 rule (whole states in direct form above acc_split_max off-pipe mixtures): its subset launch has
     // no coarse pass, and at a high share of off-pipe mixtures the whole-state kernel is the cheaper of its two routes
     int acc_split_max = 0;
-    float *mean32 = nullptr;     // J * Mpad * D raw means (accumulate kernel)
-    double *mean64 = nullptr;    // float64 master copy of the model: mean, var (J*Mpad*D), weight (J*Mpad)
-    double *var64 = nullptr, *w64 = nullptr;
     // frames (device)
     int64_t F = 0;
     int FD = 0, FDhost = 0;
-    float *frames32 = nullptr;
-    double *frames64 = nullptr;
-    // streaming: two frame slots; frames32 points into slot frames_front (or is a plain upload when frames_front < 0);
-    // pcl_frames_stage copies the next chunk into the other slot on stream_aux, pcl_frames_swap makes it current
-    float *frames_slot[2] = {nullptr, nullptr};
-    size_t frames_slot_cap[2] = {0, 0};
+    float *frames32 = nullptr;            // VIEW: the current f32 frame matrix -- frames_up (a plain upload, frames_front < 0) or frames_slot[frames_front]
+    DevBuf<float> frames_up;
+    DevBuf<double> frames64;
+    // streaming: two frame slots (grow only); pcl_frames_stage copies the next chunk into the slot that is not current on stream_aux,
+    // pcl_frames_swap makes it current
+    DevBuf<float> frames_slot[2];
     int frames_front = -1, staged_slot = -1, staged_D = 0;
     int64_t staged_F = 0;
-    hipEvent_t ev_stage = nullptr, ev_slot_free = nullptr;
+    LazyEvent ev_stage, ev_slot_free;
     bool have_slot_free = false;
-    // E-step statistics (device, float64, linear domain)
-    double *stats = nullptr;  // one allocation: [acc J*Mpad | alpha J | mean J*Mpad*D | cov J*Mpad*D]
+    // E-step statistics (ModelDev::stats)
     size_t stats_len = 0;
-    double *st_acc = nullptr, *st_alpha = nullptr, *st_mean = nullptr, *st_cov = nullptr;
-    double *d_softplus = nullptr;   // table of log1p(exp(-d)) for the forward-backward recursion (hmm_dp.hip)
+    double *st_acc = nullptr, *st_alpha = nullptr, *st_mean = nullptr, *st_cov = nullptr;   // VIEWS into stats
+    DevBuf<double> d_softplus;  // table of log1p(exp(-d)) for the forward-backward recursion (hmm_dp.hip)
     bool stats_fresh = false;
     // pcl_stats_zero clears the block on the auxiliary stream (3.9 GB: 0.58 ms on the main stream in front of every E-step's scoring,
     // which does not touch it); whoever touches the statistics next on the main stream waits for it first (pcl_stats_join)
-    hipEvent_t ev_zero = nullptr, ev_zero_src = nullptr;
+    LazyEvent ev_zero, ev_zero_src;
     bool zero_pending = false;
     double acc_prune_log2 = -1e300;   // pcl_accumulate_prune: frames with gamma_t(j) below 2^this are left out (default: only exact zeros)    // all zero since pcl_stats_zero: the first accumulate pass may store instead of read-modify-write
     // unit inventory (hmm_units.hip): n_units HMMs of S states, unit i owns GMM states i*(S-2) .. i*(S-2)+S-3
     int n_units = 0, S = 0;
     std::vector<double> unit_trans, unit_logtrans;   // host copies [n_units][S][S]: transmat and np.log(transmat)
-    double *d_unit_trans = nullptr;                  // device copy of unit_trans (the transition M-step writes it)
-    double *hmm_ksai = nullptr, *hmm_gamma = nullptr;   // per-unit accumulators, LOG domain: [n_units][S-2][S], [n_units][S-2]
-    // pronunciation tree for the decoder (hmm_decode.hip)
-    int *lex_units = nullptr, *lex_nunits = nullptr, *lex_child_ptr = nullptr, *lex_child_idx = nullptr, *lex_word = nullptr, *lex_roots = nullptr;
-    int4 *lex_info = nullptr;                        // per node (first child, children, words end here, unit pair)
-    double *d_unit_logtrans = nullptr;
+    double *hmm_gamma = nullptr;                     // VIEW into hmm_ksai (UnitsDev): [n_units][S-2]
+    // pronunciation tree for the decoder (LexiconDev)
     int lex_nodes = 0, lex_nroots = 0;
     // multi-GPU (pcl_comm.hip): RCCL communicator, or the host-callback rehearsal transport
     void *comm = nullptr;
@@ -218,13 +224,12 @@ struct pcl_ctx {
     int transport = 0;                               // 0 none, 1 RCCL, 2 host callback (several ranks on ONE device)
     pcl_allgather_fn host_allgather = nullptr;
     void *host_user = nullptr;
-    float *payload32 = nullptr;                      // f32 staging of the statistics / parameters (payload = PCL_F32)
-    size_t payload32_len = 0;
+    DevBuf<float> payload32;                         // f32 staging of the statistics / parameters (payload = PCL_F32)
     // pipelined exchange (pcl_comm.hip): state chunks go through reduce-scatter -> M-step -> all-gather -> derive on stream_comm
     // as soon as the accumulate pass has queued the last kernel that touches them
     hipStream_t stream_comm = nullptr;
-    std::vector<hipEvent_t> pipe_ev;
-    hipEvent_t pipe_done = nullptr;
+    std::vector<LazyEvent> pipe_ev;
+    LazyEvent pipe_done;
     bool pipe_active = false;
     int pipe_early = 0;                                            // chunks of the last pipelined call that left while the pass was still running
     int pipe_K = 0, pipe_next = 0, pipe_payload = 0, pipe_mode = 1;   // mode 1: only the reduce-scatter leaves early; 0: the whole chain
@@ -251,7 +256,16 @@ struct pcl_ctx {
     MfccTables mfcc_tab;
 };
 
-struct pcl_batch {
+// Decoder state of a batch (hmm_decode.hip): token buffers, node -> token map, scratch, results; re-made as a group when a call needs more room
+struct BatchDecodeDev {
+    DevBuf<double> dec_f64;
+    DevBuf<int> dec_slot, dec_work, dec_int;
+    DevBuf<double> dec_score;
+    int dec_cap = 0, dec_cand = 0, dec_nodes = 0;    // what the buffers were sized for
+};
+
+// Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_api.hip).
+struct pcl_batch : BatchDecodeDev {
     pcl_ctx *ctx = nullptr;
     int U = 0, Nmax = 0, Tmax = 0;
     bool has_one_frame = false;   // an utterance of ONE frame: the reference's Baum-Welch raises on it (golden G15) and it adds nothing to any accumulator
@@ -267,70 +281,66 @@ struct pcl_batch {
     int max_outdeg = 0, max_indeg = 0;
     long long nnz = 0;
     // device
-    UttDesc *d_utt = nullptr;
-    double *Bt = nullptr, *alpha = nullptr, *beta = nullptr, *lgam = nullptr;
-    double *logpi = nullptr, *pi_out = nullptr, *gamma_out = nullptr, *ksai = nullptr;
-    double *logp = nullptr, *qtrace = nullptr, *point = nullptr;
-    int32_t *npass = nullptr, *path = nullptr;
-    int *row_ptr = nullptr, *col_idx = nullptr;   // CSR (successors)
-    double *csr_val = nullptr;
-    int *col_ptr = nullptr, *row_idx = nullptr;   // CSC (predecessors, ascending source index)
-    double *csc_val = nullptr;
-    double *xi_m = nullptr, *xi_s = nullptr;      // per CSR entry online-LSE state
+    DevBuf<UttDesc> d_utt;
+    DevBuf<double> Bt, alpha, beta, lgam;
+    DevBuf<double> logpi, pi_out, gamma_out, ksai;
+    DevBuf<double> logp, qtrace, point;
+    DevBuf<int32_t> npass, path;
+    DevBuf<int> row_ptr, col_idx;   // CSR (successors)
+    DevBuf<double> csr_val;
+    DevBuf<int> col_ptr, row_idx;   // CSC (predecessors, ascending source index)
+    DevBuf<double> csc_val;
+    DevBuf<double> xi_m, xi_s;      // per CSR entry online-LSE state
     // scaled linear-domain forward-backward (hmm_fb_linear.hip): packed exp(B), the int32 exponents of alpha / beta (their
     // mantissas live in `alpha` / `beta`), per utterance the exponent maxima of the range test
-    unsigned long long *Bp = nullptr;
-    int *alpha_e = nullptr, *beta_e = nullptr, *fb_kmax = nullptr;
-    double *fb_dump = nullptr;
-    double *fb_part_m = nullptr;                  // per utterance, sum and wave: the posterior kernel's partial sums (mantissa, exponent)
-    int *fb_part_e = nullptr;
+    DevBuf<unsigned long long> Bp;
+    DevBuf<int> alpha_e, beta_e, fb_kmax;
+    DevBuf<double> fb_dump;
+    DevBuf<double> fb_part_m;                  // per utterance, sum and wave: the posterior kernel's partial sums (mantissa, exponent)
+    DevBuf<int> fb_part_e;
     bool left_right = false;                      // every state is reached from itself / the state before it only (AcousticModel.embedded)
     bool fb_linear = false;                       // the last forward-backward left (mantissa, exponent) pairs in alpha / beta
-    unsigned short *bp = nullptr;                 // Viterbi back-pointers, time-major (t, n)
-    int32_t *d_row_state = nullptr;
+    DevBuf<unsigned short> bp;                 // Viterbi back-pointers, time-major (t, n)
+    DevBuf<int32_t> d_row_state;
     // scoring work lists
-    ScoreSeg *d_segs = nullptr;
+    DevBuf<ScoreSeg> d_segs;
     std::vector<ScoreSeg> segs;              // host copy, sorted by state
     std::vector<int> state_seg_lo, state_seg_hi;  // per state with work: segment range
     std::vector<int> state_seg_hip;               // ... of which [lo, hip) are scored and [hip, hi) are copies of a scored row
     std::vector<DupRow> dups;
-    DupRow *d_dups = nullptr;
+    DevBuf<DupRow> d_dups;
     std::vector<int> work_states;
-    ScoreTile *d_tiles = nullptr;            // tiles for the precision last scored with (MFMA kernel in MFMA mode)
+    DevBuf<ScoreTile> d_tiles;            // tiles for the precision last scored with (MFMA kernel in MFMA mode)
     std::vector<int> acc_ws, acc_lo, acc_hi, acc_split; // accumulate's state order (well-conditioned first)
-    hipEvent_t ev_main = nullptr, ev_dp = nullptr;   // main stream -> stream_dp hand-over, and back
+    LazyEvent ev_main, ev_dp;   // main stream -> stream_dp hand-over, and back
     bool mark_is_score = false;              // ev_mark sits right behind this batch's last scoring: the second stream may wait for IT instead of a new record on the main stream
-    hipEvent_t ev_mark = nullptr;            // the main stream behind the last work this batch queued there (pcl_batch_mark): what pcl_batch_destroy waits for -- not the work later batches queued behind it
+    LazyEvent ev_mark;            // the main stream behind the last work this batch queued there (pcl_batch_mark): what pcl_batch_destroy waits for -- not the work later batches queued behind it
     bool dp_pending = false;                 // forward-backward queued on stream_dp and not yet joined
-    hipEvent_t ev_fetch = nullptr, ev_fetch_src = nullptr;   // pcl_batch_fetch_async: copies done / the main stream at the time of the call
+    LazyEvent ev_fetch, ev_fetch_src;   // pcl_batch_fetch_async: copies done / the main stream at the time of the call
     bool fetch_pending = false;              // result copies queued on stream_d2h: the next compute call on this batch waits for them
-    int *d_tile_flags = nullptr;             // split-f16 scoring: per tile, 1 = a scaled feature left the f16 range (rescored)
-    ScoreTile *d_tiles_v = nullptr;          // MFMA mode only: tiles of ill-conditioned states for the VALU kernel
-    ScoreTile *d_tiles_s = nullptr;          // MFMA mode only: tiles of the split states for the subset launch (their off-pipe mixtures)
-    ScoreTile *d_tiles_c = nullptr;          // ... and for the coarse pass (gmm_score_coarse.hip): the same states at the matrix-pipe tile size
-    int *d_tile_flags_c = nullptr;           // coarse pass: per tile, 1 = a scaled feature left the f16 range (the direct-form subset kernel rescored it)
+    DevBuf<int> d_tile_flags;             // split-f16 scoring: per tile, 1 = a scaled feature left the f16 range (rescored)
+    DevBuf<ScoreTile> d_tiles_v;          // MFMA mode only: tiles of ill-conditioned states for the VALU kernel
+    DevBuf<ScoreTile> d_tiles_s;          // MFMA mode only: tiles of the split states for the subset launch (their off-pipe mixtures)
+    DevBuf<ScoreTile> d_tiles_c;          // ... and for the coarse pass (gmm_score_coarse.hip): the same states at the matrix-pipe tile size
+    DevBuf<int> d_tile_flags_c;           // coarse pass: per tile, 1 = a scaled feature left the f16 range (the direct-form subset kernel rescored it)
     int n_tiles_c = 0;
     int n_segs = 0, n_tiles = 0, n_tiles_v = 0, n_tiles_s = 0, tile_frames = 0, tile_gen = -1;
-    double *tmp = nullptr;                   // sumNT staging buffer for layout conversion
-    double *nz_tmp = nullptr;                // nnz staging buffer for the sparse xi download
+    DevBuf<double> tmp;                   // sumNT staging buffer for layout conversion
+    DevBuf<double> nz_tmp;                // nnz staging buffer for the sparse xi download
     std::vector<int> seg_of_row;              // (utterance, row) -> its segment (-1: not a GMM row); d_seg_of_row: the device copy (sumN ints)
-    int *d_seg_of_row = nullptr;
+    DevBuf<int> d_seg_of_row;
     int max_N = 0;                            // rows of the largest sentence HMM of the batch
     // (the accumulate pass's device work lists and tile images are the CONTEXT's scratch, pcl_ctx::acc; the host staging of its state order is acc_ws ... above)
-    // decoder state (hmm_decode.hip): token buffers, node -> token map, scratch, results
-    double *dec_f64 = nullptr;
-    int *dec_slot = nullptr, *dec_work = nullptr, *dec_int = nullptr;
-    double *dec_score = nullptr;
-    int dec_cap = 0, dec_cand = 0, dec_nodes = 0;
+    // decoder state: BatchDecodeDev
     bool have_dec = false;
     // label-built batches (pcl_batch_create_labels): the labels, and per unit the list of its occurrences
     bool from_labels = false;
     std::vector<int32_t> label_len, labels;
     std::vector<double> logpi_u;             // ln pi of every state of utterance u (uniform 1/N, AcousticModel.py:1003-1006)
     int n_occ = 0;
-    int *occ_ptr = nullptr, *occ_utt = nullptr, *occ_row0 = nullptr;   // unit -> [occ_ptr[u], occ_ptr[u+1]) -> (utterance, first emitting row)
-    int32_t *d_labels = nullptr;             // the labels on the device and the U + 1 offsets into them: uploaded by the first
-    int *d_label_off = nullptr;              // pcl_batch_align_segments of the batch, kept for the next
+    DevBuf<int> occ_ptr, occ_utt, occ_row0;   // unit -> [occ_ptr[u], occ_ptr[u+1]) -> (utterance, first emitting row)
+    DevBuf<int32_t> d_labels;             // the labels on the device and the U + 1 offsets into them: uploaded by the first
+    DevBuf<int> d_label_off;              // pcl_batch_align_segments of the batch, kept for the next
     int label_max = 0, label_len_max = 0;    // largest unit id / longest label of the batch
 };
 
@@ -355,64 +365,19 @@ __device__ __forceinline__ bool pcl_fb_linear_ok(const int *kmax, int u, int T) 
     return kb < 32760 && ((long long)kb + ka + 4) * (long long)(T + 2) + kp < (long long)LE_LIMIT;
 }
 
-// ---------------------------------------------------------------- error helpers
-#define PCL_FAIL(ctx, code, ...)                         \
-    do {                                                 \
-        char _b[512];                                    \
-        snprintf(_b, sizeof(_b), __VA_ARGS__);           \
-        pcl_set_error((ctx), _b);                        \
-        return (code);                                   \
-    } while (0)
-#define HIPCHK(ctx, call)                                                                         \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) PCL_FAIL(ctx, PCL_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e)); \
-    } while (0)
-
-void pcl_set_error(pcl_ctx *ctx, const char *msg);
-
-// Device memory comes from a process-wide caching pool (pcl_api.hip): hipMalloc / hipFree cost 0.1-1 ms each and hipFree
-// waits for the whole device, which a library that creates and drops a batch per utterance (the drop-in classes) or per
-// chunk (streaming) cannot afford.  A freed block goes back to the pool; dev_free first waits for the device, as hipFree
-// did, unless the caller has already made sure the GPU is done with the block (pcl_free_synced_scope).
-void *pcl_pool_alloc(int device, size_t bytes);           // nullptr: out of memory even after the cache was released
-void pcl_pool_free(void *p);
-extern thread_local int pcl_tls_free_synced;              // > 0: dev_free skips its device-wide wait
-struct pcl_free_synced_scope {
-    pcl_free_synced_scope() { ++pcl_tls_free_synced; }
-    ~pcl_free_synced_scope() { --pcl_tls_free_synced; }
+// ---------------------------------------------------------------- helpers (the error macros, dev_alloc / dev_free and the owning types: pcl_own.h)
+inline int pcl_ctx_device(const pcl_ctx *ctx) { return ctx->device; }
+// The launchers and their timers read the stream from the context: work for another stream is launched inside one of these.
+struct pcl_stream_scope {
+    pcl_ctx *ctx;
+    hipStream_t keep;
+    pcl_stream_scope(pcl_ctx *c, hipStream_t s) : ctx(c), keep(c->stream) { c->stream = s; }
+    ~pcl_stream_scope() { ctx->stream = keep; }
+    pcl_stream_scope(const pcl_stream_scope &) = delete;
+    pcl_stream_scope &operator=(const pcl_stream_scope &) = delete;
 };
-template <typename T>
-static inline int dev_alloc(pcl_ctx *ctx, T **p, size_t n) {
-    if (n == 0) n = 1;
-    *p = static_cast<T *>(pcl_pool_alloc(ctx->device, n * sizeof(T)));
-    if (!*p) PCL_FAIL(ctx, PCL_ERR_NOMEM, "device memory: %zu bytes", n * sizeof(T));
-    return PCL_OK;
-}
-template <typename T>
-static inline void dev_free(T *&p) {
-    if (p) pcl_pool_free((void *)p);
-    p = nullptr;
-}
-template <typename T>
-int GrowBuf<T>::reserve(pcl_ctx *ctx, size_t n) {
-    if (n <= cap) return PCL_OK;
-    release();
-    const int rc = dev_alloc(ctx, &p, n);
-    if (rc == PCL_OK) cap = n;
-    return rc;
-}
-template <typename T>
-void GrowBuf<T>::release() { dev_free(p); cap = 0; }
 // Host -> device copy on the context's main stream, complete on return: unlike hipMemcpy (legacy null stream) it does not
 // wait for the work of the other streams (a decoder running on the second stream while the next chunk's batch is built).
-static inline hipError_t pcl_h2d(pcl_ctx *ctx, void *dst, const void *src, size_t bytes);
-#define TRY(x)                    \
-    do {                          \
-        int _r = (x);             \
-        if (_r != PCL_OK) return _r; \
-    } while (0)
-
 static inline hipError_t pcl_h2d(pcl_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!bytes) return hipSuccess;
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
@@ -493,10 +458,8 @@ static inline hipError_t pcl_stats_join(pcl_ctx *ctx) {
 // Called at the end of every entry point that queues main-stream work reading or writing the batch's buffers (the auxiliary
 // stream's producers are always joined by a main-stream consumer queued behind them).
 static inline hipError_t pcl_batch_mark(pcl_batch *b) {
-    if (!b->ev_mark) {
-        hipError_t e = hipEventCreateWithFlags(&b->ev_mark, hipEventDisableTiming);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e = b->ev_mark.make();
+    if (e != hipSuccess) return e;
     return hipEventRecord(b->ev_mark, b->ctx->stream);
 }
 
@@ -520,9 +483,25 @@ static inline hipError_t pcl_dp_follows_main(pcl_batch *b, bool after_fetch = fa
     const bool shortcut = pcl_fewer_markers() && b->mark_is_score && b->ev_mark;
     b->mark_is_score = false;
     if (shortcut) return hipStreamWaitEvent(ctx->stream_dp, b->ev_mark, 0);
-    if (!b->ev_main && (e = hipEventCreateWithFlags(&b->ev_main, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = b->ev_main.make()) != hipSuccess) return e;
     if ((e = hipEventRecord(b->ev_main, ctx->stream)) != hipSuccess) return e;
     return hipStreamWaitEvent(ctx->stream_dp, b->ev_main, 0);
+}
+
+// A recursion of batch `b` (forward-backward, Viterbi, decode) on the second stream: stream_dp goes behind the batch's main-stream work,
+// `launch` runs with ctx->stream redirected to it, and ev_dp is left for whoever touches the batch next (batch_join, pcl_batch_fetch_async).
+template <typename Launch>
+static inline int pcl_run_on_dp_stream(pcl_batch *b, bool after_fetch, Launch launch) {
+    pcl_ctx *ctx = b->ctx;
+    HIPCHK(ctx, b->ev_dp.make());
+    HIPCHK(ctx, pcl_dp_follows_main(b, after_fetch));
+    {
+        pcl_stream_scope on_dp(ctx, ctx->stream_dp);
+        TRY(launch());
+    }
+    HIPCHK(ctx, hipEventRecord(b->ev_dp, ctx->stream_dp));
+    b->dp_pending = true;
+    return PCL_OK;
 }
 
 // shared by pcl_api.hip and hmm_units.hip (C linkage, internal)
@@ -618,14 +597,12 @@ int pcl_launch_hmm_acc_merge_scale(pcl_ctx *ctx, const double *top);      // acc
 int pcl_launch_hmm_acc_merge_finish(pcl_ctx *ctx, const double *top);     // acc[i] = top[i] + ln(acc[i])
 int pcl_launch_trans_mstep(pcl_ctx *ctx);
 void pcl_units_release(pcl_ctx *ctx);
-void pcl_batch_units_release(pcl_batch *b);
 void pcl_comm_release(pcl_ctx *ctx);
 void pcl_lexicon_release(pcl_ctx *ctx);
-void pcl_batch_decode_release(pcl_batch *b);
 int pcl_launch_pack(pcl_ctx *ctx, const double *src, int inner, double *dst);
 extern "C" {   // defined inside pcl_api.hip's extern "C" block; hidden like every symbol the public header does not declare
 int pcl_device_dim(int D);                                   // the padded feature dimension the kernels have an instance for (-1: D > 64)
-void pcl_frames_adopt(pcl_ctx *ctx, float *f32, double *f64, int64_t F, int D);   // device-built (F, pcl_device_dim(D)) matrices become the current frames
+void pcl_frames_adopt(pcl_ctx *ctx, DevBuf<float> &&f32, DevBuf<double> &&f64, int64_t F, int D);   // device-built (F, pcl_device_dim(D)) matrices become the current frames
 // pcl_model_upload in two halves, for a model that is MADE on the device (bootstrap.hip): pcl_model_alloc drops the old model, allocates the
 // float64 master copy (mean64 / var64 / w64, padded device layout, contents undefined) and every derived buffer, and sets the shape fields;
 // the caller fills the master copy on ctx->stream; pcl_model_finish derives the layouts, conditioning and split lists and makes the
@@ -636,12 +613,12 @@ int pcl_model_finish(pcl_ctx *ctx);
 // pcl_seg_create from an owner array that is already on the device (F = ctx->F entries, every one -1 or in [0, J): the CALLER guarantees it,
 // nothing is validated here); the array is only read and stays the caller's.  gmm_segment.hip.
 int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_frame_state, pcl_seg **out);
-// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (from the pool: the caller dev_free's it),
+// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (in *d_out: the caller's from then on),
 // complete on return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.  pcm16: `signal` is int16_t
 // samples, which travel through the context's page-locked staging; otherwise double, copied from the caller's memory as it is.
 int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const void *signal, bool pcm16, const int64_t *sig_off, int framerate,
                     double sampletime, double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos,
-                    const double *twiddle_sin, const double *mel_response, const double *dct_matrix, int64_t out_rows, double **d_out,
+                    const double *twiddle_sin, const double *mel_response, const double *dct_matrix, int64_t out_rows, DevBuf<double> *d_out,
                     std::vector<long long> *row_off);
 void pcl_mfcc_release(pcl_ctx *ctx);          // the staging buffers, their events and stream, the cached tables (pcl_destroy, streams drained)
 void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms);   // a host-clock entry of a timer group (only while timing is on)

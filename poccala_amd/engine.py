@@ -78,6 +78,16 @@ class Engine(object):
     def sync(self):
         self._check(self._lib.pcl_sync(self._ctx))
 
+    @staticmethod
+    def pool_stats():
+        """The process-wide device memory pool's books (pcl_pool_stats): blocks / bytes handed out and not yet given back, bytes cached,
+        hipMalloc calls and device-wide waits so far."""
+        blocks, nbytes, cached = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        allocs, waits = C.c_uint64(), C.c_uint64()
+        _lib.load().pcl_pool_stats(C.byref(blocks), C.byref(nbytes), C.byref(cached), C.byref(allocs), C.byref(waits))
+        return dict(handed_out_blocks=blocks.value, handed_out_bytes=nbytes.value, cached_bytes=cached.value,
+                    device_allocs=allocs.value, device_waits=waits.value)
+
     def device_info(self):
         name = C.create_string_buffer(256)
         cus = C.c_int()
