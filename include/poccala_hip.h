@@ -108,7 +108,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
+ * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -420,6 +420,32 @@ int pcl_flat_start(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_b
  * matrix, no frames loaded: PCL_ERR_INVALID.  Integer arithmetic only.  Synchronous. */
 int pcl_uniform_segments(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T, const int64_t *frame_begin,
                          int gmm_num, int J, int32_t *frame_state_out, pcl_seg **out);
+
+/* ----------------------------------------------------------------- mix-up (row f9): growing a trained model by splitting mixtures
+ * The context's (J, M, D) model becomes a (J, M_new, D) model, M < M_new <= 8192, without leaving the device (csrc/model_mixup.hip): the
+ * way a GMM-HMM is grown 1 -> 2 -> 4 -> ... between rounds of EM instead of being started at its full size.  Not in the reference, which
+ * clusters again when its mix_level changes.  THE RULE, per state j independently, in float64, one rounding per operation, cur = M:
+ * while cur < M_new
+ *   live = the mixtures i < cur with weight[i] > 0 (a NaN weight is not live);  n = min(M_new - cur, |live|)
+ *   the n heaviest of live -- weight descending, equal weights by ascending index -- are split: the r-th of that order, i, gets child c = cur + r
+ *     delta_d     = perturb * sqrt(var[i,d])        (one rounded product)
+ *     mean[c,d]   = mean[i,d] + delta_d;   mean[i,d] = mean[i,d] - delta_d        (both from the parent's mean before this round)
+ *     var[c,d]    = var[i,d];              weight[i] = weight[c] = 0.5 * weight[i]
+ *   cur += n
+ * A mixture may be split again in a later round.  perturb >= 0 and finite (HTK's MU uses 0.2).  The plan -- which slot descends from which
+ * old mixture through which rounds -- is a function of the weights alone and is made by one workgroup per state (ranks by counting, no
+ * atomics: two runs give the same bits); the new float64 master copy is then filled from the old one through that plan (padding as an
+ * upload leaves it: mean 0, variance 1, weight 0) and everything pcl_model_upload runs after its copy follows: derived layouts,
+ * conditioning, split lists, a zeroed statistics block of the new shape.  pcl_model_download and every scoring path see the model an
+ * upload of the same (J, M_new, D) arrays would give; flags are the old model's.  The unit transitions, the frames and a live pcl_seg
+ * are untouched (pcl_seg_em then runs from the grown model); a live batch is in whatever state a pcl_model_upload of another shape
+ * leaves it in.  origin_out (J, M_new) int32 or NULL: the index in the OLD model that mixture m descends from, m itself for m < M -- the
+ * only thing that travels to the host.
+ * No model: PCL_ERR_STATE.  M_new <= M, M_new > 8192, a negative or non-finite perturb, or a state without a live mixture (it cannot
+ * grow; the message names the state): PCL_ERR_INVALID, checked before anything is changed -- the model in place stays.  If the new
+ * model's allocation fails the context is left WITHOUT a model, as a failed upload leaves it.  pcl_kernel_time group "mixup": the plan
+ * and the fill ("derive": the pass behind them).  Synchronous. */
+int pcl_model_mixup(pcl_ctx *ctx, int M_new, double perturb, int32_t *origin_out /* (J, M_new) or NULL */);
 
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /

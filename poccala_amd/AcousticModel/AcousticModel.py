@@ -6,7 +6,8 @@ per-utterance E-step or alignment can be written exactly as the reference's work
 (`multi_embedded_training_1` :884-916, `multi_process_data` :723-768).  Batched equivalents that keep
 everything on the GPU are `estep_batch` / `align_batch`, and `train_segments_batch` / `train_segments_data` for training
 scheme 1 (`__cal_gmm` :532-561: clustering + stand-alone EM of every state), and `flat_start_batch` (`__flat_start` :479-517) /
-`init_segments_batch` (`multi_process_data(init=True)` :734-735) for the model-free step either scheme begins with.  `load_audio` is `__load_audio` (:463-477: wav -> MFCC ->
+`init_segments_batch` (`multi_process_data(init=True)` :734-735) for the model-free step either scheme begins with.  `mixup_batch` grows the
+units' models between rounds of EM by splitting mixtures on the device (no counterpart in the reference).  `load_audio` is `__load_audio` (:463-477: wav -> MFCC ->
 VAD); `load_audio_batch` does it for many files in one call and leaves the frames resident.  Orchestration (Pool fan-out, file
 walking, recording) is out of scope.
 """
@@ -492,6 +493,38 @@ class AcousticModel(DataInitialization):
             for k in range(e):
                 unit_hmms[unit].profunction[1 + k].set_model(g_mean, g_var, np.ones(m) / m)
         return mean, var, diff[:, 0].copy()
+
+    def mixup_batch(self, unit_hmms, mix_level, perturb=0.2, engine=None):
+        """Grow every GMM state of every unit in `unit_hmms` to `mix_level` mixtures by splitting its heaviest mixtures on the device
+        (Engine.mixup; the rule: include/poccala_hip.h, pcl_model_mixup) -- what HTK's MU and Kaldi's mix-up do between rounds of EM; the
+        reference has no such step (it clusters again when mix_level changes).  The model grown is the engine's when it holds one of the
+        units' shape (states unit-major over sorted(unit_hmms), as every batch helper lays them out and flat_start_batch /
+        train_segments_batch leave it); otherwise the units' GMM objects are uploaded first.  The grown parameters are written into the
+        GMM objects, whose mixture count follows, and this object's mix_level with it, so save_parameter works afterwards and
+        train_segments_batch(..., mix_level=None) / estep_batch continue from the grown model without clustering again:
+        flat_start_batch at mix_level 1 -> EM -> mixup_batch(2) -> EM -> mixup_batch(4) -> ...  Returns origin (J, mix_level) int32: the
+        old mixture every new one descends from."""
+        engine = engine or default_engine()
+        units = sorted(unit_hmms)
+        e = self.__state_num - 2
+        gmms = [unit_hmms[u].profunction[1 + k] for u in units for k in range(e)]
+        have = (len(gmms), gmms[0].mixture, gmms[0].dimension)
+        if any((len(gmms), g.mixture, g.dimension) != have for g in gmms):
+            raise ValueError('mixup_batch: the units\' GMM states differ in mixture count or dimension')
+        if (engine.J, engine.M, engine.D) != have:
+            engine.load_model(*self._model_arrays(unit_hmms)[2])
+        origin = engine.mixup(mix_level, perturb=perturb, want_origin=True)
+        self._adopt_model(engine.model_download(), units, unit_hmms)
+        return origin
+
+    def _adopt_model(self, model, units, unit_hmms):
+        """(mean, var, weight) of a model laid out unit-major over `units` into the units' GMM objects; this object's mix_level follows."""
+        mean, var, w = model
+        e = self.__state_num - 2
+        for ui, unit in enumerate(units):
+            for k in range(e):
+                unit_hmms[unit].profunction[1 + k].set_model(mean[ui * e + k], var[ui * e + k], w[ui * e + k])
+        self.__mix_level = int(mean.shape[1])
 
     def init_segments_batch(self, labels, data_list, unit_hmms, mix_level=None, c_covariance=1e-3, seed=0, precision=PCL_F64, engine=None):
         """The first round of training scheme 1, which needs no model: uniform segmentation (multi_process_data(init=True),

@@ -66,6 +66,7 @@ PROTOTYPES = {
     'pcl_model_flat_start': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i]),
     'pcl_flat_start': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'pcl_uniform_segments': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
+    'pcl_model_mixup': (_i, [_vp, _i, _d, _vp]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

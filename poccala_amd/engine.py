@@ -334,6 +334,19 @@ class Engine(object):
         self._model_key = None
         return mean[:self.FD], var[:self.FD], int(n[0])
 
+    def mixup(self, M_new, perturb=0.2, want_origin=False):
+        """Grow the resident model from M to M_new mixtures per state on the device (pcl_model_mixup): per state, rounds in which the
+        heaviest mixtures with a weight > 0 are split -- parent and child share the halved weight and the variance, their means move
+        apart by perturb * sqrt(var) -- until the state holds M_new.  Afterwards the engine holds the model exactly as load_model of
+        the grown (J, M_new, D) arrays would have left it, with a zeroed statistics block; frames, unit transitions and live Segments
+        stay.  want_origin=True: returns origin (J, M_new) int32, the old mixture every new one descends from."""
+        M_new = int(M_new)
+        origin = np.empty((self.J, M_new), dtype=np.int32) if want_origin and self.J > 0 and M_new > 0 else None
+        self._check(self._lib.pcl_model_mixup(self._ctx, M_new, float(perturb), ptr(origin)))
+        self.M = M_new
+        self._model_key = None
+        return origin if want_origin else None
+
     def uniform_segments(self, unit_ids, T, frame_begin, gmm_num, J, want_map=False):
         """Uniform segmentation of labelled utterances (multi_process_data(init=True): __eq_segment mode 'e', then __get_gmmdata,
         AcousticModel.py:605-644): every utterance is cut into equal chunks, one per label unit, every chunk into gmm_num slices.
