@@ -108,7 +108,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
+ * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -446,6 +446,56 @@ int pcl_uniform_segments(pcl_ctx *ctx, int U, const int32_t *label_len, const in
  * model's allocation fails the context is left WITHOUT a model, as a failed upload leaves it.  pcl_kernel_time group "mixup": the plan
  * and the fill ("derive": the pass behind them).  Synchronous. */
 int pcl_model_mixup(pcl_ctx *ctx, int M_new, double perturb, int32_t *origin_out /* (J, M_new) or NULL */);
+
+/* ----------------------------------------------------------------- speaker adaptation (row f10): MLLR mean transforms, MAP means
+ * Both schemes read the resident statistics of pcl_batch_accumulate -- acc[j,m] = sum_t gamma_t(j,m) and mean_acc[j,m,d] = sum_t
+ * gamma_t(j,m) (o_td + bias), bias = 100 -- and change the MEANS of the context's model in place, without the model or the statistics
+ * leaving the device (csrc/model_adapt.hip).  Not in the reference.  Everything is float64.  With s[j,m,d] = mean_acc[j,m,d] - bias acc[j,m]:
+ *
+ * MLLR (Leggetter & Woodland), diagonal covariances: every state j has a regression class state_class[j] in [0, R), or -1 = "leave this
+ * state alone" (silence); state_class = NULL puts every state in class 0.  A mixture (j, m), m < M, CONTRIBUTES when acc[j,m] is finite and
+ * > 0; a mixture with acc == 0 (or a NaN / infinite / negative acc) contributes exactly nothing, and the padding mixtures of the device
+ * layout are never visited.  For class r and feature dimension i, with xi = (1, mu_1 .. mu_D) of a mixture, over r's contributing mixtures:
+ *     G[r,i] = sum (acc / var_i) xi xi^T        (D+1) x (D+1), symmetric          k[r,i] = sum (s_i / var_i) xi
+ *     row i of W[r] = w with G[r,i] w = k[r,i], by Cholesky G = L L^T and two triangular solves
+ * W[r] is D x (D+1): column 0 is the offset b_r, the rest the matrix A_r.  A class is REFUSED -- it gets the identity [0 | I] and a
+ * non-zero status -- when, tested in this order,
+ *     PCL_MLLR_LOW_OCCUPANCY          its occupancy, the sum of acc over its contributing mixtures, is below min_occ
+ *     PCL_MLLR_FEW_MIXTURES           fewer than D+1 of its mixtures contribute (G cannot have full rank)
+ *     PCL_MLLR_NOT_POSITIVE_DEFINITE  a pivot of any of its D factorisations is not finite or not > 0
+ * (a class without states has occupancy 0 and no mixture).  G and k are a GEMM with K = the class's mixtures: the states are grouped by
+ * class on the host (J ints travel), a class's mixtures are cut into chunks of PCL_MLLR_CHUNK mixtures (env, read on every call; default
+ * 65536), one workgroup per (chunk, i) forms the chunk's partial on the float64 matrix pipe (env PCL_MLLR_VALU=1: on the VALU), a second
+ * kernel sums a class's partials in chunk order.  No floating-point atomics: two calls on the same statistics give the same bits.
+ * pcl_mllr_estimate changes nothing of the model.  It keeps W resident with the model it was estimated for (any call that makes a new
+ * model -- an upload, a flat start, a mix-up -- drops it), so that estimate followed by pcl_model_transform_means(W = NULL) moves nothing
+ * to the host but the R statuses.  W_out (R, D, D+1), occ_out (R,), status_out (R,): NULLs are skipped.  D <= 48.
+ *
+ * pcl_model_transform_means: mean[j,m,:] <- A_r mean[j,m,:] + b_r (the offset first, then the products in ascending feature order, one
+ * rounding each) for every mixture m < M of every state with class r >= 0.  A class whose W[r] is exactly [0 | I] -- every refused class --
+ * is skipped: its means keep their bits, as do those of the states of class -1.  Variances, weights and padding are untouched.  W: host
+ * (R, D, D+1), or NULL = the resident estimate, which must be of the same R.  Then the pass pcl_mstep runs after its kernel: derived
+ * layouts, conditioning, split lists, so that every scoring path sees the model an upload of the downloaded arrays would give.
+ *
+ * pcl_mstep_map (Gauvain & Lee, means only): mean <- (tau mean + s) / (tau + acc) for every mixture with a finite acc > 0, the others keep
+ * their mean; tau = 0 is pcl_mstep's ML mean.  Variances and weights are untouched.  The same derive pass follows.
+ *
+ * The statistics block is treated as pcl_mstep treats it: read, neither cleared nor marked -- it describes the model BEFORE the call until
+ * the caller's next pcl_stats_zero.  With more than one rank the caller runs pcl_stats_allreduce first: all three calls read the block as
+ * it is on this rank, and the ranks then make the same model.
+ * No model (and so no statistics): PCL_ERR_STATE.  R < 1, a class outside [-1, R), a negative or non-finite min_occ / tau, D > 48, W = NULL
+ * without a resident estimate of R classes for this model: PCL_ERR_INVALID.  All checked before anything is changed.  Synchronous.
+ * pcl_kernel_time group "adapt": the kernels of each call ("adapt_gk": the GEMM and its reduction, "adapt_solve": the factorisations;
+ * "derive": the pass behind the two calls that change the model). */
+#define PCL_MLLR_OK 0
+#define PCL_MLLR_LOW_OCCUPANCY 1
+#define PCL_MLLR_FEW_MIXTURES 2
+#define PCL_MLLR_NOT_POSITIVE_DEFINITE 3
+int pcl_mllr_estimate(pcl_ctx *ctx, int R, const int32_t *state_class /* J, or NULL = all 0 */, double min_occ,
+                      double *W_out /* R*D*(D+1) or NULL */, double *occ_out /* R or NULL */, int32_t *status_out /* R or NULL */);
+int pcl_model_transform_means(pcl_ctx *ctx, int R, const int32_t *state_class /* J, or NULL = all 0 */,
+                              const double *W /* host R*D*(D+1), or NULL = the resident last estimate */);
+int pcl_mstep_map(pcl_ctx *ctx, double tau);
 
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /

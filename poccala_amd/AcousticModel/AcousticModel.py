@@ -517,6 +517,48 @@ class AcousticModel(DataInitialization):
         self._adopt_model(engine.model_download(), units, unit_hmms)
         return origin
 
+    def adapt_batch(self, labels, data_list, unit_hmms, method='mllr', unit_class=None, iterations=1, min_occ=1000.0, tau=10.0,
+                    precision=PCL_F32, engine=None):
+        """Adapt the units' means to the labelled utterances on the device: per iteration an E-step with the accumulate pass (as
+        estep_batch runs it), then method='mllr': Engine.mllr_estimate + transform_means -- unit_class {unit: class} gives every unit a
+        regression class (its emitting states inherit it; -1 or a unit left out = not transformed; None = one class of everything) --
+        or method='map': Engine.mstep_map(tau).  Variances, weights and transitions stay.  data_list: (T_u, D) arrays, or the
+        (lens, begin) of resident frames.  The GMM objects' means follow the device, as in mixup_batch.  Returns a dict:
+        logp = per iteration the total ln P(O) of the model the iteration STARTED from, and for MLLR W / occ / status per iteration.
+        Transforms of successive iterations are not composed: each is estimated for, and applied to, the current means."""
+        if method not in ('mllr', 'map'):
+            raise ValueError("adapt_batch: method must be 'mllr' or 'map', got %r" % (method,))
+        engine = engine or default_engine()
+        keep = self._nonempty(data_list)
+        if len(keep) < self._utt_count(data_list):          # empty utterances add nothing to the statistics
+            labels, data_list = [labels[u] for u in keep], self._utt_subset(data_list, keep)
+        units = sorted(unit_hmms)
+        e = self.__state_num - 2
+        state_class, n_classes = None, 1
+        if method == 'mllr' and unit_class is not None:
+            per_unit = np.array([int(unit_class.get(u, -1)) for u in units], dtype=np.int32)
+            state_class = np.repeat(per_unit, e)
+            n_classes = max(int(per_unit.max()) + 1, 1)
+        out = dict(logp=[], W=[], occ=[], status=[])
+        for _ in range(int(iterations)):
+            b, n, units, idx = self._sentence_batch(labels, data_list, unit_hmms, engine)
+            b.score(precision)
+            b.forward_backward()
+            engine.stats_zero()
+            b.accumulate(precision)
+            out['logp'].append(float(np.sum(b.get('logp'))))
+            b.close()
+            if method == 'mllr':
+                W, occ, status = engine.mllr_estimate(state_class, n_classes, min_occ)
+                engine.transform_means(None, state_class, n_classes)
+                out['W'].append(W), out['occ'].append(occ), out['status'].append(status)
+            else:
+                engine.mstep_map(tau)
+            self._adopt_model(engine.model_download(), units, unit_hmms)
+        if method == 'map':
+            del out['W'], out['occ'], out['status']
+        return out
+
     def _adopt_model(self, model, units, unit_hmms):
         """(mean, var, weight) of a model laid out unit-major over `units` into the units' GMM objects; this object's mix_level follows."""
         mean, var, w = model

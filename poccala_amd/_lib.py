@@ -17,6 +17,7 @@ PCL_ROW_ENTRY, PCL_ROW_EXIT = -1, -2
 PCL_MAX_PASS = 16
 PCL_VAD_DIST_IN, PCL_VAD_OSF_IN = 1, 2
 PCL_FRONTEND_NO_VAD, PCL_FRONTEND_KEEP_F64 = 1, 2
+PCL_MLLR_OK, PCL_MLLR_LOW_OCCUPANCY, PCL_MLLR_FEW_MIXTURES, PCL_MLLR_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3
 SEG_GET = dict(counts=0, order=1, assign=2, seeds=3)
 GET = dict(B=0, alpha=1, beta=2, lgamma=3, ksai=4, gamma=5, pi=6, logp=7, npass=8, qtrace=9, path=10, point=11, ksai_nz=12)
 
@@ -67,6 +68,9 @@ PROTOTYPES = {
     'pcl_flat_start': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'pcl_uniform_segments': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, C.POINTER(_vp)]),
     'pcl_model_mixup': (_i, [_vp, _i, _d, _vp]),
+    'pcl_mllr_estimate': (_i, [_vp, _i, _vp, _d, _vp, _vp, _vp]),
+    'pcl_model_transform_means': (_i, [_vp, _i, _vp, _vp]),
+    'pcl_mstep_map': (_i, [_vp, _d]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

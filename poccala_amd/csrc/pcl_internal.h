@@ -121,6 +121,7 @@ struct ModelDev {
     DevBuf<double> mean64;       // float64 master copy of the model: mean, var (J*Mpad*D), weight (J*Mpad)
     DevBuf<double> var64, w64;
     DevBuf<double> stats;        // E-step statistics (float64, linear domain), one allocation: [acc J*Mpad | alpha J | mean J*Mpad*D | cov J*Mpad*D]
+    DevBuf<double> mllr_W;       // the last pcl_mllr_estimate's transforms [mllr_R][Dhost][Dhost + 1] (model_adapt.hip): gone with the model they were estimated for
 };
 // Coarse layout of the off-pipe mixtures (gmm_score_coarse.hip): their bound v_up on the matrix pipe, exact evaluation of what it
 // cannot rule out.  Derived on first use after the model changed (coarse_gen != model_gen).
@@ -155,6 +156,7 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     // model (device)
     int J = 0, M = 0, Mpad = 0, D = 0, Dhost = 0, row = 0;  // D = device (padded) feature dimension
     int model_flags = 0;
+    int mllr_R = 0;              // classes of mllr_W
     int Mpad32 = 0;              // M rounded up to a multiple of 32
     int layouts_valid = 0;             // PCL_LAYOUT_* derived for the current model (the f64 rows are derived on first use)
     hipStream_t stream_dp = nullptr;   // forward-backward runs here, beside the next batch's scoring on `stream`

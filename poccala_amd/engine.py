@@ -456,6 +456,47 @@ class Engine(object):
         self._check(self._lib.pcl_mstep(self._ctx, float(c_covariance)))
         self._model_key = None                       # the resident model is no longer what was uploaded
 
+    # ------------------------------------------------------------------ speaker adaptation from the resident statistics
+    def _state_class(self, state_class):
+        if state_class is None:
+            return None
+        sc = as_c(state_class, np.int32).reshape(-1)
+        if sc.shape != (self.J,):
+            raise ValueError('state_class must hold one class per state (J = %d), got %s' % (self.J, sc.shape))
+        return sc
+
+    def mllr_estimate(self, state_class=None, n_classes=1, min_occ=1000.0):
+        """MLLR mean transforms (pcl_mllr_estimate) from the statistics the last accumulate pass left: state_class (J,) int32 gives every
+        state its regression class in [0, n_classes), -1 = leave the state alone, None = one class of all states.  Returns
+        (W (R, D, D+1) -- column 0 the offset --, occ (R,), status (R,) int32: 0, or the reason a class was refused and got the
+        identity: 1 occupancy below min_occ, 2 fewer than D+1 contributing mixtures, 3 a pivot not > 0).  The model is not changed;
+        the transforms stay on the device for transform_means()."""
+        R = int(n_classes)
+        sc = self._state_class(state_class)
+        n = max(R, 1)
+        W, occ, status = np.empty((n, self.D, self.D + 1)), np.empty(n), np.empty(n, dtype=np.int32)
+        self._check(self._lib.pcl_mllr_estimate(self._ctx, R, ptr(sc), float(min_occ), ptr(W), ptr(occ), ptr(status)))
+        return W, occ, status
+
+    def transform_means(self, W=None, state_class=None, n_classes=1):
+        """mean <- A_r mean + b_r on the device (pcl_model_transform_means) for every state of class r >= 0, W[r] = [b_r | A_r]; W=None:
+        the transforms of the last mllr_estimate, which never left the device.  Variances and weights stay; the scoring layouts are
+        rebuilt as mstep() rebuilds them."""
+        R = int(n_classes)
+        sc = self._state_class(state_class)
+        if W is not None:
+            W = as_c(W, np.float64)
+            if W.shape != (R, self.D, self.D + 1):
+                raise ValueError('W must be (n_classes, D, D+1) = %s, got %s' % ((R, self.D, self.D + 1), W.shape))
+        self._check(self._lib.pcl_model_transform_means(self._ctx, R, ptr(sc), ptr(W)))
+        self._model_key = None
+
+    def mstep_map(self, tau):
+        """MAP re-estimation of the means (pcl_mstep_map): mean <- (tau mean + s) / (tau + acc) from the resident statistics for every
+        mixture the data reached; tau = 0 is mstep()'s mean.  Variances and weights stay."""
+        self._check(self._lib.pcl_mstep_map(self._ctx, float(tau)))
+        self._model_key = None
+
     def model_download(self):
         """(mean (J,M,D), var (J,M,D), weight (J,M)) float64 master copy."""
         mean = np.empty((self.J, self.M, self.D))
