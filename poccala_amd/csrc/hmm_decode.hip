@@ -39,7 +39,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "hmm_decode_args.h"
+#include "hmm_decode_common.h"
 
 namespace {
 
@@ -51,8 +51,7 @@ constexpr int NWV = DW / 64;        // wavefronts per workgroup
 constexpr int NS = 8;               // lanes per token = states of its HMM at most
 constexpr int TG = DW / NS;         // tokens stepped per pass of the workgroup
 constexpr int SEG_LDS = 4096;       // donor segments whose offsets are searched in LDS (more: searched in HBM)
-constexpr int NONE = 0x7fffffff;
-[[maybe_unused]] constexpr int N_STAMP = PCL_DEC_N_STAMP;
+constexpr int HB = 8;               // radix digit of the pruning select: 256 bins, the same words as the occupancy map; no direct ranking
 
 // What a lane (state j = sub of its token) needs of ln A of the embedded HMM (AcousticModel.py:979-989), fixed per thread:
 // predecessor i reaches j through entry rc[i] of its unit's (S,S) matrix, or not at all.
@@ -165,13 +164,13 @@ template <bool TLDS, int KMAX>
 __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a) {
     extern __shared__ double dyn[];
     __shared__ int seg_l[SEG_LDS + 1];
-    __shared__ unsigned int hist256[256];
+    __shared__ unsigned int hist256[256];                          // pruning: the occupancy map, then the radix histogram
     __shared__ int wsum[2][NWV];
     __shared__ double red_d[NWV];
     __shared__ unsigned long long red_u[2][NWV];
     __shared__ int red_i[2][NWV];
-    __shared__ unsigned long long s_sel;
-    __shared__ int s_i[4];
+    __shared__ unsigned long long s_sel;                           // pruning select: the chosen bin (pcl_select_kth's s_key)
+    __shared__ int s_i[4];                                         // [0..2] the donor phase's winner; [3] the select's rank
     __shared__ double s_d[1];
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -216,19 +215,10 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         const int u1 = (a.node_nunits[node] == 2) ? a.node_units[2 * node + 1] : 0xffff;
         return u0 | (u1 << 16);
     };
-#ifdef PCL_DEC_STAMPS
-    long long st_acc[N_STAMP] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = wall_clock64();
-#define STAMP(k)                                  \
-    if (u == 0 && tid == 0) {                     \
-        const long long now_ = wall_clock64();    \
-        st_acc[k] += now_ - st_t;                 \
-        st_t = now_;                              \
-    }
-#else
-#define STAMP(k)
-#endif
+    STAMP_BEGIN
 
     // ---- frame 0: every first-character node starts (D3)
+    if (tid < 256) hist256[tid] = 0u;                              // (the pruning steps take it zero and leave it zero)
     int cur = 0, n = min(a.n_roots, cap), ovf = a.n_roots > cap, nh = 0;
     for (int i = tid; i < n; i += DW) {
         const int node = a.roots[i];
@@ -284,16 +274,9 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         }
         nd_cnt = pcl_wave_sum(nd_cnt);
         ch_cnt = pcl_wave_sum(ch_cnt);
+        pcl_wave_best(bw, bw_i);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(bw, o, 64);
-            const int oi = __shfl_xor(bw_i, o, 64);
-            if (oi != NONE && (bw_i == NONE || ob > bw || (ob == bw && oi < bw_i))) {
-                bw = ob;
-                bw_i = oi;
-            }
-            fw = min(fw, __shfl_xor(fw, o, 64));
-        }
+        for (int o = 32; o > 0; o >>= 1) fw = min(fw, __shfl_xor(fw, o, 64));
         if (lane == 0) {
             wsum[0][wave] = nd_cnt;
             wsum[1][wave] = ch_cnt;
@@ -303,15 +286,10 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         }
         __syncthreads();
         if (tid == 0) {
-            double b = -INFINITY;
-            int bi = NONE, f = NONE;
-            for (int w = 0; w < NWV; ++w) {
-                if (red_i[0][w] != NONE && (bi == NONE || red_d[w] > b || (red_d[w] == b && red_i[0][w] < bi))) {
-                    b = red_d[w];
-                    bi = red_i[0][w];
-                }
-                f = min(f, red_i[1][w]);
-            }
+            double b;
+            int bi, f = NONE;
+            pcl_best_of_waves<NWV>(red_d, red_i[0], b, bi);
+            for (int w = 0; w < NWV; ++w) f = min(f, red_i[1][w]);
             s_d[0] = b;
             s_i[0] = bi;
             s_i[1] = f;
@@ -324,16 +302,8 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                 s_i[2] = nh;
             }
         }
-        int dbase = 0, cbase = 0, nd_tot = 0, ch_tot = 0;
-        for (int w = 0; w < NWV; ++w) {
-            const int x = wsum[0][w], y = wsum[1][w];
-            if (w < wave) {
-                dbase += x;
-                cbase += y;
-            }
-            nd_tot += x;
-            ch_tot += y;
-        }
+        int nd_tot, ch_tot;
+        const int dbase = pcl_waves_before<NWV>(wsum[0], wave, &nd_tot), cbase = pcl_waves_before<NWV>(wsum[1], wave, &ch_tot);
         __syncthreads();
         const double w_score = s_d[0];
         const int w_i = s_i[0], first_w = s_i[1], w_hist = s_i[2];
@@ -357,12 +327,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                 }
                 const unsigned long long mask = __ballot(fin);
                 const int r = drun + __popcll(mask & lt_mask);
-                int inc = cnt;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int x = __shfl_up(inc, o, 64);
-                    if (lane >= o) inc += x;
-                }
+                const int inc = pcl_wave_scan(cnt, lane);
                 if (fin) {
                     const int after = (has_w && i > first_w) ? 1 : 0, seg = r + after;
                     const int ofs = crun + inc - cnt + (after ? a.n_roots : 0);
@@ -419,12 +384,8 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
             const unsigned long long mask = __ballot(isnew);
             if (lane == 0) wsum[0][wave] = __popcll(mask);
             __syncthreads();
-            int base = 0, tot = 0;
-            for (int w = 0; w < NWV; ++w) {
-                const int x = wsum[0][w];
-                if (w < wave) base += x;
-                tot += x;
-            }
+            int tot;
+            const int base = pcl_waves_before<NWV>(wsum[0], wave, &tot);
             if (isnew) {
                 const int pos = n + created + base + __popcll(mask & lt_mask);
                 if (pos < cap) {                                   // (slots n .. cap-1 of the current buffer)
@@ -443,160 +404,28 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         // the new tokens take their first step at once (Decoder.py:138-139)
         step_range<true>(c, lt, Bs, n, n + n_new, up, nullptr, nullptr, p, sc, flag, tk8, sub);
         STAMP(3)
-        // ---- (4) pruning over the tokens that were alive before the frame and did not finish (Decoder.py:159-167):
-        //      nothing below min_distinct different scores, else the int(width (1 - beam)) lowest go (stable ascending
-        //      order: ties by token order).  One pass gives the width, the key range and a hashed occupancy map (different
-        //      bins => different scores); the m-th smallest key by radix select below the range's common prefix.
-        if (tid < 256) hist256[tid] = 0u;
-        __syncthreads();
-        constexpr unsigned long long NOKEY = ~0ull;                             // not an old unfinished token
+        // ---- (4) pruning over the tokens that were alive before the frame and did not finish (Decoder.py:159-167): the four steps
+        //      of hmm_decode_common.h; the radix histogram is the occupancy map's 256 words
         unsigned long long keys[KMAX];
-        int cnt = 0;
-        unsigned long long kmn = ~0ull, kmx = 0ull;
 #pragma unroll
         for (int kk = 0; kk < KMAX; ++kk) {
             const int i = w0 + kk * 64 + lane;
-            keys[kk] = NOKEY;
-            if (kk * 64 < C && i < n && !(flag[i] & 1)) {
-                const unsigned long long key = pcl_okey(sc[i]);
-                keys[kk] = key;
-                ++cnt;
-                kmn = min(kmn, key);
-                kmx = max(kmx, key);
-                atomicOr(&hist256[(unsigned int)((key * 0x9E3779B97F4A7C15ull) >> 56)], 1u);
-            }
+            keys[kk] = (kk * 64 < C && i < n && !(flag[i] & 1)) ? pcl_okey(sc[i]) : NOKEY;
         }
-        cnt = pcl_wave_sum(cnt);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            kmn = min(kmn, (unsigned long long)__shfl_xor((long long)kmn, o, 64));
-            kmx = max(kmx, (unsigned long long)__shfl_xor((long long)kmx, o, 64));
-        }
-        if (lane == 0) {
-            wsum[0][wave] = cnt;
-            red_u[0][wave] = kmn;
-            red_u[1][wave] = kmx;
-        }
-        __syncthreads();
-        const int bins = __syncthreads_count(tid < 256 && hist256[tid] != 0u);
-        int n_old = 0;
-        unsigned long long kmin = ~0ull, kmax = 0ull;
-        for (int w = 0; w < NWV; ++w) {
-            n_old += wsum[0][w];
-            kmin = min(kmin, red_u[0][w]);
-            kmax = max(kmax, red_u[1][w]);
-        }
+        int n_old, bins;
+        unsigned long long kmin, kmax;
+        pcl_prune_stats<DW, KMAX>(keys, hist256, wsum[0], red_u[0], red_u[1], n_old, kmin, kmax, bins);
         const int m = (int)((double)n_old * (1.0 - a.beam));                   // int(width * (1 - beam))
         bool prune = m > 0 && n_old >= a.min_distinct;
-        if (prune && bins < a.min_distinct) {                                   // few bins: count the distinct scores exactly
-            unsigned long long prev = 0ull;
-            bool have_prev = false;
-            int distinct = 0;
-            for (int round = 0; round < a.min_distinct; ++round) {              // the next larger key, min_distinct times
-                unsigned long long mn = ~0ull;
-                bool any = false;
-#pragma unroll
-                for (int kk = 0; kk < KMAX; ++kk) {
-                    const unsigned long long key = keys[kk];
-                    if (key != NOKEY && (!have_prev || key > prev) && (!any || key < mn)) {
-                        mn = key;
-                        any = true;
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const unsigned long long om = (unsigned long long)__shfl_xor((long long)mn, o, 64);
-                    const int oa = __shfl_xor((int)any, o, 64);
-                    if (oa && (!any || om < mn)) {
-                        mn = om;
-                        any = true;
-                    }
-                }
-                __syncthreads();
-                if (lane == 0) {
-                    red_u[0][wave] = mn;
-                    red_i[0][wave] = any;
-                }
-                __syncthreads();
-                unsigned long long g = ~0ull;
-                bool gany = false;
-                for (int w = 0; w < NWV; ++w)
-                    if (red_i[0][w] && (!gany || red_u[0][w] < g)) {
-                        g = red_u[0][w];
-                        gany = true;
-                    }
-                if (!gany) break;
-                prev = g;
-                have_prev = true;
-                ++distinct;
-            }
-            prune = distinct >= a.min_distinct;
-        }
+        if (prune && bins < a.min_distinct) prune = pcl_prune_distinct<DW, KMAX>(keys, a.min_distinct, red_u[0], red_i[0]);
         if (prune) {
-            unsigned long long sel = kmin;
-            int rank = m - 1;
-            const unsigned long long diff = kmin ^ kmax;
-            if (diff != 0ull) {
-                const int b0 = (63 - __clzll((long long)diff)) >> 3;           // the first byte in which the keys differ
-                unsigned long long prefix = (b0 == 7) ? 0ull : (kmin & (~0ull << (8 * (b0 + 1))));
-                for (int byte = b0; byte >= 0; --byte) {
-                    if (tid < 256) hist256[tid] = 0u;
-                    __syncthreads();
-                    const unsigned long long hi_mask = (byte == 7) ? 0ull : (~0ull << (8 * (byte + 1)));
+            unsigned long long sel;
+            int rank;
+            pcl_select_kth<DW, KMAX, HB, 0>(keys, kmin, kmax, m, hist256, nullptr, red_i[1], &s_sel, &s_i[3], sel, rank);
+            const unsigned int gone = pcl_prune_mark<DW, KMAX>(keys, sel, rank, wsum[1]);
 #pragma unroll
-                    for (int kk = 0; kk < KMAX; ++kk) {
-                        const unsigned long long key = keys[kk];
-                        if (key != NOKEY && (key & hi_mask) == prefix) atomicAdd(&hist256[(unsigned int)(key >> (8 * byte)) & 255u], 1u);
-                    }
-                    __syncthreads();
-                    if (wave == 0) {                                            // 4 bins per lane: the bin holding rank
-                        int h[4], s4 = 0;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            h[j] = (int)hist256[4 * lane + j];
-                            s4 += h[j];
-                        }
-                        int inc = s4;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1) {
-                            const int x = __shfl_up(inc, o, 64);
-                            if (lane >= o) inc += x;
-                        }
-                        const unsigned long long hit = __ballot(inc > rank);
-                        if (hit != 0ull && lane == __ffsll((long long)hit) - 1) {
-                            int acc = inc - s4, j = 0;
-                            for (; j < 3; ++j) {
-                                if (acc + h[j] > rank) break;
-                                acc += h[j];
-                            }
-                            s_sel = (unsigned long long)(4 * lane + j);
-                            s_i[3] = rank - acc;
-                        }
-                    }
-                    __syncthreads();
-                    prefix |= s_sel << (8 * byte);
-                    rank = s_i[3];
-                }
-                sel = prefix;
-            }
-            // everything below the selected key goes, and of the tokens equal to it the first (rank + 1) in token order
-            int eq = 0;
-#pragma unroll
-            for (int kk = 0; kk < KMAX; ++kk) eq += keys[kk] == sel;
-            eq = pcl_wave_sum(eq);
-            __syncthreads();
-            if (lane == 0) wsum[0][wave] = eq;
-            __syncthreads();
-            int run = 0;
-            for (int w = 0; w < wave; ++w) run += wsum[0][w];
-#pragma unroll
-            for (int kk = 0; kk < KMAX; ++kk) {
-                const unsigned long long key = keys[kk];
-                const bool is_eq = key == sel;                                 // (sel is a real key, never NOKEY)
-                const unsigned long long mask = __ballot(is_eq);
-                if (key != NOKEY && (key < sel || (is_eq && run + __popcll(mask & lt_mask) <= rank))) flag[w0 + kk * 64 + lane] |= 2;
-                run += __popcll(mask);
-            }
+            for (int kk = 0; kk < KMAX; ++kk)
+                if ((gone >> kk) & 1u) flag[w0 + kk * 64 + lane] |= 2;
         }
         __syncthreads();
         STAMP(4)
@@ -618,12 +447,8 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         keep_cnt = pcl_wave_sum(keep_cnt);
         if (lane == 0) wsum[1][wave] = keep_cnt;
         __syncthreads();
-        int krun = 0, n_keep = 0;
-        for (int w = 0; w < NWV; ++w) {
-            const int x = wsum[1][w];
-            if (w < wave) krun += x;
-            n_keep += x;
-        }
+        int n_keep;
+        int krun = pcl_waves_before<NWV>(wsum[1], wave, &n_keep);
         for (int k = 0; k < C; k += 64) {
             const int i = w0 + k + lane;
             const bool keep = i < n && !(flag[i] & 3);
@@ -658,59 +483,192 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         pcur ^= 1;
         if (tid == 0) a.trace[(size_t)u * a.Tmax + t] = n;
     }
-    // ---- transfer (Decoder.py:175-187): the `candidate` best tokens, ties in token order
-    const double *sc = scb[cur];
-    for (int i = tid; i < n; i += DW) flag[i] = 0;                 // 4 = taken
-    __syncthreads();
-    int n_out = 0;
-    for (int cc = 0; cc < a.candidate && cc < n; ++cc) {
-        double b = -INFINITY;
-        int bi = NONE;
-        for (int i = tid; i < n; i += DW)
-            if (flag[i] != 4 && (bi == NONE || sc[i] > b)) {        // (strictly greater keeps the earliest on ties)
-                b = sc[i];
-                bi = i;
-            }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(b, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (oi != NONE && (bi == NONE || ob > b || (ob == b && oi < bi))) {
-                b = ob;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red_d[wave] = b;
-            red_i[0][wave] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double g = -INFINITY;
-            int gi = NONE;
-            for (int w = 0; w < NWV; ++w)
-                if (red_i[0][w] != NONE && (gi == NONE || red_d[w] > g || (red_d[w] == g && red_i[0][w] < gi))) {
-                    g = red_d[w];
-                    gi = red_i[0][w];
-                }
-            a.out_node[(size_t)u * a.candidate + cc] = ndb[cur][gi];
-            a.out_score[(size_t)u * a.candidate + cc] = sc[gi];
-            a.out_hist[(size_t)u * a.candidate + cc] = hsb[cur][gi];
-            flag[gi] = 4;
-        }
-        ++n_out;
-        __syncthreads();
-    }
+    // ---- transfer (Decoder.py:175-187): the tokens sit where their index says; the flags are free now
+    const size_t o_out = (size_t)u * a.candidate;
+    const int n_out = pcl_transfer<DW>(n, a.candidate, scb[cur], ndb[cur], hsb[cur], [](int i) { return i; }, flag, red_d, red_i[0],
+                                       a.out_node + o_out, a.out_score + o_out, a.out_hist + o_out);
     if (tid == 0) {
         a.out_n[u] = n_out;
         a.hist_n[u] = min(nh, a.Tmax);
         a.overflow[u] = ovf;
-#ifdef PCL_DEC_STAMPS
-        if (u == 0 && a.stamps)
-            for (int k = 0; k < N_STAMP; ++k) a.stamps[k] = st_acc[k];
-#endif
     }
+    STAMP_END(a.stamps)
 }
+
+// ---- host side of pcl_batch_decode
+
+// The decoder's workspace, described ONCE: the element counts of the batch's allocations and the offset of every array in them.
+// The same DecLayout sizes the allocations, fills DecArgs and tells pcl_batch_decode_get where the results are; the per-utterance
+// extents below ([2][cap], [cap + 2], ...) are the kernels' own indexing (DecArgs, hmm_decode_common.h).  The counts do not depend
+// on the kernel: of the 8 cap ints per utterance behind upair the general kernel makes flag [cap] | dst [cap], the left-to-right
+// kernel src [2][cap] (DecArgs::dst) and no flags -- so a batch may change kernels between two calls.
+struct DecLayout {
+    static constexpr size_t ABSENT = ~(size_t)0;
+    size_t n_f64, n_work, n_int;                                               // doubles in dec_f64, ints in dec_work, ints in dec_int
+    size_t score, p, seg_score;                                                // dec_f64
+    size_t node, hist, upair, flag, dst, seg_ofs, seg_cptr, seg_hist;          // dec_work
+    size_t out_n, out_node, out_hist, hist_n, hist_prev, hist_node, trace, overflow;   // dec_int, in the order they are downloaded
+};
+
+DecLayout dec_layout(int U, int cap, int candidate, int Tmax, bool use_lr) {
+    const size_t u = (size_t)U, tok = u * cap, seg = u * ((size_t)cap + 2), out = u * candidate, frm = u * Tmax;
+    DecLayout l;
+    size_t end = 0;
+    auto take = [&end](size_t n) {
+        const size_t at = end;
+        end += n;
+        return at;
+    };
+    l.score = take(2 * tok);
+    l.p = take(2 * tok * NS);                                                  // (the left-to-right kernel: 6 of the 8 cap per buffer)
+    l.seg_score = take(seg);
+    l.n_f64 = end;
+    end = 0;
+    l.node = take(2 * tok);
+    l.hist = take(2 * tok);
+    l.upair = take(2 * tok);
+    l.flag = use_lr ? DecLayout::ABSENT : take(tok);
+    l.dst = take(use_lr ? 2 * tok : tok);
+    l.seg_ofs = take(seg);
+    l.seg_cptr = take(seg);
+    l.seg_hist = take(seg);
+    l.n_work = end;
+    end = 0;
+    l.out_n = take(u);
+    l.out_node = take(out);
+    l.out_hist = take(out);
+    l.hist_n = take(u);
+    l.hist_prev = take(frm);
+    l.hist_node = take(frm);
+    l.trace = take(frm);
+    l.overflow = take(u);
+    l.n_int = end;
+    return l;
+}
+
+int dec_validate(const pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens) {
+    pcl_ctx *ctx = b->ctx;
+    if (!ctx->lex_nodes) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: pcl_lexicon_upload first");
+    if (!b->have_B) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: no emissions (pcl_batch_score first)");
+    if (!(beam > 0.0 && beam <= 1.0) || min_distinct < 1 || candidate < 1 || max_tokens < 1)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: beam %g, min_distinct %d, candidate %d, max_tokens %d", beam, min_distinct, candidate, max_tokens);
+    // the general kernel's limit: it takes every unit inventory, so what it cannot hold nothing can (the left-to-right kernel's smaller
+    // workgroup holds half as many: pcl_decode_lr_applicable)
+    if (max_tokens > PCL_DEC_MAX_KEYS_PER_LANE * DW)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: max_tokens %d > %d (a lane keeps the sort keys of its tokens in registers)", max_tokens, PCL_DEC_MAX_KEYS_PER_LANE * DW);
+    // the emission rows must be [entry, state 0 .. J-1, exit]: the all-state matrix
+    const int J = ctx->n_units * (ctx->S - 2);
+    for (int u = 0; u < b->U; ++u) {
+        const UttDesc &d = b->utt[u];
+        bool ok = d.N == J + 2 && (int)b->row_state.size() >= d.vec_off + d.N;
+        for (int n = 0; ok && n < d.N; ++n) ok = b->row_state[d.vec_off + n] == (n == 0 ? PCL_ROW_ENTRY : n == d.N - 1 ? PCL_ROW_EXIT : n - 1);
+        if (!ok) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: utterance %d is not an all-state batch (rows entry, 0..%d, exit)", u, J - 1);
+    }
+    return PCL_OK;
+}
+
+// the batch's buffers, sized for (cap, candidate, tree); the node -> token map and the results start clean for every call
+int dec_ensure_workspace(pcl_batch *b, const DecLayout &l, int cap, int candidate) {
+    pcl_ctx *ctx = b->ctx;
+    const size_t n_slot = (size_t)b->U * ctx->lex_nodes;
+    if (b->dec_cap != cap || b->dec_cand != candidate || b->dec_nodes != ctx->lex_nodes) {
+        static_cast<BatchDecodeDev &>(*b) = {};
+        TRY(b->dec_f64.alloc(ctx, l.n_f64));
+        TRY(b->dec_work.alloc(ctx, l.n_work));
+        TRY(b->dec_slot.alloc(ctx, n_slot));
+        TRY(b->dec_int.alloc(ctx, l.n_int));
+        TRY(b->dec_score.alloc(ctx, (size_t)b->U * candidate));
+        b->dec_cap = cap;
+        b->dec_cand = candidate;
+        b->dec_nodes = ctx->lex_nodes;
+    }
+    HIPCHK(ctx, hipMemsetAsync(b->dec_slot, 0xff, n_slot * sizeof(int), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(b->dec_int, 0, l.n_int * sizeof(int), ctx->stream));
+    return PCL_OK;
+}
+
+DecArgs dec_fill_args(const pcl_batch *b, const DecLayout &l, double beam, int min_distinct, int candidate, int cap, double lpi1, double lpi2) {
+    const pcl_ctx *ctx = b->ctx;
+    DecArgs a;
+    a.utts = b->d_utt;
+    a.Bt = b->Bt;
+    a.unit_logtrans = ctx->d_unit_logtrans;
+    a.node_units = ctx->lex_units;
+    a.node_nunits = ctx->lex_nunits;
+    a.child_ptr = ctx->lex_child_ptr;
+    a.child_idx = ctx->lex_child_idx;
+    a.node_word = ctx->lex_word;
+    a.roots = ctx->lex_roots;
+    a.node_info = ctx->lex_info;
+    a.n_nodes = ctx->lex_nodes;
+    a.n_roots = ctx->lex_nroots;
+    a.n_units = ctx->n_units;
+    a.S = ctx->S;
+    a.cap = cap;
+    a.candidate = candidate;
+    a.min_distinct = min_distinct;
+    a.Tmax = b->Tmax;
+    a.beam = beam;
+    a.lpi1 = lpi1;
+    a.lpi2 = lpi2;
+    double *f = b->dec_f64;
+    a.score = f + l.score;
+    a.p = f + l.p;
+    a.seg_score = f + l.seg_score;
+    int *w = b->dec_work;
+    a.node = w + l.node;
+    a.hist = w + l.hist;
+    a.upair = w + l.upair;
+    a.flag = l.flag == DecLayout::ABSENT ? nullptr : w + l.flag;
+    a.dst = w + l.dst;
+    a.seg_ofs = w + l.seg_ofs;
+    a.seg_cptr = w + l.seg_cptr;
+    a.seg_hist = w + l.seg_hist;
+    a.slot = b->dec_slot;
+    int *r = b->dec_int;
+    a.out_n = r + l.out_n;
+    a.out_node = r + l.out_node;
+    a.out_hist = r + l.out_hist;
+    a.hist_n = r + l.hist_n;
+    a.hist_prev = r + l.hist_prev;
+    a.hist_node = r + l.hist_node;
+    a.trace = r + l.trace;
+    a.overflow = r + l.overflow;
+    a.out_score = b->dec_score;
+    a.stamps = nullptr;
+    return a;
+}
+
+int dec_launch_general(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows) {
+    // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
+    const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)n_rows) * sizeof(double);
+    const bool tlds = table_bytes <= 44u * 1024u;
+    const int cap = a.cap;
+#define PCL_DEC_LAUNCH(K)                                                                                                  \
+    do {                                                                                                                   \
+        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K>), dim3(U), dim3(DW), table_bytes, ctx->stream, a);       \
+        else hipLaunchKernelGGL((hmm_decode_kernel<false, K>), dim3(U), dim3(DW), 0, ctx->stream, a);                      \
+    } while (0)
+    if (cap <= DW) PCL_DEC_LAUNCH(1);
+    else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
+    else if (cap <= 4 * DW) PCL_DEC_LAUNCH(4);
+    else if (cap <= 8 * DW) PCL_DEC_LAUNCH(8);
+    else PCL_DEC_LAUNCH(16);
+#undef PCL_DEC_LAUNCH
+    static_assert(PCL_DEC_MAX_KEYS_PER_LANE == 16, "the largest KMAX instantiated above");
+    return PCL_OK;
+}
+
+#ifdef PCL_DEC_STAMPS
+int dec_print_stamps(pcl_ctx *ctx, DevBuf<long long> &d_stamps) {
+    long long h[PCL_DEC_N_STAMP];
+    HIPCHK(ctx, hipMemcpyAsync(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    fprintf(stderr, "decode stamps (utterance 0, 100 MHz ticks): step %lld donors %lld pairs %lld first|keys %lld prune %lld compact %lld select %lld\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
+    d_stamps.release();
+    return PCL_OK;
+}
+#endif
 
 }  // namespace
 
@@ -783,19 +741,7 @@ int pcl_lexicon_upload(pcl_ctx *ctx, int n_nodes, const int32_t *node_units, con
 int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
-    if (!ctx->lex_nodes) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: pcl_lexicon_upload first");
-    if (!b->have_B) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: no emissions (pcl_batch_score first)");
-    if (!(beam > 0.0 && beam <= 1.0) || min_distinct < 1 || candidate < 1 || max_tokens < 1)
-        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: beam %g, min_distinct %d, candidate %d, max_tokens %d", beam, min_distinct, candidate, max_tokens);
-    if (max_tokens > 16 * DW) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: max_tokens %d > %d (a lane keeps the sort keys of its tokens in registers)", max_tokens, 16 * DW);
-    // the emission rows must be [entry, state 0 .. J-1, exit]: the all-state matrix
-    const int J = ctx->n_units * (ctx->S - 2);
-    for (int u = 0; u < b->U; ++u) {
-        const UttDesc &d = b->utt[u];
-        bool ok = d.N == J + 2 && (int)b->row_state.size() >= d.vec_off + d.N;
-        for (int n = 0; ok && n < d.N; ++n) ok = b->row_state[d.vec_off + n] == (n == 0 ? PCL_ROW_ENTRY : n == d.N - 1 ? PCL_ROW_EXIT : n - 1);
-        if (!ok) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: utterance %d is not an all-state batch (rows entry, 0..%d, exit)", u, J - 1);
-    }
+    TRY(dec_validate(b, beam, min_distinct, candidate, max_tokens));
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (b->dp_pending) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_dp, 0));
@@ -804,110 +750,29 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
     // Like the forward-backward recursion, the decoder does no matrix work and is latency / bandwidth bound: it runs on
     // the second stream, beside the scoring of the next chunk on the main one (every later call on this batch joins it).
     auto launch = [&]() -> int {                                               // (on ctx->stream: the second stream when dp_async)
-    const int cap = max_tokens, U = b->U, Tm = b->Tmax;
-    // left-to-right units (every model the reference builds): one lane per token, hmm_decode_lr.hip; PCL_DEC_GENERAL=1 keeps
-    // the general kernel (the parity tests run both against the restatement)
-    const char *force_general = getenv("PCL_DEC_GENERAL");
-    const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, J + 2, cap, Tm);
-    if (b->dec_cap != cap || b->dec_cand != candidate || b->dec_nodes != ctx->lex_nodes) {
-        static_cast<BatchDecodeDev &>(*b) = {};
-        // doubles per utterance: score 2 cap | p 2 cap NS | seg_score cap + 2;  ints: node, hist, upair 2 cap each | flag, dst cap each |
-        // seg_ofs, seg_cptr, seg_hist cap + 2 each (general kernel); the left-to-right kernel lays meta 8 cap | src 2 cap over the same words
-        TRY(b->dec_f64.alloc(ctx, (size_t)U * (2 * (size_t)cap * (1 + NS) + cap + 2)));
-        TRY(b->dec_work.alloc(ctx, (size_t)U * (10 * (size_t)cap + 3 * ((size_t)cap + 2))));
-        TRY(b->dec_slot.alloc(ctx, (size_t)U * ctx->lex_nodes));
-        // ints: out_n U | out_node U*cand | out_hist U*cand | hist_n U | hist_prev U*Tm | hist_node U*Tm | trace U*Tm | overflow U
-        TRY(b->dec_int.alloc(ctx, (size_t)U * (3 + 2 * candidate + 3 * Tm)));
-        TRY(b->dec_score.alloc(ctx, (size_t)U * candidate));
-        b->dec_cap = cap;
-        b->dec_cand = candidate;
-        b->dec_nodes = ctx->lex_nodes;
-    }
-    HIPCHK(ctx, hipMemsetAsync(b->dec_slot, 0xff, (size_t)U * ctx->lex_nodes * sizeof(int), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(b->dec_int, 0, (size_t)U * (3 + 2 * candidate + 3 * Tm) * sizeof(int), ctx->stream));
-    DecArgs a;
-    a.utts = b->d_utt;
-    a.Bt = b->Bt;
-    a.unit_logtrans = ctx->d_unit_logtrans;
-    a.node_units = ctx->lex_units; a.node_nunits = ctx->lex_nunits; a.child_ptr = ctx->lex_child_ptr; a.child_idx = ctx->lex_child_idx;
-    a.node_word = ctx->lex_word; a.roots = ctx->lex_roots; a.node_info = ctx->lex_info;
-    a.n_nodes = ctx->lex_nodes; a.n_roots = ctx->lex_nroots; a.n_units = ctx->n_units; a.S = ctx->S; a.cap = cap; a.candidate = candidate;
-    a.min_distinct = min_distinct; a.Tmax = Tm;
-    a.beam = beam; a.lpi1 = logpi_one_unit; a.lpi2 = logpi_two_units;
-    {
-        double *q = b->dec_f64;
-        a.score = q; q += (size_t)U * 2 * cap;
-        a.p = q; q += (size_t)U * 2 * cap * NS;
-        a.seg_score = q;
-        int *w = b->dec_work;
-        a.meta = (int4 *)w;                          // (left-to-right kernel: 8 cap ints per utterance)
-        a.node = w; w += (size_t)U * 2 * cap;
-        a.hist = w; w += (size_t)U * 2 * cap;
-        a.upair = w; w += (size_t)U * 2 * cap;
-        a.flag = w; w += (size_t)U * cap;
-        a.dst = w; w += (size_t)U * cap;
-        if (use_lr) {                                // node, hist, upair [U][2][cap] each (as above) | 2 U cap spare | src [U][2][cap] | the seg_* arrays
-            a.dst = b->dec_work + (size_t)U * 8 * cap;
-            a.flag = nullptr;
-            w = a.dst + (size_t)U * 2 * cap;
-        }
-        a.seg_ofs = w; w += (size_t)U * (cap + 2);
-        a.seg_cptr = w; w += (size_t)U * (cap + 2);
-        a.seg_hist = w;
-    }
-    a.slot = b->dec_slot;
-    int *p = b->dec_int;
-    a.out_n = p; p += U;
-    a.out_node = p; p += (size_t)U * candidate;
-    a.out_hist = p; p += (size_t)U * candidate;
-    a.hist_n = p; p += U;
-    a.hist_prev = p; p += (size_t)U * Tm;
-    a.hist_node = p; p += (size_t)U * Tm;
-    a.trace = p; p += (size_t)U * Tm;
-    a.overflow = p;
-    a.out_score = b->dec_score;
-    a.stamps = nullptr;
+        const int cap = max_tokens, U = b->U, n_rows = ctx->n_units * (ctx->S - 2) + 2;
+        // left-to-right units (every model the reference builds): one lane per token, hmm_decode_lr.hip; PCL_DEC_GENERAL=1 keeps
+        // the general kernel (the parity tests run both against the restatement)
+        const char *force_general = getenv("PCL_DEC_GENERAL");
+        const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, n_rows, cap, b->Tmax);
+        const DecLayout l = dec_layout(U, cap, candidate, b->Tmax, use_lr);
+        TRY(dec_ensure_workspace(b, l, cap, candidate));
+        DecArgs a = dec_fill_args(b, l, beam, min_distinct, candidate, cap, logpi_one_unit, logpi_two_units);
 #ifdef PCL_DEC_STAMPS
-    DevBuf<long long> d_stamps;
-    TRY(d_stamps.alloc(ctx, (size_t)N_STAMP));
-    HIPCHK(ctx, hipMemsetAsync(d_stamps, 0, N_STAMP * sizeof(long long), ctx->stream));
-    a.stamps = d_stamps;
+        DevBuf<long long> d_stamps;
+        TRY(d_stamps.alloc(ctx, (size_t)PCL_DEC_N_STAMP));
+        HIPCHK(ctx, hipMemsetAsync(d_stamps, 0, PCL_DEC_N_STAMP * sizeof(long long), ctx->stream));
+        a.stamps = d_stamps;
 #endif
-    if (use_lr) {
         pcl_timer_begin(ctx, "decode");
-        const int rc = pcl_decode_lr_launch(ctx, a, U, J + 2);
+        const int rc = use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows) : dec_launch_general(ctx, a, U, n_rows);
         pcl_timer_end(ctx, "decode");
-        if (rc != PCL_OK) return rc;
+        TRY(rc);
         HIPCHK(ctx, hipGetLastError());
-    } else {
-    // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
-    const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)(J + 2)) * sizeof(double);
-    const bool tlds = table_bytes <= 44u * 1024u;
-    pcl_timer_begin(ctx, "decode");
-#define PCL_DEC_LAUNCH(K)                                                                                                  \
-    do {                                                                                                                   \
-        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K>), dim3(U), dim3(DW), table_bytes, ctx->stream, a);       \
-        else hipLaunchKernelGGL((hmm_decode_kernel<false, K>), dim3(U), dim3(DW), 0, ctx->stream, a);                      \
-    } while (0)
-    if (cap <= DW) PCL_DEC_LAUNCH(1);
-    else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
-    else if (cap <= 4 * DW) PCL_DEC_LAUNCH(4);
-    else if (cap <= 8 * DW) PCL_DEC_LAUNCH(8);
-    else PCL_DEC_LAUNCH(16);
-#undef PCL_DEC_LAUNCH
-    pcl_timer_end(ctx, "decode");
-    HIPCHK(ctx, hipGetLastError());
-    }
 #ifdef PCL_DEC_STAMPS
-    {
-        long long h[N_STAMP];
-        HIPCHK(ctx, hipMemcpyAsync(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        fprintf(stderr, "decode stamps (utterance 0, 100 MHz ticks): step %lld donors %lld pairs %lld first|keys %lld prune %lld compact %lld select %lld\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-        d_stamps.release();
-    }
+        TRY(dec_print_stamps(ctx, d_stamps));
 #endif
-    return PCL_OK;
+        return PCL_OK;
     };
     if (ctx->dp_async) {
         TRY(pcl_run_on_dp_stream(b, false, launch));
@@ -925,8 +790,9 @@ int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *
     pcl_ctx *ctx = b->ctx;
     if (!b->have_dec) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_get: run pcl_batch_decode first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const int U = b->U, c = b->dec_cand, Tm = b->Tmax;
-    const int *p = b->dec_int;
+    const size_t U = (size_t)b->U, c = (size_t)b->dec_cand, Tm = (size_t)b->Tmax;
+    const DecLayout l = dec_layout(b->U, b->dec_cap, b->dec_cand, b->Tmax, false);   // (the results sit alike for both kernels)
+    const int *r = b->dec_int;
     // the results come down on the stream the decoder ran on, and only that stream is waited for: the scoring of the next
     // chunk, queued on the main stream meanwhile, keeps running
     hipStream_t st = b->dp_pending ? ctx->stream_dp : ctx->stream;
@@ -934,15 +800,15 @@ int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *
         if (dst) HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
         return PCL_OK;
     };
-    TRY(get(n_final, p, (size_t)U * 4)); p += U;
-    TRY(get(node, p, (size_t)U * c * 4)); p += (size_t)U * c;
-    TRY(get(hist, p, (size_t)U * c * 4)); p += (size_t)U * c;
-    TRY(get(hist_n, p, (size_t)U * 4)); p += U;
-    TRY(get(hist_prev, p, (size_t)U * Tm * 4)); p += (size_t)U * Tm;
-    TRY(get(hist_node, p, (size_t)U * Tm * 4)); p += (size_t)U * Tm;
-    TRY(get(n_tokens, p, (size_t)U * Tm * 4)); p += (size_t)U * Tm;
-    TRY(get(overflow, p, (size_t)U * 4));
-    TRY(get(score, b->dec_score, (size_t)U * c * 8));
+    TRY(get(n_final, r + l.out_n, U * 4));
+    TRY(get(node, r + l.out_node, U * c * 4));
+    TRY(get(hist, r + l.out_hist, U * c * 4));
+    TRY(get(hist_n, r + l.hist_n, U * 4));
+    TRY(get(hist_prev, r + l.hist_prev, U * Tm * 4));
+    TRY(get(hist_node, r + l.hist_node, U * Tm * 4));
+    TRY(get(n_tokens, r + l.trace, U * Tm * 4));
+    TRY(get(overflow, r + l.overflow, U * 4));
+    TRY(get(score, b->dec_score, U * c * 8));
     HIPCHK(ctx, hipStreamSynchronize(st));
     b->dp_pending = false;                                                     // (complete: nothing left to join)
     return PCL_OK;

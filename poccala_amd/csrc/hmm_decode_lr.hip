@@ -6,9 +6,9 @@
 // recursion  p_j = max_i(p_i + ln A_ij) + B_j  (Decoder.py:278-283) has two finite terms per state, the entry state is
 // -inf from its second step on and the exit state always, so a token is SIX float64 values and a step is a short serial
 // chain one lane can run: no cross-lane traffic at all (the general kernel spends half its step in ds_bpermute and
-// LDS reads of the 8 x 8 predecessor table), and every array pass is one access per field, 4 or 8 bytes per lane (round 5: the int4
-// meta record became three int arrays, so a 64-byte line serves 16 tokens' node / history / unit pair):
-//     score [2][cap] f64 | p [2][6][cap] f64 (state-major) | node, hist, upair [2][cap] i32 | src [2][cap]
+// LDS reads of the 8 x 8 predecessor table), and every array pass is one access per field, 4 or 8 bytes per lane (node, history
+// and unit pair are three int arrays, so a 64-byte line serves 16 tokens' worth of each).  Per utterance (DecLayout, hmm_decode.hip):
+//     score [2][cap] f64 | p [2][6][cap] f64 (state-major, in [2][8 cap]) | node, hist, upair [2][cap] i32 | src [2][cap] i32
 // Two buffers of each, ONE parity: a frame reads a token's state where the previous frame left it (through its src entry) and writes
 // it at the token's dense index into the other buffers; the end of a frame compacts only the index list.
 // Terms the general kernel adds with ln A = -inf are -inf there and absent here; max and + are exact, so the bits agree.
@@ -34,7 +34,7 @@
 #include <math.h>
 #include <stdio.h>
 
-#include "hmm_decode_args.h"
+#include "hmm_decode_common.h"
 
 namespace {
 
@@ -49,11 +49,10 @@ constexpr int LNW = LW / 64;
 constexpr int E = 3, NE = 2 * E;    // emitting states per unit (S = 5) and per token at most
 constexpr int TS = 7;               // doubles per unit in LDS: ln A self[3] | next[3] (k -> k + 1, the last one leaves the unit) | entry -> 1
                                     // (an odd stride: units spread over all banks; 8 gave 16-way conflicts)
-constexpr int HB = 12, HBINS = 1 << HB, BPT = HBINS / LW;    // radix digit of the pruning select
+constexpr int HB = 12, HBINS = 1 << HB;   // radix digit of the pruning select
 constexpr int CAND = 1024;          // keys of the selected bin ranked directly
 constexpr int DLW = 128;            // donors of a wave whose list entries live in LDS (more: in the utterance's seg_* arrays in HBM)
-constexpr int NONE = 0x7fffffff;
-constexpr int SLOT_BITS = 14;       // node -> token map entry = (frame << SLOT_BITS) | dense token index (cap <= 16 LW = 8192 < 2^14), -1 = none
+constexpr int SLOT_BITS = 14;       // node -> token map entry = (frame << SLOT_BITS) | dense token index (cap <= PCL_DEC_MAX_KEYS_PER_LANE LW = 8192 < 2^14), -1 = none
 constexpr int FRESH = (int)0x80000000;   // src: the token's last step was its first (its entry state still holds ln pi)
 #ifndef PCL_DECLR_G
 #define PCL_DECLR_G 2
@@ -61,9 +60,8 @@ constexpr int FRESH = (int)0x80000000;   // src: the token's last step was its f
 #ifndef PCL_DECLR_PMAX
 #define PCL_DECLR_PMAX 4
 #endif
-constexpr int G = PCL_DECLR_G;      // rows of a lane whose old p / meta / score are in flight together
+constexpr int G = PCL_DECLR_G;      // rows of a lane whose old p / node / history / unit pair / score are in flight together
 constexpr int PMAX = PCL_DECLR_PMAX; // pairs per thread in flight together
-constexpr unsigned long long NOKEY = ~0ull;
 constexpr size_t LIST_BYTES = (size_t)LNW * DLW * 20, SEL_BYTES = (size_t)HBINS * 4 + (size_t)CAND * 8;
 constexpr size_t POOL_BYTES = LIST_BYTES > SEL_BYTES ? LIST_BYTES : SEL_BYTES;
 
@@ -132,8 +130,8 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
     __shared__ unsigned long long red_u[2][LNW];
     __shared__ int red_i[LNW];
     __shared__ double red_d[LNW];
-    __shared__ unsigned long long s_key;
-    __shared__ int s_sel, s_rank, s_cnt, s_cn;
+    __shared__ unsigned long long s_key;                           // the pruning select's result words (pcl_select_kth)
+    __shared__ int s_int[4];
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifndef PCL_DECLR_NOPRIO
     // latency bound, few instructions, 300 frames of dependent phases: beside the scoring kernel of the next chunk (the C5 pipeline)
@@ -159,17 +157,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
     const double lpi1 = a.lpi1, lpi2 = a.lpi2;
     double *tab = dyn, *Bsl = dyn + ((a.n_units * TS + 1) & ~1);
 
-#ifdef PCL_DEC_STAMPS
-    long long st_acc[PCL_DEC_N_STAMP] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = wall_clock64();
-#define STAMP(k)                                  \
-    if (u == 0 && tid == 0) {                     \
-        const long long now_ = wall_clock64();    \
-        st_acc[k] += now_ - st_t;                 \
-        st_t = now_;                              \
-    }
-#else
-#define STAMP(k)
-#endif
+    STAMP_BEGIN
 
     for (int k = tid; k < a.n_units * TS; k += LW) {               // the left-to-right entries of every unit matrix
         const double *m = a.unit_logtrans + (size_t)(k / TS) * 25;
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         if (T > 1) Bsl[NbP + k] = B[(size_t)Nb + k];
     }
     if (tid < 256) occ[tid] = 0u;
-    if (tid == 0) s_cn = 0;
+    if (tid == 0) s_int[2] = 0;
     __syncthreads();
 
     // ---- frame 0: every first-character node starts (D3) and takes its first step
@@ -333,12 +321,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                 int4 info = make_int4(0, 0, 0, 0);
                 if (valid) info = ninfo[node];
                 const int cnt = info.y;
-                int inc = cnt;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int x = __shfl_up(inc, o, 64);
-                    if (lane >= o) inc += x;
-                }
+                const int inc = pcl_wave_scan(cnt, lane);
                 const int ofs = crun + inc - cnt;
                 if (valid) {
                     if (e < DLW) {
@@ -366,17 +349,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                 }
                 crun += __shfl(inc, 63, 64);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(bw, o, 64);
-                const int oi = __shfl_xor(bw_i, o, 64), on = __shfl_xor(bw_node, o, 64), oh = __shfl_xor(bw_hist, o, 64);
-                if (oi != NONE && (bw_i == NONE || ob > bw || (ob == bw && oi < bw_i))) {
-                    bw = ob;
-                    bw_i = oi;
-                    bw_node = on;
-                    bw_hist = oh;
-                }
-            }
+            pcl_wave_best(bw, bw_i, bw_node, bw_hist);
             if (lane == 0) {
                 wd_ch[wave] = crun;
                 wd_fw[wave] = fw;
@@ -398,7 +371,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         for (int w = 0; w < LNW; ++w) {
             if (R0 < 0 && wd_fw[w] != NONE) R0 = ch_tot + wd_fwend[w];
             ch_tot += wd_ch[w];
-            if (wd_bwi[w] != NONE && (w_i == NONE || wd_bw[w] > w_score || (wd_bw[w] == w_score && wd_bwi[w] < w_i))) {
+            if (pcl_beats(wd_bw[w], wd_bwi[w], w_score, w_i)) {
                 w_score = wd_bw[w];
                 w_i = wd_bwi[w];
                 w_node = wd_bwnode[w];
@@ -493,13 +466,8 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
             __syncthreads();
 #pragma unroll
             for (int x = 0; x < PMAX; ++x) {
-                int base = 0, tot = 0;
-#pragma unroll
-                for (int w = 0; w < LNW; ++w) {
-                    const int y = wp[x][w];
-                    if (w < wave) base += y;
-                    tot += y;
-                }
+                int tot;
+                const int base = pcl_waves_before<LNW>(wp[x], wave, &tot);
                 if (val[x] && sidx[x] < 0) {
                     const int pos = n + created + base + __popcll(nmask[x] & lt_mask);
                     if (pos < cap) {                               // (slots n .. cap-1 of the current buffers)
@@ -522,213 +490,38 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         if (created > cap - n) ovf = 1;
         if (Q <= 0) __syncthreads();                               // (the donor lists are read no more: the pool changes tenant)
         STAMP(2)
-        // ---- E: pruning over the tokens that were alive before the frame and did not finish (Decoder.py:159-167): nothing
-        //      below min_distinct different scores, else the int(width (1 - beam)) lowest go (stable ascending order: ties by
-        //      token order).  One pass gives the width, the key range and a hashed occupancy map (different bins => different
-        //      scores); then the m-th smallest key: a 12-bit digit below the range's common prefix picks a bin, and the few keys
-        //      of that bin are ranked directly.
-        for (int k = tid; k < HBINS; k += LW) hist[k] = 0u;
+        // ---- E: pruning over the tokens that were alive before the frame and did not finish (Decoder.py:159-167), the four steps of
+        //      hmm_decode_common.h: a 12-bit digit below the key range's common prefix picks a bin, and the few keys of that bin are
+        //      ranked directly
+        for (int k = tid; k < HBINS; k += LW) hist[k] = 0u;        // (the pool's new tenant; the first step's barriers come before its use)
         unsigned long long keys[KMAX];
-        int cnt = 0;
-        unsigned long long kmn = ~0ull, kmx = 0ull;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             const int i = w0 + k * 64 + lane;
             const bool in = k * 64 < C && i < n && !((finmask >> k) & 1u);
             keys[k] = in ? pcl_okey(sc[i]) : NOKEY;
         }
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            const unsigned long long key = keys[k];
-            if (key != NOKEY) {
-                ++cnt;
-                kmn = min(kmn, key);
-                kmx = max(kmx, key);
-                atomicOr(&occ[(unsigned int)((key * 0x9E3779B97F4A7C15ull) >> 56)], 1u);
-            }
-        }
-        cnt = pcl_wave_sum(cnt);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            kmn = min(kmn, (unsigned long long)__shfl_xor((long long)kmn, o, 64));
-            kmx = max(kmx, (unsigned long long)__shfl_xor((long long)kmx, o, 64));
-        }
-        if (lane == 0) {
-            we_cnt[wave] = cnt;
-            red_u[0][wave] = kmn;
-            red_u[1][wave] = kmx;
-        }
-        __syncthreads();
-        const int bins = __syncthreads_count(tid < 256 && occ[tid] != 0u);
-        if (tid < 256) occ[tid] = 0u;                              // (next read: a frame and many barriers away)
-        int n_old = 0;
-        unsigned long long kmin = ~0ull, kmax = 0ull;
-#pragma unroll
-        for (int w = 0; w < LNW; ++w) {
-            n_old += we_cnt[w];
-            kmin = min(kmin, red_u[0][w]);
-            kmax = max(kmax, red_u[1][w]);
-        }
+        int n_old, bins;
+        unsigned long long kmin, kmax;
+        pcl_prune_stats<LW, KMAX>(keys, occ, we_cnt, red_u[0], red_u[1], n_old, kmin, kmax, bins);
         STAMP(3)
         const int m_cut = (int)((double)n_old * (1.0 - a.beam));                // int(width * (1 - beam))
         bool prune = m_cut > 0 && n_old >= a.min_distinct;
-        if (prune && bins < a.min_distinct) {                                   // few bins: count the distinct scores exactly
-            unsigned long long prev = 0ull;
-            bool have_prev = false;
-            int distinct = 0;
-            for (int round = 0; round < a.min_distinct; ++round) {              // the next larger key, min_distinct times
-                unsigned long long mn = ~0ull;
-                bool any = false;
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k) {
-                    const unsigned long long key = keys[k];
-                    if (key != NOKEY && (!have_prev || key > prev) && (!any || key < mn)) {
-                        mn = key;
-                        any = true;
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const unsigned long long om = (unsigned long long)__shfl_xor((long long)mn, o, 64);
-                    const int oa = __shfl_xor((int)any, o, 64);
-                    if (oa && (!any || om < mn)) {
-                        mn = om;
-                        any = true;
-                    }
-                }
-                __syncthreads();
-                if (lane == 0) {
-                    red_u[0][wave] = mn;
-                    red_i[wave] = any;
-                }
-                __syncthreads();
-                unsigned long long g = ~0ull;
-                bool gany = false;
-                for (int w = 0; w < LNW; ++w)
-                    if (red_i[w] && (!gany || red_u[0][w] < g)) {
-                        g = red_u[0][w];
-                        gany = true;
-                    }
-                if (!gany) break;
-                prev = g;
-                have_prev = true;
-                ++distinct;
-            }
-            prune = distinct >= a.min_distinct;
-            __syncthreads();
-        }
+        if (prune && bins < a.min_distinct) prune = pcl_prune_distinct<LW, KMAX>(keys, a.min_distinct, red_u[0], red_i);
         unsigned int prunemask = 0u;
         if (prune) {
-            unsigned long long sel = kmin;
-            int rank = m_cut - 1;
-            const unsigned long long diff = kmin ^ kmax;
-            if (diff != 0ull) {
-                const int hb = 63 - __clzll((long long)diff);                  // the highest bit in which the keys differ
-                const unsigned long long lowmask = (2ull << hb) - 1ull;        // (hb = 63: all ones)
-                int shift = max(hb - (HB - 1), 0);
-                unsigned long long pmask = 0ull, pval = 0ull;                   // keys still in play: (key & pmask) == pval
-                for (;;) {
-#pragma unroll
-                    for (int k = 0; k < KMAX; ++k) {
-                        const unsigned long long key = keys[k];
-                        if (key != NOKEY && (key & pmask) == pval) atomicAdd(&hist[(unsigned int)(key >> shift) & (HBINS - 1)], 1u);
-                    }
-                    __syncthreads();
-                    int h[BPT], s4 = 0;                                         // BPT bins per thread: the bin holding rank
-#pragma unroll
-                    for (int j = 0; j < BPT; ++j) {
-                        h[j] = (int)hist[BPT * tid + j];
-                        s4 += h[j];
-                        hist[BPT * tid + j] = 0u;
-                    }
-                    int inc = s4;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const int x = __shfl_up(inc, o, 64);
-                        if (lane >= o) inc += x;
-                    }
-                    if (lane == 63) ws_scan[wave] = inc;
-                    __syncthreads();
-                    int base = 0;
-#pragma unroll
-                    for (int w = 0; w < LNW; ++w)
-                        if (w < wave) base += ws_scan[w];
-                    const int lo = base + inc - s4;
-                    if (rank >= lo && rank < lo + s4) {
-                        int acc = lo, j = 0;
-                        for (; j < BPT - 1; ++j) {
-                            if (acc + h[j] > rank) break;
-                            acc += h[j];
-                        }
-                        s_sel = BPT * tid + j;
-                        s_rank = rank - acc;
-                        s_cnt = h[j];
-                    }
-                    __syncthreads();
-                    const int c = s_cnt;
-                    rank = s_rank;
-                    pmask |= (unsigned long long)(HBINS - 1) << shift;
-                    pval = (pval & ~((unsigned long long)(HBINS - 1) << shift)) | ((unsigned long long)s_sel << shift);
-                    if (shift == 0) {
-                        sel = (kmin & ~lowmask) | (pval & lowmask);
-                        break;
-                    }
-                    if (c <= CAND) {                                            // the bin's keys, ranked directly
-#pragma unroll
-                        for (int k = 0; k < KMAX; ++k) {
-                            const unsigned long long key = keys[k];
-                            if (key != NOKEY && (key & pmask) == pval) cand[atomicAdd(&s_cn, 1)] = key;
-                        }
-                        __syncthreads();
-                        for (int x = tid; x < c; x += LW) {
-                            const unsigned long long kx = cand[x];
-                            int less = 0, eq = 0;
-                            for (int y = 0; y < c; ++y) {
-                                const unsigned long long ky = cand[y];
-                                less += ky < kx;
-                                eq += ky == kx;
-                            }
-                            if (less <= rank && rank < less + eq) {             // (equal keys write the same two values)
-                                s_key = kx;
-                                s_rank = rank - less;
-                            }
-                        }
-                        __syncthreads();
-                        sel = s_key;
-                        rank = s_rank;
-                        if (tid == 0) s_cn = 0;
-                        break;
-                    }
-                    shift = max(shift - HB, 0);
-                }
-            }
+            unsigned long long sel;
+            int rank;
+            pcl_select_kth<LW, KMAX, HB, CAND>(keys, kmin, kmax, m_cut, hist, cand, ws_scan, &s_key, s_int, sel, rank);
             STAMP(6)
-            // everything below the selected key goes, and of the tokens equal to it the first (rank + 1) in token order
-            int eq = 0;
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) eq += keys[k] == sel;
-            eq = pcl_wave_sum(eq);
-            if (lane == 0) w_eq[wave] = eq;
-            __syncthreads();
-            int run = 0;
-#pragma unroll
-            for (int w = 0; w < LNW; ++w)
-                if (w < wave) run += w_eq[w];
-#pragma unroll
-            for (int k = 0; k < KMAX; ++k) {
-                const unsigned long long key = keys[k];
-                const bool is_eq = key == sel;                                 // (sel is a real key, never NOKEY)
-                const unsigned long long mask = __ballot(is_eq);
-                if (key != NOKEY && (key < sel || (is_eq && run + __popcll(mask & lt_mask) <= rank))) prunemask |= 1u << k;
-                run += __popcll(mask);
-            }
+            prunemask = pcl_prune_mark<LW, KMAX>(keys, sel, rank, w_eq);
         }
         STAMP(4)
         // ---- F: stable compaction of the INDEX LIST: the survivors of the old tokens, then the new ones (the node -> token map is
         //      re-stamped by the next frame's step: nothing to follow here).
         //      Scores, nodes, histories, unit pairs and p stay where this frame wrote them: the next frame's step gathers them through
         //      the list (an ascending sequence with the pruned tokens' gaps: nearly coalesced) and writes them dense again -- round 4
-        //      moved score + meta here as well (24 B in, 24 B out per token and frame, and a dependent load round)
+        //      moved score, node, history and unit pair here as well (24 B in, 24 B out per token and frame, and a dependent load round)
         int *__restrict__ srn = srb(cur ^ 1);
         const unsigned int dead = finmask | prunemask;
         int keep_cnt = 0;
@@ -737,13 +530,8 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         keep_cnt = pcl_wave_sum(keep_cnt);
         if (lane == 0) wf_keep[wave] = keep_cnt;
         __syncthreads();
-        int krun = 0, n_keep = 0;
-#pragma unroll
-        for (int w = 0; w < LNW; ++w) {
-            const int x = wf_keep[w];
-            if (w < wave) krun += x;
-            n_keep += x;
-        }
+        int n_keep;
+        int krun = pcl_waves_before<LNW>(wf_keep, wave, &n_keep);
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             if (k * 64 >= C) continue;                             // (wave-uniform)
@@ -771,63 +559,17 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         if (tid == 0) a.trace[(size_t)u * a.Tmax + t] = n;
     }
     // ---- transfer (Decoder.py:175-187): the `candidate` best tokens, ties in token order (token k's state sits at index src[k] of the
-    //      buffers the last frame wrote)
-    const double *sc = scb(cur);
-    const int *nd = ndb(cur), *hs = hsb(cur), *srf = srb(cur);
-    int *taken = srb(cur ^ 1);                                     // (the idle src buffer: 4 = taken)
-    for (int i = tid; i < n; i += LW) taken[i] = 0;
-    __syncthreads();
-    int n_out = 0;
-    for (int cc = 0; cc < a.candidate && cc < n; ++cc) {
-        double b = -INFINITY;
-        int bi = NONE;
-        for (int i = tid; i < n; i += LW) {
-            const double v = sc[srf[i] & 0x7fffffff];
-            if (taken[i] != 4 && (bi == NONE || v > b)) {          // (strictly greater keeps the earliest on ties)
-                b = v;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ob = __shfl_xor(b, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (oi != NONE && (bi == NONE || ob > b || (ob == b && oi < bi))) {
-                b = ob;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            red_d[wave] = b;
-            red_i[wave] = bi;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double g = -INFINITY;
-            int gi = NONE;
-            for (int w = 0; w < LNW; ++w)
-                if (red_i[w] != NONE && (gi == NONE || red_d[w] > g || (red_d[w] == g && red_i[w] < gi))) {
-                    g = red_d[w];
-                    gi = red_i[w];
-                }
-            const int at = srf[gi] & 0x7fffffff;
-            a.out_node[(size_t)u * a.candidate + cc] = nd[at];
-            a.out_score[(size_t)u * a.candidate + cc] = sc[at];
-            a.out_hist[(size_t)u * a.candidate + cc] = hs[at];
-            taken[gi] = 4;
-        }
-        ++n_out;
-        __syncthreads();
-    }
+    //      buffers the last frame wrote; the idle src buffer holds the "taken" marks)
+    const int *srf = srb(cur);
+    const size_t o_out = (size_t)u * a.candidate;
+    const int n_out = pcl_transfer<LW>(n, a.candidate, scb(cur), ndb(cur), hsb(cur), [srf](int i) { return srf[i] & 0x7fffffff; }, srb(cur ^ 1), red_d,
+                                       red_i, a.out_node + o_out, a.out_score + o_out, a.out_hist + o_out);
     if (tid == 0) {
         a.out_n[u] = n_out;
         a.hist_n[u] = min(nh, a.Tmax);
         a.overflow[u] = ovf;
-#ifdef PCL_DEC_STAMPS
-        if (u == 0 && a.stamps)
-            for (int k = 0; k < PCL_DEC_N_STAMP; ++k) a.stamps[k] = st_acc[k];
-#endif
     }
+    STAMP_END(a.stamps)
 }
 
 constexpr size_t LR_STATIC_LDS = POOL_BYTES + 256 * 4 + 2048;      // (what the kernel declares, rounded up)
@@ -841,7 +583,7 @@ size_t lr_dyn_bytes(const pcl_ctx *ctx, int n_rows) {
 }  // namespace
 
 bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max) {
-    if (ctx->S != 5 || cap > 16 * LW || cap > (1 << SLOT_BITS)) return false;
+    if (ctx->S != 5 || cap > PCL_DEC_MAX_KEYS_PER_LANE * LW || cap > (1 << SLOT_BITS)) return false;
     if (t_max >= (1 << (31 - SLOT_BITS))) return false;            // (the frame stamp of the node -> token map: utterances of up to 131071 frames)
     if (lr_dyn_bytes(ctx, n_rows) + LR_STATIC_LDS > LR_LDS_BUDGET) return false;
     const double *lt = ctx->unit_logtrans.data();

@@ -164,6 +164,64 @@ def test_decode_many_tokens_finish_in_one_frame(eng):
     assert swing > 2000                                           # (the frames this test is about did occur)
 
 
+def test_decode_prunes_through_tied_scores(eng, monkeypatch):
+    """One GMM for every state makes the emissions state-independent, so whole generations of tokens carry the SAME score: the
+    pruning cut falls between equal scores (the first rank + 1 of them in token order go), a frame has one distinct score and
+    still prunes (min_distinct 1), or fewer distinct scores than min_distinct and prunes nothing (Decoder.py:159-167).  Some 600
+    live tokens: the tied tokens span several wavefronts in both kernels.  Both kernels, bit for bit the restatement."""
+    from poccala_amd import PCL_F64, synth
+    n_units = 183
+    tree, lx = synth.make_pronunciation_tree(3000, n_units, seed=81)
+    mean, var, w, _ = synth.make_model(n_units, 2, 13, seed=82)
+    mean[:], var[:], w[:] = mean[0], var[0], w[0]                 # one GMM for every state
+    a = np.zeros((S, S))
+    a[0, 1] = 1.0
+    for r in range(1, S - 1):
+        a[r, r], a[r, r + 1] = 0.1, 0.9
+    trans = np.stack([a] * n_units)
+    frames, lens, begin = synth.make_frames(2, 12, 13, seed=83)
+    eng.load_model(mean, var, w)
+    eng.load_units(trans)
+    eng.load_lexicon(tree)
+    eng.load_frames(frames)
+    b = eng.all_state_batch(lens, begin)
+    b.score(PCL_F64)
+    B = b.get('B')
+    sets = [(0.5, 1), (0.6, 3)]
+    got = []
+    for beam, md in sets:
+        fast = b.decode(beam=beam, min_distinct=md, candidate=4, max_tokens=2048)
+        monkeypatch.setenv('PCL_DEC_GENERAL', '1')
+        general = b.decode(beam=beam, min_distinct=md, candidate=4, max_tokens=2048)
+        monkeypatch.delenv('PCL_DEC_GENERAL')
+        got.append((fast, general))
+    b.close()
+    calls, real_prune = [], do.prune                              # calls: (set, tokens, distinct scores, dropped, cut between equal scores)
+
+    def watched(scores, beam=0.85, min_distinct=8):
+        drop = real_prune(scores, beam, min_distinct)
+        kept = [s for i, s in enumerate(scores) if i not in drop]
+        tie = bool(drop) and max(scores[i] for i in drop) in kept
+        calls.append((which[0], len(scores), len(set(scores)), len(drop), tie))
+        return drop
+    monkeypatch.setattr(do, 'prune', watched)
+    which = [0]
+    for which[0], ((beam, md), (fast, general)) in enumerate(zip(sets, got)):
+        for u in range(2):
+            trace, info = [], {}
+            fin, hist = do.decode(tree, list(trans), B[u][1:-1], beam=beam, min_distinct=md, candidate=4, max_tokens=2048, trace=trace, info=info)
+            for g in (fast[u], general[u]):
+                assert np.array_equal(g['n_tokens'], np.array(trace)), (g['n_tokens'], trace)
+                assert g['history'] == [(int(p), int(n)) for p, n in hist]
+                assert [(n, h) for n, _, h in g['final']] == [(n, h) for n, _, h in fin]
+                assert [s for _, s, _ in g['final']] == [float(s) for _, s, _ in fin]
+                assert g['overflow'] == bool(info.get('overflow'))
+    # the frames this test is about did occur
+    assert any(dropped and tie for _, _, _, dropped, tie in calls)
+    assert any(k == 0 and distinct == 1 and dropped for k, _, distinct, dropped, _ in calls)
+    assert any(k == 1 and 0 < distinct < 3 and dropped == 0 and n >= 3 for k, n, distinct, dropped, _ in calls)
+
+
 @pytest.mark.parametrize('n_units', [350, 600])
 def test_decode_with_a_large_unit_inventory(eng, n_units):
     """More GMM states than the lane-per-token kernel prefetches per frame (J + 2 > 1024: the emission row is staged without the
