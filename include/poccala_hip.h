@@ -108,7 +108,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
+ * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "fmllr" | "fmllr_frames" | "fmllr_gk" | "fmllr_solve" (pcl_fmllr_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -496,6 +496,82 @@ int pcl_mllr_estimate(pcl_ctx *ctx, int R, const int32_t *state_class /* J, or N
 int pcl_model_transform_means(pcl_ctx *ctx, int R, const int32_t *state_class /* J, or NULL = all 0 */,
                               const double *W /* host R*D*(D+1), or NULL = the resident last estimate */);
 int pcl_mstep_map(pcl_ctx *ctx, double tau);
+
+/* ----------------------------------------------------------------- fMLLR (row f11): per-speaker transforms of the FEATURES, y = b + A x
+ * Constrained MLLR (Gales 1998, section 3.2 and appendix B) on the resident frames (csrc/frame_adapt.hip).  The model stays untouched; every
+ * speaker of a batch gets a transform of its own; the transformed frames stay where scoring, forward-backward, decode and the segmental
+ * trainers read them.  Not in the reference.  Everything is float64.  zeta_t = (1, x_t) (length D+1), W = [b | A] (D x (D+1), column 0 the
+ * offset, as pcl_mllr_estimate lays W out), s = the speaker of the utterance, gamma_t(j,m) = the mixture posterior of frame t,
+ *     gamma_t(j,m) = exp(ln gamma_t(row) + ln w_jm + ln N(x_t; mu_jm, var_jm) - ln b_j(x_t))        summed over the utterance's rows of state j
+ * from the batch's resident ln gamma (pcl_batch_forward_backward / pcl_batch_set_posteriors) and ln b (pcl_batch_score), in the direct
+ * float64 form of pcl_batch_accumulate(PCL_F64), on the float64 frame copy when the context holds one, else on the float32 rows widened.
+ * A mixture with weight 0 or a weight that is not finite, and the padding mixtures, contribute exactly nothing; so does a (frame, row)
+ * whose ln gamma or ln b is -inf.
+ *
+ * STATISTICS.  Per frame:   p_i(t) = sum_{j,m} gamma_t(j,m) / var_jm,i      q_i(t) = sum_{j,m} gamma_t(j,m) mu_jm,i / var_jm,i      beta(t) = sum_{j,m} gamma_t(j,m)
+ * (1 / var and mu / var are recovered from the float64 scoring row s = sqrt(log2 e / (2 var)), c = -mu s as 2 ln2 s^2 and -2 ln2 c s: the
+ * sums of gamma s^2 and gamma c s are formed and scaled once).  Order: one workgroup of four waves per (utterance, tile of 64 frames), lane
+ * l owns frame l of the tile; wave w adds, over the utterance's rows in ascending order, the row's mixtures w, w + 4, w + 8, ... in ascending
+ * order; the four waves' sums are then added through LDS as ((w0 + w1) + w2) + w3.
+ * Per speaker:  G[s,i] = sum_t p_i(t) zeta_t zeta_t^T   ((D+1) x (D+1), symmetric)      k[s,i] = sum_t q_i(t) zeta_t      beta[s] = sum_t beta(t)
+ * over the frames of the speaker's utterances: the split-K float64 GEMM pcl_mllr_estimate uses (csrc/adapt_common.h; K = the speaker's
+ * frames in batch order, cut into chunks of PCL_MLLR_CHUNK frames; column D+1 of the second operand carries q_i(t), so k comes out of the
+ * same chain; upper-triangular tiles only; on v_mfma_f64_16x16x4_f64, or on the VALU under PCL_MLLR_VALU=1); a call's chunks are added to
+ * the resident sums in chunk order, then the lower triangle mirrors the upper.  beta[s]: thread t of 256 adds the speaker's frames t,
+ * t + 256, ... in ascending order, then a fixed binary tree.  No floating-point atomics: two runs give the same bits.
+ * pcl_fmllr_zero makes (or clears) the context's statistics for S speakers -- 8 D (D+1)(D+2) bytes per speaker, at most 2^32 bytes in all and
+ * S <= 65535 -- and drops the resident estimate.  The statistics are additive over calls of pcl_batch_accumulate_fmllr (several batches of one
+ * speaker) and are dropped by any call that makes a new model (an upload, a flat start, a mix-up, k-means) or a frame matrix of another D.
+ * pcl_batch_accumulate_fmllr: utt_speaker (U,) int32 in [0, S), or -1 = the utterance is skipped.  Needs what pcl_batch_accumulate needs
+ * (emissions, posteriors, the row map, frames of the model's dimension).  Synchronous.
+ * pcl_fmllr_stats_download: G (S, D, D+1, D+1), k (S, D, D+1), beta (S,); NULLs are skipped.
+ *
+ * ESTIMATE, per speaker, from W = [0 | I], A^-1 = I; n_iter sweeps; a sweep visits the rows i = 0 .. D-1 in order:
+ *   1. p = (0, column i of A^-1): the cofactor row up to scale (the update does not depend on the scale of p, so no determinant is formed)
+ *   2. v = G_i^-1 p^T through the Cholesky factor G_i = L L^T (L y = p, L^T v = y), g = G_i^-1 k_i^T likewise (once per (s, i), as is the
+ *      factor);  a = sum_q p_q v_q,  c = sum_q p_q g_q  (ascending q)
+ *   3. disc = c c + 4 a beta;  alpha+- = (-c +- sqrt(disc)) / (2 a);  f(alpha) = beta ln|alpha a + c| - 0.5 a alpha alpha;  alpha = alpha+
+ *      when f(alpha+) >= f(alpha-), else alpha-
+ *   4. w_i = alpha v + g
+ *   5. A^-1 by a rank-one update: u = column i of A^-1 (before), denom = sum_q w_i[1+q] u_q, z = ((w_i - w_i_old)[1..] A^-1) / denom,
+ *      A^-1 <- A^-1 - u z.  Every sweep ENDS with a full re-inversion of A (in-place Gauss-Jordan with row pivoting: the first row of
+ *      largest |element| in column k at or below the diagonal is swapped up; ln|det A| = sum ln|pivot|; the swaps are undone on the columns
+ *      of the inverse in reverse order), which also gives the ln|det A| of
+ *         Q = beta ln|det A| - 1/2 sum_i (w_i G_i w_i^T - 2 w_i k_i^T)          q_trace[s, sweep]
+ * A speaker is REFUSED -- it gets [0 | I], ln|det A| = 0, NaN in q_trace and a non-zero status -- when, tested in this order,
+ *     PCL_FMLLR_LOW_OCCUPANCY          beta[s] < min_occ
+ *     PCL_FMLLR_NOT_POSITIVE_DEFINITE  a Cholesky pivot of any G[s,i] is not finite or not > 0
+ *     PCL_FMLLR_SINGULAR               a is not finite or not > 0, disc is negative or not finite, alpha is not finite, denom or a
+ *                                      Gauss-Jordan pivot is 0 or not finite
+ * Statuses are decided before anything is written.  One wave per (s, i) factors; one wave per speaker sweeps, W and A^-1 in LDS, the factor
+ * of the row at hand staged into LDS, G read through L2 for Q.  W stays resident (until the next pcl_fmllr_zero or new model) for
+ * pcl_frames_transform(W = NULL).  W_out (S, D, D+1), logdet_out (S,), q_trace_out (S, n_iter), status_out (S,) int32: NULLs are skipped.
+ * 1 <= n_iter <= 1000; min_occ finite and >= 0; D <= 48.  Synchronous.
+ *
+ * APPLY.  pcl_frames_transform: y = b + A x in place on the CURRENT frame matrix for the rows [frame_begin[u], + T[u]) of every utterance
+ * with utt_speaker[u] >= 0: the offset first, then the products in ascending feature order, one rounding per operation.  x is read from
+ * the float64 copy when the context holds one (which then receives y), else from the float32 rows widened; the float32 rows receive y
+ * rounded to nearest; the padding columns stay as pcl_frames_upload left them.  A speaker whose W is exactly [0 | I] -- every refused
+ * speaker -- and the utterances of speaker -1 keep their bits; rows outside every utterance are untouched.  W: host (S, D, D+1), or NULL =
+ * the resident estimate, which must be of the same S.  The utterances must not overlap in the frame matrix (PCL_ERR_INVALID, as
+ * pcl_batch_align_segments checks): a frame is transformed once.  A live pcl_seg has its own copy of the frames and is untouched; live
+ * batches keep the emissions they scored from the old rows until they are scored again -- the state pcl_frames_swap leaves them in.
+ *
+ * No model / no statistics (never made, or dropped): PCL_ERR_STATE.  A speaker outside [-1, S), S out of range, W = NULL without a resident
+ * estimate of S speakers, frames of another dimension than the model: PCL_ERR_INVALID.  All checked before anything is changed.
+ * pcl_kernel_time groups: "fmllr" (every kernel of each call), "fmllr_frames" (the per-frame reduction), "fmllr_gk" (the GEMM and its
+ * reduction), "fmllr_solve" (factorisations and sweeps). */
+#define PCL_FMLLR_OK 0
+#define PCL_FMLLR_LOW_OCCUPANCY 1
+#define PCL_FMLLR_NOT_POSITIVE_DEFINITE 2
+#define PCL_FMLLR_SINGULAR 3
+int pcl_fmllr_zero(pcl_ctx *ctx, int S);
+int pcl_batch_accumulate_fmllr(pcl_batch *b, const int32_t *utt_speaker /* U, -1 = skip */);
+int pcl_fmllr_stats_download(pcl_ctx *ctx, double *G /* S*D*(D+1)*(D+1) or NULL */, double *k /* S*D*(D+1) or NULL */, double *beta /* S or NULL */);
+int pcl_fmllr_estimate(pcl_ctx *ctx, int n_iter, double min_occ, double *W_out /* S*D*(D+1) or NULL */, double *logdet_out /* S or NULL */,
+                       double *q_trace_out /* S*n_iter or NULL */, int32_t *status_out /* S or NULL */);
+int pcl_frames_transform(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *utt_speaker, int S,
+                         const double *W /* host S*D*(D+1), or NULL = the resident last estimate */);
 
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /

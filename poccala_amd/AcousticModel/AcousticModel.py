@@ -559,6 +559,65 @@ class AcousticModel(DataInitialization):
             del out['W'], out['occ'], out['status']
         return out
 
+    @staticmethod
+    def compose_fmllr(W_run, logdet_run, W_new, logdet_new):
+        """The transform that applies W_run and then W_new, per speaker: A <- A_new A, b <- A_new b + b_new, ln|det A| added."""
+        A, b = W_run[:, :, 1:], W_run[:, :, 0]
+        An, bn = W_new[:, :, 1:], W_new[:, :, 0]
+        out = np.concatenate([(np.einsum('sij,sj->si', An, b) + bn)[:, :, None], np.einsum('sij,sjk->sik', An, A)], axis=2)
+        return out, np.asarray(logdet_run, dtype=np.float64) + np.asarray(logdet_new, dtype=np.float64)
+
+    def fmllr_batch(self, labels, data_list, unit_hmms, utt_speaker, iterations=1, n_iter=20, min_occ=1000.0, precision=PCL_F64, engine=None,
+                    n_speakers=None):
+        """fMLLR on the device: one affine transform of the FEATURES per speaker, y = b + A x (Engine.fmllr_estimate; the rule:
+        include/poccala_hip.h).  The model stays as it is; the engine's resident frames are transformed in place.  utt_speaker: one
+        speaker index >= 0 per utterance, -1 = leave the utterance alone.  Per iteration: an E-step on the current frames (score +
+        forward-backward), Batch.accumulate_fmllr, the estimate, Engine.transform_frames; the new transform is composed onto the running
+        one on the host (compose_fmllr).  data_list: (T_u, D) arrays (uploaded once, as float64), or the (lens, begin) of resident frames.
+        Returns a dict: logp = iterations + 1 totals of ln P(O) + sum_u T_u ln|det A_speaker(u)| -- of the frames as given, then after
+        every iteration, so that the entries are comparable --, W (S, D, D+1) / logdet (S,) = the composed transforms, status = per
+        iteration the (S,) statuses, q_trace = per iteration (S, n_iter), W_iter = per iteration (W, logdet) as estimated."""
+        engine = engine or default_engine()
+        spk = np.asarray(utt_speaker, dtype=np.int32).reshape(-1)
+        if len(spk) != self._utt_count(data_list) or len(labels) != len(spk):
+            raise ValueError('fmllr_batch: one label sequence and one speaker per utterance')
+        keep = self._nonempty(data_list)
+        if len(keep) < self._utt_count(data_list):          # empty utterances add nothing to the statistics
+            labels, data_list, spk = [labels[u] for u in keep], self._utt_subset(data_list, keep), spk[keep]
+        S = int(n_speakers) if n_speakers is not None else max(int(spk.max()) + 1, 1)
+        res = self._resident(data_list)
+        if res is None:                                      # uploaded ONCE: every later pass reads what the last one left resident
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d, dtype=np.float64) for d in data_list], axis=0))
+        else:
+            lens, begin = res
+        D = int(engine.FD)
+        W_run = np.stack([np.concatenate([np.zeros((D, 1)), np.eye(D)], axis=1)] * S)
+        logdet_run = np.zeros(S)
+        out = dict(logp=[], status=[], q_trace=[], W_iter=[])
+
+        def estep():
+            b = self._sentence_batch(labels, (lens, begin), unit_hmms, engine)[0]
+            b.score(precision)
+            b.forward_backward()
+            total = float(np.sum(b.get('logp')))
+            out['logp'].append(total + float(np.sum(lens * np.where(spk >= 0, logdet_run[np.maximum(spk, 0)], 0.0))))
+            return b
+
+        for _ in range(int(iterations)):
+            b = estep()
+            engine.fmllr_zero(S)
+            b.accumulate_fmllr(spk)
+            b.close()
+            W, logdet, q, status = engine.fmllr_estimate(n_iter, min_occ)
+            engine.transform_frames(lens, begin, spk, None, S)
+            W_run, logdet_run = self.compose_fmllr(W_run, logdet_run, W, logdet)
+            out['status'].append(status), out['q_trace'].append(q), out['W_iter'].append((W, logdet))
+        estep().close()
+        out['W'], out['logdet'] = W_run, logdet_run
+        return out
+
     def _adopt_model(self, model, units, unit_hmms):
         """(mean, var, weight) of a model laid out unit-major over `units` into the units' GMM objects; this object's mix_level follows."""
         mean, var, w = model

@@ -71,6 +71,11 @@ PROTOTYPES = {
     'pcl_mllr_estimate': (_i, [_vp, _i, _vp, _d, _vp, _vp, _vp]),
     'pcl_model_transform_means': (_i, [_vp, _i, _vp, _vp]),
     'pcl_mstep_map': (_i, [_vp, _d]),
+    'pcl_fmllr_zero': (_i, [_vp, _i]),
+    'pcl_batch_accumulate_fmllr': (_i, [_vp, _vp]),
+    'pcl_fmllr_stats_download': (_i, [_vp, _vp, _vp, _vp]),
+    'pcl_fmllr_estimate': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp]),
+    'pcl_frames_transform': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

@@ -15,116 +15,40 @@
 
 namespace {
 
+#include "adapt_common.h"                     // the GEMM over an operand source, the chunk reduction, the solve: shared with frame_adapt.hip
+
 constexpr double STAT_BIAS = 100.0;           // mean_acc holds sum gamma (o + bias): pcl_launch_mstep_range passes the same constant
-constexpr int ADAPT_D_MAX = 48;               // order D + 1 <= 49 (the solve's LDS matrix)
-constexpr long long CHUNK_DEFAULT = 65536;    // mixtures per K-chunk: 93 chunks x 39 dimensions = 3600 workgroups at config 4's shape
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// Chunk length in mixtures, env PCL_MLLR_CHUNK, read on EVERY call (as PCL_PCM_CHUNK is): tests force several chunks on a small model.
-long long mllr_chunk() {
-    const char *e = getenv("PCL_MLLR_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : CHUNK_DEFAULT;
-}
-bool mllr_use_valu() {                        // env PCL_MLLR_VALU=1 (read on every call): the float64 VALU form of the GEMM (A/B, tools/adapt_bench.py)
-    const char *e = getenv("PCL_MLLR_VALU");
-    return e && atoi(e) != 0;
-}
-
-// What the kernels below share: the model, the statistics and the walk over a class's mixtures.  A class's mixture space is its states in
+// The GEMM's operand source: the model, the statistics and the walk over a class's mixtures.  A class's mixture space is its states in
 // list order (cls_states[cls_off[r] ...], ascending state index), M real mixtures each; chunk c covers [chunk_e0[c], + chunk_n[c]) of it.
+// The two operands of mixture `le` of a chunk for feature dimension i and row / column p of the padded (D + 2) grid:
+//   a = xi[p]                        xi = (1, mu_1 .. mu_D), 0 beyond
+//   b = (acc / var_i) xi[p]  (p <= D),  (mean_acc_i - bias acc) / var_i  (p = D + 1: the column that sums to k),  0 beyond
+// so that sum a[p] b[q] = G[p][q] (q <= D) and k[p] (q = D + 1).  A mixture that does not contribute gives exact zeros.
 struct GkArgs {
     const double *mean, *var, *acc, *macc;
     const int *cls_states, *cls_off, *chunk_cls, *chunk_e0, *chunk_n;
     int M, Mpad, Dd, Dh;
-};
-
-// The two operands of mixture `le` of chunk (r, e0, n) for feature dimension i and row / column p of the padded (D + 2) grid:
-//   a = xi[p]                        xi = (1, mu_1 .. mu_D), 0 beyond
-//   b = (acc / var_i) xi[p]  (p <= D),  (mean_acc_i - bias acc) / var_i  (p = D + 1: the column that sums to k),  0 beyond
-// so that sum a[p] b[q] = G[p][q] (q <= D) and k[p] (q = D + 1).  A mixture that does not contribute gives exact zeros.
-__device__ __forceinline__ void gk_operands(const GkArgs &g, int s0, int e0, int n, int le, int i, int p, double &a, double &b) {
-    a = b = 0.0;
-    if (le >= n || p > g.Dh + 1) return;
-    const int e = e0 + le, js = e / g.M, m = e - js * g.M;
-    const size_t jm = (size_t)g.cls_states[s0 + js] * g.Mpad + m;
-    const double oc = g.acc[jm];
-    if (!(oc > 0.0 && oc < INFINITY)) return;
-    const double v = g.var[jm * g.Dd + i];
-    if (p == g.Dh + 1) {
-        b = (g.macc[jm * g.Dd + i] - STAT_BIAS * oc) / v;
-        return;
-    }
-    a = p == 0 ? 1.0 : g.mean[jm * g.Dd + p - 1];
-    b = (oc / v) * a;
-}
-
-// One workgroup per (chunk, feature dimension): the upper-triangular 16 x 16 tiles (tp <= tq) of the chunk's contribution to [G | k].
-// A wave takes every fourth k-step of 4 mixtures; lane l holds row / column l & 15 of mixture l >> 4 (the f32 16x16x4 operand map, one
-// double per lane); xi xi^T exists only in the accumulators.  C/D of the f64 form: col = l & 15, row = (l >> 4) + 4 reg.
-// partial: [chunk][i][tile][row * 16 + col]
-template <int NT>
-__global__ __launch_bounds__(256) void mllr_gk_mfma_kernel(GkArgs g, double *__restrict__ partial) {
-    constexpr int NTILES = NT * (NT + 1) / 2;
-    __shared__ double red[4][NTILES][256];
-    const int i = blockIdx.x % g.Dh, c = blockIdx.x / g.Dh;
-    const int r = g.chunk_cls[c], e0 = g.chunk_e0[c], n = g.chunk_n[c], s0 = g.cls_off[r];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, kk = lane >> 4, c16 = lane & 15;
-    d4 accv[NTILES];
-#pragma unroll
-    for (int t = 0; t < NTILES; ++t) accv[t] = d4{0.0, 0.0, 0.0, 0.0};
-    const int nsteps = (n + 3) / 4;
-    for (int s = wave; s < nsteps; s += 4) {                      // (uniform in the wave: every lane reaches every MFMA)
-        double a[NT], b[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) gk_operands(g, s0, e0, n, 4 * s + kk, i, 16 * t + c16, a[t], b[t]);
-        int idx = 0;
-#pragma unroll
-        for (int tp = 0; tp < NT; ++tp)
-#pragma unroll
-            for (int tq = tp; tq < NT; ++tq, ++idx) accv[idx] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tp], b[tq], accv[idx], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NTILES; ++t)
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) red[wave][t][reg * 64 + lane] = accv[t][reg];
-    __syncthreads();
-    double *out = partial + ((size_t)c * g.Dh + i) * (NTILES * 256);
-    for (int e = tid; e < NTILES * 256; e += 256) {
-        const int t = e >> 8, x = e & 255, reg = x >> 6, ln = x & 63;
-        const double sum = ((red[0][t][x] + red[1][t][x]) + red[2][t][x]) + red[3][t][x];      // wave order
-        out[t * 256 + ((ln >> 4) + 4 * reg) * 16 + (ln & 15)] = sum;
-    }
-}
-
-// The same partials on the float64 VALU (PCL_MLLR_VALU=1): 64 mixtures of operands staged in LDS, thread t owns element t of every tile.
-template <int NT>
-__global__ __launch_bounds__(256) void mllr_gk_valu_kernel(GkArgs g, double *__restrict__ partial) {
-    constexpr int NTILES = NT * (NT + 1) / 2, P = NT * 16;
-    __shared__ double xa[64][P], xb[64][P];
-    const int i = blockIdx.x % g.Dh, c = blockIdx.x / g.Dh;
-    const int r = g.chunk_cls[c], e0 = g.chunk_e0[c], n = g.chunk_n[c], s0 = g.cls_off[r];
-    const int tid = threadIdx.x, row = tid >> 4, col = tid & 15;
-    double sum[NTILES];
-#pragma unroll
-    for (int t = 0; t < NTILES; ++t) sum[t] = 0.0;
-    for (int k0 = 0; k0 < n; k0 += 64) {
-        __syncthreads();
-        for (int x = tid; x < 64 * P; x += 256) gk_operands(g, s0, e0, n, k0 + x / P, i, x % P, xa[x / P][x % P], xb[x / P][x % P]);
-        __syncthreads();
-        for (int k = 0; k < 64; ++k) {
-            int idx = 0;
-#pragma unroll
-            for (int tp = 0; tp < NT; ++tp)
-#pragma unroll
-                for (int tq = tp; tq < NT; ++tq, ++idx) sum[idx] += xa[k][16 * tp + row] * xb[k][16 * tq + col];
+    struct Chunk {
+        int s0, e0, n;
+    };
+    __device__ __forceinline__ Chunk chunk(int c) const { return Chunk{cls_off[chunk_cls[c]], chunk_e0[c], chunk_n[c]}; }
+    __device__ __forceinline__ void operands(const Chunk &ch, int le, int i, int p, double &a, double &b) const {
+        a = b = 0.0;
+        if (le >= ch.n || p > Dh + 1) return;
+        const int e = ch.e0 + le, js = e / M, m = e - js * M;
+        const size_t jm = (size_t)cls_states[ch.s0 + js] * Mpad + m;
+        const double oc = acc[jm];
+        if (!(oc > 0.0 && oc < INFINITY)) return;
+        const double v = var[jm * Dd + i];
+        if (p == Dh + 1) {
+            b = (macc[jm * Dd + i] - STAT_BIAS * oc) / v;
+            return;
         }
+        a = p == 0 ? 1.0 : mean[jm * Dd + p - 1];
+        b = (oc / v) * a;
     }
-    double *out = partial + ((size_t)c * g.Dh + i) * (NTILES * 256);
-#pragma unroll
-    for (int t = 0; t < NTILES; ++t) out[t * 256 + tid] = sum[t];
-}
+};
 
 // Per chunk: the occupancy and the number of its contributing mixtures (a fixed tree: the same bits every run)
 __global__ __launch_bounds__(256) void mllr_occ_kernel(GkArgs g, double *__restrict__ occ_part, int *__restrict__ cnt_part) {
@@ -173,71 +97,6 @@ __global__ void mllr_class_kernel(const int *__restrict__ cls_chunk0, const doub
     status[r] = o < min_occ ? PCL_MLLR_LOW_OCCUPANCY : k < Dh + 1 ? PCL_MLLR_FEW_MIXTURES : PCL_MLLR_OK;
 }
 
-__device__ __forceinline__ int tile_index(int tp, int tq, int NT) { return tp * NT - tp * (tp - 1) / 2 + (tq - tp); }
-
-// One workgroup per (class, dimension): the class's chunks summed in chunk order into the full symmetric [G | k], n x (n + 1), n = D + 1.
-// The lower triangle mirrors the upper one (a diagonal tile holds both, rounded differently: only its upper half is read).
-__global__ __launch_bounds__(256) void mllr_reduce_kernel(const double *__restrict__ partial, const int *__restrict__ cls_chunk0, int Dh, int NT,
-                                                          double *__restrict__ Gk) {
-    const int r = blockIdx.x / Dh, i = blockIdx.x % Dh, n = Dh + 1, ntiles = NT * (NT + 1) / 2;
-    const int c_lo = cls_chunk0[r], c_hi = cls_chunk0[r + 1];
-    for (int x = threadIdx.x; x < n * (n + 1); x += 256) {
-        const int p = x / (n + 1), q = x % (n + 1);
-        const int pp = q == n ? p : min(p, q), qq = q == n ? n : max(p, q);
-        const size_t at = (size_t)tile_index(pp >> 4, qq >> 4, NT) * 256 + (pp & 15) * 16 + (qq & 15);
-        double sum = 0.0;
-        for (int c = c_lo; c < c_hi; ++c) sum += partial[((size_t)c * Dh + i) * (ntiles * 256) + at];
-        Gk[(size_t)blockIdx.x * n * (n + 1) + x] = sum;
-    }
-}
-
-// One workgroup (one wave) per (class, dimension): G = L L^T in LDS, L y = k, L^T w = y; w is row i of W[r].  A pivot that is not finite
-// or not > 0 stops the factorisation and flags the class (mllr_finish_kernel refuses it as a whole).
-__global__ __launch_bounds__(64) void mllr_solve_kernel(const double *__restrict__ Gk, const int *__restrict__ status, int Dh, double *__restrict__ W,
-                                                        int *__restrict__ pivot_bad) {
-    __shared__ double A[ADAPT_D_MAX + 1][ADAPT_D_MAX + 3];
-    const int r = blockIdx.x / Dh, n = Dh + 1, tid = threadIdx.x;
-    if (status[r] != PCL_MLLR_OK) {
-        if (tid == 0) pivot_bad[blockIdx.x] = 0;
-        return;
-    }
-    for (int x = tid; x < n * (n + 1); x += 64) A[x / (n + 1)][x % (n + 1)] = Gk[(size_t)blockIdx.x * n * (n + 1) + x];
-    __syncthreads();
-    bool bad = false;
-    for (int j = 0; j < n; ++j) {
-        const double piv = A[j][j];
-        if (!(piv > 0.0 && piv < INFINITY)) {                     // (every thread reads the same value: uniform)
-            bad = true;
-            break;
-        }
-        const double d = sqrt(piv);
-        __syncthreads();
-        if (tid == j) A[j][j] = d;
-        if (tid > j && tid < n) A[tid][j] = A[tid][j] / d;
-        __syncthreads();
-        if (tid > j && tid < n)
-            for (int q = j + 1; q <= tid; ++q) A[tid][q] -= A[tid][j] * A[q][j];
-        __syncthreads();
-    }
-    if (tid == 0) pivot_bad[blockIdx.x] = bad ? 1 : 0;
-    if (bad) return;
-    for (int j = 0; j < n; ++j) {                                 // L y = k, column by column
-        const double y = A[j][n] / A[j][j];
-        __syncthreads();
-        if (tid == j) A[j][n] = y;
-        else if (tid > j && tid < n) A[tid][n] -= A[tid][j] * y;
-        __syncthreads();
-    }
-    for (int j = n - 1; j >= 0; --j) {                            // L^T w = y
-        const double w = A[j][n] / A[j][j];
-        __syncthreads();
-        if (tid == j) A[j][n] = w;
-        else if (tid < j) A[tid][n] -= A[j][tid] * w;
-        __syncthreads();
-    }
-    if (tid < n) W[(size_t)blockIdx.x * n + tid] = A[tid][n];
-}
-
 // Per class: a failed pivot in any of its D factorisations refuses it; a refused class gets the identity [0 | I]
 __global__ __launch_bounds__(64) void mllr_finish_kernel(const int *__restrict__ pivot_bad, int Dh, int *__restrict__ status, double *__restrict__ W) {
     __shared__ int st;
@@ -253,18 +112,6 @@ __global__ __launch_bounds__(64) void mllr_finish_kernel(const int *__restrict__
     __syncthreads();
     if (st == PCL_MLLR_OK) return;
     for (int x = tid; x < Dh * n; x += 64) W[(size_t)r * Dh * n + x] = (x % n == x / n + 1) ? 1.0 : 0.0;
-}
-
-// skip[r] = 1 when W[r] is exactly [0 | I]: the apply kernel leaves such a class's means alone, bit for bit
-__global__ __launch_bounds__(64) void mllr_identity_kernel(const double *__restrict__ W, int Dh, int *__restrict__ skip) {
-    __shared__ int same;
-    const int r = blockIdx.x, n = Dh + 1;
-    if (threadIdx.x == 0) same = 1;
-    __syncthreads();
-    for (int x = threadIdx.x; x < Dh * n; x += 64)
-        if (!(W[(size_t)r * Dh * n + x] == ((x % n == x / n + 1) ? 1.0 : 0.0))) same = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) skip[r] = same;
 }
 
 // mean[j, m, :] <- b_r + A_r mean[j, m, :], one workgroup per (32 mixtures, state): the tile's rows and W[r] are staged in LDS, so the
@@ -321,12 +168,6 @@ int check_classes(pcl_ctx *ctx, const char *who, int R, const int32_t *state_cla
             if (state_class[j] < -1 || state_class[j] >= R)
                 PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: state %d has class %d, outside [-1, %d)", who, j, (int)state_class[j], R);
     return PCL_OK;
-}
-
-template <int NT>
-void launch_gk(bool valu, int blocks, hipStream_t st, const GkArgs &g, double *partial) {
-    if (valu) hipLaunchKernelGGL(mllr_gk_valu_kernel<NT>, dim3(blocks), dim3(256), 0, st, g, partial);
-    else hipLaunchKernelGGL(mllr_gk_mfma_kernel<NT>, dim3(blocks), dim3(256), 0, st, g, partial);
 }
 
 }  // namespace
@@ -402,17 +243,14 @@ extern "C" int pcl_mllr_estimate(pcl_ctx *ctx, int R, const int32_t *state_class
     if (C > 0) {
         const bool valu = mllr_use_valu();
         const int blocks = C * Dh;
-        if (NT == 1) launch_gk<1>(valu, blocks, st, g, d_partial);
-        else if (NT == 2) launch_gk<2>(valu, blocks, st, g, d_partial);
-        else if (NT == 3) launch_gk<3>(valu, blocks, st, g, d_partial);
-        else launch_gk<4>(valu, blocks, st, g, d_partial);
+        launch_gk(valu, NT, blocks, st, g, d_partial);
         hipLaunchKernelGGL(mllr_occ_kernel, dim3(C), dim3(256), 0, st, g, d_occ_part, d_cnt);
     }
-    hipLaunchKernelGGL(mllr_reduce_kernel, dim3(R * Dh), dim3(256), 0, st, d_partial, d_chunk0, Dh, NT, d_Gk);
+    hipLaunchKernelGGL(gk_reduce_kernel, dim3(R * Dh), dim3(256), 0, st, d_partial, d_chunk0, Dh, NT, d_Gk, false);
     pcl_timer_end(ctx, "adapt_gk");
     pcl_timer_begin(ctx, "adapt_solve");
     hipLaunchKernelGGL(mllr_class_kernel, dim3((R + 63) / 64), dim3(64), 0, st, d_chunk0, d_occ_part, d_cnt, R, Dh, min_occ, d_occ, d_status);
-    hipLaunchKernelGGL(mllr_solve_kernel, dim3(R * Dh), dim3(64), 0, st, d_Gk, d_status, Dh, d_W, d_pivot);
+    hipLaunchKernelGGL(gk_solve_kernel, dim3(R * Dh), dim3(64), 0, st, d_Gk, d_status, Dh, d_W, d_pivot, (double *)nullptr);
     hipLaunchKernelGGL(mllr_finish_kernel, dim3(R), dim3(64), 0, st, d_pivot, Dh, d_status, d_W);
     pcl_timer_end(ctx, "adapt_solve");
     pcl_timer_end(ctx, "adapt");
@@ -454,7 +292,7 @@ extern "C" int pcl_model_transform_means(pcl_ctx *ctx, int R, const int32_t *sta
     }
     const double *dW = W ? d_W.p : ctx->mllr_W.p;
     pcl_timer_begin(ctx, "adapt");
-    hipLaunchKernelGGL(mllr_identity_kernel, dim3(R), dim3(64), 0, st, dW, Dh, d_skip);
+    hipLaunchKernelGGL(gk_identity_kernel, dim3(R), dim3(64), 0, st, dW, Dh, d_skip);
     for (int j0 = 0; j0 < J; j0 += 65535)                        // (the grid's y extent)
         hipLaunchKernelGGL(mllr_apply_kernel, dim3((M + APPLY_TM - 1) / APPLY_TM, std::min(J - j0, 65535)), dim3(256), 0, st,
                            ctx->mean64 + (size_t)j0 * ctx->Mpad * ctx->D, d_class + j0, dW, d_skip, M, ctx->Mpad, ctx->D, Dh);

@@ -411,6 +411,7 @@ void pcl_frames_adopt(pcl_ctx *ctx, DevBuf<float> &&f32, DevBuf<double> &&f64, i
     ctx->F = F;
     ctx->FD = device_dim(D);
     ctx->FDhost = D;
+    if (ctx->fmllr_Gk && D != ctx->Dhost) pcl_fmllr_release(ctx);
 }
 
 // The first half of pcl_model_upload (also bootstrap.hip: a model made on the device): the old model goes, the master copy and every derived
@@ -543,6 +544,7 @@ int pcl_frames_upload(pcl_ctx *ctx, int64_t F, int D, const void *frames, int dt
     ctx->F = F;
     ctx->FD = Dd;
     ctx->FDhost = D;
+    if (ctx->fmllr_Gk && D != ctx->Dhost) pcl_fmllr_release(ctx);   // fMLLR statistics describe frames of the model's dimension
     return PCL_OK;
 }
 
@@ -589,6 +591,7 @@ int pcl_frames_swap(pcl_ctx *ctx) {
     ctx->frames32 = ctx->frames_slot[ctx->frames_front];
     ctx->F = ctx->staged_F;
     ctx->FDhost = ctx->staged_D;
+    if (ctx->fmllr_Gk && ctx->FDhost != ctx->Dhost) pcl_fmllr_release(ctx);
     ctx->FD = device_dim(ctx->staged_D);
     ctx->staged_slot = -1;
     return PCL_OK;
@@ -1480,6 +1483,19 @@ int pcl_batch_accumulate(pcl_batch *b, int precision) {
     ctx->stats_fresh = false;
     if (rc == PCL_OK) HIPCHK(ctx, pcl_batch_mark(b));
     return rc;                                               // (accumulate writes nothing the recursion reads: mark_is_score stays)
+}
+
+// fMLLR statistics of the batch's utterances (frame_adapt.hip): what pcl_batch_accumulate needs of the batch, in float64
+int pcl_batch_accumulate_fmllr(pcl_batch *b, const int32_t *utt_speaker) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    TRY(batch_join(b));
+    TRY(accumulate_precheck(b, PCL_F64, "pcl_batch_accumulate_fmllr"));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TRY(pcl_ensure_layouts(ctx, PCL_LAYOUT_P64));
+    const int rc = pcl_launch_fmllr_accumulate(ctx, b, utt_speaker);
+    if (rc == PCL_OK) HIPCHK(ctx, pcl_batch_mark(b));
+    return rc;
 }
 
 int pcl_batch_accumulate_exchange(pcl_batch *b, int precision, double c_covariance, int payload, int update_transitions, int n_chunks) {

@@ -121,6 +121,9 @@ struct ModelDev {
     DevBuf<double> mean64;       // float64 master copy of the model: mean, var (J*Mpad*D), weight (J*Mpad)
     DevBuf<double> var64, w64;
     DevBuf<double> stats;        // E-step statistics (float64, linear domain), one allocation: [acc J*Mpad | alpha J | mean J*Mpad*D | cov J*Mpad*D]
+    DevBuf<double> fmllr_Gk;     // fMLLR statistics (frame_adapt.hip): [fmllr_S][Dhost][Dhost + 1][Dhost + 2], row p of a pair = (G[p][0 .. D], k[p]); gone with the model
+    DevBuf<double> fmllr_beta;   // [fmllr_S] occupancies
+    DevBuf<double> fmllr_W;      // the last pcl_fmllr_estimate's transforms [fmllr_S][Dhost][Dhost + 1]; pcl_fmllr_zero drops it
     DevBuf<double> mllr_W;       // the last pcl_mllr_estimate's transforms [mllr_R][Dhost][Dhost + 1] (model_adapt.hip): gone with the model they were estimated for
 };
 // Coarse layout of the off-pipe mixtures (gmm_score_coarse.hip): their bound v_up on the matrix pipe, exact evaluation of what it
@@ -157,6 +160,7 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     int J = 0, M = 0, Mpad = 0, D = 0, Dhost = 0, row = 0;  // D = device (padded) feature dimension
     int model_flags = 0;
     int mllr_R = 0;              // classes of mllr_W
+    int fmllr_S = 0;             // speakers of fmllr_Gk / fmllr_beta / fmllr_W
     int Mpad32 = 0;              // M rounded up to a multiple of 32
     int layouts_valid = 0;             // PCL_LAYOUT_* derived for the current model (the f64 rows are derived on first use)
     hipStream_t stream_dp = nullptr;   // forward-backward runs here, beside the next batch's scoring on `stream`
@@ -530,6 +534,8 @@ int pcl_launch_align_segments(pcl_ctx *ctx, pcl_batch *b, int Lmax, int gmm_num,
 int pcl_launch_ksai_gather(pcl_ctx *ctx, pcl_batch *b, double *dst);
 int pcl_launch_clock_probe(pcl_ctx *ctx, int spin_us, unsigned long long *d_out);
 int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision);
+int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_speaker);   // frame_adapt.hip, behind pcl_batch_accumulate_fmllr's checks
+void pcl_fmllr_release(pcl_ctx *ctx);                // the fMLLR statistics and estimate (a frame matrix of another dimension)
 void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate scratch (pcl_destroy, pcl_model_upload)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);

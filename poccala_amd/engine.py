@@ -497,6 +497,46 @@ class Engine(object):
         self._check(self._lib.pcl_mstep_map(self._ctx, float(tau)))
         self._model_key = None
 
+    # ------------------------------------------------------------------ fMLLR: per-speaker transforms of the resident frames
+    def fmllr_zero(self, n_speakers):
+        """Make (or clear) the context's fMLLR statistics for n_speakers speakers (pcl_fmllr_zero); a resident estimate is dropped."""
+        self._check(self._lib.pcl_fmllr_zero(self._ctx, int(n_speakers)))
+        self.fmllr_S = int(n_speakers)
+
+    def fmllr_stats(self):
+        """(G (S, D, D+1, D+1), k (S, D, D+1), beta (S,)): what Batch.accumulate_fmllr has summed since fmllr_zero."""
+        S, D = int(getattr(self, 'fmllr_S', 0)), self.D
+        n = max(S, 1)
+        G, k, beta = np.empty((n, D, D + 1, D + 1)), np.empty((n, D, D + 1)), np.empty(n)
+        self._check(self._lib.pcl_fmllr_stats_download(self._ctx, ptr(G), ptr(k), ptr(beta)))
+        return G[:S], k[:S], beta[:S]
+
+    def fmllr_estimate(self, n_iter=20, min_occ=1000.0):
+        """One transform W[s] = [b | A] per speaker from the resident statistics (pcl_fmllr_estimate; the rule: include/poccala_hip.h):
+        (W (S, D, D+1), logdet (S,) = ln|det A|, q_trace (S, n_iter) = the auxiliary value after every sweep, status (S,) int32: 0, or why
+        the speaker was refused and got [0 | I]: 1 occupancy below min_occ, 2 a G not positive definite, 3 a singular step).  The
+        transforms stay on the device for transform_frames()."""
+        S, D, K = max(int(getattr(self, 'fmllr_S', 0)), 1), self.D, max(int(n_iter), 1)
+        W, logdet, q, status = np.empty((S, D, D + 1)), np.empty(S), np.empty((S, K)), np.empty(S, dtype=np.int32)
+        self._check(self._lib.pcl_fmllr_estimate(self._ctx, int(n_iter), float(min_occ), ptr(W), ptr(logdet), ptr(q), ptr(status)))
+        return W, logdet, q, status
+
+    def transform_frames(self, T, frame_begin, utt_speaker, W=None, n_speakers=None):
+        """y = b + A x in place on the resident frame matrix (pcl_frames_transform) for the rows [frame_begin[u], + T[u]) of every
+        utterance whose utt_speaker[u] >= 0; W (S, D, D+1) or None = the transforms of the last fmllr_estimate.  Speakers whose W is
+        [0 | I] and rows outside the utterances keep their bits.  Batches scored before the call keep their old emissions."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        spk = as_c(utt_speaker, np.int32).reshape(-1)
+        if fb is None or spk.shape != T.shape:
+            raise ValueError('T, frame_begin and utt_speaker must be equal-length')
+        if W is not None:
+            W = as_c(W, np.float64)
+            if W.ndim != 3 or W.shape[1:] != (self.FD, self.FD + 1):
+                raise ValueError('W must be (n_speakers, D, D+1) with D = %d, got %s' % (self.FD, W.shape))
+        S = int(n_speakers) if n_speakers is not None else (W.shape[0] if W is not None else int(getattr(self, 'fmllr_S', 0)))
+        self._check(self._lib.pcl_frames_transform(self._ctx, T.size, ptr(T), ptr(fb), ptr(spk), S, ptr(W)))
+        self._frames_key = None                      # the resident frames are no longer what was uploaded
+
     def model_download(self):
         """(mean (J,M,D), var (J,M,D), weight (J,M)) float64 master copy."""
         mean = np.empty((self.J, self.M, self.D))
@@ -736,6 +776,15 @@ class Batch(object):
         self._check(self._lib.pcl_batch_accumulate_exchange(self._b, int(precision), float(c_covariance), int(payload),
                                                              1 if update_transitions else 0, int(n_chunks)))
         self.eng._model_key = None
+
+    def accumulate_fmllr(self, utt_speaker):
+        """fMLLR statistics of this batch's utterances into the engine's per-speaker sums (pcl_batch_accumulate_fmllr): utt_speaker (U,)
+        int32 in [0, S) of the last Engine.fmllr_zero(S), -1 = leave the utterance out.  Needs score() and forward_backward() (or
+        set_posteriors)."""
+        spk = as_c(utt_speaker, np.int32).reshape(-1)
+        if spk.shape != (self.U,):
+            raise ValueError('utt_speaker must hold one speaker per utterance (U = %d), got %s' % (self.U, spk.shape))
+        self._check(self._lib.pcl_batch_accumulate_fmllr(self._b, ptr(spk)))
 
     def accumulate_hmm(self):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
