@@ -478,7 +478,8 @@ int pcl_model_mixup(pcl_ctx *ctx, int M_new, double perturb, int32_t *origin_out
  * layouts, conditioning, split lists, so that every scoring path sees the model an upload of the downloaded arrays would give.
  *
  * pcl_mstep_map (Gauvain & Lee, means only): mean <- (tau mean + s) / (tau + acc) for every mixture with a finite acc > 0, the others keep
- * their mean; tau = 0 is pcl_mstep's ML mean.  Variances and weights are untouched.  The same derive pass follows.
+ * their mean; tau = 0 is pcl_mstep's ML mean.  Variances and weights are untouched.  The same derive pass follows.  There is no solve
+ * behind it and no limit on D beyond the model's own (D <= 64).
  *
  * The statistics block is treated as pcl_mstep treats it: read, neither cleared nor marked -- it describes the model BEFORE the call until
  * the caller's next pcl_stats_zero.  With more than one rank the caller runs pcl_stats_allreduce first: all three calls read the block as

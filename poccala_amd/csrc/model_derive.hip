@@ -537,11 +537,11 @@ int pcl_launch_mstep(pcl_ctx *ctx, double floor_var) {
     return r;
 }
 
-int pcl_launch_pack(pcl_ctx *ctx, const double *src, int inner, double *dst) {
-    // inner = D for (J,M,D) arrays, 1 for (J,M)
-    const long long n = (long long)ctx->J * ctx->M * (inner == 1 ? 1 : ctx->Dhost);
+int pcl_launch_pack(pcl_ctx *ctx, const double *src, bool per_dim, double *dst) {
+    // per_dim: a (J,M,D) array at the device's row stride; otherwise (J,M).  (Not told by the row length: D = 1 is a (J,M,D) array too.)
+    const long long n = (long long)ctx->J * ctx->M * (per_dim ? ctx->Dhost : 1);
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, src, ctx->J, ctx->M, ctx->Mpad,
-                       inner == 1 ? 1 : ctx->D, inner == 1 ? 1 : ctx->Dhost, dst);
+                       per_dim ? ctx->D : 1, per_dim ? ctx->Dhost : 1, dst);
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }

@@ -1578,7 +1578,7 @@ int pcl_model_download(pcl_ctx *ctx, double *mean, double *var, double *weight) 
     for (int k = 0; k < 3; ++k) {
         if (!dsts[k]) continue;
         const int inner = (k == 2) ? 1 : ctx->Dhost;
-        TRY(pcl_launch_pack(ctx, srcs[k], inner, tmp));
+        TRY(pcl_launch_pack(ctx, srcs[k], k != 2, tmp));
         HIPCHK(ctx, hipMemcpyAsync(dsts[k], tmp, (size_t)ctx->J * ctx->M * inner * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -607,7 +607,7 @@ int pcl_launch_trans_mstep(pcl_ctx *ctx);
 void pcl_units_release(pcl_ctx *ctx);
 void pcl_comm_release(pcl_ctx *ctx);
 void pcl_lexicon_release(pcl_ctx *ctx);
-int pcl_launch_pack(pcl_ctx *ctx, const double *src, int inner, double *dst);
+int pcl_launch_pack(pcl_ctx *ctx, const double *src, bool per_dim, double *dst);
 extern "C" {   // defined inside pcl_api.hip's extern "C" block; hidden like every symbol the public header does not declare
 int pcl_device_dim(int D);                                   // the padded feature dimension the kernels have an instance for (-1: D > 64)
 void pcl_frames_adopt(pcl_ctx *ctx, DevBuf<float> &&f32, DevBuf<double> &&f64, int64_t F, int D);   // device-built (F, pcl_device_dim(D)) matrices become the current frames

@@ -106,7 +106,8 @@ def map_means(mean, acc, mean_acc, tau):
 J, M = 7, 70
 CLASSES3 = np.array([-1, 0, 0, 0, 0, 1, 2], dtype=np.int32)     # state 0 left alone; class 1 = state 5 (few mixtures); class 2 = state 6 (low occupancy)
 MIN_OCC3 = 10.0
-ALIVE5 = 10                                                      # state 5 keeps 10 mixtures with a weight: fewer than D + 1 for every D the tests use (13 .. 48)
+ALIVE5 = 10                                                      # state 5 keeps 10 mixtures with a weight: fewer than D + 1 for every D >= 10 the tests use (12 .. 48);
+                                                                 # at D = 1 and 2 it is NOT short of mixtures, and the tests take the statuses from the twin
 
 
 def make_case(D, seed=0, frames_n=900):

@@ -27,7 +27,7 @@ def rel_rows(got, want):
     return float((np.abs(got - want).max(axis=-1) / np.abs(want).max(axis=-1)).max())
 
 
-@pytest.mark.parametrize('D', [13, 39])
+@pytest.mark.parametrize('D', [13, 39, 20, 31])
 def test_statistics_at_the_models_means_give_the_identity(D):
     rng, mean, var, acc = synthetic(1, M=4 * (D + 1), D=D)
     cls = np.array([0, 0, 1, 1, 1, -1])
@@ -38,7 +38,7 @@ def test_statistics_at_the_models_means_give_the_identity(D):
     np.testing.assert_allclose(out['occ'], [acc[:2].sum(), acc[2:5].sum()], rtol=1e-12)
 
 
-@pytest.mark.parametrize('D', [13, 39])
+@pytest.mark.parametrize('D', [13, 39, 20, 31])
 def test_a_known_transform_is_recovered(D):
     rng, mean, var, acc = synthetic(2, M=4 * (D + 1), D=D)
     acc[1, ::5] = 0.0                                                                 # dead mixtures, and junk behind them
@@ -100,20 +100,22 @@ def test_the_limits_of_map():
             tw.map_means(mean, acc, macc, bad)
 
 
-@pytest.mark.parametrize('D', [13, 26, 39, 48])
+@pytest.mark.parametrize('D', [13, 26, 39, 48, 1, 2, 12, 14, 15, 20, 30, 31, 40, 46, 47])
 def test_the_gpu_tests_inputs_are_well_conditioned(D):
     """cond(G[r, i]) < 1e4 for every accepted class of the models and batches tests/test_gpu_adapt.py runs on, from statistics formed here
-    in NumPy (the device's differ from them by its float64 rounding); at least 4 (D + 1) contributing mixtures per accepted class."""
+    in NumPy (the device's differ from them by its float64 rounding); at least 4 (D + 1) contributing mixtures per accepted class.
+    12 .. 47: the dimensions the device pads.  D = 1 and 2: state 5's ALIVE5 = 10 live mixtures are no longer fewer than D + 1, so class 1
+    is accepted too (and must then be as well conditioned)."""
     model, frames, gamma = tw.make_case(D)
     acc, macc = tw.numpy_stats(model, frames, gamma)
     assert (acc[2, ::3] == 0).all() and (acc[5, tw.ALIVE5:] == 0).all()
     for cls, R, min_occ in ((None, 1, 1.0), (tw.CLASSES3, 3, tw.MIN_OCC3)):
         out = tw.mllr_estimate(*model[:2], acc, macc, cls, R, min_occ)
         print('D = %d, R = %d: status %s, occ %s, cond <= %s' % (D, R, out['status'], out['occ'], np.nanmax(out['cond'], axis=1)))
-        assert out['status'].tolist() == ([tw.OK] if R == 1 else [tw.OK, tw.FEW_MIXTURES, tw.LOW_OCCUPANCY])
+        assert out['status'].tolist() == ([tw.OK] if R == 1 else [tw.OK, tw.FEW_MIXTURES if D + 1 > tw.ALIVE5 else tw.OK, tw.LOW_OCCUPANCY])
         members = np.ones(tw.J, bool) if cls is None else cls == 0
         assert tw.contributes(acc[members]).sum() >= 4 * (D + 1)
-        assert out['cond'][0].max() < COND_MAX
+        assert out['cond'][out['status'] == tw.OK].max() < COND_MAX
         for i in range(D):                                                            # the residual the GPU test asserts holds for the twin itself
             Gm, km, wv = out['G'][0, i], out['k'][0, i], out['W'][0, i]
             assert (np.abs(Gm @ wv - km) <= 1e-10 * (np.abs(Gm) @ np.abs(wv) + np.abs(km))).all()

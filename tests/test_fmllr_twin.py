@@ -130,11 +130,10 @@ def test_composition_is_application_in_turn():
     assert y64.tobytes() == frames.tobytes() and y32.dtype == np.float32
 
 
-@pytest.mark.parametrize('D', [13, 26, 39, 48])
-def test_the_gpu_inputs_are_well_conditioned(D):
-    """cond(G[s, i]) < 1e4 on the inputs of tests/test_gpu_fmllr.py, with every frame given to the state it was drawn along (the GPU test
-    asserts the same on the twin's statistics of the real posteriors)"""
-    model, labels, frames, T, begin, spk, W_true = tw.make_case(D)
+def hard_stats(D, frames=None):
+    """the twin's statistics of tests/test_gpu_fmllr.py's case with every frame given to the state it was drawn along"""
+    model, labels, fr, T, begin, spk, W_true = tw.make_case(D)
+    frames = fr if frames is None else frames
     rows, lg, lb = [], [], []
     for u, lab in enumerate(labels):
         L = len(lab)
@@ -145,11 +144,46 @@ def test_the_gpu_inputs_are_well_conditioned(D):
         x = frames[begin[u]:begin[u] + T[u]]
         b = np.stack([tw.mixture_posteriors(model, x, np.zeros(T[u]), np.zeros(T[u]), j).sum(axis=1) for j in lab])
         lb.append(np.log(b))
-    st = tw.frame_stats(model, frames, T, begin, rows, lg, lb, spk, tw.S_SPK)
+    return tw.frame_stats(model, frames, T, begin, rows, lg, lb, spk, tw.S_SPK)
+
+
+@pytest.mark.parametrize('D', [13, 26, 39, 48, 1, 2, 12, 14, 15, 20, 30, 31, 40, 46, 47])
+def test_the_gpu_inputs_are_well_conditioned(D):
+    """cond(G[s, i]) < 1e4 on the inputs of tests/test_gpu_fmllr.py, with every frame given to the state it was drawn along (the GPU test
+    asserts the same on the twin's statistics of the real posteriors); 12 .. 47 are the dimensions the device pads, 1 and 2 the smallest"""
+    st = hard_stats(D)
     assert abs(st['beta'][0] - 193.0) < 1e-9 and abs(st['beta'][1] - 129.0) < 1e-9 and st['beta'][2] < tw.MIN_OCC and st['beta'][3] == 0
     worst = max(np.linalg.cond(st['G'][s, i]) for s in (0, 1) for i in range(D))
     print('D = %d: cond(G) <= %.1f' % (D, worst))
     assert worst < 1e4
+    out = tw.estimate(st['G'], st['k'], st['beta'], 2, tw.MIN_OCC)
+    assert out['status'].tolist() == [tw.OK, tw.OK, tw.LOW_OCCUPANCY, tw.LOW_OCCUPANCY]
+
+
+@pytest.mark.parametrize('D', [13, 20])
+def test_a_speaker_of_zero_frames_is_refused_alone(D):
+    """the input of test_gpu_fmllr.py::test_a_speaker_refused_in_the_middle: speaker 1's frames exactly 0 -> zeta = (1, 0 .. 0), every
+    G[1, i] = diag(sum p, 0 .. 0) EXACTLY, the second pivot 0; the densities stay finite (the means are N(0, 1)), speaker 0's statistics
+    and transform keep their bits"""
+    model, labels, fr, T, begin, spk, W_true = tw.make_case(D)
+    z = fr.copy()
+    for u in np.flatnonzero(spk == 1):
+        z[begin[u]:begin[u] + T[u]] = 0.0
+    plain, st = hard_stats(D), hard_stats(D, z)
+    assert all(np.isfinite(st[key]).all() for key in ('G', 'k', 'beta'))
+    G1 = st['G'][1]
+    assert (G1[:, 0, 0] > 0).all() and not G1[:, 1:, :].any() and not G1[:, :, 1:].any() and not st['k'][1][:, 1:].any()
+    assert abs(st['beta'][1] - 129.0) < 1e-9                                # above MIN_OCC: the occupancy is not what refuses it
+    out, ref = tw.estimate(st['G'], st['k'], st['beta'], 3, tw.MIN_OCC), tw.estimate(plain['G'], plain['k'], plain['beta'], 3, tw.MIN_OCC)
+    assert out['status'].tolist() == [tw.OK, tw.NOT_POSITIVE_DEFINITE, tw.LOW_OCCUPANCY, tw.LOW_OCCUPANCY]
+    assert out['W'][1].tobytes() == tw.identity(D).tobytes() and out['logdet'][1] == 0 and np.isnan(out['q_trace'][1]).all()
+    assert st['G'][0].tobytes() == plain['G'][0].tobytes() and out['W'][0].tobytes() == ref['W'][0].tobytes()
+    assert out['q_trace'][0].tobytes() == ref['q_trace'][0].tobytes() and not np.array_equal(out['W'][0], tw.identity(D))
+    y = tw.apply(z, out['W'], T, begin, spk)[0]
+    own1 = np.zeros(len(z), bool)
+    for u in np.flatnonzero(spk == 1):
+        own1[begin[u]:begin[u] + T[u]] = True
+    assert own1.sum() == 129 and y[own1].tobytes() == z[own1].tobytes() and not y[own1].any()
 
 
 # ------------------------------------------------------------------ fmllr_batch's bookkeeping

@@ -14,7 +14,13 @@ bit-identical.  MAP against the twin: 1e-10 relative, bit equality behind it.  M
 relative plus 1e-10 absolute (both routes subtract the bias of 100 from a number of its size; that rounding is 1e-14).  Closed form and
 ln P(O): 1e-9, the PCL_F64 contract of DESIGN.md section 2.  Every figure is printed before it is asserted.
 
-The padded mixtures of the device layout (M = 70 is padded to 72) cannot be read through the C-ABI, whose downloads strip them."""
+The padded mixtures of the device layout (M = 70 is padded to 72) and its padded feature columns (the device keeps D at 13, 26, 39, 47, 48
+or 64) cannot be read through the C-ABI, whose downloads strip them.  They are held through their effect: the dimensions of PADDED_D run
+every kernel with a host dimension below the device stride, and test_the_padding_stays_zero compares ln b from the model a call left with
+ln b after an upload of the downloaded arrays, bit for bit -- a padded mean, variance or coefficient that a call made non-zero breaks it.
+D = 1 and 2 (SMALL_D) have 10 live mixtures in state 5 >= D + 1, so class 1 is no longer short of mixtures: there the statuses are the
+twin's, and at least one class must be accepted.  D > 48: the estimate and the transform are refused; pcl_mstep_map has no solve and no
+limit (include/poccala_hip.h), and is held to the twin at D = 50 and 64."""
 import numpy as np
 import pytest
 
@@ -57,6 +63,15 @@ def accumulate(eng, model, frames, gamma):
     return st
 
 
+# Host dimensions below the device stride, and what each reaches in the split-K GEMM (16-wide tiles over D + 2 columns, k the last one):
+# 12 -> 13 (one padded column, one tile), 14 -> 26 (k in column 15 of the only tile), 15 -> 26 (a second tile that holds only k),
+# 20 -> 26 (interior), 30 -> 39 (k in column 15 of the second tile), 31 -> 39 (a third tile of k alone), 40 -> 47 (7 padded columns),
+# 46 -> 47 (k in column 15 of the third tile), 47 -> 47 (a fourth tile of k alone)
+PADDED_D = [12, 14, 15, 20, 30, 31, 40, 46, 47]
+TILE_EDGE_D = [14, 15, 30, 31, 46, 47]
+APPLY_D = [12, 20, 40, 47]
+SMALL_D = [1, 2]             # n = 2 and 3; a 13-wide device row that is almost all padding
+
 _CASES = {}
 
 
@@ -89,6 +104,18 @@ def test_the_other_instances_of_the_gemm_kernels(eng, monkeypatch, D, what):
     estimate_and_apply(eng, monkeypatch, D, what)
 
 
+@pytest.mark.parametrize('D,what', [(D, 'R3') for D in PADDED_D] + [(D, 'R3-valu') for D in TILE_EDGE_D] + [(D, 'R1') for D in APPLY_D])
+def test_estimate_and_apply_below_the_device_stride(eng, monkeypatch, D, what):
+    """host dimension < device stride (PADDED_D): a stride used for a dimension or a slip at a tile edge of the GEMM shows here first"""
+    estimate_and_apply(eng, monkeypatch, D, what)
+
+
+@pytest.mark.parametrize('D', SMALL_D)
+@pytest.mark.parametrize('what', ['R1', 'R3', 'R3-valu'])
+def test_estimate_and_apply_at_the_smallest_dimensions(eng, monkeypatch, D, what):
+    estimate_and_apply(eng, monkeypatch, D, what)
+
+
 def estimate_and_apply(eng, monkeypatch, D, what):
     model, frames, gamma = case(D)
     R, cls, min_occ = (3, tw.CLASSES3, tw.MIN_OCC3) if what.startswith('R3') else (1, None, 1.0)
@@ -98,6 +125,7 @@ def estimate_and_apply(eng, monkeypatch, D, what):
         monkeypatch.setenv('PCL_MLLR_VALU', '1')
     st = accumulate(eng, model, frames, gamma)
     before = eng.model_download()
+    assert all(same_bits(a, b) for a, b in zip(before, model))                                    # the download is the upload, at every D
     assert (st['acc'][2, ::3] == 0).all() and (st['acc'][5, tw.ALIVE5:] == 0).all()              # dead mixtures: acc == 0 exactly
     W, occ, status = eng.mllr_estimate(cls, R, min_occ)
     W2, occ2, status2 = eng.mllr_estimate(cls, R, min_occ)
@@ -108,7 +136,9 @@ def estimate_and_apply(eng, monkeypatch, D, what):
     tag = 'adapt D=%d %s' % (D, what)
     print('%s: status %s (twin %s), occ %s, cond(G) <= %.1f' % (tag, status, t['status'], occ, np.nanmax(t['cond'][0])))
     assert status.dtype == np.int32 and status.tolist() == t['status'].tolist()
-    assert status.tolist() == ([0] if R == 1 else [tw.OK, tw.FEW_MIXTURES, tw.LOW_OCCUPANCY])
+    if D + 1 > tw.ALIVE5:
+        assert status.tolist() == ([0] if R == 1 else [tw.OK, tw.FEW_MIXTURES, tw.LOW_OCCUPANCY])
+    assert status[0] == tw.OK                                                                     # (SMALL_D: the twin's statuses, one class accepted at least)
     assert np.nanmax(t['cond'][0]) < 1e4
     hold(tag, 'occ vs twin', occ, t['occ'], RTOL)
     worst = 0.0
@@ -121,8 +151,8 @@ def estimate_and_apply(eng, monkeypatch, D, what):
     print('%s: W vs twin, worst element: relative %.3e at |w| = %.3e (row maximum %.3e)' % ((tag,) + worst_element(W, t['W'])))
     r = hold(tag, 'W vs twin', W, t['W'], RTOL)
     print('%s: max |dW| = %.3e' % (tag, r['max_abs']))
-    for k in range(1, R):
-        assert same_bits(W[k], tw.identity(D))                                                    # refused: the identity
+    for k in range(R):
+        assert same_bits(W[k], tw.identity(D)) == (status[k] != tw.OK)                            # refused: the identity
     eng.transform_means(None, cls, R)
     m1, v1, w1 = eng.model_download()
     assert same_bits(v1, before[1]) and same_bits(w1, before[2])                                  # variances and weights: untouched
@@ -131,7 +161,7 @@ def estimate_and_apply(eng, monkeypatch, D, what):
     r = hold(tag, 'transformed means vs twin', m1, tm, RTOL)
     print('%s: max |d mean| = %.3e' % (tag, r['max_abs']))
     assert same_bits(m1, tm)
-    moved = np.ones(tw.J, bool) if cls is None else cls == 0
+    moved = np.ones(tw.J, bool) if cls is None else np.isin(cls, np.flatnonzero(status == tw.OK))
     assert same_bits(m1[~moved], before[0][~moved])                                               # class -1 and refused classes keep their bits
     assert not same_bits(m1[moved], before[0][moved])
     eng.load_model(*before)                                                                       # (drops the resident estimate)
@@ -248,8 +278,47 @@ def test_lnb_after_the_call_equals_an_upload(eng, route, how):
         assert np.isfinite(B1[u][1:-1]).any() and same_bits(B1[u], B2[u])
 
 
+def split_model(D):
+    mean, var, w = [a.copy() for a in case(D)[0]]
+    mean[:, :3] += 3.0
+    var[:, :3] = 0.02                                                                             # three tight mixtures far from the centre: off the matrix pipe
+    return mean, var, w
+
+
+def known_transform(D, seed=3):
+    rng = np.random.default_rng(seed)
+    return np.concatenate([0.3 * rng.standard_normal((D, 1)), np.eye(D) * 0.9 + 0.05 * rng.standard_normal((D, D))], axis=1)[None]
+
+
+def lnb_all_rows(eng, precision):
+    return lnb(eng, np.array([eng.F], dtype=np.int32), np.array([0], dtype=np.int64), precision)[0]
+
+
+@pytest.mark.parametrize('how', ['mllr', 'map'])
+@pytest.mark.parametrize('D', [12, 40])
+def test_the_padding_stays_zero(eng, how, D):
+    """ln b over every row from the model the call left == ln b after an upload of the arrays it downloads, on the default, the split and
+    the PCL_F64 route: the upload zeroes every padded column, so a padded mean or coefficient the call wrote would move the bits"""
+    from poccala_amd import PCL_F32, PCL_F64
+    _, frames, gamma = case(D)
+    for route, model in (('default', case(D)[0]), ('split', split_model(D))):
+        accumulate(eng, model, frames, gamma)
+        before = eng.model_download()
+        if how == 'mllr':
+            eng.transform_means(known_transform(D))
+        else:
+            eng.mstep_map(5.0)
+        assert not same_bits(eng.model_download()[0], before[0])
+        if route == 'split':
+            assert eng.model_split_info()[0].min() > 0                                            # the states ARE on the split route
+        B1 = {P: lnb_all_rows(eng, P) for P in (PCL_F32, PCL_F64)}
+        eng.load_model(*eng.model_download())
+        for P in (PCL_F32, PCL_F64):
+            assert np.isfinite(B1[P][1:-1]).any() and same_bits(B1[P], lnb_all_rows(eng, P)), (route, P)
+
+
 # ------------------------------------------------------------------ MAP
-@pytest.mark.parametrize('D', [13, 39])
+@pytest.mark.parametrize('D', [13, 39] + SMALL_D + APPLY_D + [50, 64])
 def test_map_means_are_the_twins(eng, D):
     model, frames, gamma = case(D)
     st = accumulate(eng, model, frames, gamma)
@@ -311,6 +380,26 @@ def test_refused_calls_leave_the_model_as_it_was(eng):
     assert ei.value.code == -1
     for a, b in zip(eng.model_download(), other):
         assert same_bits(a, b)
+
+
+@pytest.mark.parametrize('D', [49, 64])
+def test_beyond_48_dimensions_the_estimate_and_the_transform_are_refused(eng, D):
+    """the solve's LDS matrix and the apply kernel's tile hold D <= 48: PCL_ERR_INVALID, the model as it was (its arrays, and ln b from it)"""
+    from poccala_amd import PCL_F64, PoccalaHipError
+    model, frames, gamma = case(D)
+    accumulate(eng, model, frames, gamma)
+    before, B = eng.model_download(), lnb_all_rows(eng, PCL_F64)
+    for call in (lambda: eng.mllr_estimate(None, 1, 1.0), lambda: eng.mllr_estimate(tw.CLASSES3, 3, tw.MIN_OCC3),
+                 lambda: eng.transform_means(known_transform(D)), lambda: eng.transform_means(None, None, 1)):
+        with pytest.raises(PoccalaHipError) as ei:
+            call()
+        print(D, ei.value)
+        assert ei.value.code == -1 and 'dimension %d' % D in str(ei.value)
+        for a, b in zip(eng.model_download(), before):
+            assert same_bits(a, b)
+        assert same_bits(lnb_all_rows(eng, PCL_F64), B)
+    eng.mstep_map(5.0)                                                                            # (MAP has no such limit: test_map_means_are_the_twins)
+    assert not same_bits(eng.model_download()[0], before[0])
 
 
 def test_the_calls_give_back_every_block_they_took(eng, monkeypatch):

@@ -12,7 +12,14 @@ the DEVICE's statistics: statuses exact; max |W_dev - W_longdouble| <= 8 e_ref, 
 Q(W_twin) - 1e-9 |Q|; q_trace non-decreasing; the last row's stationarity equation within 1e-10 of its terms; beta 1e-10 relative, logdet
 1e-10 against ln|det| of the device's own A.  Apply: the C-ABI has no frame download, so the transformed rows are compared through ln b,
 bit for bit, with ln b after load_frames of the twin's transformed array: the default and the split route read the float32 rows, PCL_F64
-the float64 copy; the all-rows batch covers the unowned rows.  Every figure is printed before it is asserted."""
+the float64 copy; the all-rows batch covers the unowned rows -- and, at the dimensions of PADDED_D (host dimension below the device's row stride), the padded
+frame columns: load_frames zeroes them, so a padded column the apply kernel wrote would move the bits.  Every figure is printed before it
+is asserted.
+
+Refusals.  LOW_OCCUPANCY: speakers 2 and 3 of every case.  NOT_POSITIVE_DEFINITE: test_a_speaker_refused_in_the_middle, from frames that
+are exactly zero.  PCL_FMLLR_SINGULAR cannot be reached through the C-ABI from finite frames -- there is no statistics upload, and for a
+positive definite G the step's a = p G^-1 p^T is > 0, its discriminant c^2 + 4 a beta too -- so it is held on the twin alone
+(tests/test_fmllr_twin.py, with beta = inf) and no injection hook is built for it."""
 import numpy as np
 import pytest
 
@@ -36,6 +43,13 @@ def eng():
 def same_bits(a, b):
     return np.asarray(a).tobytes() == np.asarray(b).tobytes()
 
+
+# Host dimensions below the device stride (tests/test_gpu_adapt.py lists what each reaches in the GEMM); 40, 46 and 47 run the
+# fmllr_frames_kernel<47, 2> instance, whose second half of 24 dimensions runs over the row's constant at D = 47
+PADDED_D = [12, 14, 15, 20, 30, 31, 40, 46, 47]
+TILE_EDGE_D = [14, 15, 30, 31, 46, 47]
+APPLY_D = [12, 20, 40, 47]
+SMALL_D = [1, 2]             # n = 2 and 3, a 1 x 1 inversion at D = 1, a 13-wide device row that is almost all padding
 
 _CASES = {}
 
@@ -66,9 +80,9 @@ def estep(eng, D, frames=None):
     return b, rows, b.get('lgamma'), b.get('B')
 
 
-def twin_stats(D, rows, lg, lb):
+def twin_stats(D, rows, lg, lb, frames=None):
     model, labels, fr, T, begin, spk, _ = case(D)
-    return tw.frame_stats(model, fr, T, begin, rows, lg, lb, spk, tw.S_SPK)
+    return tw.frame_stats(model, fr if frames is None else frames, T, begin, rows, lg, lb, spk, tw.S_SPK)
 
 
 def hold_stats(tag, got, t, scale=1.0):
@@ -90,7 +104,8 @@ def lnb(eng, precision):
 
 # ------------------------------------------------------------------ statistics and estimate against the twin
 @pytest.mark.parametrize('D,what', [(13, 'chunk'), (13, 'default-chunk'), (13, 'valu'), (39, 'chunk'), (39, 'default-chunk'), (39, 'valu'),
-                                    (26, 'chunk'), (26, 'valu'), (48, 'chunk'), (48, 'valu')])
+                                    (26, 'chunk'), (26, 'valu'), (48, 'chunk'), (48, 'valu')]
+                         + [(D, 'chunk') for D in PADDED_D + SMALL_D] + [(D, 'valu') for D in TILE_EDGE_D])
 def test_statistics_and_estimate_are_the_twins(eng, monkeypatch, D, what):
     if 'default' not in what:
         monkeypatch.setenv('PCL_MLLR_CHUNK', CHUNK)
@@ -128,7 +143,7 @@ def test_statistics_and_estimate_are_the_twins(eng, monkeypatch, D, what):
     assert status.dtype == np.int32 and status.tolist() == t64['status'].tolist() == [0, 0, tw.LOW_OCCUPANCY, tw.LOW_OCCUPANCY]
     e_ref = float(np.abs(t64['W'] - tld['W']).max())
     e_dev = float(np.abs(W - tld['W']).max())
-    print('%s: e_ref = max |W_f64 - W_longdouble| = %.3e, device max |W_dev - W_longdouble| = %.3e (ratio %.2f)' % (tag, e_ref, e_dev, e_dev / e_ref))
+    print('%s: e_ref = max |W_f64 - W_longdouble| = %.3e, device max |W_dev - W_longdouble| = %.3e (ratio %.2f)' % (tag, e_ref, e_dev, e_dev / e_ref if e_ref else np.inf))
     for s in (0, 1):
         qd, qt = tw.aux(W[s], G[s], k[s], beta[s]), tw.aux(t64['W'][s], G[s], k[s], beta[s])
         print('%s: speaker %d Q(W_dev) %.9f Q(W_twin) %.9f, device trace end %.9f, logdet %.12f' % (tag, s, qd, qt, q[s, -1], logdet[s]))
@@ -157,7 +172,7 @@ def split_model(D):
     return mean, var, w
 
 
-@pytest.mark.parametrize('D', [13, 39])
+@pytest.mark.parametrize('D', [13, 39] + APPLY_D + SMALL_D)
 def test_transformed_frames_score_as_the_twins(eng, D):
     from poccala_amd import PCL_F32, PCL_F64, PoccalaHipError
     model, labels, fr, T, begin, spk, _ = case(D)
@@ -199,6 +214,65 @@ def test_transformed_frames_score_as_the_twins(eng, D):
     got32 = lnb(eng, PCL_F32)
     eng.load_frames(tw.apply(np.asarray(fr, dtype=np.float32), W, T, begin, spk)[1])
     assert same_bits(got32, lnb(eng, PCL_F32))
+
+
+# ------------------------------------------------------------------ a speaker refused between two accepted ones
+def zeroed_frames(D):
+    """the case's frames with every frame of speaker 1 (utterances 1 and 5) exactly 0: zeta = (1, 0 .. 0), G[1, i] = diag(sum p, 0 .. 0)"""
+    model, labels, fr, T, begin, spk, _ = case(D)
+    z = fr.copy()
+    for u in np.flatnonzero(spk == 1):
+        z[begin[u]:begin[u] + T[u]] = 0.0
+    return z
+
+
+@pytest.mark.parametrize('D', [13, 20])
+def test_a_speaker_refused_in_the_middle(eng, monkeypatch, D):
+    """speaker 1's second Cholesky pivot is exactly 0: fmllr_pivot_kernel, the refused branch of gk_solve_kernel with a factor to write,
+    and the sweep kernel's refused outputs for a speaker between an accepted one and two refused for another reason"""
+    from poccala_amd import PCL_F64
+    monkeypatch.setenv('PCL_MLLR_CHUNK', CHUNK)
+    tag = 'fmllr D=%d zero frames' % D
+    model, labels, fr, T, begin, spk, _ = case(D)
+    zf = zeroed_frames(D)
+    run = {}
+    for name, frames in (('plain', fr), ('zeroed', zf)):
+        b, rows, lg, lb = estep(eng, D, frames)
+        assert all(np.isfinite(x[1:-1]).all() for x in lb)                                         # the posteriors stay finite
+        eng.fmllr_zero(tw.S_SPK)
+        b.accumulate_fmllr(spk)
+        b.close()
+        run[name] = eng.fmllr_stats() + eng.fmllr_estimate(N_ITER, tw.MIN_OCC)
+    G, k, beta, W, logdet, q, status = run['zeroed']
+    hold_stats(tag, (G, k, beta), twin_stats(D, rows, lg, lb, zf))
+    assert (G[1][:, 0, 0] > 0).all() and not G[1][:, 1:, :].any() and not G[1][:, :, 1:].any() and not k[1][:, 1:].any()
+    t64 = tw.estimate(G, k, beta, N_ITER, tw.MIN_OCC)
+    print('%s: status %s (twin %s), beta %s' % (tag, status, t64['status'], beta))
+    assert status.tolist() == t64['status'].tolist() == [tw.OK, tw.NOT_POSITIVE_DEFINITE, tw.LOW_OCCUPANCY, tw.LOW_OCCUPANCY]
+    assert same_bits(W[1], tw.identity(D)) and logdet[1] == 0 and np.isnan(q[1]).all()
+    for s in (2, 3):
+        assert same_bits(W[s], tw.identity(D)) and logdet[s] == 0 and np.isnan(q[s]).all()
+    tld = tw.estimate(G, k, beta, N_ITER, tw.MIN_OCC, dtype=np.longdouble)
+    e_ref, e_dev = float(np.abs(t64['W'] - tld['W']).max()), float(np.abs(W - tld['W']).max())
+    print('%s: e_ref = %.3e, device %.3e (ratio %.2f)' % (tag, e_ref, e_dev, e_dev / e_ref if e_ref else np.inf))
+    assert e_dev <= 8 * e_ref
+    # one speaker's refusal does not move another's result: speaker 0's utterances, chunks and statistics are those of the plain run
+    Gp, kp, betap, Wp, logdetp, qp, statusp = run['plain']
+    assert statusp.tolist() == [tw.OK, tw.OK, tw.LOW_OCCUPANCY, tw.LOW_OCCUPANCY]
+    assert same_bits(G[0], Gp[0]) and same_bits(k[0], kp[0]) and same_bits(beta[0], betap[0])
+    assert same_bits(W[0], Wp[0]) and same_bits(logdet[0], logdetp[0]) and same_bits(q[0], qp[0])
+    assert not same_bits(W[0], tw.identity(D))
+    own = {s: np.zeros(len(fr), bool) for s in (0, 1)}
+    for u in range(len(T)):
+        if spk[u] in own:
+            own[spk[u]][begin[u]:begin[u] + T[u]] = True
+    before = lnb(eng, PCL_F64)
+    eng.transform_frames(T, begin, spk)                                                            # the resident W
+    after = lnb(eng, PCL_F64)
+    assert same_bits(after[:, ~own[0]], before[:, ~own[0]]) and own[1].sum() == 129                # speaker 1's rows (and all others) keep their bits
+    assert not same_bits(after[:, own[0]], before[:, own[0]])
+    eng.load_frames(tw.apply(zf, W, T, begin, spk)[0])
+    assert same_bits(after, lnb(eng, PCL_F64))
 
 
 # ------------------------------------------------------------------ end to end
@@ -243,6 +317,27 @@ def test_fmllr_batch_raises_the_likelihood(eng):
 
 
 # ------------------------------------------------------------------ what is refused, and what the calls give back
+@pytest.mark.parametrize('D', [49, 64])
+def test_beyond_48_dimensions_the_calls_are_refused(eng, D):
+    """the estimate's LDS matrices and the apply kernel's tile hold D <= 48: PCL_ERR_INVALID, model and frames as they were"""
+    from poccala_amd import PCL_F64, PoccalaHipError
+    model, labels, fr, T, begin, spk, W_true = case(D)
+    eng.load_model(*model)
+    eng.load_frames(np.asarray(fr, dtype=np.float64))
+    before = lnb(eng, PCL_F64)
+    for call in (lambda: eng.fmllr_zero(tw.S_SPK), lambda: eng.transform_frames(T, begin, spk, W_true)):
+        with pytest.raises(PoccalaHipError) as ei:
+            call()
+        print(D, ei.value)
+        assert ei.value.code == -1 and 'dimension %d' % D in str(ei.value)
+        assert same_bits(lnb(eng, PCL_F64), before)
+        for a, b2 in zip(eng.model_download(), model):
+            assert same_bits(a, b2)
+    with pytest.raises(PoccalaHipError) as ei:
+        eng.fmllr_stats()                                                                           # the refused pcl_fmllr_zero made nothing
+    assert ei.value.code == -3
+
+
 def test_refusals_and_the_pool(eng):
     from poccala_amd import Engine, PoccalaHipError
     D = 13

@@ -5,7 +5,11 @@ Bounds.  origin, weights and variances: exact -- integers, halvings and copies. 
 (f7), 1e-10 relative, through tests/_parity.py:hold, which records the measured worst case; the device and the twin run the same rounded
 operations (no contraction, a correctly rounded sqrt), so bit equality is expected and asserted behind the bound.  ln b from the
 device-made model against ln b after an upload of the downloaded arrays: bit-identical on every route.  perturb = 0 leaves the mixture density as it was: ln b under PCL_F64 within that mode's contract, 1e-9
-(DESIGN.md section 2).  Every figure is printed before it is asserted."""
+(DESIGN.md section 2).  Every figure is printed before it is asserted.
+
+The device keeps the model at a padded feature stride (13, 26, 39, 47, 48 or 64).  WIDE_D runs the fill kernel with a host dimension below
+that stride (12, 20, 40, 50) and with an even stride (26, 48, 64; 50 -> 64), where none of its two-element stores straddles two mixtures
+-- 13, 39 and 47 are odd, there one does.  50 and 64 lie beyond what the adaptation calls take: mix-up has no such limit."""
 import numpy as np
 import pytest
 
@@ -17,6 +21,8 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-10                 # float64 restatements of the model
 F64_RTOL = 1e-9              # ln b under PCL_F64
 J = 4
+WIDE_D = [12, 20, 26, 40, 47, 48, 50, 64]
+SMALL_GROWTHS = [(3, 7), (8, 16), (2, 5)]      # 7 and 5 are no multiple of 4: a padded mixture follows the last real one, at an even stride too
 
 
 @pytest.fixture()
@@ -36,7 +42,17 @@ def same_bits(a, b):
 @pytest.mark.parametrize('case', range(len(CASES)))
 def test_the_grown_model_is_the_twins(eng, case, D):
     M, M_new, what = CASES[case]
-    mean, var, w = random_model(10 + case, J, M, D, what)
+    grown_model_is_the_twins(eng, 10 + case, M, M_new, D, what)
+
+
+@pytest.mark.parametrize('D', WIDE_D)
+@pytest.mark.parametrize('M,M_new', SMALL_GROWTHS)
+def test_the_grown_model_is_the_twins_at_every_device_stride(eng, M, M_new, D):
+    grown_model_is_the_twins(eng, 100 + M, M, M_new, D, 'stride')
+
+
+def grown_model_is_the_twins(eng, seed, M, M_new, D, what):
+    mean, var, w = random_model(seed, J, M, D, what)
     eng.load_model(mean, var, w)
     origin = eng.mixup(M_new, perturb=0.2, want_origin=True)
     assert (eng.J, eng.M, eng.D) == (J, M_new, D)
@@ -109,13 +125,22 @@ def lnb(eng, T, begin, precision):
 
 @pytest.mark.parametrize('route', ['default', 'split', 'f64'])
 def test_lnb_from_the_device_made_model_equals_an_upload(eng, route):
+    lnb_equals_an_upload(eng, route, 8, 16, 39, np.array([37, 20, 64], dtype=np.int32), np.array([0, 40, 61], dtype=np.int64))
+
+
+@pytest.mark.parametrize('D', [12, 40])
+@pytest.mark.parametrize('route', ['default', 'split', 'f64'])
+def test_the_padding_stays_zero(eng, route, D):
+    """the device rows are 13 and 47 wide, and an upload zeroes the padded columns: a padded mean, variance or coefficient the fill left
+    non-zero would move the bits of ln b; one utterance of every row of the frame matrix, 15 mixtures padded to 16"""
+    lnb_equals_an_upload(eng, route, 8, 15, D, np.array([130], dtype=np.int32), np.array([0], dtype=np.int64))
+
+
+def lnb_equals_an_upload(eng, route, M, M_new, D, T, begin):
     from poccala_amd import PCL_F32, PCL_F64
     P = PCL_F64 if route == 'f64' else PCL_F32
-    M, M_new, D = 8, 16, 39
     mean, var, w = scoring_model(50, M, D, route == 'split')
     rng = np.random.default_rng(51)
-    T = np.array([37, 20, 64], dtype=np.int32)
-    begin = np.array([0, 40, 61], dtype=np.int64)
     frames = (rng.standard_normal((130, D)) * 1.2).astype(np.float32)
     eng.load_frames(frames)
     eng.load_model(mean, var, w)
@@ -136,8 +161,17 @@ def test_lnb_from_the_device_made_model_equals_an_upload(eng, route):
 
 @pytest.mark.parametrize('M,M_new', [(3, 7), (8, 16)])
 def test_without_perturbation_the_density_stays(eng, M, M_new):
+    density_stays(eng, M, M_new, 13, 'mixup perturb 0, %d->%d' % (M, M_new))
+
+
+@pytest.mark.parametrize('D', WIDE_D)
+@pytest.mark.parametrize('M,M_new', [(3, 7), (8, 16)])
+def test_without_perturbation_the_density_stays_at_every_device_stride(eng, M, M_new, D):
+    density_stays(eng, M, M_new, D, 'mixup perturb 0, %d->%d D=%d' % (M, M_new, D))
+
+
+def density_stays(eng, M, M_new, D, tag):
     from poccala_amd import PCL_F64
-    D = 13
     mean, var, w = scoring_model(60, M, D, False)
     rng = np.random.default_rng(61)
     T, begin = np.array([50, 33], dtype=np.int32), np.array([0, 50], dtype=np.int64)
@@ -147,7 +181,7 @@ def test_without_perturbation_the_density_stays(eng, M, M_new):
     eng.mixup(M_new, perturb=0.0)
     after = lnb(eng, T, begin, PCL_F64)
     for u in range(len(T)):
-        hold('mixup perturb 0, %d->%d' % (M, M_new), 'ln b (PCL_F64) before vs after', after[u][1:-1], before[u][1:-1], F64_RTOL)
+        hold(tag, 'ln b (PCL_F64) before vs after', after[u][1:-1], before[u][1:-1], F64_RTOL)
 
 
 # ------------------------------------------------------------------ (f): EM from the grown model, on segments made before the call

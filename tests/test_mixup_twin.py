@@ -29,7 +29,7 @@ def random_model(seed, J, M, D, what=''):
     return mean, var, w
 
 
-@pytest.mark.parametrize('D', [13, 39])
+@pytest.mark.parametrize('D', [13, 39, 20, 48])
 @pytest.mark.parametrize('case', range(len(CASES)))
 def test_invariants_on_random_models(case, D):
     M, M_new, what = CASES[case]
