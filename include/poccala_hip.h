@@ -262,6 +262,29 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
  * word ended); n_tokens (U, Tmax): live tokens after every frame; overflow (U,): 1 if max_tokens was hit. */
 int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *score, int32_t *hist, int32_t *hist_n,
                          int32_t *hist_prev, int32_t *hist_node, int32_t *n_tokens, int32_t *overflow);
+/* Rule D6: a bigram language model at word ends.  The reference's decoder imports `LanguageModel.Ngram` (Decoder.py:17), builds
+ * `Ngram(n=i+1).init_gram()` (:200-204) and asks it for the followers of a finished word in `passing_between_word` (:146-156), a stub on a
+ * module it never shipped; without a language model a finished word hands its raw score to every first-character node (D4).  Here:
+ * words have ids 0 .. W-1, id 0 = the sentence start (no node spells it); a word-end node i has the homophones
+ * node_word_ids[node_word_ptr[i] .. node_word_ptr[i+1]) in the tree's order.  lm(v, w) = val[k] where col[k] == w in row
+ * [row_ptr[v], row_ptr[v+1]) of the CSR bigram (col strictly ascending in a row), else bow[v] + uni[w]: float64, finite, ARPA-shaped and
+ * PRE-SCALED by the caller (val = scale ln P(w|v) + penalty, uni = scale ln P(w) + penalty, bow = scale ln bow(v)) -- the device only
+ * adds.  A finished token at word-end node n with score s whose history entry chose word v (0 without one) offers the roots
+ * s + max_w lm(v, w) over the node's homophones, the first w on ties = its chosen word; its offer to the node's own children stays s.
+ * The frame's best offer (earliest donor on ties) seeds every root and makes the frame's one history entry (donor's entry, node, chosen
+ * word).  Everything else is pcl_batch_decode's; with all tables zero so is every output, bit for bit.  Final scores hold the terms of
+ * the words already ended, not of a word pending at the token's own node.  Single tree, no tree copies, no look-ahead.
+ * Needs pcl_lexicon_upload first; whatever drops the tree (a new pcl_lexicon_upload, a pcl_units_upload of another shape) drops the
+ * language model.  Rejected with PCL_ERR_INVALID and a pcl_last_error text: non-finite values, col unsorted or outside [0,W), ids in
+ * node_word_ids outside [1,W), a word-end node without a word, a node with words whose node_word is 0. */
+int pcl_lm_upload(pcl_ctx *ctx, int W, const double *uni, const double *bow, const int64_t *row_ptr, const int32_t *col, const double *val,
+                  const int32_t *node_word_ptr, const int32_t *node_word_ids);
+/* pcl_batch_decode with the resident language model (the kernels' LM = true instantiations); PCL_ERR_STATE if none is resident.
+ * Results through pcl_batch_decode_get, and the chosen word of every history entry, hist_word (U, Tmax), through
+ * pcl_batch_decode_get_words (PCL_ERR_STATE unless the batch's last decode was pcl_batch_decode_lm). */
+int pcl_batch_decode_lm(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit,
+                        double logpi_two_units);
+int pcl_batch_decode_get_words(pcl_batch *b, int32_t *hist_word);
 
 /* Copy a result to a caller buffer (layouts in pcl_get_what). */
 int pcl_batch_get(pcl_batch *b, int what, void *host);

@@ -9,6 +9,10 @@ source cannot run (D1-D5: exit test on the last emitting state, tokens keyed by 
 word ends re-seed the first characters with a uniform language model, "all step, then all hand over" frames) are listed in
 include/poccala_hip.h and in the tests' CPU restatement.  Parity: recursion, pruning, frame loop and in-word hand-over are pinned
 by golden G14 (the reference's own pieces, run with a stand-in for the missing import); D1-D5 are the builder's completion.
+
+With `lm=` (a LanguageModel.Ngram: the module the reference imports at Decoder.py:17, builds at :200-204 and queries in its stub
+passing_between_word, :146-156) rule D6 replaces the uniform language model of D4: where a word ends, the bigram score of the best
+homophone after the token's previous word is added to what the first characters receive, and that homophone is the word reported.
 """
 import os
 
@@ -30,6 +34,33 @@ def load_inventory(engine, unit_names, means, variances, weights, unit_trans, le
     return tree
 
 
+def load_language_model(engine, tree, lm, lm_scale=1.0, word_penalty=0.0):
+    """Compile `lm` (LanguageModel.Ngram) against the tree and upload it; returns the compiled tables."""
+    compiled = lm.compile(tree, lm_scale=lm_scale, word_penalty=word_penalty)
+    engine.load_language_model(compiled)
+    return compiled
+
+
+def _report_lm(res, tree, compiled):
+    """_report with a language model: every word ONE string -- the chosen homophone of each history entry, and for a word pending at
+    the final token's own node the host's choice by the same rule (max over the homophones of lm(previous word, w), first on ties)."""
+    from .LanguageModel.Ngram import best_word
+    out = []
+    for r in res:
+        words, score = [], -np.inf
+        if r['final']:
+            node, score, h = r['final'][0]
+            prev = r['history'][h][2] if h >= 0 else 0
+            while h >= 0:
+                h, _, w = r['history'][h]
+                words.append(compiled['words'][w])
+            words.reverse()
+            if tree['node_word'][node]:
+                words.append(compiled['words'][best_word(compiled, prev, node)[0]])
+        out.append((words, score, r))
+    return out
+
+
 def _report(res, tree):
     """Per utterance (words, score, detail): the word sequence behind the best final token, as transfer() reports it
     (Decoder.py:183-186) -- each entry the list of homophones of a word-end node."""
@@ -48,13 +79,17 @@ def _report(res, tree):
     return out
 
 
-def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096):
+def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096, lm=None, lm_scale=1.0,
+                 word_penalty=0.0):
     """data_list: MFCC matrices (T_u, D), which are uploaded -- or the (lens, begin) of frames already resident (Engine.frontend /
     load_audio_batch(fetch=False)), the form AcousticModel's batch helpers take: nothing is uploaded, PCM goes to words without a host
     round trip.  Scores every GMM state for every frame (the decoder has no label) and runs the token passing.  Returns per utterance
     (words, score, detail); on the resident route an utterance of length 0 (the detector kept no frame) is left out of the batch and
-    reported as ([], -inf, None)."""
+    reported as ([], -inf, None).  lm: a LanguageModel.Ngram -- compiled with lm_scale / word_penalty, uploaded, and applied at word
+    ends (D6); every word then comes back as one string instead of the node's list of homophones."""
     engine = engine or default_engine()
+    compiled = load_language_model(engine, tree, lm, lm_scale, word_penalty) if lm is not None else None
+    report = (lambda res: _report_lm(res, tree, compiled)) if lm is not None else (lambda res: _report(res, tree))
     if isinstance(data_list, tuple) and len(data_list) == 2 and np.ndim(data_list[0]) == 1:       # AcousticModel._resident's test
         lens, begin = np.asarray(data_list[0], dtype=np.int32), np.asarray(data_list[1], dtype=np.int64)
         keep = np.flatnonzero(lens > 0)
@@ -62,9 +97,9 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
         if len(keep):
             b = engine.all_state_batch(lens[keep], begin[keep])
             b.score(precision)
-            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens)
+            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None)
             b.close()
-            for u, r in zip(keep, _report(res, tree)):
+            for u, r in zip(keep, report(res)):
                 out[u] = r
         return out
     lens = np.array([len(d) for d in data_list], dtype=np.int32)
@@ -72,12 +107,13 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
     engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
     b = engine.all_state_batch(lens, begin)
     b.score(precision)
-    res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens)
+    res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None)
     b.close()
-    return _report(res, tree)
+    return report(res)
 
 
-def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096):
+def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096, lm=None, lm_scale=1.0,
+                  word_penalty=0.0):
     """The streaming form (BASELINE config 5: a corpus that is fed chunk by chunk).  `chunks` yields lists of (T_u, D)
     float32 MFCC matrices; for every chunk, in order, decode_batch's result list is yielded.  Three legs overlap:
       copy stream    frames of chunk k+1 travel into the frame slot that is not being scored (Engine.stage_frames)
@@ -89,6 +125,8 @@ def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, cand
     running on the second stream."""
     engine = engine or default_engine()
     bm = beam if beam_ is None else beam_
+    compiled = load_language_model(engine, tree, lm, lm_scale, word_penalty) if lm is not None else None   # (lm: as in decode_batch)
+    report = (lambda res: _report_lm(res, tree, compiled)) if lm is not None else (lambda res: _report(res, tree))
     # batches (three per chunk shape, the four most recent shapes) and the page-locked staging buffer live with the ENGINE: a
     # second stream of the same chunk shapes (or the same stream read in several calls) starts warm; Engine.close() frees them
     pool, pinned = engine._stream_pool, engine._stream_pinned
@@ -149,7 +187,7 @@ def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, cand
             layout = pack(nxt)                                     # host packing + H2D of chunk 1 beside the GPU work
         k = 0
         while b is not None:
-            b.decode_launch(bm, 8, candidate, max_tokens)          # decode(k): second stream, behind score(k)
+            b.decode_launch(bm, 8, candidate, max_tokens, lm is not None)   # decode(k): second stream, behind score(k)
             inflight.append(b)
             b = None
             if nxt is not None:
@@ -163,11 +201,11 @@ def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, cand
                     layout = pack(nxt)                             # chunk k+2 on its way (behind the last readers of its slot)
             if len(inflight) > 1 or b is None:
                 done = inflight.pop(0)
-                yield _report(done.decode_unpack(done.decode_fetch()), tree)   # waits for THAT decoder only
+                yield report(done.decode_unpack(done.decode_fetch()))   # waits for THAT decoder only
             k += 1
         while inflight:
             done = inflight.pop(0)
-            yield _report(done.decode_unpack(done.decode_fetch()), tree)
+            yield report(done.decode_unpack(done.decode_fetch()))
     finally:
         engine.score_occupancy(0)
         inflight[:] = []                                           # (an abandoned stream: the batches stay in the engine's pool)

@@ -160,8 +160,13 @@ __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, c
 #else
 #define PCL_DEC_WAVES_ATTR
 #endif
-template <bool TLDS, int KMAX>
-__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a) {
+// LM (compile time): rule D6, the bigram language model at word ends (pcl_batch_decode_lm; hmm_decode_common.h) -- a word-end donor's
+// offer to the roots is its score plus pcl_lm_word_term, the chosen word goes into the history beside the node.  LM = false is
+// pcl_batch_decode's kernel and does not read `lm`.  As for the left-to-right kernel, the LM = true instantiations are compiled in a
+// translation unit of their own (hmm_decode_lm.hip defines PCL_DEC_LM and includes this file), so the LM = false ones come out as they
+// did before there was a switch.
+template <bool TLDS, int KMAX, bool LM>
+__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a, DecLmArg<LM> lm) {
     extern __shared__ double dyn[];
     __shared__ int seg_l[SEG_LDS + 1];
     __shared__ unsigned int hist256[256];                          // pruning: the occupancy map, then the radix histogram
@@ -187,6 +192,10 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
     double *seg_score = a.seg_score + (size_t)u * (cap + 2);
     int *slot = a.slot + (size_t)u * a.n_nodes;
     int *hprev = a.hist_prev + (size_t)u * a.Tmax, *hnode = a.hist_node + (size_t)u * a.Tmax;
+    // LM: the chosen word of every history entry (thread 0 writes it in the donor phase; donors of later frames read it, behind the
+    // barriers in between).  The waves' winning words borrow red_u[1]'s slots: the pruning phase's, idle in the donor phase.
+    [[maybe_unused]] int *hword = nullptr, *w_word = (int *)red_u[1];
+    if constexpr (LM) hword = lm.hist_word + (size_t)u * a.Tmax;
     const int tk8 = tid >> 3, sub = tid & 7;                       // token group of 8 lanes
 
     LaneCtx c;
@@ -255,6 +264,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         // ---- (2) donors = finished tokens.  The best finished word-end token (earliest on ties) re-seeds the first
         //      characters (D4); first_w = the first finished word-end token: the roots are created right after its children
         int nd_cnt = 0, ch_cnt = 0, bw_i = NONE, fw = NONE;
+        [[maybe_unused]] int bw_word = 0;
         double bw = -INFINITY;
         for (int k = 0; k < C; k += 64) {
             const int i = w0 + k + lane;
@@ -264,17 +274,21 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                 ch_cnt += a.child_ptr[node + 1] - a.child_ptr[node];
                 if (a.node_word[node]) {
                     fw = min(fw, i);
-                    const double s = sc[i];
+                    double s = sc[i];
+                    [[maybe_unused]] int wsel = 0;
+                    if constexpr (LM) s += pcl_lm_word_term(lm, hword, hs[i], node, wsel);   // D6: the offer to the roots
                     if (bw_i == NONE || s > bw) {                  // (a thread's tokens come in ascending order)
                         bw = s;
                         bw_i = i;
+                        if constexpr (LM) bw_word = wsel;
                     }
                 }
             }
         }
         nd_cnt = pcl_wave_sum(nd_cnt);
         ch_cnt = pcl_wave_sum(ch_cnt);
-        pcl_wave_best(bw, bw_i);
+        if constexpr (LM) pcl_wave_best(bw, bw_i, bw_word);
+        else pcl_wave_best(bw, bw_i);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) fw = min(fw, __shfl_xor(fw, o, 64));
         if (lane == 0) {
@@ -283,6 +297,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
             red_d[wave] = bw;
             red_i[0][wave] = bw_i;
             red_i[1][wave] = fw;
+            if constexpr (LM) w_word[wave] = bw_word;
         }
         __syncthreads();
         if (tid == 0) {
@@ -298,6 +313,10 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                 if (nh < a.Tmax) {
                     hprev[nh] = hs[bi];
                     hnode[nh] = nd[bi];
+                    if constexpr (LM) {
+                        for (int w = 0; w < NWV; ++w)
+                            if (red_i[0][w] == bi) hword[nh] = w_word[w];   // (the wave the winner came from: token indices are unique)
+                    }
                 }
                 s_i[2] = nh;
             }
@@ -495,6 +514,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
     STAMP_END(a.stamps)
 }
 
+#ifndef PCL_DEC_LM
 // ---- host side of pcl_batch_decode
 
 // The decoder's workspace, described ONCE: the element counts of the batch's allocations and the offset of every array in them.
@@ -639,15 +659,23 @@ DecArgs dec_fill_args(const pcl_batch *b, const DecLayout &l, double beam, int m
     return a;
 }
 
-int dec_launch_general(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows) {
+int dec_launch_general(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm) {
+    if (lm) return pcl_decode_general_launch_lm(ctx, a, U, n_rows, *lm);     // (hmm_decode_lm.hip)
+    constexpr bool LM = false;
+    const DecNoLm lma;
+#else
+}  // namespace
+int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
+    constexpr bool LM = true;
+#endif
     // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
     const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)n_rows) * sizeof(double);
     const bool tlds = table_bytes <= 44u * 1024u;
     const int cap = a.cap;
-#define PCL_DEC_LAUNCH(K)                                                                                                  \
-    do {                                                                                                                   \
-        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K>), dim3(U), dim3(DW), table_bytes, ctx->stream, a);       \
-        else hipLaunchKernelGGL((hmm_decode_kernel<false, K>), dim3(U), dim3(DW), 0, ctx->stream, a);                      \
+#define PCL_DEC_LAUNCH(K)                                                                                                      \
+    do {                                                                                                                       \
+        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K, LM>), dim3(U), dim3(DW), table_bytes, ctx->stream, a, lma);  \
+        else hipLaunchKernelGGL((hmm_decode_kernel<false, K, LM>), dim3(U), dim3(DW), 0, ctx->stream, a, lma);                 \
     } while (0)
     if (cap <= DW) PCL_DEC_LAUNCH(1);
     else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
@@ -658,6 +686,8 @@ int dec_launch_general(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows) {
     static_assert(PCL_DEC_MAX_KEYS_PER_LANE == 16, "the largest KMAX instantiated above");
     return PCL_OK;
 }
+
+#ifndef PCL_DEC_LM
 
 #ifdef PCL_DEC_STAMPS
 int dec_print_stamps(pcl_ctx *ctx, DevBuf<long long> &d_stamps) {
@@ -673,8 +703,10 @@ int dec_print_stamps(pcl_ctx *ctx, DevBuf<long long> &d_stamps) {
 }  // namespace
 
 void pcl_lexicon_release(pcl_ctx *ctx) {
-    static_cast<LexiconDev &>(*ctx) = {};
+    static_cast<LexiconDev &>(*ctx) = {};                // (the language model's tables with it)
     ctx->lex_nodes = ctx->lex_nroots = 0;
+    ctx->lex_word_host.clear();
+    ctx->lm_W = 0;
 }
 
 extern "C" {
@@ -735,13 +767,71 @@ int pcl_lexicon_upload(pcl_ctx *ctx, int n_nodes, const int32_t *node_units, con
     HIPCHK(ctx, hipMemcpy(ctx->d_unit_logtrans, ctx->unit_logtrans.data(), ctx->unit_logtrans.size() * 8, hipMemcpyHostToDevice));
     ctx->lex_nodes = n_nodes;
     ctx->lex_nroots = n_roots;
+    ctx->lex_word_host.assign(node_word, node_word + n_nodes);
     return PCL_OK;
 }
 
-int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units) {
+int pcl_lm_upload(pcl_ctx *ctx, int W, const double *uni, const double *bow, const int64_t *row_ptr, const int32_t *col, const double *val,
+                  const int32_t *node_word_ptr, const int32_t *node_word_ids) {
+    if (!ctx) return PCL_ERR_INVALID;
+    if (!ctx->lex_nodes) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_lm_upload: pcl_lexicon_upload first");
+    if (W < 2 || !uni || !bow || !row_ptr || !node_word_ptr) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: bad arguments (W=%d)", W);
+    const int n_nodes = ctx->lex_nodes;
+    if (row_ptr[0] != 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: row_ptr[0] = %lld, must be 0", (long long)row_ptr[0]);
+    for (int v = 0; v < W; ++v) {
+        if (!std::isfinite(uni[v]) || !std::isfinite(bow[v])) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: uni / bow of word %d is not finite", v);
+        if (row_ptr[v + 1] < row_ptr[v]) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: row_ptr is not monotone at word %d", v);
+    }
+    const int64_t nnz = row_ptr[W];
+    if (nnz > 0 && (!col || !val)) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: col / val is NULL");
+    for (int v = 0; v < W; ++v)
+        for (int64_t k = row_ptr[v]; k < row_ptr[v + 1]; ++k) {
+            if (col[k] < 0 || col[k] >= W) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: successor %d of word %d outside [0,%d)", col[k], v, W);
+            if (k > row_ptr[v] && col[k] <= col[k - 1]) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: the successors of word %d are not strictly ascending", v);
+            if (!std::isfinite(val[k])) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: bigram (%d, %d) is not finite", v, col[k]);
+        }
+    if (node_word_ptr[0] != 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: node_word_ptr[0] = %d, must be 0", node_word_ptr[0]);
+    for (int i = 0; i < n_nodes; ++i) {
+        const int cnt = node_word_ptr[i + 1] - node_word_ptr[i];
+        if (cnt < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: node_word_ptr is not monotone at node %d", i);
+        if (ctx->lex_word_host[i] && cnt == 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: words end at node %d and it has no word", i);
+        if (!ctx->lex_word_host[i] && cnt != 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: node %d has %d words and no word ends there (node_word is 0)", i, cnt);
+    }
+    const int n_ids = node_word_ptr[n_nodes];
+    if (n_ids > 0 && !node_word_ids) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: node_word_ids is NULL");
+    for (int k = 0; k < n_ids; ++k)
+        if (node_word_ids[k] < 1 || node_word_ids[k] >= W) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_lm_upload: word id %d outside [1,%d) (0 is the sentence start)", node_word_ids[k], W);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));             // (a decoder may still be reading the old tables on the second stream)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->lm_W = 0;
+    TRY(ctx->lm_uni.alloc(ctx, (size_t)W));
+    TRY(ctx->lm_bow.alloc(ctx, (size_t)W));
+    TRY(ctx->lm_row_ptr.alloc(ctx, (size_t)W + 1));
+    TRY(ctx->lm_col.alloc(ctx, (size_t)std::max<int64_t>(nnz, 1)));
+    TRY(ctx->lm_val.alloc(ctx, (size_t)std::max<int64_t>(nnz, 1)));
+    TRY(ctx->lm_node_word_ptr.alloc(ctx, (size_t)n_nodes + 1));
+    TRY(ctx->lm_node_word_ids.alloc(ctx, (size_t)std::max(n_ids, 1)));
+    static_assert(sizeof(long long) == sizeof(int64_t), "row_ptr travels as it is");
+    HIPCHK(ctx, hipMemcpy(ctx->lm_uni, uni, (size_t)W * 8, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->lm_bow, bow, (size_t)W * 8, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(ctx->lm_row_ptr, row_ptr, ((size_t)W + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz) {
+        HIPCHK(ctx, hipMemcpy(ctx->lm_col, col, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(ctx->lm_val, val, (size_t)nnz * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(ctx, hipMemcpy(ctx->lm_node_word_ptr, node_word_ptr, ((size_t)n_nodes + 1) * 4, hipMemcpyHostToDevice));
+    if (n_ids) HIPCHK(ctx, hipMemcpy(ctx->lm_node_word_ids, node_word_ids, (size_t)n_ids * 4, hipMemcpyHostToDevice));
+    ctx->lm_W = W;
+    return PCL_OK;
+}
+
+// pcl_batch_decode (with_lm = false: the LM = false kernels, nothing of the language model is touched) and pcl_batch_decode_lm
+static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, bool with_lm) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
     TRY(dec_validate(b, beam, min_distinct, candidate, max_tokens));
+    if (with_lm && !ctx->lm_W) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_lm: no language model (pcl_lm_upload after pcl_lexicon_upload)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (b->dp_pending) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_dp, 0));
@@ -758,6 +848,13 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
         const DecLayout l = dec_layout(U, cap, candidate, b->Tmax, use_lr);
         TRY(dec_ensure_workspace(b, l, cap, candidate));
         DecArgs a = dec_fill_args(b, l, beam, min_distinct, candidate, cap, logpi_one_unit, logpi_two_units);
+        DecLm lm = {};
+        if (with_lm) {
+            const size_t n_word = (size_t)U * b->Tmax;
+            if (!b->dec_word || b->dec_word.cap < n_word) TRY(b->dec_word.alloc(ctx, n_word));
+            HIPCHK(ctx, hipMemsetAsync(b->dec_word, 0, n_word * sizeof(int), ctx->stream));
+            lm = DecLm{ctx->lm_uni, ctx->lm_bow, ctx->lm_row_ptr, ctx->lm_col, ctx->lm_val, ctx->lm_node_word_ptr, ctx->lm_node_word_ids, b->dec_word};
+        }
 #ifdef PCL_DEC_STAMPS
         DevBuf<long long> d_stamps;
         TRY(d_stamps.alloc(ctx, (size_t)PCL_DEC_N_STAMP));
@@ -765,7 +862,7 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
         a.stamps = d_stamps;
 #endif
         pcl_timer_begin(ctx, "decode");
-        const int rc = use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows) : dec_launch_general(ctx, a, U, n_rows);
+        const int rc = use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows, with_lm ? &lm : nullptr) : dec_launch_general(ctx, a, U, n_rows, with_lm ? &lm : nullptr);
         pcl_timer_end(ctx, "decode");
         TRY(rc);
         HIPCHK(ctx, hipGetLastError());
@@ -781,6 +878,28 @@ int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate,
         HIPCHK(ctx, pcl_batch_mark(b));
     }
     b->have_dec = true;
+    b->dec_has_words = with_lm;
+    return PCL_OK;
+}
+
+int pcl_batch_decode(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units) {
+    return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, false);
+}
+
+int pcl_batch_decode_lm(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units) {
+    return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, true);
+}
+
+// the chosen words of the history entries, on the stream the decoder ran on (before or after pcl_batch_decode_get)
+int pcl_batch_decode_get_words(pcl_batch *b, int32_t *hist_word) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    if (!b->have_dec || !b->dec_has_words) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_get_words: run pcl_batch_decode_lm first");
+    if (!hist_word) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode_get_words: hist_word is NULL");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = b->dp_pending ? ctx->stream_dp : ctx->stream;
+    HIPCHK(ctx, hipMemcpyAsync(hist_word, b->dec_word, (size_t)b->U * b->Tmax * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
     return PCL_OK;
 }
 
@@ -815,3 +934,4 @@ int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *
 }
 
 }  // extern "C"
+#endif  // PCL_DEC_LM

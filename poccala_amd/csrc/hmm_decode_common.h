@@ -8,6 +8,8 @@
 // scratch is the caller's and comes in as pointers ([NT / 64] per-wave slots unless said otherwise), so each kernel keeps its
 // own LDS plan; a helper says which barrier protects its slots.
 #pragma once
+#include <type_traits>
+
 #include "pcl_internal.h"
 
 // Token state is kept as separate arrays (coalesced passes), two buffers of each.  upair = the node's units, u0 | u1 << 16
@@ -32,6 +34,21 @@ struct DecArgs {
     double *out_score;
     long long *stamps;              // PCL_DEC_STAMPS: clock ticks per phase, utterance 0
 };
+
+// The resident bigram language model (pcl_lm_upload) and the batch's chosen words, for the LM = true instantiations of the two kernels
+// (pcl_batch_decode_lm).  A kernel argument of its own, so DecArgs and with it the LM = false kernels stay what they were.
+// Tables are pre-scaled float64, ARPA-shaped: the kernels only add.
+struct DecLm {
+    const double *uni, *bow;        // [W]: scale ln P(w) + penalty, scale ln bow(v)
+    const long long *row_ptr;       // [W + 1] CSR over predecessors ...
+    const int *col;                 // ... successors, strictly ascending inside a row
+    const double *val;              // ... scale ln P(w|v) + penalty
+    const int *node_word_ptr, *node_word_ids;   // [n_nodes + 1], ids of a word-end node's homophones (1 .. W-1) in the tree's order
+    int *hist_word;                 // [U][Tmax]: the chosen word of every history entry, beside hist_prev / hist_node
+};
+struct DecNoLm {};                  // what the LM = false kernels take in its place: nothing
+template <bool LM>
+using DecLmArg = std::conditional_t<LM, DecLm, DecNoLm>;
 
 constexpr int PCL_DEC_N_STAMP = 8;
 // A lane keeps the sort keys of the old tokens it owns in registers through the pruning phase, at most this many: a kernel of NT
@@ -78,6 +95,37 @@ __device__ __forceinline__ int pcl_wave_scan(int v, int lane) {          // incl
         if (lane >= o) inc += x;
     }
     return inc;
+}
+
+// Rule D6, the language model at a word end (the reference's stub: passing_between_word, Decoder.py:146-156, on the n-gram model it
+// imports at :17 and builds at :200-204).  A finished token at word-end node `node` whose history entry is `hist` offers the roots its
+// score plus the value returned here: max over the node's homophones w of lm(v, w), where v = the chosen word of the token's history
+// entry (0, the sentence start, without one) and lm(v, w) = the explicit bigram val[k] (col[k] == w in row v, binary search), else
+// bow[v] + uni[w].  `word` = the first w that reaches the maximum.  hword = the utterance's row of DecLm::hist_word: entry `hist` was
+// written by one thread in an earlier frame, behind that frame's barriers.  Additions only (no product: nothing to contract), so the
+// host restatement gets the same bits; compiles for the host as well.
+__host__ __device__ __forceinline__ double pcl_lm_word_term(const DecLm &lm, const int *hword, int hist, int node, int &word) {
+    const int v = hist < 0 ? 0 : hword[hist];
+    const long long r0 = lm.row_ptr[v], r1 = lm.row_ptr[v + 1];
+    const double bv = lm.bow[v];
+    const int k0 = lm.node_word_ptr[node], k1 = lm.node_word_ptr[node + 1];
+    double best = 0.0;
+    word = 0;
+    for (int k = k0; k < k1; ++k) {
+        const int w = lm.node_word_ids[k];
+        long long lo = r0, hi = r1;                                // the first entry of the row with col >= w
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (lm.col[mid] < w) lo = mid + 1;
+            else hi = mid;
+        }
+        const double x = (lo < r1 && lm.col[lo] == w) ? lm.val[lo] : bv + lm.uni[w];
+        if (k == k0 || x > best) {                                 // strictly greater: the first homophone on ties
+            best = x;
+            word = w;
+        }
+    }
+    return best;
 }
 
 // (ob, oi) replaces (b, bi) as the best (score, index): greater, or equal and earlier; NONE = nothing yet
@@ -407,4 +455,6 @@ __device__ __forceinline__ int pcl_transfer(int n, int candidate, const double *
 // hmm_decode_lr.hip: true when every unit matrix is left-to-right (row 0 reaches state 1 only, an emitting state itself and
 // its successor only) and S = 5 -- then the fast kernel gives the general kernel's bits and pcl_decode_lr_launch runs it.
 bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max);
-int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows);
+int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm = nullptr);   // lm: the LM = true instantiation ...
+int pcl_decode_lr_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lm);           // ... which hmm_decode_lr_lm.hip holds
+int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lm);      // the general kernel's, hmm_decode_lm.hip

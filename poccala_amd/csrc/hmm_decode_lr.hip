@@ -112,8 +112,14 @@ __device__ __forceinline__ void lr_step(const double *tab, const double *Bs, int
 #else
 #define PCL_DECLR_WAVES_ATTR
 #endif
-template <int KMAX>
-__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP) {
+// LM (compile time): rule D6, the bigram language model at word ends (pcl_batch_decode_lm) -- a word-end donor's offer to the roots
+// is its score plus pcl_lm_word_term, and the chosen word travels with the winner into the history.  LM = false is pcl_batch_decode's
+// kernel: `lm` is not read and nothing of the switch is left in it.  The two sets of instantiations are compiled in SEPARATE translation
+// units -- this file for LM = false; hmm_decode_lr_lm.hip defines PCL_DECLR_LM and includes this file for LM = true: with both in one
+// module the compiler schedules and allocates the LM = false kernels differently (same source, 4 more spilled registers at KMAX = 16,
+// 40.8 -> 43.5 ms per C5 shard), alone they come out instruction for instruction as before there was a switch.
+template <int KMAX, bool LM>
+__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP, DecLmArg<LM> lm) {
     extern __shared__ double dyn[];                                // unit table [n_units][TS] | two emission rows [NbP]
     // one pool, two tenants: the donor lists (phases A - C) and the pruning select's histogram + candidates (phase E)
     __shared__ __attribute__((aligned(16))) unsigned char pool[POOL_BYTES];
@@ -153,6 +159,10 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
     double *seg_score = a.seg_score + (size_t)u * (cap + 2);
     int *__restrict__ slot = a.slot + (size_t)u * a.n_nodes;
     int *hprev = a.hist_prev + (size_t)u * a.Tmax, *hnode = a.hist_node + (size_t)u * a.Tmax;
+    // LM: the chosen word of every history entry.  Written by thread 0 in phase C, read by the donors' lanes in phase A2 of later frames:
+    // the barriers that end a frame lie between.  The waves' winning words borrow wf_keep's slots (phase F's, idle from A2 to C).
+    [[maybe_unused]] int *hword = nullptr;
+    if constexpr (LM) hword = lm.hist_word + (size_t)u * a.Tmax;
     const int4 *__restrict__ ninfo = a.node_info;
     const double lpi1 = a.lpi1, lpi2 = a.lpi2;
     double *tab = dyn, *Bsl = dyn + ((a.n_units * TS + 1) & ~1);
@@ -298,6 +308,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         //      are created right behind that donor's children)
         {
             int crun = 0, bw_i = NONE, bw_node = 0, bw_hist = 0, fw = NONE, fw_end = 0;
+            [[maybe_unused]] int bw_word = 0;
             double bw = -INFINITY;
             for (int e0 = 0; e0 < dcount; e0 += 64) {
                 const int e = e0 + lane;
@@ -340,17 +351,24 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                         fw = __shfl(tok, f, 64);
                         fw_end = __shfl(ofs + cnt, f, 64);
                     }
+                    [[maybe_unused]] int wsel = 0;
+                    if constexpr (LM) {                            // D6: the offer to the roots (the children keep the raw score)
+                        if (word) s += pcl_lm_word_term(lm, hword, hs, node, wsel);
+                    }
                     if (word && (bw_i == NONE || s > bw)) {        // (a lane's donors come in ascending token order)
                         bw = s;
                         bw_i = tok;
                         bw_node = node;
                         bw_hist = hs;
+                        if constexpr (LM) bw_word = wsel;
                     }
                 }
                 crun += __shfl(inc, 63, 64);
             }
-            pcl_wave_best(bw, bw_i, bw_node, bw_hist);
+            if constexpr (LM) pcl_wave_best(bw, bw_i, bw_node, bw_hist, bw_word);
+            else pcl_wave_best(bw, bw_i, bw_node, bw_hist);
             if (lane == 0) {
+                if constexpr (LM) wf_keep[wave] = bw_word;           // (the borrowed slots)
                 wd_ch[wave] = crun;
                 wd_fw[wave] = fw;
                 wd_fwend[wave] = fw_end;
@@ -366,6 +384,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         //      tokens: donors in token order, each donor's children in child order, the first characters (as the children of a
         //      pseudo-donor) right behind the children of the first word-end donor, at pair R0.
         int ch_tot = 0, w_i = NONE, w_node = 0, w_dhist = 0, R0 = -1;
+        [[maybe_unused]] int w_word = 0;
         double w_score = -INFINITY;
 #pragma unroll
         for (int w = 0; w < LNW; ++w) {
@@ -376,6 +395,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                 w_i = wd_bwi[w];
                 w_node = wd_bwnode[w];
                 w_dhist = wd_bwhist[w];
+                if constexpr (LM) w_word = wf_keep[w];
             }
         }
         const bool has_w = w_i != NONE;
@@ -384,6 +404,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
             if (tid == 0 && nh < a.Tmax) {                         // one history entry per frame: the winning donor's word
                 hprev[nh] = w_dhist;
                 hnode[nh] = w_node;
+                if constexpr (LM) hword[nh] = w_word;
             }
             ++nh;
         }
@@ -582,6 +603,7 @@ size_t lr_dyn_bytes(const pcl_ctx *ctx, int n_rows) {
 
 }  // namespace
 
+#ifndef PCL_DECLR_LM
 bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max) {
     if (ctx->S != 5 || cap > PCL_DEC_MAX_KEYS_PER_LANE * LW || cap > (1 << SLOT_BITS)) return false;
     if (t_max >= (1 << (31 - SLOT_BITS))) return false;            // (the frame stamp of the node -> token map: utterances of up to 131071 frames)
@@ -596,14 +618,21 @@ bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max
     return true;
 }
 
-int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows) {
+int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm) {
+    if (lm) return pcl_decode_lr_launch_lm(ctx, a, U, n_rows, *lm);           // (hmm_decode_lr_lm.hip)
+    constexpr bool LM = false;
+    const DecNoLm lma;
+#else
+int pcl_decode_lr_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
+    constexpr bool LM = true;
+#endif
     const int cap = a.cap, NbP = (n_rows + 1) & ~1;
     const size_t dyn = lr_dyn_bytes(ctx, n_rows);
 #define PCL_DECLR_LAUNCH(K)                                                                                                       \
     do {                                                                                                                          \
         if (dyn + LR_STATIC_LDS > 64u * 1024u)                                                                                    \
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-        hipLaunchKernelGGL((hmm_decode_lr_kernel<K>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP);                               \
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K, LM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+        hipLaunchKernelGGL((hmm_decode_lr_kernel<K, LM>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP, lma);                      \
     } while (0)
     if (cap <= 8 * LW) PCL_DECLR_LAUNCH(8);
     else PCL_DECLR_LAUNCH(16);

@@ -148,6 +148,10 @@ struct LexiconDev {
     DevBuf<int> lex_units, lex_nunits, lex_child_ptr, lex_child_idx, lex_word, lex_roots;
     DevBuf<int4> lex_info;                        // per node (first child, children, words end here, unit pair)
     DevBuf<double> d_unit_logtrans;
+    // the bigram language model over the tree's words (pcl_lm_upload; DecLm, hmm_decode_common.h): gone with the tree
+    DevBuf<double> lm_uni, lm_bow, lm_val;
+    DevBuf<long long> lm_row_ptr;
+    DevBuf<int> lm_col, lm_node_word_ptr, lm_node_word_ids;
 };
 
 struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
@@ -224,6 +228,8 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     double *hmm_gamma = nullptr;                     // VIEW into hmm_ksai (UnitsDev): [n_units][S-2]
     // pronunciation tree for the decoder (LexiconDev)
     int lex_nodes = 0, lex_nroots = 0;
+    std::vector<int> lex_word_host;                  // node_word as uploaded: pcl_lm_upload checks its node -> word lists against it
+    int lm_W = 0;                                    // words of the resident language model (0: none)
     // multi-GPU (pcl_comm.hip): RCCL communicator, or the host-callback rehearsal transport
     void *comm = nullptr;
     int rank = 0, nranks = 1;
@@ -268,6 +274,8 @@ struct BatchDecodeDev {
     DevBuf<int> dec_slot, dec_work, dec_int;
     DevBuf<double> dec_score;
     int dec_cap = 0, dec_cand = 0, dec_nodes = 0;    // what the buffers were sized for
+    DevBuf<int> dec_word;                            // pcl_batch_decode_lm only: [U][Tmax] the chosen word of every history entry
+    bool dec_has_words = false;                      // the last decode was pcl_batch_decode_lm
 };
 
 // Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_api.hip).

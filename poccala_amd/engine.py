@@ -406,6 +406,21 @@ class Engine(object):
         self._check(self._lib.pcl_lexicon_upload(self._ctx, len(nn), ptr(nu), ptr(nn), ptr(cp), ptr(ci), ptr(nw), len(ro), ptr(ro)))
         self.n_nodes = len(nn)
 
+    def load_language_model(self, compiled):
+        """The tables of LanguageModel.Ngram.compile (pre-scaled, ARPA-shaped; rule D6 in include/poccala_hip.h) for the loaded tree:
+        Batch.decode(lm=True) then adds the bigram term where words end.  A new tree drops them."""
+        uni, bow = as_c(compiled['uni'], np.float64), as_c(compiled['bow'], np.float64)
+        rp = as_c(compiled['row_ptr'], np.int64)
+        col, val = as_c(compiled['col'], np.int32), as_c(compiled['val'], np.float64)
+        nwp, nwi = as_c(compiled['node_word_ptr'], np.int32), as_c(compiled['node_word_ids'], np.int32)
+        if len(bow) != len(uni) or len(rp) != len(uni) + 1 or len(col) != len(val) or len(nwp) != self.n_nodes + 1:
+            raise ValueError('language model tables do not fit together (W = %d, row_ptr %d, col %d, val %d, node_word_ptr %d for %d nodes)'
+                             % (len(uni), len(rp), len(col), len(val), len(nwp), self.n_nodes))
+        if len(rp) and int(rp[-1]) != len(col) or len(nwp) and int(nwp[-1]) != len(nwi):
+            raise ValueError('language model tables: the last pointer entry is not the length of the list it points into')
+        pad = lambda a: a if len(a) else np.zeros(1, dtype=a.dtype)
+        self._check(self._lib.pcl_lm_upload(self._ctx, len(uni), ptr(uni), ptr(bow), ptr(rp), ptr(pad(col)), ptr(pad(val)), ptr(nwp), ptr(pad(nwi))))
+
     def all_state_batch(self, T, frame_begin):
         """Batch whose emission rows are [entry, every GMM state 0..J-1, exit]: what the decoder reads (BASELINE config 5:
         no label, every state of the inventory is scored for every frame)."""
@@ -790,19 +805,21 @@ class Batch(object):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
         self._check(self._lib.pcl_batch_accumulate_hmm(self._b))
 
-    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096):
+    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False):
         """Token passing over the loaded pronunciation tree (Decoder.py:91-167, 250-288) for every utterance of an all-state
         batch.  Returns a list (one dict per utterance): final = [(node, score, hist)] best first, history = [(prev, node)],
-        n_tokens (T,) live tokens after every frame, overflow."""
-        self.decode_launch(beam, min_distinct, candidate, max_tokens)
+        n_tokens (T,) live tokens after every frame, overflow.  lm=True: with the loaded language model at word ends
+        (Engine.load_language_model); history entries are then (prev, node, chosen word id)."""
+        self.decode_launch(beam, min_distinct, candidate, max_tokens, lm)
         return self.decode_results()
 
-    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096):
+    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False):
         """Queue the token passing (on the library's second stream, behind this batch's scoring) and return at once."""
         e = self.eng.S - 2
         lp = np.log(np.array([1.0 / (e + 2), 1.0 / (2 * e + 2)]))               # np.log(np.ones(N) / N), AcousticModel.py:1005
-        self._check(self._lib.pcl_batch_decode(self._b, float(beam), int(min_distinct), int(candidate), int(max_tokens), float(lp[0]), float(lp[1])))
-        self._dec_candidate = int(candidate)
+        launch = self._lib.pcl_batch_decode_lm if lm else self._lib.pcl_batch_decode
+        self._check(launch(self._b, float(beam), int(min_distinct), int(candidate), int(max_tokens), float(lp[0]), float(lp[1])))
+        self._dec_candidate, self._dec_lm = int(candidate), bool(lm)
 
     def decode_fetch(self):
         """Wait for the queued token passing of THIS batch (nothing else) and bring its result arrays to the host."""
@@ -815,16 +832,22 @@ class Batch(object):
                   ((U, tm), np.int32), ((U, tm), np.int32), ((U, tm), np.int32), ((U,), np.int32)]
         nf, node, score, hist, hn, hp, hnode, nt, ov = self.eng._pinned_views('decode_results', shapes)
         self._check(self._lib.pcl_batch_decode_get(self._b, ptr(nf), ptr(node), ptr(score), ptr(hist), ptr(hn), ptr(hp), ptr(hnode), ptr(nt), ptr(ov)))
-        return tuple(x.copy() for x in (nf, node, score, hist, hn, hp, hnode, nt, ov)) + (self.T.copy(),)
+        raw = tuple(x.copy() for x in (nf, node, score, hist, hn, hp, hnode, nt, ov)) + (self.T.copy(),)
+        if getattr(self, '_dec_lm', False):                                     # the chosen words travel behind T: an eleventh array
+            hw = np.empty((U, tm), dtype=np.int32)
+            self._check(self._lib.pcl_batch_decode_get_words(self._b, ptr(hw)))
+            raw += (hw,)
+        return raw
 
     @staticmethod
     def decode_unpack(raw):
         """decode_fetch's arrays as the per-utterance dicts decode() returns (host work only)."""
-        nf, node, score, hist, hn, hp, hnode, nt, ov, T = raw
+        nf, node, score, hist, hn, hp, hnode, nt, ov, T = raw[:10]
         out = []
         for u in range(len(nf)):
+            cols = (hp[u, :hn[u]].tolist(), hnode[u, :hn[u]].tolist()) + ((raw[10][u, :hn[u]].tolist(),) if len(raw) > 10 else ())
             out.append(dict(final=list(zip(node[u, :nf[u]].tolist(), score[u, :nf[u]].tolist(), hist[u, :nf[u]].tolist())),
-                            history=list(zip(hp[u, :hn[u]].tolist(), hnode[u, :hn[u]].tolist())),
+                            history=list(zip(*cols)),
                             n_tokens=nt[u, :T[u]].copy(), overflow=bool(ov[u])))
         return out
 
