@@ -597,6 +597,65 @@ int pcl_fmllr_estimate(pcl_ctx *ctx, int n_iter, double min_occ, double *W_out /
 int pcl_frames_transform(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *utt_speaker, int S,
                          const double *W /* host S*D*(D+1), or NULL = the resident last estimate */);
 
+/* ----------------------------------------------------------------- LDA (row f12): class statistics of spliced frames, projection to a new width
+ * Linear discriminant analysis of the resident frames (csrc/frame_lda.hip): the step between the front-end's static cepstra and fMLLR in a
+ * GMM-HMM recipe -- splice +-4 frames, project 117 dimensions to 39 or 40.  Not in the reference; tests/_lda_twin.py is the rule's NumPy twin.
+ *
+ * SPLICE.  Utterance u occupies the rows [begin_u, begin_u + T_u) of the resident (F, D) matrix.  With context (left, right) the spliced
+ * vector of row g is the concatenation, for k = -left .. right, of row clamp(g + k, begin_u, begin_u + T_u - 1): edge replication, the
+ * rule the front-end's deltas use; nothing is read across an utterance boundary.  Ds = (left + right + 1) D; the calls refuse Ds + 1 > 128.
+ *
+ * STATISTICS.  frame_class[g] in [0, R), or -1 = the row is skipped; rows outside every utterance of the call are skipped.  Per class
+ *     n_r = the rows     s_r = sum x     S_r = sum x x^T                    (x the spliced vector, float64)
+ * formed as ONE product of the augmented vector [x | 1] with itself, of order Ds + 1, read from the float64 frame copy when the context
+ * holds one, else from the float32 rows widened.  Order: the kept rows are counting-sorted by class (stable: a class's rows ascend); a
+ * class's rows are cut into chunks of PCL_LDA_CHUNK rows (env, read on every call; default 1024) that never straddle a class; a chunk's
+ * upper-triangular 16 x 16 tiles are formed on v_mfma_f64_16x16x4_f64 -- 32 rows are staged per step, wave w of four takes the 4-row
+ * k-steps w and w + 4 of every step, the waves' sums are added ((w0 + w1) + w2) + w3 -- or, under PCL_LDA_VALU=1, on the VALU with the
+ * chunk's rows in ascending order; the chunks' partials are then added onto the running statistics in chunk order.  No floating-point
+ * atomics: two runs give the same bits.  n_r is exact (a sum of ones).
+ * pcl_lda_zero makes (and clears) the context's statistics for R classes and the context (left, right) at the dimension of the CURRENT
+ * frame matrix: 8 R (Ds + 1)^2 bytes from the context's pool, at most 2^32, R <= 65535; freed by pcl_destroy and by the next pcl_lda_zero.
+ * The statistics are additive over calls of pcl_lda_accumulate / pcl_batch_accumulate_lda.
+ * pcl_lda_accumulate: T / frame_begin (U,) as pcl_frames_transform takes them (disjoint: a row is spliced inside ONE utterance),
+ * frame_class (F,) int32 on the host, one entry per row of the frame matrix.
+ * pcl_batch_accumulate_lda: the classes come from the batch's Viterbi paths -- everything pcl_batch_align_segments needs and checks (a
+ * label-built batch, pcl_batch_viterbi run, its drop rule); the owner map stays on the device.  state_class (J,) int32 in [-1, R) maps the
+ * owner state to its class (-1: skipped), as pcl_mllr_estimate takes it; NULL = every state its own class (needs J <= R).
+ * pcl_lda_stats_download: n (R,), s (R, Ds), S (R, Ds, Ds) float64, S as full symmetric matrices mirrored from the upper triangle; NULLs
+ * are skipped.
+ *
+ * ESTIMATE: on the host, in float64 (poccala_amd.Engine.lda_estimate; at most 127 x 127, once per training stage).  N = sum n_r, m = sum s_r / N,
+ * m_r = s_r / n_r over the classes with n_r > 0:
+ *   1. W = sum_r (S_r - s_r s_r^T / n_r) / N          2. B = sum_r n_r (m_r - m)(m_r - m)^T / N
+ *   3. W += eps trace(W) / Ds on the diagonal         4. W = L L^T          5. eigh(L^-1 B L^-T)
+ *   6. V = the D_out leading eigenvectors, eigenvalues descending          7. A = V^T L^-1, b = -A m  (the projected data: zero mean, unit
+ *   within-class covariance)                          8. every row's sign is fixed so that its largest-magnitude entry is positive
+ *
+ * PROJECT.  pcl_frames_splice_project: y = b + A x over the spliced vector x of every row of the listed utterances, float64, b first, then
+ * the products in ascending index order, one rounding per operation; the float32 row is float32(y).  One pass, the splice at load, into
+ * NEW buffers which then replace the resident ones: the frame matrix becomes (F, D_out) with the row stride and bookkeeping
+ * pcl_frames_upload would leave for that width (padding columns zero), the float64 copy kept when one was held.  Rows that belong to no
+ * listed utterance become zero.  A (D_out, Ds) row-major, b (D_out,), finite; 1 <= D_out <= min(Ds, 64).  A resident model stays: a model
+ * of another dimension is the caller's business, as after pcl_frames_upload (fMLLR statistics of another dimension are dropped, as there).
+ * Live batches: pcl_frames_upload lets a batch outlive it and re-checks the batch's ROWS against the new matrix at its next use.  That
+ * check cannot see this call -- the rows stay, the width changes -- so it refuses (PCL_ERR_STATE) while any batch or pcl_seg made on the
+ * old matrix is alive: destroy them first.
+ * pcl_frames_download: the resident frames as held, unpadded (F, D): f64 from the float64 copy (PCL_ERR_STATE when the context holds
+ * none), f32 from the float32 rows; NULLs are skipped.
+ *
+ * No frames / no statistics: PCL_ERR_STATE; so is an accumulate after the frame matrix changed its dimension since pcl_lda_zero (the
+ * context (left, right) no longer gives the statistics' order).  Ds + 1 > 128, D_out outside 1 .. Ds, a class outside [-1, R), R out of
+ * range, an utterance outside the frame matrix or overlapping another: PCL_ERR_INVALID.  All checked before anything is changed.
+ * pcl_kernel_time groups: "lda_sort" (keys and counting sort), "lda_stats" (the product and its reduction), "lda_project".  Synchronous. */
+int pcl_lda_zero(pcl_ctx *ctx, int R, int left, int right);
+int pcl_lda_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *frame_class /* host, F */);
+int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class /* J, or NULL = identity */);
+int pcl_lda_stats_download(pcl_ctx *ctx, double *n /* R or NULL */, double *s /* R*Ds or NULL */, double *S /* R*Ds*Ds or NULL */);
+int pcl_frames_splice_project(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, int left, int right, int D_out,
+                              const double *A /* D_out*Ds */, const double *b /* D_out */);
+int pcl_frames_download(pcl_ctx *ctx, double *f64 /* F*D or NULL */, float *f32 /* F*D or NULL */);
+
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /
  * (2 var_jmd) (about 5e-7 * cond nats).  States with cond[j] > *cond_max (default 96, env PCL_MFMA_COND_MAX) are scored

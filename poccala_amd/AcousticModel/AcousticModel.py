@@ -618,6 +618,41 @@ class AcousticModel(DataInitialization):
         out['W'], out['logdet'] = W_run, logdet_run
         return out
 
+    def lda_batch(self, labels, data_list, unit_hmms, D_out, left=4, right=4, state_class=None, eps=1e-10, precision=PCL_F64, engine=None):
+        """LDA on the device, beside flat_start_batch: forced alignment of the labelled utterances with the units' current model, the class
+        statistics of the spliced frames from the Viterbi owner map (Batch.accumulate_lda: every GMM state its own class, or state_class
+        (J,) folding tied states), the estimate (Engine.lda_estimate) and the projection (Engine.splice_project) in one call.  Afterwards
+        the engine's resident frames are (F, D_out) -- the rows of empty utterances zero -- and the model is of the OLD dimension: start
+        again with flat_start_batch at D_out.  data_list: (T_u, D) arrays (uploaded here as float64), or the (lens, begin) of resident
+        frames.  Utterances the alignment drops add nothing to the statistics but are projected like the others.  Returns a dict: A
+        (D_out, Ds), b (D_out,), eigenvalues (D_out,), n (classes,) rows per class, dropped = the utterances left out of the statistics,
+        lens / begin of the projected utterances."""
+        engine = engine or default_engine()
+        res = self._resident(data_list)
+        if res is None:
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d, dtype=np.float64).reshape(len(d), -1) for d in data_list], axis=0))
+        else:
+            lens, begin = np.asarray(res[0], dtype=np.int32), np.asarray(res[1], dtype=np.int64)
+        keep = [u for u in range(len(lens)) if lens[u] > 0]
+        b = self._sentence_batch([labels[u] for u in keep], (lens[keep], begin[keep]), unit_hmms, engine)[0]
+        try:
+            b.score(precision)
+            b.viterbi()
+            R = int(engine.J) if state_class is None else int(np.max(state_class)) + 1
+            engine.lda_zero(max(R, 1), left, right)
+            b.accumulate_lda(state_class)
+            seg, dropped = b.align_segments()                 # (only for the list of utterances its drop rule leaves out)
+            seg.close()
+        finally:
+            b.close()
+        A, bias, lam = engine.lda_estimate(D_out, eps)
+        n = engine.lda_stats()[0]
+        engine.splice_project(lens, begin, left, right, A, bias)
+        gone = sorted(set(range(len(lens))) - set(keep)) + [keep[u] for u in dropped]
+        return dict(A=A, b=bias, eigenvalues=lam, n=n, dropped=sorted(gone), lens=lens, begin=begin)
+
     def _adopt_model(self, model, units, unit_hmms):
         """(mean, var, weight) of a model laid out unit-major over `units` into the units' GMM objects; this object's mix_level follows."""
         mean, var, w = model

@@ -512,7 +512,36 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
         HIPCHK(ctx, hipGetLastError());
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ++ctx->live_segs;
     *out = s.release();
+    return PCL_OK;
+}
+
+// The histogram / scan / stable scatter above without a pcl_seg around them (frame_lda.hip sorts rows by class)
+int pcl_count_sort_device(pcl_ctx *ctx, long long F, int J, const int *d_key, std::vector<int> *counts, DevBuf<int> *d_order) {
+    const long long per_tile = std::max<long long>(std::max<long long>(2048, (F + 4095) / 4096), (F * (long long)J + (1LL << 26) - 1) >> 26);
+    const int tile = (int)((per_tile + SEG_T - 1) / SEG_T * SEG_T);
+    const int n_tiles = (int)((F + tile - 1) / tile);
+    DevBuf<int> d_tilecnt, d_counts, d_off;
+    TRY(d_tilecnt.alloc(ctx, (size_t)n_tiles * J));
+    TRY(d_counts.alloc(ctx, (size_t)J));
+    TRY(d_off.alloc(ctx, (size_t)J + 1));
+    HIPCHK(ctx, hipMemsetAsync(d_tilecnt, 0, (size_t)n_tiles * J * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(seg_hist_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_key, F, J, tile, d_tilecnt);
+    hipLaunchKernelGGL(seg_colscan_kernel, dim3((J + 255) / 256), dim3(256), 0, ctx->stream, d_tilecnt, n_tiles, J, d_counts);
+    HIPCHK(ctx, hipGetLastError());
+    counts->resize(J);
+    HIPCHK(ctx, hipMemcpyAsync(counts->data(), d_counts, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int> off(J + 1, 0);
+    for (int j = 0; j < J; ++j) off[j + 1] = off[j] + (*counts)[j];
+    HIPCHK(ctx, pcl_h2d(ctx, d_off, off.data(), (size_t)(J + 1) * sizeof(int)));
+    TRY(d_order->alloc(ctx, (size_t)off[J]));
+    if (off[J] > 0) {
+        hipLaunchKernelGGL(seg_scatter_kernel, dim3(n_tiles), dim3(SEG_T), 0, ctx->stream, d_key, F, J, tile, d_tilecnt, d_off, d_order->p);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }
 
@@ -521,6 +550,7 @@ extern "C" {
 int pcl_seg_destroy(pcl_seg *seg) {
     if (!seg) return PCL_ERR_INVALID;
     (void)hipSetDevice(seg->ctx->device);
+    --seg->ctx->live_segs;
     delete seg;                                                  // (every block with its device-wide wait: nothing says the GPU is done with them)
     return PCL_OK;
 }

@@ -260,6 +260,7 @@ static void ctx_teardown(pcl_ctx *ctx) {
     drop_timers(ctx);                                            // (the per-chunk events of the staging stream's "pcm_h2d" group among them)
     pcl_mfcc_release(ctx);                                       // drained: no copy reads the staging buffers, no event is waited for
     free_model(ctx);
+    pcl_lda_release(ctx);
     pcl_units_release(ctx);
     release_frames32(ctx);
     ctx->frames64.release();
@@ -683,6 +684,8 @@ int pcl_batch_create(pcl_ctx *ctx, int U, const int32_t *N, const int32_t *T, co
         pcl_batch_destroy(b);
         return r;
     }
+    b->counted = true;
+    ++ctx->live_batches;
     *out = b;
     return PCL_OK;
 }
@@ -728,6 +731,8 @@ int pcl_batch_destroy(pcl_batch *b) {
     if (!b) return PCL_OK;
     pcl_ctx *ctx = b->ctx;
     hipSetDevice(ctx->device);
+    if (b->counted) --ctx->live_batches;
+    b->counted = false;
     pcl_batch_reap(ctx, false);
     static const bool sync_destroy = getenv("PCL_DESTROY_SYNC") && atoi(getenv("PCL_DESTROY_SYNC")) != 0;   // A/B: rounds 1-4 (wait here)
     if (batch_work_done(b, sync_destroy)) batch_free_now(b);
@@ -1228,12 +1233,9 @@ int pcl_batch_regroup(pcl_batch *b, const int32_t *row_unit, int gmm_num, int32_
     return PCL_OK;
 }
 
-int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dropped_out, pcl_seg **out) {
-    if (!b) return PCL_ERR_INVALID;
+// What the owner map of a batch's Viterbi paths needs (pcl_batch_align_segments, pcl_batch_accumulate_lda), checked before anything is queued
+static int align_precheck(pcl_batch *b, const char *who) {
     pcl_ctx *ctx = b->ctx;
-    const char *who = "pcl_batch_align_segments";
-    if (out) *out = nullptr;
-    if (!frame_state_out && !out) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: neither frame_state_out nor out is given", who);
     if (!b->from_labels) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch was not created from labels (pcl_batch_create_labels)", who);
     if (!b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: run pcl_batch_viterbi first", who);
     const int e = ctx->S - 2;
@@ -1261,10 +1263,13 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
             prev = u;
         }
     }
-    TRY(batch_join(b));
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const long long F = ctx->F;
-    if (!b->d_labels) {                                             // once per batch
+    return PCL_OK;
+}
+
+// the batch's labels and the U + 1 offsets into them on the device: once per batch
+static int align_labels_up(pcl_batch *b) {
+    pcl_ctx *ctx = b->ctx;
+    if (!b->d_labels) {
         std::vector<int> loff((size_t)b->U + 1, 0);
         for (int u = 0; u < b->U; ++u) loff[u + 1] = loff[u] + b->label_len[u];
         b->d_label_off.release();                                   // (left by a call whose second allocation failed)
@@ -1273,6 +1278,21 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
         HIPCHK(ctx, pcl_h2d(ctx, b->d_label_off, loff.data(), loff.size() * sizeof(int)));
         HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->labels.data(), b->labels.size() * sizeof(int32_t)));
     }
+    return PCL_OK;
+}
+
+int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dropped_out, pcl_seg **out) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    const char *who = "pcl_batch_align_segments";
+    if (out) *out = nullptr;
+    if (!frame_state_out && !out) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: neither frame_state_out nor out is given", who);
+    TRY(align_precheck(b, who));
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long F = ctx->F;
+    const int e = ctx->S - 2;
+    TRY(align_labels_up(b));
     DevBuf<int32_t> d_state, d_drop;
     auto align = [&]() -> int {
         TRY(d_state.alloc(ctx, (size_t)F));
@@ -1291,6 +1311,49 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
     }
     if (rc == PCL_OK && out) rc = pcl_seg_create_device(ctx, F, ctx->J, d_state, out);
     pcl_free_synced_scope done;                                     // the stream these two were used on has been waited for
+    d_state.release();
+    d_drop.release();
+    return rc;
+}
+
+// LDA class statistics from the batch's Viterbi paths (frame_lda.hip): the owner map pcl_batch_align_segments makes stays on the device
+int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    const char *who = "pcl_batch_accumulate_lda";
+    if (!ctx->lda_stats || ctx->lda_R <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no statistics: pcl_lda_zero first", who);
+    TRY(align_precheck(b, who));
+    if (!state_class && ctx->J > ctx->lda_R)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: state_class is NULL (every state its own class) but the model has %d states and the statistics %d classes", who, ctx->J, ctx->lda_R);
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long F = ctx->F;
+    TRY(align_labels_up(b));
+    DevBuf<int32_t> d_state, d_drop;
+    auto align = [&]() -> int {
+        TRY(d_state.alloc(ctx, (size_t)F));
+        TRY(d_drop.alloc(ctx, (size_t)b->U));
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
+        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, ctx->S - 2, d_state, d_drop));
+        HIPCHK(ctx, pcl_batch_mark(b));
+        return PCL_OK;
+    };
+    int rc = align();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) {      // (on every path: the frees below rely on it)
+        pcl_set_error(ctx, "pcl_batch_accumulate_lda: HIP error");
+        rc = PCL_ERR_HIP;
+    }
+    if (rc == PCL_OK) {
+        std::vector<int32_t> T(b->U);
+        std::vector<int64_t> begin(b->U);
+        for (int u = 0; u < b->U; ++u) {
+            T[u] = b->utt[u].T;
+            begin[u] = b->utt[u].frame0;
+        }
+        rc = pcl_launch_lda_accumulate(ctx, who, b->U, T.data(), begin.data(), d_state, state_class, ctx->J);   // (waits for its kernels)
+        if (rc != PCL_OK) (void)hipStreamSynchronize(ctx->stream);  // ... unless it gave up half-way
+    }
+    pcl_free_synced_scope done;
     d_state.release();
     d_drop.release();
     return rc;

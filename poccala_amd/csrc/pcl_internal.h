@@ -205,6 +205,13 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     float *frames32 = nullptr;            // VIEW: the current f32 frame matrix -- frames_up (a plain upload, frames_front < 0) or frames_slot[frames_front]
     DevBuf<float> frames_up;
     DevBuf<double> frames64;
+    // What was made ON the current frame matrix and is alive for the caller (pcl_batch_create .. pcl_batch_destroy, pcl_seg_create ..
+    // pcl_seg_destroy): pcl_frames_splice_project changes the matrix's width under an unchanged row count and refuses while any is left
+    int live_batches = 0, live_segs = 0;
+    // LDA class statistics (frame_lda.hip): [lda_R][n][n], n = (lda_left + lda_right + 1) lda_D + 1, the upper triangle of sum [x | 1][x | 1]^T
+    // over the class's spliced rows; lda_D = the frame dimension pcl_lda_zero saw.  Freed by pcl_destroy and by the next pcl_lda_zero.
+    DevBuf<double> lda_stats;
+    int lda_R = 0, lda_left = 0, lda_right = 0, lda_D = 0;
     // streaming: two frame slots (grow only); pcl_frames_stage copies the next chunk into the slot that is not current on stream_aux,
     // pcl_frames_swap makes it current
     DevBuf<float> frames_slot[2];
@@ -344,6 +351,7 @@ struct pcl_batch : BatchDecodeDev {
     std::vector<int> seg_of_row;              // (utterance, row) -> its segment (-1: not a GMM row); d_seg_of_row: the device copy (sumN ints)
     DevBuf<int> d_seg_of_row;
     int max_N = 0;                            // rows of the largest sentence HMM of the batch
+    bool counted = false;                     // in ctx->live_batches (a batch pcl_batch_create gave out)
     // (the accumulate pass's device work lists and tile images are the CONTEXT's scratch, pcl_ctx::acc; the host staging of its state order is acc_ws ... above)
     // decoder state: BatchDecodeDev
     bool have_dec = false;
@@ -545,6 +553,11 @@ int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision);
 int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_speaker);   // frame_adapt.hip, behind pcl_batch_accumulate_fmllr's checks
 void pcl_fmllr_release(pcl_ctx *ctx);                // the fMLLR statistics and estimate (a frame matrix of another dimension)
 void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate scratch (pcl_destroy, pcl_model_upload)
+// frame_lda.hip, behind the checks of pcl_lda_accumulate / pcl_batch_accumulate_lda: d_src (rows of the frame matrix, on the device) = the
+// class of every row, or with state_class (host, J entries) its owner state; -1 = not kept
+int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src,
+                              const int32_t *state_class, int J);
+void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (pcl_destroy)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);
@@ -629,6 +642,9 @@ int pcl_model_finish(pcl_ctx *ctx);
 // pcl_seg_create from an owner array that is already on the device (F = ctx->F entries, every one -1 or in [0, J): the CALLER guarantees it,
 // nothing is validated here); the array is only read and stays the caller's.  gmm_segment.hip.
 int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_frame_state, pcl_seg **out);
+// pcl_seg_create's counting sort alone (gmm_segment.hip): d_key[f] in [0, J) or anything else = not kept -> counts (J, host) and the kept
+// rows key by key, each key in ascending row order (*d_order, sum counts entries).  Complete on return.
+int pcl_count_sort_device(pcl_ctx *ctx, long long F, int J, const int *d_key, std::vector<int> *counts, DevBuf<int> *d_order);
 // pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (in *d_out: the caller's from then on),
 // complete on return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.  pcm16: `signal` is int16_t
 // samples, which travel through the context's page-locked staging; otherwise double, copied from the caller's memory as it is.

@@ -552,6 +552,86 @@ class Engine(object):
         self._check(self._lib.pcl_frames_transform(self._ctx, T.size, ptr(T), ptr(fb), ptr(spk), S, ptr(W)))
         self._frames_key = None                      # the resident frames are no longer what was uploaded
 
+    # ------------------------------------------------------------------ LDA: class statistics of spliced frames, projection to a new width
+    def lda_zero(self, n_classes, left, right):
+        """Make (and clear) the context's LDA class statistics (pcl_lda_zero) for n_classes classes and the splice context (left, right)
+        at the dimension of the resident frames: per class the rows, sum x and sum x x^T of the spliced vectors x."""
+        self._check(self._lib.pcl_lda_zero(self._ctx, int(n_classes), int(left), int(right)))
+        self._lda = (int(n_classes), int(left), int(right), (int(left) + int(right) + 1) * int(self.FD))
+
+    def lda_accumulate(self, T, frame_begin, frame_class):
+        """Add the rows [frame_begin[u], + T[u]) of the resident frames to the statistics (pcl_lda_accumulate): frame_class (F,) int32, one
+        class in [0, n_classes) per row of the frame matrix, -1 = skip the row.  A row is spliced inside its own utterance."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        cls = as_c(frame_class, np.int32).reshape(-1)
+        if fb is None or cls.shape != (int(self.F),):
+            raise ValueError('frame_begin is needed and frame_class must hold one class per frame row (F = %d), got %s' % (self.F, cls.shape))
+        self._check(self._lib.pcl_lda_accumulate(self._ctx, T.size, ptr(T), ptr(fb), ptr(cls)))
+
+    def lda_stats(self):
+        """(n (R,), s (R, Ds), S (R, Ds, Ds)) float64: what lda_accumulate / Batch.accumulate_lda have summed since lda_zero."""
+        R, _, _, Ds = getattr(self, '_lda', (0, 0, 0, 0))
+        r, d = max(R, 1), max(Ds, 1)
+        n, s, S = np.empty(r), np.empty((r, d)), np.empty((r, d, d))
+        self._check(self._lib.pcl_lda_stats_download(self._ctx, ptr(n), ptr(s), ptr(S)))
+        return n[:R], s[:R, :Ds], S[:R, :Ds, :Ds]
+
+    def lda_estimate(self, D_out, eps=1e-10):
+        """The LDA transform from the resident statistics, on the host in float64 (the rule: include/poccala_hip.h, ESTIMATE): within-class
+        covariance W (floored by eps trace(W) / Ds on the diagonal) = L L^T, the D_out leading eigenvectors V of L^-1 B L^-T, A = V^T L^-1,
+        b = -A m, every row's largest-magnitude entry made positive.  Returns (A (D_out, Ds), b (D_out,), eigenvalues (D_out,) descending);
+        the projected data has zero mean and unit within-class covariance."""
+        n, s, S = self.lda_stats()
+        Ds, D_out = s.shape[1], int(D_out)
+        live = np.flatnonzero(n > 0)
+        if D_out < 1 or D_out > Ds:
+            raise ValueError('lda_estimate: D_out = %d, need 1 .. the spliced dimension %d' % (D_out, Ds))
+        if live.size == 0:
+            raise ValueError('lda_estimate: the statistics are empty')
+        N = n[live].sum()
+        m = s[live].sum(axis=0) / N
+        W, B = np.zeros((Ds, Ds)), np.zeros((Ds, Ds))
+        for r in live:
+            W += S[r] - np.outer(s[r], s[r]) / n[r]
+            d = s[r] / n[r] - m
+            B += n[r] * np.outer(d, d)
+        W, B = W / N, B / N
+        W = 0.5 * (W + W.T)
+        W[np.diag_indices(Ds)] += float(eps) * np.trace(W) / Ds
+        L = np.linalg.cholesky(W)
+        Li = np.linalg.solve(L, np.eye(Ds))
+        M = Li.dot(B).dot(Li.T)
+        lam, V = np.linalg.eigh(0.5 * (M + M.T))
+        top = np.argsort(-lam, kind='stable')[:D_out]
+        A = V[:, top].T.dot(Li)
+        b = -A.dot(m)
+        flip = A[np.arange(D_out), np.abs(A).argmax(axis=1)] < 0
+        A[flip], b[flip] = -A[flip], -b[flip]
+        return np.ascontiguousarray(A), b, lam[top]
+
+    def splice_project(self, T, frame_begin, left, right, A, b):
+        """The resident (F, D) frames become (F, D_out): y = b + A x over the spliced vector x (context (left, right), edge replication
+        inside the utterance) of every row of the listed utterances, rows of no utterance zero (pcl_frames_splice_project).  A (D_out,
+        (left + right + 1) D), b (D_out,).  Refused while a Batch or Segments made on the old frames is open."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        A, b = as_c(A, np.float64), as_c(b, np.float64).reshape(-1)
+        Ds = (int(left) + int(right) + 1) * int(self.FD)
+        if fb is None or A.ndim != 2 or A.shape[1] != Ds or b.shape != (A.shape[0],):
+            raise ValueError('frame_begin is needed, A must be (D_out, %d) and b (D_out,), got %s and %s' % (Ds, A.shape, b.shape))
+        self._check(self._lib.pcl_frames_splice_project(self._ctx, T.size, ptr(T), ptr(fb), int(left), int(right), A.shape[0], ptr(A), ptr(b)))
+        self.FD = int(A.shape[0])
+        self._frames_key = None                      # the resident frames are no longer what was uploaded
+
+    def frames_download(self, dtype=np.float64):
+        """The resident frames as held, (F, D): np.float64 = the float64 copy (an error when the frames were uploaded as float32 and no
+        copy exists), np.float32 = the float32 rows every default-precision kernel reads."""
+        out = np.empty((max(int(self.F), 1), max(int(self.FD), 1)), dtype=np.float32 if np.dtype(dtype) == np.float32 else np.float64)
+        if out.dtype == np.float32:
+            self._check(self._lib.pcl_frames_download(self._ctx, None, ptr(out)))
+        else:
+            self._check(self._lib.pcl_frames_download(self._ctx, ptr(out), None))
+        return out[:int(self.F), :int(self.FD)]
+
     def model_download(self):
         """(mean (J,M,D), var (J,M,D), weight (J,M)) float64 master copy."""
         mean = np.empty((self.J, self.M, self.D))
@@ -800,6 +880,18 @@ class Batch(object):
         if spk.shape != (self.U,):
             raise ValueError('utt_speaker must hold one speaker per utterance (U = %d), got %s' % (self.U, spk.shape))
         self._check(self._lib.pcl_batch_accumulate_fmllr(self._b, ptr(spk)))
+
+    def accumulate_lda(self, state_class=None):
+        """LDA class statistics from this batch's Viterbi paths (pcl_batch_accumulate_lda) into the sums of the last Engine.lda_zero: every
+        frame of an utterance align_segments() would keep counts for the class of its owner state -- state_class (J,) int32 in
+        [-1, n_classes), -1 = skip; None = every state its own class.  Label-built batches only; needs score() and viterbi().  The owner
+        map stays on the device."""
+        sc = None
+        if state_class is not None:
+            sc = as_c(state_class, np.int32).reshape(-1)
+            if sc.shape != (int(self.eng.J),):
+                raise ValueError('state_class must hold one class per model state (J = %d), got %s' % (self.eng.J, sc.shape))
+        self._check(self._lib.pcl_batch_accumulate_lda(self._b, ptr(sc)))
 
     def accumulate_hmm(self):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
