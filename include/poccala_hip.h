@@ -108,7 +108,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "fmllr" | "fmllr_frames" | "fmllr_gk" | "fmllr_solve" (pcl_fmllr_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
+ * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "fmllr" | "fmllr_frames" | "fmllr_gk" | "fmllr_solve" (pcl_fmllr_estimate and its kin, below) | "mllt" | "mllt_frames" | "mllt_gk" | "mllt_solve" (pcl_mllt_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -596,6 +596,83 @@ int pcl_fmllr_estimate(pcl_ctx *ctx, int n_iter, double min_occ, double *W_out /
                        double *q_trace_out /* S*n_iter or NULL */, int32_t *status_out /* S or NULL */);
 int pcl_frames_transform(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *utt_speaker, int S,
                          const double *W /* host S*D*(D+1), or NULL = the resident last estimate */);
+
+/* ----------------------------------------------------------------- MLLT (row f13): one square transform of the features for the whole corpus
+ * The maximum-likelihood linear transform of semi-tied covariances (Gales 1999; Kaldi's est-mllt) on the resident frames and statistics
+ * (csrc/frame_mllt.hip): the step between LDA (f12) and fMLLR (f11).  An LDA projection does not decorrelate the classes it separates and
+ * every Gaussian here is diagonal; ONE matrix A, estimated under the current alignment and applied to the frames AND the means, makes the
+ * diagonal model fit better.  Not in the reference; tests/_mllt_twin.py is the rule's NumPy twin.  Everything is float64, built with
+ * -ffp-contract=off; no floating-point atomics: two runs give the same bits.
+ *
+ * THE RULE.  With gamma_t(j,m) the mixture posterior as fMLLR defines it above, over the KEPT states (state_keep[j] != 0; NULL = all), for
+ * feature dimension i:
+ *     G_i = sum_t sum_jm gamma_t(j,m) / var_jm,i (x_t - mu_jm)(x_t - mu_jm)^T        (D x D, symmetric)          beta = sum_t sum_jm gamma_t(j,m)
+ *     Q(A) = beta ln|det A| - 1/2 sum_i a_i G_i a_i^T                                (a_i = row i of A)
+ * The centred product per (frame, mixture) pair costs D^2 per pair.  It is expanded instead: with n_jm = acc[j,m] and s_jm = mean_acc[j,m,:]
+ * - bias acc[j,m] of the resident statistics block (bias = 100, the accumulate pass's),
+ *     G_i = F_i - C_i
+ *     F_i = sum_t p_i(t) x_t x_t^T,   p_i(t) = sum_jm gamma_t(j,m) / var_jm,i                             the frame side, per batch
+ *     C_i = sum_jm (s_jm mu_jm^T + mu_jm s_jm^T - n_jm mu_jm mu_jm^T) / var_jm,i                          the mixture side, at estimate time
+ * which is exact when both sides saw the same posteriors: the caller runs pcl_batch_accumulate AND pcl_batch_accumulate_mllt on the same
+ * batches (and the same utterances of them), with pcl_stats_zero and pcl_mllt_zero in front.  pcl_batch_accumulate(PCL_F32) carries its
+ * 1e-4 error into C_i; PCL_F64 does not.  The estimate returns both occupancies -- beta from the frames, the sum of acc over the kept
+ * contributing mixtures -- so that a caller can tell when the two sides do not belong together.
+ * Which mixtures contribute to C_i follows pcl_mllr_estimate: m < M with acc finite and > 0, padding is never visited.  Which (frame, row)
+ * pairs contribute to F_i follows fMLLR: ln gamma or ln b = -inf, a weight of 0 or a weight that is not finite contribute exactly nothing.
+ * A state with state_keep[j] == 0 -- silence, say -- is left out of both sides.
+ *
+ * STATISTICS.  pcl_mllt_zero makes (or clears) F (D, D, D) and beta for the current model and stores state_keep (J,) with them.  They
+ * are additive over calls of pcl_batch_accumulate_mllt and are dropped by any call that makes a new model (an upload, a flat start, a
+ * mix-up, k-means) or a frame matrix of another D, as fMLLR's are.
+ * pcl_batch_accumulate_mllt: utt_keep (U,) int32, 0 = the utterance is skipped, NULL = all.  Needs what pcl_batch_accumulate needs.  p_i(t)
+ * and beta(t): fMLLR's reduction without q, in its order, all D + 1 sums of a frame in one workgroup.  F_i += the split-K float64 GEMM of
+ * csrc/adapt_common.h with K = the call's kept frames in batch order -- ONE group -- cut into chunks of PCL_MLLT_CHUNK frames (env, read on
+ * every call; default 4096 for this side); operands a = x_t[p], b = p_i(t) x_t[p]; upper-triangular 16 x 16 tiles on
+ * v_mfma_f64_16x16x4_f64 (wave w of four takes the 4-frame k-steps w, w + 4, ..; the waves' sums are added ((w0 + w1) + w2) + w3), or on the
+ * VALU under PCL_MLLR_VALU=1; the chunks' partials are added from 0 in chunk order, that sum is added to the resident element, and the
+ * lower triangle takes the upper one's values.  beta += the frames' beta(t): thread t of 256 adds the frames t, t + 256, .. in ascending
+ * order, then a fixed binary tree.
+ * pcl_mllt_stats_download: F (D, D, D), beta (1,); NULLs are skipped.
+ *
+ * ESTIMATE.  C_i is the same GEMM with K = the kept states' mixtures -- states ascending, the M real mixtures of each ascending -- in the
+ * TWO-PRODUCT form: every mixture is two consecutive K-elements,
+ *     a = s[p], b = mu[p] / var_i              then              a = mu[p], b = (s[p] - n mu[p]) / var_i
+ * whose sum over K is C_i; a 4-element k-step holds two mixtures; chunks of PCL_MLLT_CHUNK K-elements (default 65536 for this side),
+ * waves and chunks added as above.  Then G_i = F_i - C_i, once per element of the full matrix, the lower triangle from the upper one's
+ * partials.  The occupancy of the mixtures: up to 1024 blocks each add a contiguous range (thread t its mixtures t, t + 256, .., a fixed
+ * tree), the blocks' sums are added likewise.
+ * From A = I, A^-1 = I, n_iter sweeps over the rows i = 0 .. D-1 -- fMLLR's sweep above with k = 0 and no offset column, the same kernel:
+ *   1. c = column i of A^-1: the cofactor row up to scale
+ *   2. v = G_i^-1 c through the Cholesky factor G_i = L L^T (factored once per i: one wave each);  a = sum_q c_q v_q  (ascending q)
+ *   3. alpha = sqrt(4 a beta) / (2 a)  (= sqrt(beta / (c . v)): with k = 0 fMLLR's two roots are +- this and the + root is taken)
+ *   4. a_i = alpha v
+ *   5. A^-1 by fMLLR's rank-one update; every sweep ENDS with the full re-inversion of A with row pivoting, which gives ln|det A|
+ * q_trace has n_iter + 1 entries: entry 0 is Q(I) = -1/2 sum_i G_i[i,i], entry s is Q after sweep s.
+ * The estimate is REFUSED -- A = I, ln|det A| = 0, NaN in q_trace and a non-zero status -- when, tested in this order,
+ *     PCL_MLLT_LOW_OCCUPANCY          beta < min_occ
+ *     PCL_MLLT_NOT_POSITIVE_DEFINITE  a Cholesky pivot of any G_i is not finite or not > 0
+ *     PCL_MLLT_SINGULAR               PCL_FMLLR_SINGULAR's conditions
+ * The status is decided before anything is written.  G_out (D, D, D) and occ_out (2,) = (beta, sum of acc) are given either way.
+ * A_out (D, D), logdet_out (1,), q_trace_out (n_iter + 1,), status_out (1,) int32: NULLs are skipped.  1 <= n_iter <= 1000; min_occ finite
+ * and >= 0; D <= 48.  Neither the model nor the statistics are changed.
+ *
+ * APPLY.  No call of its own: pcl_frames_transform with one speaker and pcl_model_transform_means with one class take W = [0 | A], and
+ * ln P(O) of the transformed frames is comparable after adding (frames) x ln|det A|.  The VARIANCES ARE NOT TRANSFORMED: diag(A Sigma A^T)
+ * would need a full covariance per mixture.  The next M-step on the transformed frames re-estimates them (as Kaldi's recipes do after
+ * est-mllt); until then the model's variances are those of the old space.
+ *
+ * No model / no statistics (never made, or dropped): PCL_ERR_STATE.  D > 48, n_iter or min_occ out of range: PCL_ERR_INVALID.  All checked
+ * before anything is changed.  Synchronous.  pcl_kernel_time groups: "mllt" (every kernel of each call), "mllt_frames" (the per-frame
+ * reduction), "mllt_gk" (both GEMMs and their reductions), "mllt_solve" (factorisations and sweeps). */
+#define PCL_MLLT_OK 0
+#define PCL_MLLT_LOW_OCCUPANCY 1
+#define PCL_MLLT_NOT_POSITIVE_DEFINITE 2
+#define PCL_MLLT_SINGULAR 3
+int pcl_mllt_zero(pcl_ctx *ctx, const int32_t *state_keep /* J or NULL */);
+int pcl_batch_accumulate_mllt(pcl_batch *b, const int32_t *utt_keep /* U or NULL; 0 = skip */);
+int pcl_mllt_stats_download(pcl_ctx *ctx, double *F /* D*D*D or NULL */, double *beta /* 1 or NULL */);
+int pcl_mllt_estimate(pcl_ctx *ctx, int n_iter, double min_occ, double *A_out /* D*D */, double *logdet_out, double *q_trace_out /* n_iter+1 */,
+                      double *G_out /* D*D*D or NULL */, double *occ_out /* 2: beta, sum acc */, int32_t *status_out);
 
 /* ----------------------------------------------------------------- LDA (row f12): class statistics of spliced frames, projection to a new width
  * Linear discriminant analysis of the resident frames (csrc/frame_lda.hip): the step between the front-end's static cepstra and fMLLR in a

@@ -618,6 +618,91 @@ class AcousticModel(DataInitialization):
         out['W'], out['logdet'] = W_run, logdet_run
         return out
 
+    def mllt_batch(self, labels, data_list, unit_hmms, iterations=1, n_iter=20, min_occ=1000.0, state_keep=None, precision=PCL_F64, engine=None,
+                   c_covariance=1e-3):
+        """MLLT on the device: ONE square transform A of the features for all utterances (Engine.mllt_estimate; the rule:
+        include/poccala_hip.h), applied to the engine's resident frames AND to the model's means.  The step between lda_batch and
+        fmllr_batch.
+
+        Per iteration:
+          1. an E-step on the current frames (score + forward-backward) with Batch.accumulate and Batch.accumulate_mllt on the same batch;
+          2. the estimate (n_iter row sweeps, refused below min_occ);
+          3. Engine.transform_frames and Engine.transform_means with [0 | A] -- the variances are left alone;
+          4. a second E-step on the new frames and Engine.mstep(c_covariance), which re-estimates the variances there (c_covariance is
+             the M-step's variance floor, as everywhere else).
+        The transforms are composed on the host.  The units' GMM objects follow the device after every change.
+
+        state_keep (J,): 0 = the state is left out of the statistics; it is transformed like the others.
+        data_list: (T_u, D) arrays (uploaded once, as float64), or the (lens, begin) of resident frames, so that lda_batch -> flat start /
+        EM -> mllt_batch uploads no frame.
+        Raises ValueError when the two occupancies of an estimate differ by more than 1e-3 relative: the frame side and the statistics
+        block did not see the same posteriors.
+
+        Returns a dict:
+          logp              iterations + 1 totals of ln P(O) + F ln|det A_composed|: of the model and frames as given, then after every
+                            iteration's M-step.  F = the frames the sentence HMMs emit (the E-step's total occupancy), so the entries
+                            are comparable.
+          logp_transformed  per iteration the same total right after step 3, before the M-step.  It is never below the iteration's logp
+                            entry: that is what EM promises of the transform.
+          A, logdet         the composed transform (D, D) and its ln|det|.
+          A_iter            per iteration the A the estimate gave (A = A_iter[-1] .. A_iter[0]).
+          status, q_trace, occ   per iteration what Engine.mllt_estimate returned under these names.
+        logp may FALL from the second iteration on.  The M-step sets the variances to second moments, and the reference's log density
+        (util.py:29) carries -1/2 sum(var), not -1/2 sum(ln var), in its constant, so those variances do not maximise it.  With a proper
+        Gaussian constant both steps would raise it (DESIGN.md section 7 (f13) has the figures)."""
+        engine = engine or default_engine()
+        if len(labels) != self._utt_count(data_list):
+            raise ValueError('mllt_batch: one label sequence per utterance')
+        keep = self._nonempty(data_list)
+        if len(keep) < self._utt_count(data_list):          # empty utterances add nothing to the statistics
+            labels, data_list = [labels[u] for u in keep], self._utt_subset(data_list, keep)
+        res = self._resident(data_list)
+        if res is None:                                      # uploaded ONCE: every later pass reads what the last one left resident
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d, dtype=np.float64) for d in data_list], axis=0))
+        else:
+            lens, begin = np.asarray(res[0], dtype=np.int32), np.asarray(res[1], dtype=np.int64)
+        D = int(engine.FD)
+        A_run, logdet_run = np.eye(D), 0.0
+        one = np.zeros(len(lens), dtype=np.int32)
+        out = dict(logp=[], logp_transformed=[], status=[], q_trace=[], occ=[], A_iter=[])
+
+        def estep(key):
+            b, _, units, _ = self._sentence_batch(labels, (lens, begin), unit_hmms, engine)
+            b.score(precision)
+            b.forward_backward()
+            engine.stats_zero()
+            b.accumulate(precision)
+            emitted = float(engine.stats_download(moments=False)['acc'].sum())   # every emitted frame carries one ln|det A|
+            out[key].append(float(np.sum(b.get('logp'))) + emitted * logdet_run)
+            return b, units
+
+        for _ in range(int(iterations)):
+            b, units = estep('logp')
+            engine.mllt_zero(state_keep)
+            b.accumulate_mllt()
+            b.close()
+            est = engine.mllt_estimate(n_iter, min_occ)
+            beta, occ = float(est['occ'][0]), float(est['occ'][1])
+            if abs(beta - occ) > 1e-3 * max(abs(beta), abs(occ)):
+                raise ValueError('mllt_batch: the frames\' occupancy %.9g and the statistics block\'s %.9g differ by more than 1e-3: the two '
+                                 'sides of G did not see the same posteriors' % (beta, occ))
+            W = np.concatenate([np.zeros((D, 1)), est['A']], axis=1)[None]
+            engine.transform_frames(lens, begin, one, W)
+            engine.transform_means(W)
+            self._adopt_model(engine.model_download(), units, unit_hmms)
+            A_run, logdet_run = est['A'].dot(A_run), logdet_run + est['logdet']
+            out['status'].append(est['status']), out['q_trace'].append(est['q_trace']), out['occ'].append(est['occ']), out['A_iter'].append(est['A'])
+            b, units = estep('logp_transformed')                       # the statistics of the transformed frames: the variances of the new space
+            b.close()
+            engine.mstep(c_covariance)
+            self._adopt_model(engine.model_download(), units, unit_hmms)
+        b, units = estep('logp')
+        b.close()
+        out['A'], out['logdet'] = A_run, logdet_run
+        return out
+
     def lda_batch(self, labels, data_list, unit_hmms, D_out, left=4, right=4, state_class=None, eps=1e-10, precision=PCL_F64, engine=None):
         """LDA on the device, beside flat_start_batch: forced alignment of the labelled utterances with the units' current model, the class
         statistics of the spliced frames from the Viterbi owner map (Batch.accumulate_lda: every GMM state its own class, or state_class

@@ -76,6 +76,10 @@ PROTOTYPES = {
     'pcl_fmllr_stats_download': (_i, [_vp, _vp, _vp, _vp]),
     'pcl_fmllr_estimate': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp]),
     'pcl_frames_transform': (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
+    'pcl_mllt_zero': (_i, [_vp, _vp]),
+    'pcl_batch_accumulate_mllt': (_i, [_vp, _vp]),
+    'pcl_mllt_stats_download': (_i, [_vp, _vp, _vp]),
+    'pcl_mllt_estimate': (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcl_lda_zero': (_i, [_vp, _i, _i, _i]),
     'pcl_lda_accumulate': (_i, [_vp, _i, _vp, _vp, _vp]),
     'pcl_batch_accumulate_lda': (_i, [_vp, _vp]),

@@ -32,15 +32,26 @@ constexpr int APPLY_TF = 32;                  // frames per workgroup of the app
 // dimensions whose sums the workgroup keeps -- all 2 D + 1 sums of a frame beside the posterior's operands need more than 256 VGPRs per lane,
 // and hipcc's AGPR spill code for 64-bit values is what gmm_accumulate_kernel's float64 path had to avoid; each half forms the posterior
 // itself, with the same bits.  Outputs at the frame's VIRTUAL index v = vbase[u] + t (the call's frames in speaker order): P[v][i], Q[v][i], B[v], vrow[v] = its row.
-template <int DP, int NH>
+// MLLT (compile time; row f13, frame_mllt.hip): the same reduction without q -- a frame's D + 1 sums fit the registers, so NH = 1 -- and
+// with a mask over the states: a row whose state has keep[j] == 0 is passed over like an entry row.  MLLT = false does not read `keep`.
+// The MLLT = true instantiations are compiled in a translation unit of their own (frame_mllt.hip defines PCL_FRAME_MLLT and includes this
+// file), so the fMLLR kernels come out as they did before there was a switch.
+template <bool MLLT>
+struct MlltKeep {};
+template <>
+struct MlltKeep<true> {
+    const int32_t *keep;                      // J entries, or nullptr = every state
+};
+template <int DP, int NH, bool MLLT>
 __global__ __launch_bounds__(256) void fmllr_frames_kernel(const UttDesc *__restrict__ utt, const int32_t *__restrict__ row_state,
                                                            const int *__restrict__ vbase, const double *__restrict__ Bt,
                                                            const double *__restrict__ lgam, const double *__restrict__ x64,
                                                            const float *__restrict__ x32, int FD, const double *__restrict__ params,
                                                            int prow, const double *__restrict__ w64, int M, int Mpad, int Dh,
                                                            double *__restrict__ P, double *__restrict__ Q, double *__restrict__ Bv,
-                                                           long long *__restrict__ vrow) {
-    constexpr int DH = (DP + NH - 1) / NH, NOUT = 2 * DH + 1;
+                                                           long long *__restrict__ vrow, MlltKeep<MLLT> mk) {
+    constexpr int DH = (DP + NH - 1) / NH, NOUT = (MLLT ? DH : 2 * DH) + 1;
+    static_assert(!MLLT || NH == 1, "without q one workgroup keeps every sum of its frames");
     static_assert(2 * (NH * DH) <= (2 * DP + 1 + 3) / 4 * 4, "the last half may read the row's constant and padding as if they were s and c (never stored)");
     static_assert(NOUT >= DP, "the frames share the sums' LDS");
     const int d0 = blockIdx.z * DH;
@@ -70,6 +81,8 @@ __global__ __launch_bounds__(256) void fmllr_frames_kernel(const UttDesc *__rest
     for (int n = 0; n < ud.N; ++n) {
         const int j = __builtin_amdgcn_readfirstlane(row_state[ud.vec_off + n]);
         if (j < 0) continue;                                      // entry / exit rows
+        if constexpr (MLLT)
+            if (mk.keep && mk.keep[j] == 0) continue;             // (uniform: j is)
         double cf = -INFINITY;
         if (valid) {
             const double lg = lgam[ud.b_off + (long long)t * ud.N + n], lb = Bt[ud.b_off + (long long)t * ud.N + n];
@@ -93,7 +106,7 @@ __global__ __launch_bounds__(256) void fmllr_frames_kernel(const UttDesc *__rest
             for (int d = 0; d < DH; ++d) {
                 const double gs = g * pr[2 * (d0 + d)];
                 ap[d] = __builtin_fma(gs, pr[2 * (d0 + d)], ap[d]);
-                aq[d] = __builtin_fma(gs, pr[2 * (d0 + d) + 1], aq[d]);
+                if constexpr (!MLLT) aq[d] = __builtin_fma(gs, pr[2 * (d0 + d) + 1], aq[d]);
             }
         }
     }
@@ -105,23 +118,23 @@ __global__ __launch_bounds__(256) void fmllr_frames_kernel(const UttDesc *__rest
 #pragma unroll
                 for (int d = 0; d < DH; ++d) {
                     sh[d * FT + lane] = ap[d];
-                    sh[(DH + d) * FT + lane] = aq[d];
+                    if constexpr (!MLLT) sh[(DH + d) * FT + lane] = aq[d];
                 }
-                sh[2 * DH * FT + lane] = ab;
+                sh[(NOUT - 1) * FT + lane] = ab;
             } else {
 #pragma unroll
                 for (int d = 0; d < DH; ++d) {
                     ap[d] = sh[d * FT + lane] + ap[d];
-                    aq[d] = sh[(DH + d) * FT + lane] + aq[d];
+                    if constexpr (!MLLT) aq[d] = sh[(DH + d) * FT + lane] + aq[d];
                 }
-                ab = sh[2 * DH * FT + lane] + ab;
+                ab = sh[(NOUT - 1) * FT + lane] + ab;
                 if (w < 3) {
 #pragma unroll
                     for (int d = 0; d < DH; ++d) {
                         sh[d * FT + lane] = ap[d];
-                        sh[(DH + d) * FT + lane] = aq[d];
+                        if constexpr (!MLLT) sh[(DH + d) * FT + lane] = aq[d];
                     }
-                    sh[2 * DH * FT + lane] = ab;
+                    sh[(NOUT - 1) * FT + lane] = ab;
                 }
             }
         }
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(256) void fmllr_frames_kernel(const UttDesc *__rest
         for (int d = 0; d < DH; ++d)
             if (d0 + d < Dh) {
                 P[v * Dh + d0 + d] = TWO_LN2 * ap[d];
-                Q[v * Dh + d0 + d] = -(TWO_LN2 * aq[d]);
+                if constexpr (!MLLT) Q[v * Dh + d0 + d] = -(TWO_LN2 * aq[d]);
             }
         if (blockIdx.z == 0) {
             Bv[v] = ab;
@@ -265,29 +278,34 @@ __device__ bool invert_in_place(double (*Ai)[LDA], int Dh, double *colk, int *pe
 }
 
 // One wave per speaker: the sweeps, in LDS.  L[s][i] (the Cholesky factor of G[s,i]) is staged per row update; Gk is read through L2 for Q.
+// MLLT (compile time; row f13): the same sweeps with k = 0 and no offset column -- W is the square A (n = D), G[s,i] is D x D with no k
+// column behind its rows, g = G^-1 k is 0 and is not read -- and a trace of n_iter + 1 entries whose first is Q at the start, A = I.
+// Instantiated in frame_mllt.hip, as the frame reduction's MLLT form is.
+template <bool MLLT>
 __global__ __launch_bounds__(64) void fmllr_sweep_kernel(const double *__restrict__ Gk, const double *__restrict__ Lall, const double *__restrict__ gkall,
                                                          const double *__restrict__ beta_all, int Dh, int n_iter, int *__restrict__ status,
                                                          double *__restrict__ W_out, double *__restrict__ logdet_out, double *__restrict__ qtrace) {
     __shared__ double Ls[LDA][LDA + 1], Ai[ADAPT_D_MAX][LDA], Wl[ADAPT_D_MAX][LDA + 1];
     __shared__ double vv[64], pv[64], gki[64], wn[64], ucol[64], zrow[64], colk[64];
     __shared__ int perm[64];
-    const int s = blockIdx.x, n = Dh + 1, tid = threadIdx.x;
+    constexpr int O = MLLT ? 0 : 1;                               // columns in front of A in a row of W
+    const int s = blockIdx.x, n = Dh + O, gs = MLLT ? n : n + 1, nq = MLLT ? n_iter + 1 : n_iter, tid = threadIdx.x;
     int st = status[s];
     const double beta = beta_all[s];
     double logdet = 0.0;
-    for (int x = tid; x < Dh * n; x += 64) Wl[x / n][x % n] = (x % n == x / n + 1) ? 1.0 : 0.0;
+    for (int x = tid; x < Dh * n; x += 64) Wl[x / n][x % n] = (x % n == x / n + O) ? 1.0 : 0.0;
     for (int x = tid; x < Dh * Dh; x += 64) Ai[x / Dh][x % Dh] = (x % Dh == x / Dh) ? 1.0 : 0.0;
     __syncthreads();
-    for (int it = 0; it < n_iter && st == PCL_FMLLR_OK; ++it) {
-        for (int i = 0; i < Dh && st == PCL_FMLLR_OK; ++i) {
+    for (int it = MLLT ? -1 : 0; it < n_iter && st == PCL_FMLLR_OK; ++it) {   // (MLLT: pass -1 only forms Q of the start)
+        for (int i = 0; it >= 0 && i < Dh && st == PCL_FMLLR_OK; ++i) {
             const size_t pair = (size_t)s * Dh + i;
             for (int x = tid; x < n * n; x += 64) Ls[x / n][x % n] = Lall[pair * n * n + x];
             if (tid < n) {
-                const double p = tid == 0 ? 0.0 : Ai[tid - 1][i];  // p = (0, column i of A^-1)
+                const double p = (O && tid == 0) ? 0.0 : Ai[tid - O][i];   // p = (0, column i of A^-1)
                 pv[tid] = p;
                 vv[tid] = p;
-                gki[tid] = gkall[pair * n + tid];
-                if (tid > 0) ucol[tid - 1] = p;
+                gki[tid] = MLLT ? 0.0 : gkall[pair * n + tid];
+                if (tid >= O) ucol[tid - O] = p;
             }
             __syncthreads();
             for (int j = 0; j < n; ++j) {                         // L y = p
@@ -325,14 +343,14 @@ __global__ __launch_bounds__(64) void fmllr_sweep_kernel(const double *__restric
             if (tid < n) wn[tid] = alpha * vv[tid] + gki[tid];
             __syncthreads();
             double denom = 0.0;                                   // w_new . (column i of A^-1) = det A_new / det A
-            for (int q = 0; q < Dh; ++q) denom = denom + wn[1 + q] * ucol[q];
+            for (int q = 0; q < Dh; ++q) denom = denom + wn[O + q] * ucol[q];
             if (!(fabs(denom) > 0.0 && fabs(denom) < INFINITY)) {
                 st = PCL_FMLLR_SINGULAR;
                 break;
             }
             if (tid < Dh) {                                       // z = (w_new - w_old) A^-1, then A^-1 <- A^-1 - u z / denom
                 double z = 0.0;
-                for (int q = 0; q < Dh; ++q) z = z + (wn[1 + q] - Wl[i][1 + q]) * Ai[q][tid];
+                for (int q = 0; q < Dh; ++q) z = z + (wn[O + q] - Wl[i][O + q]) * Ai[q][tid];
                 zrow[tid] = z / denom;
             }
             __syncthreads();
@@ -342,25 +360,27 @@ __global__ __launch_bounds__(64) void fmllr_sweep_kernel(const double *__restric
             __syncthreads();
         }
         if (st != PCL_FMLLR_OK) break;
-        for (int x = tid; x < Dh * Dh; x += 64) Ai[x / Dh][x % Dh] = Wl[x / Dh][1 + x % Dh];       // the full re-inversion that ends every sweep
-        __syncthreads();
-        if (!invert_in_place(Ai, Dh, colk, perm, &logdet)) {
-            st = PCL_FMLLR_SINGULAR;
-            break;
+        if (it >= 0) {
+            for (int x = tid; x < Dh * Dh; x += 64) Ai[x / Dh][x % Dh] = Wl[x / Dh][O + x % Dh];   // the full re-inversion that ends every sweep
+            __syncthreads();
+            if (!invert_in_place(Ai, Dh, colk, perm, &logdet)) {
+                st = PCL_FMLLR_SINGULAR;
+                break;
+            }
         }
         double quad = 0.0;                                        // Q = beta ln|det A| - 1/2 sum_i (w_i G_i w_i^T - 2 w_i k_i^T)
         for (int i = 0; i < Dh; ++i) {
-            const double *G = Gk + ((size_t)s * Dh + i) * n * (n + 1);
+            const double *G = Gk + ((size_t)s * Dh + i) * n * gs;
             __syncthreads();
             if (tid < n) {
                 double t = 0.0;
-                for (int q = 0; q < n; ++q) t = t + G[tid * (n + 1) + q] * Wl[i][q];
-                vv[tid] = Wl[i][tid] * t - 2.0 * (Wl[i][tid] * G[tid * (n + 1) + n]);
+                for (int q = 0; q < n; ++q) t = t + G[tid * gs + q] * Wl[i][q];
+                vv[tid] = MLLT ? Wl[i][tid] * t : Wl[i][tid] * t - 2.0 * (Wl[i][tid] * G[tid * gs + n]);
             }
             __syncthreads();
             for (int q = 0; q < n; ++q) quad = quad + vv[q];
         }
-        if (tid == 0) qtrace[(size_t)s * n_iter + it] = beta * logdet - 0.5 * quad;
+        if (tid == 0) qtrace[(size_t)s * nq + it + (MLLT ? 1 : 0)] = beta * logdet - 0.5 * quad;
     }
     __syncthreads();
     // statuses are decided: now, and only now, the outputs are written
@@ -369,11 +389,12 @@ __global__ __launch_bounds__(64) void fmllr_sweep_kernel(const double *__restric
         logdet_out[s] = st == PCL_FMLLR_OK ? logdet : 0.0;
     }
     if (st != PCL_FMLLR_OK)
-        for (int x = tid; x < n_iter; x += 64) qtrace[(size_t)s * n_iter + x] = NAN;
+        for (int x = tid; x < nq; x += 64) qtrace[(size_t)s * nq + x] = NAN;
     for (int x = tid; x < Dh * n; x += 64)
-        W_out[(size_t)s * Dh * n + x] = st == PCL_FMLLR_OK ? Wl[x / n][x % n] : ((x % n == x / n + 1) ? 1.0 : 0.0);
+        W_out[(size_t)s * Dh * n + x] = st == PCL_FMLLR_OK ? Wl[x / n][x % n] : ((x % n == x / n + O) ? 1.0 : 0.0);
 }
 
+#ifndef PCL_FRAME_MLLT
 // ---------------------------------------------------------------- apply
 // y = b + A x for the frames of utterance u, one workgroup per (32-frame tile, utterance): W of the speaker and the tile's rows are staged
 // in LDS, so the update is in place.  The sum runs b, then the terms in ascending feature order, one rounded product and one rounded sum each.
@@ -407,9 +428,11 @@ const char *fmllr_ready(pcl_ctx *ctx) {       // nullptr, or why the statistics 
     if (!ctx->fmllr_Gk || ctx->fmllr_S <= 0) return "no statistics: pcl_fmllr_zero first (a new model or a frame matrix of another dimension dropped them)";
     return nullptr;
 }
+#endif  // PCL_FRAME_MLLT
 
 }  // namespace
 
+#ifndef PCL_FRAME_MLLT
 void pcl_fmllr_release(pcl_ctx *ctx) {
     ctx->fmllr_Gk.release();
     ctx->fmllr_beta.release();
@@ -500,8 +523,8 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
     {
         const unsigned tiles = (unsigned)((b->Tmax + FT - 1) / FT);
 #define FRAMES_CASE(DP, NH)                                                                                                                              \
-    hipLaunchKernelGGL((fmllr_frames_kernel<DP, NH>), dim3(tiles, (unsigned)U, NH), dim3(256), 0, st, b->d_utt, b->d_row_state, d_lists, b->Bt, b->lgam, ctx->frames64, ctx->frames32, \
-                       ctx->FD, ctx->params64, ctx->row, ctx->w64, ctx->M, ctx->Mpad, Dh, d_P, d_Q, d_B, d_vrow)
+    hipLaunchKernelGGL((fmllr_frames_kernel<DP, NH, false>), dim3(tiles, (unsigned)U, NH), dim3(256), 0, st, b->d_utt, b->d_row_state, d_lists, b->Bt, b->lgam, ctx->frames64, ctx->frames32, \
+                       ctx->FD, ctx->params64, ctx->row, ctx->w64, ctx->M, ctx->Mpad, Dh, d_P, d_Q, d_B, d_vrow, MlltKeep<false>{})
         switch (ctx->D) {                                         // (pcl_device_dim of a dimension <= 48)
             case 13: FRAMES_CASE(13, 1); break;
             case 26: FRAMES_CASE(26, 1); break;
@@ -571,7 +594,7 @@ extern "C" int pcl_fmllr_estimate(pcl_ctx *ctx, int n_iter, double min_occ, doub
     hipLaunchKernelGGL(fmllr_occ_kernel, dim3((S + 63) / 64), dim3(64), 0, st, ctx->fmllr_beta, S, min_occ, d_status);
     hipLaunchKernelGGL(gk_solve_kernel, dim3(S * Dh), dim3(64), 0, st, ctx->fmllr_Gk, d_status, Dh, d_gk, d_pivot, d_L);
     hipLaunchKernelGGL(fmllr_pivot_kernel, dim3((S + 63) / 64), dim3(64), 0, st, d_pivot, S, Dh, d_status);
-    hipLaunchKernelGGL(fmllr_sweep_kernel, dim3(S), dim3(64), 0, st, ctx->fmllr_Gk, d_L, d_gk, ctx->fmllr_beta, Dh, n_iter, d_status, d_W, d_logdet, d_q);
+    hipLaunchKernelGGL(fmllr_sweep_kernel<false>, dim3(S), dim3(64), 0, st, ctx->fmllr_Gk, d_L, d_gk, ctx->fmllr_beta, Dh, n_iter, d_status, d_W, d_logdet, d_q);
     pcl_timer_end(ctx, "fmllr_solve");
     pcl_timer_end(ctx, "fmllr");
     HIPCHK(ctx, hipGetLastError());
@@ -636,3 +659,4 @@ extern "C" int pcl_frames_transform(pcl_ctx *ctx, int U, const int32_t *T, const
     HIPCHK(ctx, hipStreamSynchronize(st));
     return PCL_OK;
 }
+#endif  // PCL_FRAME_MLLT

@@ -413,6 +413,7 @@ void pcl_frames_adopt(pcl_ctx *ctx, DevBuf<float> &&f32, DevBuf<double> &&f64, i
     ctx->FD = device_dim(D);
     ctx->FDhost = D;
     if (ctx->fmllr_Gk && D != ctx->Dhost) pcl_fmllr_release(ctx);
+    if (ctx->mllt_F && D != ctx->Dhost) pcl_mllt_release(ctx);
 }
 
 // The first half of pcl_model_upload (also bootstrap.hip: a model made on the device): the old model goes, the master copy and every derived
@@ -546,6 +547,7 @@ int pcl_frames_upload(pcl_ctx *ctx, int64_t F, int D, const void *frames, int dt
     ctx->FD = Dd;
     ctx->FDhost = D;
     if (ctx->fmllr_Gk && D != ctx->Dhost) pcl_fmllr_release(ctx);   // fMLLR statistics describe frames of the model's dimension
+    if (ctx->mllt_F && D != ctx->Dhost) pcl_mllt_release(ctx);      // ... and so do MLLT's
     return PCL_OK;
 }
 
@@ -593,6 +595,7 @@ int pcl_frames_swap(pcl_ctx *ctx) {
     ctx->F = ctx->staged_F;
     ctx->FDhost = ctx->staged_D;
     if (ctx->fmllr_Gk && ctx->FDhost != ctx->Dhost) pcl_fmllr_release(ctx);
+    if (ctx->mllt_F && ctx->FDhost != ctx->Dhost) pcl_mllt_release(ctx);
     ctx->FD = device_dim(ctx->staged_D);
     ctx->staged_slot = -1;
     return PCL_OK;
@@ -1557,6 +1560,19 @@ int pcl_batch_accumulate_fmllr(pcl_batch *b, const int32_t *utt_speaker) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TRY(pcl_ensure_layouts(ctx, PCL_LAYOUT_P64));
     const int rc = pcl_launch_fmllr_accumulate(ctx, b, utt_speaker);
+    if (rc == PCL_OK) HIPCHK(ctx, pcl_batch_mark(b));
+    return rc;
+}
+
+// MLLT statistics of the batch's utterances (frame_mllt.hip): the frame side of G_i, from the posteriors pcl_batch_accumulate reads
+int pcl_batch_accumulate_mllt(pcl_batch *b, const int32_t *utt_keep) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    TRY(batch_join(b));
+    TRY(accumulate_precheck(b, PCL_F64, "pcl_batch_accumulate_mllt"));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TRY(pcl_ensure_layouts(ctx, PCL_LAYOUT_P64));
+    const int rc = pcl_launch_mllt_accumulate(ctx, b, utt_keep);
     if (rc == PCL_OK) HIPCHK(ctx, pcl_batch_mark(b));
     return rc;
 }

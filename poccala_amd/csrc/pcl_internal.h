@@ -125,6 +125,10 @@ struct ModelDev {
     DevBuf<double> fmllr_beta;   // [fmllr_S] occupancies
     DevBuf<double> fmllr_W;      // the last pcl_fmllr_estimate's transforms [fmllr_S][Dhost][Dhost + 1]; pcl_fmllr_zero drops it
     DevBuf<double> mllr_W;       // the last pcl_mllr_estimate's transforms [mllr_R][Dhost][Dhost + 1] (model_adapt.hip): gone with the model they were estimated for
+    DevBuf<double> mllt_F;       // MLLT statistics (frame_mllt.hip): the frame side F[Dhost][Dhost][Dhost], full symmetric matrices; gone with the model
+    DevBuf<double> mllt_beta;    // [1] their occupancy
+    DevBuf<int> mllt_keep;       // [J] pcl_mllt_zero's state_keep on the device (empty: every state is kept) ...
+    std::vector<int32_t> mllt_keep_host;   // ... and on the host, for the estimate's walk over the kept states' mixtures
 };
 // Coarse layout of the off-pipe mixtures (gmm_score_coarse.hip): their bound v_up on the matrix pipe, exact evaluation of what it
 // cannot rule out.  Derived on first use after the model changed (coarse_gen != model_gen).
@@ -552,6 +556,8 @@ int pcl_launch_clock_probe(pcl_ctx *ctx, int spin_us, unsigned long long *d_out)
 int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision);
 int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_speaker);   // frame_adapt.hip, behind pcl_batch_accumulate_fmllr's checks
 void pcl_fmllr_release(pcl_ctx *ctx);                // the fMLLR statistics and estimate (a frame matrix of another dimension)
+int pcl_launch_mllt_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_keep);        // frame_mllt.hip, behind pcl_batch_accumulate_mllt's checks
+void pcl_mllt_release(pcl_ctx *ctx);                 // the MLLT statistics (a frame matrix of another dimension)
 void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate scratch (pcl_destroy, pcl_model_upload)
 // frame_lda.hip, behind the checks of pcl_lda_accumulate / pcl_batch_accumulate_lda: d_src (rows of the frame matrix, on the device) = the
 // class of every row, or with state_class (host, J entries) its owner state; -1 = not kept

@@ -552,6 +552,36 @@ class Engine(object):
         self._check(self._lib.pcl_frames_transform(self._ctx, T.size, ptr(T), ptr(fb), ptr(spk), S, ptr(W)))
         self._frames_key = None                      # the resident frames are no longer what was uploaded
 
+    # ------------------------------------------------------------------ MLLT: one square transform of the features for the whole corpus
+    def mllt_zero(self, state_keep=None):
+        """Make (or clear) the context's MLLT statistics for the resident model (pcl_mllt_zero): state_keep (J,), 0 = the state -- silence,
+        say -- is left out of both sides of G; None = every state counts."""
+        sk = None
+        if state_keep is not None:
+            sk = as_c(np.asarray(state_keep) != 0, np.int32).reshape(-1)
+            if sk.shape != (self.J,):
+                raise ValueError('state_keep must hold one entry per state (J = %d), got %s' % (self.J, sk.shape))
+        self._check(self._lib.pcl_mllt_zero(self._ctx, ptr(sk)))
+
+    def mllt_stats(self):
+        """(F (D, D, D), beta): the frame side of G and its occupancy, what Batch.accumulate_mllt has summed since mllt_zero."""
+        D = self.D
+        F, beta = np.empty((D, D, D)), np.empty(1)
+        self._check(self._lib.pcl_mllt_stats_download(self._ctx, ptr(F), ptr(beta)))
+        return F, float(beta[0])
+
+    def mllt_estimate(self, n_iter=20, min_occ=1000.0):
+        """The MLLT matrix from the resident statistics (pcl_mllt_estimate; the rule: include/poccala_hip.h): G_i = F_i - C_i with the
+        mixture side C_i from the E-step statistics block and the model, then n_iter row sweeps from A = I.  Returns a dict: A (D, D),
+        logdet = ln|det A|, q_trace (n_iter + 1,) = the auxiliary value at A = I and after every sweep, G (D, D, D), occ = (beta of
+        the frames, sum of acc over the kept contributing mixtures), status: 0, or why the estimate was refused and A = I: 1 beta
+        below min_occ, 2 a G_i not positive definite, 3 a singular step.  Neither the model nor the frames are changed: apply A with
+        transform_frames(T, begin, zeros, W) and transform_means(W), W = [0 | A][None]."""
+        D, K = self.D, max(int(n_iter), 1) + 1
+        A, logdet, q, G, occ, status = np.empty((D, D)), np.empty(1), np.empty(K), np.empty((D, D, D)), np.empty(2), np.empty(1, dtype=np.int32)
+        self._check(self._lib.pcl_mllt_estimate(self._ctx, int(n_iter), float(min_occ), ptr(A), ptr(logdet), ptr(q), ptr(G), ptr(occ), ptr(status)))
+        return dict(A=A, logdet=float(logdet[0]), q_trace=q, G=G, occ=occ, status=int(status[0]))
+
     # ------------------------------------------------------------------ LDA: class statistics of spliced frames, projection to a new width
     def lda_zero(self, n_classes, left, right):
         """Make (and clear) the context's LDA class statistics (pcl_lda_zero) for n_classes classes and the splice context (left, right)
@@ -880,6 +910,17 @@ class Batch(object):
         if spk.shape != (self.U,):
             raise ValueError('utt_speaker must hold one speaker per utterance (U = %d), got %s' % (self.U, spk.shape))
         self._check(self._lib.pcl_batch_accumulate_fmllr(self._b, ptr(spk)))
+
+    def accumulate_mllt(self, utt_keep=None):
+        """The frame side of the MLLT statistics from this batch's posteriors into the sums of the last Engine.mllt_zero
+        (pcl_batch_accumulate_mllt): utt_keep (U,), 0 = leave the utterance out, None = all.  Needs score() and forward_backward() (or
+        set_posteriors); run accumulate() on the same batch -- the estimate takes the mixture side from the E-step statistics."""
+        uk = None
+        if utt_keep is not None:
+            uk = as_c(np.asarray(utt_keep) != 0, np.int32).reshape(-1)
+            if uk.shape != (self.U,):
+                raise ValueError('utt_keep must hold one entry per utterance (U = %d), got %s' % (self.U, uk.shape))
+        self._check(self._lib.pcl_batch_accumulate_mllt(self._b, ptr(uk)))
 
     def accumulate_lda(self, state_class=None):
         """LDA class statistics from this batch's Viterbi paths (pcl_batch_accumulate_lda) into the sums of the last Engine.lda_zero: every
