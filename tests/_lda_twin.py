@@ -1,6 +1,6 @@
 """NumPy float64 twin of csrc/frame_lda.hip and Engine.lda_estimate (row f12; the rule: include/poccala_hip.h): splice, class
-statistics, the LDA estimate, the projection.  tests/test_lda_twin.py holds its own invariants; tests/test_gpu_lda.py compares the device
-with it."""
+statistics, the LDA estimate, the projection.  tests/test_lda_twin.py holds its own invariants; tests/test_gpu_lda.py and
+tests/test_gpu_lda_edges.py compare the device with it."""
 import numpy as np
 
 
@@ -168,3 +168,94 @@ def planted_case(seed=7, D=3, left=1, right=1, R=4, U=12, T_each=60):
         cls[begin[u]:begin[u] + T_each] = c
     basis = np.concatenate([v] * (left + right + 1), axis=0)
     return frames, T, begin, cls, basis
+
+
+# ------------------------------------------------------------------ the edges of the device's tiling (tests/test_gpu_lda_edges.py)
+TILE, KSTEP_ROWS, STEP_ROWS, CHUNK_DEFAULT, ROUND = 16, 4, 32, 1024, 1024      # frame_lda.hip: a tile's order, rows per MFMA, KB, LDA_CHUNK_DEFAULT, LDA_ROUND
+
+# (D, left, right, order n = Ds + 1, tile rows NT): every NT the launcher has an instance for.  n = 16, 64, 112, 128: no zero padding column,
+# the ones column is the last column of the last tile; n = 17, 65: the ones column alone in its tile; n = 128: the cap
+EDGE_SHAPES = [(1, 0, 0, 2, 1), (5, 1, 1, 16, 1), (16, 0, 0, 17, 2), (13, 1, 1, 40, 3), (7, 4, 4, 64, 4), (16, 2, 1, 65, 5), (5, 9, 8, 91, 6),
+               (37, 1, 1, 112, 7), (1, 63, 63, 128, 8)]
+
+# one class per row count, an empty class in the middle and one at the end
+KEDGE_COUNTS = [1, 3, 4, 5, 15, 16, 17, 0, 31, 32, 33, 63, 64, 65, 97, 0]
+KEDGE_LENGTHS = [1, 2, 3, 9, 40, 64, 65, 130, 150]
+# PCL_LDA_CHUNK=1: class 0 ends ON the edge of round 0, class 1 is empty at that edge, class 2 lies in rounds 1 and 2
+ROUND_COUNTS = [1024, 0, 1500, 0, 30, 0]
+ROUND_LENGTHS = [1, 2, 3, 700, 900, 1000]
+# ... and at order 40 (6 tiles per chunk) the edge of round 0 falls inside class 2
+ROUND40_COUNTS = [1000, 0, 70, 0, 30, 0]
+ROUND40_LENGTHS = [1, 2, 3, 400, 750]
+LONG_ROWS = 64 * 256 + 300                                    # behind what one pass of the key kernel's grid covers
+LONG_LENGTHS = [5, LONG_ROWS, 3]
+# two projections in a row, (D, left, right, D_out) each: the first leaves 40 dimensions, held at a row stride of 47, for the second to splice
+CHAIN = [(13, 2, 1, 40), (40, 1, 0, 64)]
+DEVICE_DIMS = (13, 26, 39, 47, 48, 64)                        # the row strides the device holds a frame matrix at (pcl_api.hip, device_dim)
+LONG_PERIOD, LONG_R = 7, 6                                     # the class of row t of an utterance: t mod 7, 6 -> not kept
+
+
+def place(lengths, D, rng):
+    """make_case's layout for any list of lengths: gaps of 1 .. 3 rows between the utterances, rows of no utterance far from everything,
+    neighbouring utterances offset by +-1000.  -> frames (F, D), T, begin, owned (F,) bool"""
+    T = np.array(lengths, dtype=np.int32)
+    begin = np.empty(len(T), dtype=np.int64)
+    row = 3
+    for u, t in enumerate(T):
+        begin[u] = row
+        row += int(t) + int(rng.integers(1, 4))
+    F = row + 2
+    frames = rng.standard_normal((F, D)) * 5 + 7777.0
+    owned = np.zeros(F, dtype=bool)
+    for u, (t, b) in enumerate(zip(T, begin)):
+        frames[b:b + t] = rng.standard_normal((t, D)) + (1000.0 if u % 2 else -1000.0) + np.arange(D)
+        owned[b:b + t] = True
+    return frames, T, begin, owned
+
+
+def plant_case(D, lengths, counts, seed=0):
+    """Utterances of the given lengths with EXACTLY counts[r] rows of class r (0: an empty class), drawn without replacement from all
+    the utterances' rows, so that a class is scattered over the utterances; the utterances' other rows are -1.  Every row of NO utterance is
+    labelled with the last non-empty class: labelled, and not to be kept.  -> frames (F, D) float64, T, begin, frame_class (F,)"""
+    rng = np.random.default_rng(500 + seed + D)
+    counts = np.asarray(counts, dtype=np.int64)
+    frames, T, begin, owned = place(lengths, D, rng)
+    if counts.sum() > owned.sum() or (counts < 0).any() or not (counts > 0).any():
+        raise ValueError('%d rows to plant in utterances of %d rows' % (counts.sum(), owned.sum()))
+    cls = np.full(len(frames), -1, dtype=np.int32)
+    rows = rng.permutation(np.flatnonzero(owned))[:counts.sum()]
+    cls[rows] = np.repeat(np.arange(len(counts), dtype=np.int32), counts)
+    cls[~owned] = np.flatnonzero(counts > 0)[-1]
+    return frames, T, begin, cls
+
+
+def long_case(D=2, seed=0):
+    """One utterance of LONG_ROWS rows between two short ones; the class of row t of an utterance is t mod LONG_PERIOD (a period co-prime
+    to the key kernel's 256 threads and to the projection's 16-frame tiles), LONG_R = 6 classes, residue 6 not kept; rows of no utterance
+    labelled 0."""
+    frames, T, begin, owned = place(LONG_LENGTHS, D, np.random.default_rng(900 + seed + D))
+    cls = np.zeros(len(frames), dtype=np.int32)
+    for t, b in zip(T, begin):
+        c = np.arange(t, dtype=np.int32) % LONG_PERIOD
+        cls[b:b + t] = np.where(c < LONG_R, c, -1)
+    return frames, T, begin, cls
+
+
+def chunk_plan(counts, chunk=None, round_chunks=ROUND):
+    """How pcl_launch_lda_accumulate cuts class counts into K-chunks and launch rounds (chunk None: the default).  -> dict: rows (per chunk),
+    cls_chunk0 (R + 1,), chunks, rounds, split (the classes whose chunks lie in more than one round)"""
+    chunk = CHUNK_DEFAULT if chunk is None else int(chunk)
+    rows, cls_chunk0 = [], [0]
+    for c in np.asarray(counts, dtype=np.int64):
+        rows += [int(min(chunk, c - v)) for v in range(0, int(c), chunk)]
+        cls_chunk0.append(len(rows))
+    split = [r for r in range(len(cls_chunk0) - 1)
+             if cls_chunk0[r + 1] > cls_chunk0[r] and cls_chunk0[r] // round_chunks != (cls_chunk0[r + 1] - 1) // round_chunks]
+    return dict(rows=rows, cls_chunk0=np.array(cls_chunk0), chunks=len(rows), rounds=-(-len(rows) // round_chunks), split=split)
+
+
+def chunk_steps(n):
+    """What the product kernel's loops do for a chunk of n rows: steps = iterations of the k0 loop (32 rows each); second = a wave issues
+    its second MFMA k-step (rows 16 .. 31 of a step); early = a wave leaves a step at the break (a step with fewer than 29 rows)"""
+    left = [min(STEP_ROWS, n - k0) for k0 in range(0, n, STEP_ROWS)]
+    return dict(steps=len(left), second=any(m > 4 * KSTEP_ROWS for m in left), early=any(m <= STEP_ROWS - KSTEP_ROWS for m in left))
