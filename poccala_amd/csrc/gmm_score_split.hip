@@ -34,7 +34,9 @@
 // History (profiles/r01_split_variants.txt, r01_score_variants.txt; the superseded kernels were removed in round 2): VALU
 // kernel 64 TFLOP/s -> f32-input MFMA 102 -> three-piece bf16 split (six products) 186 -> two-piece f16 split with a separate
 // constant MFMA 274 -> constants folded into the spare slot 300; the same scheme on 16x16x32 MFMAs measured 16.7 ms against
-// 15.1 (more B-operand registers, 45 % more LDS fragment traffic).
+// 15.1 (more B-operand registers, more LDS fragment traffic: this kernel reads each of the 2 KS8 fragments of an m-tile once,
+// 10 ds_read_b128 at D = 39, not once per pass) -> the m-tile loop scheduled by hand (process(), profiles/r19_score_schedule.txt):
+// 14.8 -> 14.2 ms per step, results bit for bit.
 #include <stdlib.h>
 
 #include "pcl_internal.h"
@@ -165,12 +167,25 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
     constexpr int MTS = PCL_SPLIT16_MTS;
     __shared__ __attribute__((aligned(16))) uint4 abuf[2][MTS * CH * 64];
     const uint4 *pstate = pm + (size_t)tile.state * nmt_max * (CH * 64);
+    // every wave issues its share of the stage's 1-KiB chunks: the chunk index is wave-uniform, so it is kept on the scalar unit
+    // (readfirstlane) and the 2-3 trips are unrolled -- as a loop over threadIdx.x >> 6 each trip cost ~5 VALU instructions
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     auto dma = [&](int buf, int stage) {
         const uint4 *src = pstate + (size_t)stage * (MTS * CH * 64);
         const int nch = min(MTS, n_mtiles - stage * MTS) * CH;
-        for (int p = wave; p < nch; p += WG / 64)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p * 64 + lane),
-                                             (__attribute__((address_space(3))) void *)&abuf[buf][p * 64], 16, 0, 0);
+        if constexpr (KS8 > 5) {                   // D = 47 keeps the loop: unrolled it measured 3 % slower there (one more spill in the m-tile loop)
+            for (int p = wave; p < nch; p += WG / 64)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p * 64 + lane),
+                                                 (__attribute__((address_space(3))) void *)&abuf[buf][p * 64], 16, 0, 0);
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < (MTS * CH + WG / 64 - 1) / (WG / 64); ++i) {
+            const int p = wave_s + i * (WG / 64);
+            if (p < nch)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p * 64 + lane),
+                                                 (__attribute__((address_space(3))) void *)&abuf[buf][p * 64], 16, 0, 0);
+        }
     };
 
 #ifdef PCL_SPLIT_STAMPS
@@ -186,20 +201,109 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
         for (int c = 0; c < NT; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-        auto pass = [&](int pa, int pb) {
+        // Schedule (the results are those of the plain three-pass loop bit for bit: every accumulator still sees a2x1 s0.., a1x2 s0..,
+        // a1x1 s0.. in that order).  All 2 KS8 fragments of the m-tile are read once, ahead of use: two before the first MFMA, the
+        // rest under the first MFMAs, so that the waits of the later steps find them landed -- left to itself the compiler issues
+        // every batch of reads right before a full lgkmcnt(0), three exposed LDS round trips per m-tile.  The a1 passes then run one frame
+        // tile at a time, so that the log-sum-exp of frame tile c - 1 issues in the gaps of tile c's MFMAs (two exponentials and an
+        // add per 32-cycle gap) and only the last tile's runs with no MFMA of this wave in flight.  sched_barrier pins that order.
+        auto frag = [&](int pa, int s) { return *reinterpret_cast<const h8v *>(&ab[(pa * KS8 + s) * 64 + lane]); };
+        auto mfma = [&](const h8v &a, int c, int pb, int s) { acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, xb[c][pb][s], acc[c], 0, 0, 0); };
+        // the log-sum-exp of frame tile c as 32 single operations in a fixed order (the sums are those of the pairwise tree
+        // es[r] += es[r + w], w = 8, 4, 2, 1, whichever way the operations are spread over the MFMA gaps).  Plain v_add_f32: under
+        // -O3 the compiler SLP-packs such adds into v_pk_add_f32, which costs far more than its issue slot beside MFMAs (in-kernel
+        // stamps: log-sum-exp phase 1830 -> 1230 cycles per m-tile), so this file is built with -fno-slp-vectorize (Makefile).
+        // (Pinning the adds with inline asm instead returned wrong sums: the hazard recogniser does not cover a transcendental
+        // result consumed inside an asm block.)
+        float es[8], eh, snew[NT];
+        auto lse_op = [&](int c, int k) {
+            if (k < 24) {
+                const int r = k / 3;
+                if (k % 3 == 0) es[r] = __builtin_amdgcn_exp2f(acc[c][r]);
+                else if (k % 3 == 1) eh = __builtin_amdgcn_exp2f(acc[c][r + 8]);
+                else es[r] += eh;
+            } else if (k < 28) es[k - 24] += es[k - 24 + 4];
+            else if (k < 30) es[k - 28] += es[k - 28 + 2];
+            else if (k == 30) es[0] += es[1];
+            else snew[c] = sm[c] + es[0];
+        };
+        // (KS8 > 5, D = 47: the fragments held ahead do not fit the 168 registers of three waves per SIMD beside the wider frame
+        //  operand -- that kernel keeps the plain three-pass loop and the compiler's own order)
+        if constexpr (KS8 <= 5) {
+            // fragment f of the m-tile in the order of first use: the a2 set, then the a1 set
+            h8v af[2 * KS8];
+            auto rd = [&](int f) { af[f] = frag(f < KS8 ? 1 : 0, f % KS8); };
+            constexpr int LATE = KS8 > 2 ? 2 : 0;          // read into the registers the first two a2 fragments leave
+            rd(0);
+            rd(1);
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef PCL_SPLIT_PRIO
+            __builtin_amdgcn_s_setprio(1);
+#endif
 #pragma unroll
             for (int s = 0; s < KS8; ++s) {
-                const h8v a = *reinterpret_cast<const h8v *>(&ab[(pa * KS8 + s) * 64 + lane]);
 #pragma unroll
-                for (int c = 0; c < NT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, xb[c][pb][s], acc[c], 0, 0, 0);
+                for (int c = 0; c < NT; ++c) {
+                    mfma(af[s], c, 0, s);
+                    if (s == 0 && c == 0) {                // behind the first MFMA: its wait is the one exposed round trip
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int f = 2; f < 2 * KS8 - LATE; ++f) rd(f);
+                    }
+                }
+                if (s == 2) {
+#pragma unroll
+                    for (int f = 2 * KS8 - LATE; f < 2 * KS8; ++f) rd(f);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-        };
-#ifdef PCL_SPLIT_PRIO
-        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int c = 0; c < NT; ++c) {
+                // beside tile c's MFMAs: three operations of tile c - 1's log-sum-exp per gap
+                int k = 0;
+#pragma unroll
+                for (int g = 0; g < 2 * KS8; ++g) {
+                    mfma(af[KS8 + g % KS8], c, g < KS8 ? 1 : 0, g % KS8);
+                    if (c == 0) __builtin_amdgcn_sched_barrier(0);
+#ifndef PCL_DIAG_NOLSE
+                    if (c > 0) {
+#pragma unroll
+                        for (int q = 0; q < 3 && k < 32; ++q, ++k) lse_op(c - 1, k);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
 #endif
-        pass(1, 0);
-        pass(0, 1);
-        pass(0, 0);
+                }
+#ifndef PCL_DIAG_NOLSE
+                if (c > 0) {
+#pragma unroll
+                    for (; k < 32; ++k) lse_op(c - 1, k);
+                }
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            auto pass = [&](int pa, int pb) {
+#pragma unroll
+                for (int s = 0; s < KS8; ++s) {
+                    const h8v a = frag(pa, s);
+#pragma unroll
+                    for (int c = 0; c < NT; ++c) mfma(a, c, pb, s);
+                }
+            };
+            pass(1, 0);
+            pass(0, 1);
+            pass(0, 0);
+#ifndef PCL_DIAG_NOLSE
+#pragma unroll
+            for (int c = 0; c + 1 < NT; ++c)
+#pragma unroll
+                for (int k = 0; k < 32; ++k) lse_op(c, k);
+#endif
+        }
+#ifndef PCL_DIAG_NOLSE
+#pragma unroll
+        for (int k = 0; k < 32; ++k) lse_op(NT - 1, k);
+#endif
         SSTAMP(1)
 #ifdef PCL_SPLIT_PRIO
         __builtin_amdgcn_s_setprio(0);
@@ -211,22 +315,11 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 #endif
 #pragma unroll
         for (int c = 0; c < NT; ++c) {
-            float es[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) es[r] = __builtin_amdgcn_exp2f(acc[c][r]);
-            // plain v_add_f32 tree: under -O3 the compiler SLP-packs such adds into v_pk_add_f32, which costs far more than
-            // its issue slot beside MFMAs (in-kernel stamps: log-sum-exp phase 1830 -> 1230 cycles per m-tile), so this
-            // file is built with -fno-slp-vectorize (Makefile).  (Pinning the adds with inline asm instead returned wrong
-            // sums: the hazard recogniser does not cover a transcendental result consumed inside an asm block.)
-#pragma unroll
-            for (int w = 8; w >= 1; w >>= 1)
-#pragma unroll
-                for (int r = 0; r < w; ++r) es[r] += es[r + w];
-            const float snew = sm[c] + es[0];
             // (round 6: the reference is taken at the first tile that HAS a real value, not at tile 0 -- with most of a state's mixtures off
             //  the pipe its first 32 are often all log zero, which used to flag every tile of the state for the direct-form fix-up: 34 ms
             //  per EM iteration at 91 % off-pipe mixtures; a frame that never sees a value above the f16 constants' reach is flagged at the end)
-            if (__any(!inited[c]) || __any(!(snew < 3.0e38f))) {
+            // (both votes always evaluated: the sum above stays in the block of the MFMAs it is scheduled beside)
+            if (__any(!inited[c]) | __any(!(snew[c] < 3.0e38f))) {
                 float gm = acc[c][0];
 #pragma unroll
                 for (int r = 1; r < 16; ++r) gm = __builtin_fmaxf(gm, acc[c][r]);
@@ -256,7 +349,7 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
                 for (int r = 0; r < 16; ++r) s += __builtin_amdgcn_exp2f(acc[c][r]);
                 sm[c] = s;
             } else {
-                sm[c] = snew;
+                sm[c] = snew[c];
             }
         }
         SSTAMP(2)
