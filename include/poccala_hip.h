@@ -733,6 +733,66 @@ int pcl_frames_splice_project(pcl_ctx *ctx, int U, const int32_t *T, const int64
                               const double *A /* D_out*Ds */, const double *b /* D_out */);
 int pcl_frames_download(pcl_ctx *ctx, double *f64 /* F*D or NULL */, float *f32 /* F*D or NULL */);
 
+/* ----------------------------------------------------------------- CMVN (row f14): cepstral mean and variance normalisation of the resident frames
+ * The step every recipe puts in front of splice + LDA (f12), MLLT (f13) and fMLLR (f11): per speaker (or per utterance) from resident
+ * statistics, or over a sliding window, in place on the resident frame matrix (csrc/frame_cmvn.hip).  Not in the reference;
+ * tests/_cmvn_twin.py is the rule's NumPy twin.  Everything is float64: x is read from the float64 copy when the context holds one (which
+ * then receives y), else from the float32 rows widened; the float32 rows always receive y rounded to nearest.  Padding columns, rows
+ * outside every listed utterance and the utterances that are skipped or refused keep their bits.  No floating-point atomics: two runs give
+ * the same bits.  Utterance u occupies the rows [frame_begin[u], + T[u]) of the (F, D) matrix, as pcl_frames_transform takes them; the
+ * utterances of a call must not overlap.
+ *
+ * STATISTICS.  Per speaker  n = the rows (an exact integer)    s_d = sum x_d    q_d = sum x_d x_d   (x_d x_d rounded, then added)
+ * at the dimension D of the CURRENT frame matrix.  Order: an utterance's rows are cut into chunks of 1024; in a chunk, row lane r of four
+ * adds the chunk's rows r, r + 4, r + 8, ... in ascending order from 0, and the four lanes' sums are added ((l0 + l1) + l2) + l3; the
+ * utterance's sum is its chunks' sums added in chunk order from 0; the sums of a speaker's utterances with T > 0 are added onto the
+ * speaker's resident sums in ascending utterance index.  One workgroup per (utterance, chunk), then one per speaker walking its utterances.
+ * pcl_cmvn_zero makes (and clears) the statistics for S <= 65535 speakers; needs a frame matrix.  They are additive over calls of
+ * pcl_cmvn_accumulate (a speaker may span several calls and several frame matrices of the same D) and are dropped by the next
+ * pcl_cmvn_zero, by pcl_destroy, and by a frame matrix of another D: every call that uses them is then PCL_ERR_STATE until the next
+ * pcl_cmvn_zero.  utt_speaker (U,) int32 in [0, S), or -1 = the utterance is skipped.
+ * pcl_cmvn_stats_download: n (S,) int64, s (S, D), q (S, D) float64; NULLs are skipped.
+ *
+ * APPLY.  pcl_frames_cmvn, from the resident statistics, which must be of the same S.  Per speaker and column, one rounding per operation,
+ * in this order:
+ *     m = s / n        t = q / n - m m        v = t when t > var_floor, else var_floor        y = (x - m) / sqrt(v)   (norm_vars != 0)
+ *                                                                                             y = x - m                (norm_vars == 0)
+ * A speaker is REFUSED -- its utterances keep their bits, its status is non-zero -- when, tested in this order,
+ *     PCL_CMVN_LOW_COUNT    n < min_count  (so is every speaker without a row: min_count >= 1)
+ *     PCL_CMVN_NOT_FINITE   any s_d or q_d is not finite
+ * Statuses are decided before anything is written (one wave per speaker, which also forms m and sqrt(v)); status_out (S,) int32 or NULL.
+ * Per-utterance CMVN is utt_speaker = 0 .. U-1 with S = U.  The apply is elementwise over an utterance's contiguous run of rows, in aligned
+ * 16-byte groups.
+ *
+ * SLIDING WINDOW.  pcl_frames_cmvn_sliding: no resident statistics.  For frame t of an utterance of T rows the window [lo, hi) is
+ *     center != 0:  lo = t - window / 2 (integer division), hi = lo + window;  if lo < 0: hi -= lo, lo = 0;
+ *                   if hi > T: lo = max(0, lo - (hi - T)), hi = T
+ *     center == 0:  lo = max(0, t - window + 1), hi = t + 1;  if hi - lo < min_window: hi = min(T, lo + min_window)
+ * n = hi - lo, s = P[hi] - P[lo], q = Pq[hi] - Pq[lo], then m, t, v, y as above, from the sums of the ORIGINAL rows: the prefix arrays of
+ * x and of x x are built into a block of the context's pool before any row is written.  Order of a prefix: the utterance is cut into
+ * blocks of 64 rows; local[r] = the inclusive sum of the block's rows up to r in ascending order from 0; offset[0] = 0, offset[b + 1] =
+ * offset[b] + (the total of block b), in ascending block order; P[0] = 0 and P[r + 1] = offset[block of r] + local[r].  One wave per
+ * (utterance, block) with a lane per feature, one workgroup per utterance for the offsets.  Nothing is read across an utterance
+ * boundary; T = 0 is a no-op.  1 <= min_window <= window <= 2^20.  The block holds 16 D bytes per row: the utterances are processed in
+ * groups of consecutive utterances of at most PCL_CMVN_GROUP_ROWS rows (env, read on every call; default 2^28 / D; a single longer
+ * utterance is a group of its own), on which the result does not depend.
+ *
+ * No frames, no statistics (never made, or dropped): PCL_ERR_STATE.  Overlapping utterances, an utterance outside the matrix, a speaker
+ * outside [-1, S), S out of range or not the statistics', var_floor not finite or not > 0 under norm_vars, min_count < 1, the window limits:
+ * PCL_ERR_INVALID.  All checked before anything is changed.  A live pcl_seg has its own copy of the frames and is untouched; live batches
+ * keep the emissions they scored from the old rows until they are scored again, as after pcl_frames_transform.  The statistics of the
+ * fMLLR, MLLT and LDA rows are not touched.  pcl_kernel_time groups: "cmvn_stats", "cmvn_apply", "cmvn_sliding".  Synchronous. */
+#define PCL_CMVN_OK 0
+#define PCL_CMVN_LOW_COUNT 1
+#define PCL_CMVN_NOT_FINITE 2
+int pcl_cmvn_zero(pcl_ctx *ctx, int S);
+int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *utt_speaker /* U, -1 = skip */);
+int pcl_cmvn_stats_download(pcl_ctx *ctx, int64_t *n /* S or NULL */, double *s /* S*D or NULL */, double *q /* S*D or NULL */);
+int pcl_frames_cmvn(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *utt_speaker, int S, int norm_vars,
+                    double var_floor, int64_t min_count, int32_t *status_out /* S or NULL */);
+int pcl_frames_cmvn_sliding(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, int window, int min_window, int center,
+                            int norm_vars, double var_floor);
+
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /
  * (2 var_jmd) (about 5e-7 * cond nats).  States with cond[j] > *cond_max (default 96, env PCL_MFMA_COND_MAX) are scored

@@ -738,6 +738,32 @@ class AcousticModel(DataInitialization):
         gone = sorted(set(range(len(lens))) - set(keep)) + [keep[u] for u in dropped]
         return dict(A=A, b=bias, eigenvalues=lam, n=n, dropped=sorted(gone), lens=lens, begin=begin)
 
+    def cmvn_batch(self, lens, begin=None, utt_speaker=None, norm_vars=True, var_floor=1e-20, min_count=1, engine=None):
+        """CMVN on the device, in front of lda_batch / mllt_batch / fmllr_batch: Engine.cmvn_zero + cmvn_accumulate + cmvn_apply in one call on
+        the engine's resident frames, which are normalised in place (the rule: include/poccala_hip.h).  (lens, begin): the utterances of
+        resident frames (Engine.frontend / load_audio_batch(fetch=False)), also as one tuple in `lens`; or `lens` a list of (T_u, D)
+        arrays, uploaded here as float64 and laid back to back.  utt_speaker: one speaker index >= 0 per utterance, -1 = leave the
+        utterance alone, None = every utterance by its own statistics.  Returns a dict: status (S,) int32 (0, or why the speaker was
+        left alone: 1 fewer than min_count frames, 2 a sum that is not finite), n (S,) frames per speaker, lens / begin of the utterances."""
+        engine = engine or default_engine()
+        res = self._resident(lens) if begin is None else (np.asarray(lens, dtype=np.int32).reshape(-1), np.asarray(begin, dtype=np.int64).reshape(-1))
+        if res is None:
+            data_list = lens
+            lens = np.array([len(d) for d in data_list], dtype=np.int32)
+            begin = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.int64))]).astype(np.int64)
+            engine.load_frames(np.concatenate([np.asarray(d, dtype=np.float64).reshape(len(d), -1) for d in data_list], axis=0))
+        else:
+            lens, begin = res
+        spk = np.arange(len(lens), dtype=np.int32) if utt_speaker is None else np.asarray(utt_speaker, dtype=np.int32).reshape(-1)
+        if len(spk) != len(lens):
+            raise ValueError('cmvn_batch: one speaker per utterance')
+        S = max(int(spk.max()) + 1, 1)
+        engine.cmvn_zero(S)
+        engine.cmvn_accumulate(lens, begin, spk)
+        n = engine.cmvn_stats()[0]
+        status = engine.cmvn_apply(lens, begin, spk, norm_vars, var_floor, min_count, S)
+        return dict(status=status, n=n, lens=lens, begin=begin)
+
     def _adopt_model(self, model, units, unit_hmms):
         """(mean, var, weight) of a model laid out unit-major over `units` into the units' GMM objects; this object's mix_level follows."""
         mean, var, w = model

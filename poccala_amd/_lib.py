@@ -18,6 +18,7 @@ PCL_MAX_PASS = 16
 PCL_VAD_DIST_IN, PCL_VAD_OSF_IN = 1, 2
 PCL_FRONTEND_NO_VAD, PCL_FRONTEND_KEEP_F64 = 1, 2
 PCL_MLLR_OK, PCL_MLLR_LOW_OCCUPANCY, PCL_MLLR_FEW_MIXTURES, PCL_MLLR_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3
+PCL_CMVN_OK, PCL_CMVN_LOW_COUNT, PCL_CMVN_NOT_FINITE = 0, 1, 2
 SEG_GET = dict(counts=0, order=1, assign=2, seeds=3)
 GET = dict(B=0, alpha=1, beta=2, lgamma=3, ksai=4, gamma=5, pi=6, logp=7, npass=8, qtrace=9, path=10, point=11, ksai_nz=12)
 
@@ -86,6 +87,11 @@ PROTOTYPES = {
     'pcl_lda_stats_download': (_i, [_vp, _vp, _vp, _vp]),
     'pcl_frames_splice_project': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'pcl_frames_download': (_i, [_vp, _vp, _vp]),
+    'pcl_cmvn_zero': (_i, [_vp, _i]),
+    'pcl_cmvn_accumulate': (_i, [_vp, _i, _vp, _vp, _vp]),
+    'pcl_cmvn_stats_download': (_i, [_vp, _vp, _vp, _vp]),
+    'pcl_frames_cmvn': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _d, C.c_int64, _vp]),
+    'pcl_frames_cmvn_sliding': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _d]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

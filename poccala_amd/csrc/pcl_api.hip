@@ -261,6 +261,7 @@ static void ctx_teardown(pcl_ctx *ctx) {
     pcl_mfcc_release(ctx);                                       // drained: no copy reads the staging buffers, no event is waited for
     free_model(ctx);
     pcl_lda_release(ctx);
+    pcl_cmvn_release(ctx);
     pcl_units_release(ctx);
     release_frames32(ctx);
     ctx->frames64.release();

@@ -216,6 +216,11 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     // over the class's spliced rows; lda_D = the frame dimension pcl_lda_zero saw.  Freed by pcl_destroy and by the next pcl_lda_zero.
     DevBuf<double> lda_stats;
     int lda_R = 0, lda_left = 0, lda_right = 0, lda_D = 0;
+    // CMVN speaker statistics (frame_cmvn.hip): cmvn_n [cmvn_S] rows, cmvn_sq [cmvn_S][2][cmvn_D] = (sum x | sum x^2); cmvn_D = the frame
+    // dimension pcl_cmvn_zero saw.  Freed by pcl_destroy and by the next pcl_cmvn_zero.
+    DevBuf<long long> cmvn_n;
+    DevBuf<double> cmvn_sq;
+    int cmvn_S = 0, cmvn_D = 0;
     // streaming: two frame slots (grow only); pcl_frames_stage copies the next chunk into the slot that is not current on stream_aux,
     // pcl_frames_swap makes it current
     DevBuf<float> frames_slot[2];
@@ -564,6 +569,7 @@ void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate
 int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src,
                               const int32_t *state_class, int J);
 void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (pcl_destroy)
+void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; pcl_destroy)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);

@@ -652,6 +652,56 @@ class Engine(object):
         self.FD = int(A.shape[0])
         self._frames_key = None                      # the resident frames are no longer what was uploaded
 
+    # ------------------------------------------------------------------ CMVN: mean and variance normalisation of the resident frames
+    def cmvn_zero(self, n_speakers):
+        """Make (and clear) the context's CMVN statistics for n_speakers speakers at the dimension of the resident frames (pcl_cmvn_zero)."""
+        self._check(self._lib.pcl_cmvn_zero(self._ctx, int(n_speakers)))
+        self._cmvn = (int(n_speakers), int(self.FD))
+
+    def _cmvn_args(self, T, frame_begin, utt_speaker):
+        T, fb = self._utt_ranges(T, frame_begin)
+        spk = as_c(np.arange(T.size) if utt_speaker is None else utt_speaker, np.int32).reshape(-1)
+        if fb is None or spk.shape != T.shape:
+            raise ValueError('T, frame_begin and utt_speaker must be equal-length')
+        return T, fb, spk
+
+    def cmvn_accumulate(self, T, frame_begin, utt_speaker=None):
+        """Add the rows [frame_begin[u], + T[u]) of the resident frames to the statistics of speaker utt_speaker[u] (pcl_cmvn_accumulate);
+        -1 = the utterance is skipped, None = every utterance its own speaker."""
+        T, fb, spk = self._cmvn_args(T, frame_begin, utt_speaker)
+        self._check(self._lib.pcl_cmvn_accumulate(self._ctx, T.size, ptr(T), ptr(fb), ptr(spk)))
+
+    def cmvn_stats(self):
+        """(n (S,) int64, s (S, D), q (S, D)): per speaker the rows, sum x and sum x^2 that cmvn_accumulate has summed since cmvn_zero."""
+        S, D = getattr(self, '_cmvn', (0, 0))
+        n, s, q = np.empty(max(S, 1), dtype=np.int64), np.empty((max(S, 1), max(D, 1))), np.empty((max(S, 1), max(D, 1)))
+        self._check(self._lib.pcl_cmvn_stats_download(self._ctx, ptr(n), ptr(s), ptr(q)))
+        return n[:S], s[:S, :D], q[:S, :D]
+
+    def cmvn_apply(self, T, frame_begin, utt_speaker=None, norm_vars=True, var_floor=1e-20, min_count=1, n_speakers=None):
+        """y = (x - m) / sqrt(v) (norm_vars) or x - m in place on the resident frames, per speaker from the resident statistics
+        (pcl_frames_cmvn; the rule: include/poccala_hip.h).  Returns the (S,) int32 statuses: 0, or why the speaker's utterances were
+        left as they were: 1 fewer than min_count rows, 2 a sum that is not finite.  Batches scored before the call keep their old
+        emissions."""
+        T, fb, spk = self._cmvn_args(T, frame_begin, utt_speaker)
+        S = int(n_speakers) if n_speakers is not None else int(getattr(self, '_cmvn', (0, 0))[0])
+        status = np.zeros(max(S, 1), dtype=np.int32)
+        self._check(self._lib.pcl_frames_cmvn(self._ctx, T.size, ptr(T), ptr(fb), ptr(spk), S, 1 if norm_vars else 0, float(var_floor),
+                                              int(min_count), ptr(status)))
+        self._frames_key = None                      # the resident frames are no longer what was uploaded
+        return status[:S]
+
+    def cmvn_sliding(self, T, frame_begin, window=600, min_window=100, center=False, norm_vars=False, var_floor=1e-20):
+        """Sliding-window CMVN in place on the resident frames (pcl_frames_cmvn_sliding): frame t is normalised by the mean (and variance)
+        of a window of `window` rows of its own utterance -- centred on t, or the rows up to t (at least min_window of them where the
+        utterance has as many) -- taken from the rows as they were before the call."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        if fb is None:
+            raise ValueError('frame_begin is needed')
+        self._check(self._lib.pcl_frames_cmvn_sliding(self._ctx, T.size, ptr(T), ptr(fb), int(window), int(min_window), 1 if center else 0,
+                                                      1 if norm_vars else 0, float(var_floor)))
+        self._frames_key = None
+
     def frames_download(self, dtype=np.float64):
         """The resident frames as held, (F, D): np.float64 = the float64 copy (an error when the frames were uploaded as float32 and no
         copy exists), np.float32 = the float32 rows every default-precision kernel reads."""
