@@ -43,15 +43,11 @@
 
 namespace {
 
-#ifndef PCL_DEC_DW
-#define PCL_DEC_DW 1024
-#endif
-constexpr int DW = PCL_DEC_DW;      // threads per workgroup
+#include "hmm_decode_dims.inc"      // DW: threads per workgroup; HB: the radix digit of the pruning select
 constexpr int NWV = DW / 64;        // wavefronts per workgroup
 constexpr int NS = 8;               // lanes per token = states of its HMM at most
 constexpr int TG = DW / NS;         // tokens stepped per pass of the workgroup
 constexpr int SEG_LDS = 4096;       // donor segments whose offsets are searched in LDS (more: searched in HBM)
-constexpr int HB = 8;               // radix digit of the pruning select: 256 bins, the same words as the occupancy map; no direct ranking
 
 // What a lane (state j = sub of its token) needs of ln A of the embedded HMM (AcousticModel.py:979-989), fixed per thread:
 // predecessor i reaches j through entry rc[i] of its unit's (S,S) matrix, or not at all.

@@ -38,19 +38,11 @@
 
 namespace {
 
-// 512 threads at 4 waves per SIMD: two workgroups share a CU, so the 417 utterances of a C5 shard run in ONE round of the 256 CUs
-// (1024 threads: two rounds, 63 ms against 51; groups of 4 rows spill and lose 9 ms: profiles/r03_decode_c5.txt)
-#ifndef PCL_DECLR_DW
-#define PCL_DECLR_DW 512
-#define PCL_DECLR_WAVES 4
-#endif
-constexpr int LW = PCL_DECLR_DW;    // threads per workgroup
+#include "hmm_decode_lr_dims.inc"   // LW: threads per workgroup; HB, HBINS, CAND: the pruning select's digit and direct ranking
 constexpr int LNW = LW / 64;
 constexpr int E = 3, NE = 2 * E;    // emitting states per unit (S = 5) and per token at most
 constexpr int TS = 7;               // doubles per unit in LDS: ln A self[3] | next[3] (k -> k + 1, the last one leaves the unit) | entry -> 1
                                     // (an odd stride: units spread over all banks; 8 gave 16-way conflicts)
-constexpr int HB = 12, HBINS = 1 << HB;   // radix digit of the pruning select
-constexpr int CAND = 1024;          // keys of the selected bin ranked directly
 constexpr int DLW = 128;            // donors of a wave whose list entries live in LDS (more: in the utterance's seg_* arrays in HBM)
 constexpr int SLOT_BITS = 14;       // node -> token map entry = (frame << SLOT_BITS) | dense token index (cap <= PCL_DEC_MAX_KEYS_PER_LANE LW = 8192 < 2^14), -1 = none
 constexpr int FRESH = (int)0x80000000;   // src: the token's last step was its first (its entry state still holds ln pi)

@@ -164,6 +164,65 @@ def test_decode_many_tokens_finish_in_one_frame(eng):
     assert swing > 2000                                           # (the frames this test is about did occur)
 
 
+@pytest.mark.parametrize('max_tokens,n_words,general_knob', [(8192, 3000, True), (16384, 8000, False)])
+def test_general_kernel_prunes_with_8_and_16_keys_per_lane(eng, monkeypatch, max_tokens, n_words, general_knob):
+    """The many-donors shape of the test above through the GENERAL kernel's two largest instantiations, 8 and 16 sort keys per lane
+    (hmm_decode.hip is compiled for 1, 2, 4, 8, 16; 8192 tokens go to the left-to-right kernel unless PCL_DEC_GENERAL=1, and at 16384
+    only the general kernel applies), at beam 0.85 so that the pruning select runs: a frame's pruning call sees more than half of
+    max_tokens old tokens -- more than the next smaller instantiation holds -- and drops some of them.  Bit for bit the restatement."""
+    from poccala_amd import PCL_F64, synth
+    n_units = 183
+    tree, lx = synth.make_pronunciation_tree(n_words, n_units, seed=81)
+    mean, var, w, _ = synth.make_model(n_units, 2, 13, seed=82)
+    mean[:], var[:], w[:] = mean[0], var[0], w[0]                 # one GMM for every state
+    a = np.zeros((S, S))
+    a[0, 1] = 1.0
+    for r in range(1, S - 1):
+        a[r, r], a[r, r + 1] = 0.1, 0.9
+    trans = np.stack([a] * n_units)
+    frames, lens, begin = synth.make_frames(2, 12, 13, seed=83)
+    eng.load_model(mean, var, w)
+    eng.load_units(trans)
+    eng.load_lexicon(tree)
+    eng.load_frames(frames)
+    b = eng.all_state_batch(lens, begin)
+    b.score(PCL_F64)
+    B = b.get('B')
+    b.close()
+    # the condition, from the restatement alone and before the kernel runs
+    calls, real_prune = [], do.prune                              # calls: (old tokens, dropped)
+
+    def watched(scores, beam=0.85, min_distinct=8):
+        drop = real_prune(scores, beam, min_distinct)
+        calls.append((len(scores), len(drop)))
+        return drop
+    monkeypatch.setattr(do, 'prune', watched)
+    want = []
+    for u in range(2):
+        trace, info = [], {}
+        fin, hist = do.decode(tree, list(trans), B[u][1:-1], beam=0.85, candidate=4, max_tokens=max_tokens, trace=trace, info=info)
+        want.append((trace, info, fin, hist))
+    monkeypatch.setattr(do, 'prune', real_prune)
+    assert any(n_old > max_tokens // 2 and dropped for n_old, dropped in calls), calls
+    b = eng.all_state_batch(lens, begin)
+    b.score(PCL_F64)
+    assert all(np.array_equal(x, y) for x, y in zip(b.get('B'), B))
+    if general_knob:
+        monkeypatch.setenv('PCL_DEC_GENERAL', '1')
+    got = b.decode(beam=0.85, candidate=4, max_tokens=max_tokens)
+    if general_knob:
+        monkeypatch.delenv('PCL_DEC_GENERAL')
+    b.close()
+    for u in range(2):
+        trace, info, fin, hist = want[u]
+        g = got[u]
+        assert np.array_equal(g['n_tokens'], np.array(trace)), (g['n_tokens'], trace)
+        assert g['history'] == [(int(p), int(n)) for p, n in hist]
+        assert [(n, h) for n, _, h in g['final']] == [(n, h) for n, _, h in fin]
+        assert [s for _, s, _ in g['final']] == [float(s) for _, s, _ in fin]
+        assert g['overflow'] == bool(info.get('overflow'))
+
+
 def test_decode_prunes_through_tied_scores(eng, monkeypatch):
     """One GMM for every state makes the emissions state-independent, so whole generations of tokens carry the SAME score: the
     pruning cut falls between equal scores (the first rank + 1 of them in token order go), a frame has one distinct score and
