@@ -26,7 +26,7 @@
 // h = l>>5), element j <-> feature d = 8s + j of the side h selects:
 //   B (frames):     h = 0: x'_d^2 2^e,  h = 1: x'_d 2^e     -- two f16 pieces, resident in VGPRs (a wave owns NT = 2 tiles)
 //   A (parameters): h = 0: a_md 2^-e,   h = 1: b_md 2^-e    -- layout [m-tile][piece 2][KS8][64 lanes][8 f16] = 10 KB per 32
-//                   mixtures, staged in LDS by LDS-DMA one tile ahead (double buffered) and shared by the 4 waves.
+//                   mixtures, staged in LDS by LDS-DMA one stage of two m-tiles ahead (a ring, PCL_SPLIT16_RING) and shared by the 4 waves.
 // Pass order a2x1, a1x2, a1x1 (small terms first).  In the accumulator a lane owns 16 mixture values of ONE frame, so the
 // log-sum-exp is per lane: s += exp2(v - ref) (one v_exp_f32 + one add per Gaussian); ref is a true earlier maximum,
 // raised on a wave-uniform slow path (first tile, or when a sum overflows f32).  ln2 (ref + K0 + log2 s) is finished in f64.
@@ -36,7 +36,8 @@
 // constant MFMA 274 -> constants folded into the spare slot 300; the same scheme on 16x16x32 MFMAs measured 16.7 ms against
 // 15.1 (more B-operand registers, more LDS fragment traffic: this kernel reads each of the 2 KS8 fragments of an m-tile once,
 // 10 ds_read_b128 at D = 39, not once per pass) -> the m-tile loop scheduled by hand (process(), profiles/r19_score_schedule.txt):
-// 14.8 -> 14.2 ms per step, results bit for bit.
+// 14.8 -> 14.2 ms per step, results bit for bit -> the double buffer made a ring, two m-tiles per stage and barrier
+// (profiles/r22_score_ring.txt): 14.03 -> 13.73 ms per step on one device, 13.63 -> 13.20 on another, results bit for bit.
 #include <stdlib.h>
 
 #include "pcl_internal.h"
@@ -55,10 +56,37 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 #ifndef PCL_SPLIT16_MINW
 #define PCL_SPLIT16_MINW 3    // waves per SIMD (f16 x2 kernel: fits 168 VGPRs)
 #endif
+// The parameter ring of the m-tile loop: PCL_SPLIT16_RING stages of PCL_SPLIT16_MTS m-tiles each, one workgroup barrier per stage, a stage
+// refilled RING - 1 stages ahead of its use.  RING x MTS <= 5 keeps three workgroups of the D = 39 kernel on a CU (10 KB per m-tile).
+// Measured (profiles/r22_score_ring.txt; 2 x 1 is the double buffer of rounds 1-19): 2 x 2 is 2-3 % faster per step -- half the barriers,
+// and a DMA has two m-tile periods to land; 3 x 1, 4 x 1 and 5 x 1 (a barrier per m-tile, counted waits) are no faster than 2 x 1.
+#ifndef PCL_SPLIT16_RING
+#define PCL_SPLIT16_RING 2
+#endif
 #ifndef PCL_SPLIT16_MTS
-#define PCL_SPLIT16_MTS 1     // m-tiles staged per workgroup barrier (2 and 4 measured no faster)
+#define PCL_SPLIT16_MTS 2     // m-tiles staged per workgroup barrier
 #endif
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+
+// The ring of the D-dimensional kernel.  D = 47 (KS8 = 6: 12 KB per m-tile, the rolled DMA loop) keeps the double buffer.
+template <int D>
+struct Ring {
+    static constexpr int KS8 = (D + 7) / 8;
+    static constexpr int R = KS8 > 5 ? 2 : PCL_SPLIT16_RING;
+    static constexpr int MTS = KS8 > 5 ? 1 : PCL_SPLIT16_MTS;
+    static constexpr int STAGE_CH = MTS * 2 * KS8;                              // 1-KiB chunks per stage
+    static constexpr size_t LDS = (size_t)R * STAGE_CH * 64 * 16 + 16;          // static LDS per workgroup: the ring and s_ovf
+    static_assert(R >= 2 && MTS >= 1, "a ring has at least two stages");
+    static_assert(3 * LDS <= (160u << 10), "three workgroups per CU: the ring does not fit a third of the 160 KB of LDS");
+    static_assert(LDS <= (56u << 10), "pcl_score_occupancy(ctx, 2) pads a workgroup to 56 KB");
+};
+
+// (a counted wait takes its count as an immediate)
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 
 template <int D, int NT>
 __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_MINW * 256 / WG : 1) void gmm_score_split16_kernel(
@@ -163,9 +191,9 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
     }
     bool ref_ovf = false;
 
-    // MTS m-tiles per LDS stage: one workgroup barrier per MTS x 32 mixtures
-    constexpr int MTS = PCL_SPLIT16_MTS;
-    __shared__ __attribute__((aligned(16))) uint4 abuf[2][MTS * CH * 64];
+    // a ring of R stages of MTS m-tiles each: one workgroup barrier per MTS x 32 mixtures
+    constexpr int R = Ring<D>::R, MTS = Ring<D>::MTS;
+    __shared__ __attribute__((aligned(16))) uint4 abuf[R][MTS * CH * 64];
     const uint4 *pstate = pm + (size_t)tile.state * nmt_max * (CH * 64);
     // every wave issues its share of the stage's 1-KiB chunks: the chunk index is wave-uniform, so it is kept on the scalar unit
     // (readfirstlane) and the 2-3 trips are unrolled -- as a loop over threadIdx.x >> 6 each trip cost ~5 VALU instructions
@@ -182,9 +210,20 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 #pragma unroll
         for (int i = 0; i < (MTS * CH + WG / 64 - 1) / (WG / 64); ++i) {
             const int p = wave_s + i * (WG / 64);
-            if (p < nch)
+            if (p >= nch) continue;
+            if constexpr (R == 2) {
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p * 64 + lane),
                                                  (__attribute__((address_space(3))) void *)&abuf[buf][p * 64], 16, 0, 0);
+            } else {
+                // The same instruction written out (m0 = the chunk's LDS address, as the builtin sets it).  The compiler counts the
+                // builtin's DMAs itself, and with one of them in flight across the loop's back edge it puts vmcnt(0) in front of the first
+                // LDS read of every m-tile, whichever buffer that reads: the ring would drain once per m-tile.  The waits of these are the
+                // counted ones of the stage loop below and nothing else.  (m0 is reserved: the compiler keeps nothing in it from one
+                // statement to the next and sets it in front of every instruction that reads it, so it is not on the clobber list.)
+                const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) char *)&abuf[buf][p * 64];
+                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off"
+                             :: "s"(lds), "v"(src + p * 64 + lane) : "memory");
+            }
         }
     };
 
@@ -195,7 +234,7 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 #define SSTAMP(k)
 #endif
     auto process = [&](int mt) {
-        const uint4 *ab = &abuf[(mt / MTS) & 1][(mt % MTS) * (CH * 64)];
+        const uint4 *ab = &abuf[(unsigned)(mt / MTS) % R][(mt % MTS) * (CH * 64)];
         f16v acc[NT];
 #pragma unroll
         for (int c = 0; c < NT; ++c)
@@ -354,18 +393,40 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
         }
         SSTAMP(2)
     };
+    // The ring.  Stage st + R - 1 is issued right behind the barrier of stage st, which proves all four waves done with stage st - 1, whose
+    // buffer it takes: R - 1 stages ahead of its use, so its DMA has (R - 1) x MTS m-tile periods to land.  With R = 2 (the default) nothing
+    // younger is in flight at the wait: vmcnt(0) and the plain barrier.  With R > 2 a wave waits for ITS pieces of the oldest stage only:
+    // LDS-DMA returns in order, so vmcnt(n) with n = the wave's DMA instructions of the R - 2 younger stages (a constant per wave while those
+    // stages are full; anything else the wave has in flight only makes the wait stricter); the tail, where a younger stage is short or
+    // absent, waits for everything; and the barrier is the bare instruction behind a wait for the wave's LDS operations, since the fence of
+    // __syncthreads() (any fence, an LDS-only one included) drains the DMAs in flight with vmcnt(0).
     const int n_stages = (n_mtiles + MTS - 1) / MTS;
     dma(0, 0);
+#pragma unroll
+    for (int s = 1; s < R - 1; ++s)
+        if (s < n_stages) dma(s, s);
 #ifdef PCL_SPLIT_STAMPS
     st_t = __builtin_amdgcn_s_memtime();
 #endif
+    constexpr int NW = WG / 64, YLO = (R - 2) * ((MTS * CH) / NW), YHI = (R - 2) * ((MTS * CH) / NW + 1);
     for (int st = 0; st < n_stages; ++st) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of stage st have landed
+        // this wave's pieces of stage st have landed
+        if (R > 2 && (st + R - 1) * MTS <= n_mtiles) {
+            if (wave_s < (MTS * CH) % NW) wait_vmcnt<YHI>(); else wait_vmcnt<YLO>();
+        } else {
+            wait_vmcnt<0>();
+        }
         SSTAMP(3)
-        __syncthreads();                                    // everyone's have; the other buffer is free
+        if constexpr (R == 2) {                             // nothing in flight here: the plain barrier, as ever
+            __syncthreads();
+        } else {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }                                                   // everyone's have landed; the buffer of stage st - 1 is free
         SSTAMP(0)
         if (st == 0 && threadIdx.x == 0) flags[blockIdx.x] = s_ovf;
-        if (st + 1 < n_stages) dma((st + 1) & 1, st + 1);
+        if (st + R - 1 < n_stages) dma((unsigned)(st + R - 1) % R, st + R - 1);
         if (wave_active) {
             const int mend = min(n_mtiles, (st + 1) * MTS);
             for (int mt = st * MTS; mt < mend; ++mt) process(mt);
@@ -399,7 +460,7 @@ void launch16_t(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles)
     // pcl_score_occupancy(ctx, 2): dynamic LDS nobody reads, so that two instead of three scoring workgroups fit a CU and another kernel's
     // waves -- the token passing of a streamed decode -- find registers beside them (config 5 streamed: 0.79 -> 0.87 M frames/s; the
     // scoring kernel alone loses ~9 %, so the streamed decoder asks for it and nobody else does).  Per workgroup: 56 KB > 160 / 3.
-    constexpr size_t static_lds = 2 * (size_t)(2 * ((D + 7) / 8)) * 64 * 16;
+    constexpr size_t static_lds = Ring<D>::LDS;
     const size_t pad = (ctx->score_wgs_per_cu == 2 && static_lds < (56u << 10)) ? (56u << 10) - static_lds : 0;
     hipLaunchKernelGGL((gmm_score_split16_kernel<D, PCL_SPLIT16_NT>), dim3(n_tiles), dim3(WG), pad, ctx->stream, ctx->frames32,
                        reinterpret_cast<const uint4 *>(ctx->pm16f.p), ctx->fscale, ctx->centers32, ctx->Mpad32 / 32, tiles, b->d_segs,
