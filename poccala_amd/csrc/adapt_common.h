@@ -1,6 +1,8 @@
-// What the two adaptation files share (model_adapt.hip: MLLR over the mixtures, row f10; frame_adapt.hip: fMLLR over the frames, row f11):
+// What the adaptation files share (model_adapt.hip: MLLR over the mixtures, row f10; frame_adapt.hip: fMLLR over the frames, row f11;
+// frame_mllt.hip: MLLT, row f13):
 // the split-K float64 GEMM that forms [G | k] per (group, feature dimension) on v_mfma_f64_16x16x4_f64 or on the VALU, the reduction of the
-// chunks' partials in chunk order, the Cholesky solve of one [G | k] and the test for W == [0 | I].  The kernels are templates over the
+// chunks' partials in chunk order, the in-LDS Cholesky factorisation and the two solves behind it (chol_factor_lds, chol_solve_lds: the ONE
+// copy of each), the solve of one [G | k] and the test for W == [0 | I].  The kernels are templates over the
 // operand SOURCE, which knows where chunk c's K-range lies and what element `le` of it contributes:
 //     int Dh;                                                         feature dimension: row / column p of the padded grid runs over D + 2
 //     struct Chunk { ...; int n; };   Chunk chunk(int c) const;       chunk c and its length
@@ -19,11 +21,7 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 // Chunk length in K-elements (mixtures for MLLR, frames for fMLLR), env PCL_MLLR_CHUNK, read on EVERY call (as PCL_PCM_CHUNK is): tests
 // force several chunks on a small input.
-static long long mllr_chunk() {
-    const char *e = getenv("PCL_MLLR_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? v : CHUNK_DEFAULT;
-}
+static long long mllr_chunk() { return env_positive_ll("PCL_MLLR_CHUNK", CHUNK_DEFAULT); }
 static bool mllr_use_valu() {                 // env PCL_MLLR_VALU=1 (read on every call): the float64 VALU form of the GEMM (A/B, tools/adapt_bench.py)
     const char *e = getenv("PCL_MLLR_VALU");
     return e && atoi(e) != 0;
@@ -130,6 +128,46 @@ static __global__ __launch_bounds__(256) void gk_reduce_kernel(const double *__r
     }
 }
 
+// A = L L^T in place in LDS, one wave, thread t owns row t: the n x n matrix in the top left of A (rows of LD doubles) becomes L in its
+// lower triangle and diagonal.  -> bad: a pivot is not finite or not > 0, and the factorisation stopped there (uniform).  Three barriers
+// per column; the caller's barrier stands before the call.
+template <int LD>
+__device__ __forceinline__ bool chol_factor_lds(double (*A)[LD], int n, int tid) {
+    for (int j = 0; j < n; ++j) {
+        const double piv = A[j][j];
+        if (!(piv > 0.0 && piv < INFINITY)) return true;          // (every thread reads the same value: uniform)
+        const double d = sqrt(piv);
+        __syncthreads();
+        if (tid == j) A[j][j] = d;
+        if (tid > j && tid < n) A[tid][j] = A[tid][j] / d;
+        __syncthreads();
+        if (tid > j && tid < n)
+            for (int q = j + 1; q <= tid; ++q) A[tid][q] -= A[tid][j] * A[q][j];
+        __syncthreads();
+    }
+    return false;
+}
+
+// The two solves behind the factorisation, in LDS, one wave, column by column: L y = rhs, then L^T w = y; rhs ends as w = (L L^T)^-1 rhs.
+// L(r, c) and rhs(r) give references into the caller's arrays (lambdas: the address arithmetic is the caller's own).
+template <class Mat, class Vec>
+__device__ __forceinline__ void chol_solve_lds(Mat L, Vec rhs, int n, int tid) {
+    for (int j = 0; j < n; ++j) {                                 // L y = rhs
+        const double y = rhs(j) / L(j, j);
+        __syncthreads();
+        if (tid == j) rhs(j) = y;
+        else if (tid > j && tid < n) rhs(tid) -= L(tid, j) * y;
+        __syncthreads();
+    }
+    for (int j = n - 1; j >= 0; --j) {                            // L^T w = y
+        const double w = rhs(j) / L(j, j);
+        __syncthreads();
+        if (tid == j) rhs(j) = w;
+        else if (tid < j) rhs(tid) -= L(j, tid) * w;
+        __syncthreads();
+    }
+}
+
 // One workgroup (one wave) per (group, dimension): G = L L^T in LDS, L y = k, L^T w = y; w = G^-1 k goes to W.  A pivot that is not finite
 // or not > 0 stops the factorisation and flags the pair.  L_out (or NULL): the factor, [pair][n][n] row-major, lower triangle and diagonal.
 static __global__ __launch_bounds__(64) void gk_solve_kernel(const double *__restrict__ Gk, const int *__restrict__ status, int Dh, double *__restrict__ W,
@@ -142,40 +180,12 @@ static __global__ __launch_bounds__(64) void gk_solve_kernel(const double *__res
     }
     for (int x = tid; x < n * (n + 1); x += 64) A[x / (n + 1)][x % (n + 1)] = Gk[(size_t)blockIdx.x * n * (n + 1) + x];
     __syncthreads();
-    bool bad = false;
-    for (int j = 0; j < n; ++j) {
-        const double piv = A[j][j];
-        if (!(piv > 0.0 && piv < INFINITY)) {                     // (every thread reads the same value: uniform)
-            bad = true;
-            break;
-        }
-        const double d = sqrt(piv);
-        __syncthreads();
-        if (tid == j) A[j][j] = d;
-        if (tid > j && tid < n) A[tid][j] = A[tid][j] / d;
-        __syncthreads();
-        if (tid > j && tid < n)
-            for (int q = j + 1; q <= tid; ++q) A[tid][q] -= A[tid][j] * A[q][j];
-        __syncthreads();
-    }
+    const bool bad = chol_factor_lds(A, n, tid);
     if (tid == 0) pivot_bad[blockIdx.x] = bad ? 1 : 0;
     if (bad) return;
     if (L_out)
         for (int x = tid; x < n * n; x += 64) L_out[(size_t)blockIdx.x * n * n + x] = x % n <= x / n ? A[x / n][x % n] : 0.0;
-    for (int j = 0; j < n; ++j) {                                 // L y = k, column by column
-        const double y = A[j][n] / A[j][j];
-        __syncthreads();
-        if (tid == j) A[j][n] = y;
-        else if (tid > j && tid < n) A[tid][n] -= A[tid][j] * y;
-        __syncthreads();
-    }
-    for (int j = n - 1; j >= 0; --j) {                            // L^T w = y
-        const double w = A[j][n] / A[j][j];
-        __syncthreads();
-        if (tid == j) A[j][n] = w;
-        else if (tid < j) A[tid][n] -= A[j][tid] * w;
-        __syncthreads();
-    }
+    chol_solve_lds([&](int r, int c) -> double & { return A[r][c]; }, [&](int r) -> double & { return A[r][n]; }, n, tid);   // k sits in column n
     if (tid < n) W[(size_t)blockIdx.x * n + tid] = A[tid][n];
 }
 

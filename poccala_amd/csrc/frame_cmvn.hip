@@ -15,6 +15,8 @@
 
 namespace {
 
+#include "frame_spans.h"                      // the checks and the upload of a call's utterances
+
 constexpr int CH_ROWS = 1024;                 // rows per chunk of the statistics: the fixed partition the summation order is defined on
 constexpr int ROW_LANES = 4;                  // row lanes of a chunk's workgroup (x 64 feature lanes)
 constexpr int SCAN_ROWS = 64;                 // rows per block of the sliding form's prefix
@@ -306,32 +308,10 @@ __global__ __launch_bounds__(256) void cmvn_sliding_kernel(const int *__restrict
 }
 
 // ---------------------------------------------------------------- host side
-// T / frame_begin of a call: inside the frame matrix, disjoint (a frame is counted, or normalised, ONCE)
+// T / frame_begin of a call: frames loaded, then inside the frame matrix and disjoint (a frame is counted, or normalised, ONCE)
 int cmvn_check_ranges(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, int *Tmax_out) {
-    if (!ctx->frames32 || ctx->F <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no frames loaded", who);
-    if (U < 1 || U > 65535 || !T || !frame_begin) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: U = %d utterances (1 .. 65535), or a NULL argument", who, U);
-    std::vector<std::pair<long long, long long>> spans;
-    int Tmax = 0;
-    for (int u = 0; u < U; ++u) {
-        if (T[u] < 0 || frame_begin[u] < 0 || frame_begin[u] + T[u] > ctx->F)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d covers rows [%lld, %lld) of a frame matrix of %lld rows", who, u, (long long)frame_begin[u],
-                     (long long)frame_begin[u] + T[u], (long long)ctx->F);
-        if (T[u] > 0) spans.emplace_back((long long)frame_begin[u], (long long)frame_begin[u] + T[u]);
-        Tmax = std::max(Tmax, (int)T[u]);
-    }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        if (spans[i].first < spans[i - 1].second)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the utterances overlap in the frame matrix at row %lld (a frame is normalised ONCE)", who, spans[i].first);
-    *Tmax_out = Tmax;
-    return PCL_OK;
-}
-
-int cmvn_check_speakers(pcl_ctx *ctx, const char *who, int U, const int32_t *utt_speaker, int S) {
-    if (!utt_speaker) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utt_speaker is NULL", who);
-    for (int u = 0; u < U; ++u)
-        if (utt_speaker[u] < -1 || utt_speaker[u] >= S) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has speaker %d, outside [-1, %d)", who, u, (int)utt_speaker[u], S);
-    return PCL_OK;
+    TRY(frames_loaded_check(ctx, who));
+    return spans_check(ctx, who, "a frame is normalised ONCE", U, T, frame_begin, Tmax_out);
 }
 
 int cmvn_ready(pcl_ctx *ctx, const char *who) {
@@ -385,9 +365,9 @@ extern "C" int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
     TRY(cmvn_check_ranges(ctx, who, U, T, frame_begin, &Tmax));
     TRY(cmvn_ready(ctx, who));
     const int S = ctx->cmvn_S, Dh = ctx->cmvn_D;
-    TRY(cmvn_check_speakers(ctx, who, U, utt_speaker, S));
+    TRY(speakers_check(ctx, who, U, utt_speaker, S));
     // per utterance the offset of its chunks' partials; per speaker the list of its utterances with frames, ascending
-    std::vector<long long> begin(frame_begin, frame_begin + U), choff(U, 0);
+    std::vector<long long> choff(U, 0);
     std::vector<int> lists(S + 1, 0);
     long long C = 0;
     int Tspk = 0;
@@ -409,24 +389,20 @@ extern "C" int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    DevBuf<int> d_T, d_spk, d_lists;
-    DevBuf<long long> d_begin, d_choff;
+    DevSpans d;
+    DevBuf<int> d_lists;
+    DevBuf<long long> d_choff;
     DevBuf<double> d_partial;
-    TRY(d_T.alloc(ctx, (size_t)U));
-    TRY(d_spk.alloc(ctx, (size_t)U));
+    TRY(d.upload(ctx, U, T, frame_begin, utt_speaker));
     TRY(d_lists.alloc(ctx, lists.size()));
-    TRY(d_begin.alloc(ctx, (size_t)U));
     TRY(d_choff.alloc(ctx, (size_t)U));
     TRY(d_partial.alloc(ctx, (size_t)C * 128));
-    HIPCHK(ctx, pcl_h2d(ctx, d_T, T, (size_t)U * sizeof(int32_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_spk, utt_speaker, (size_t)U * sizeof(int32_t)));
     HIPCHK(ctx, pcl_h2d(ctx, d_lists, lists.data(), lists.size() * sizeof(int)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), (size_t)U * sizeof(long long)));
     HIPCHK(ctx, pcl_h2d(ctx, d_choff, choff.data(), (size_t)U * sizeof(long long)));
     pcl_timer_begin(ctx, "cmvn_stats");
-    hipLaunchKernelGGL(cmvn_partial_kernel, dim3((unsigned)((Tspk + CH_ROWS - 1) / CH_ROWS), (unsigned)U), dim3(256), 0, st, d_T, d_begin, d_spk, d_choff,
+    hipLaunchKernelGGL(cmvn_partial_kernel, dim3((unsigned)((Tspk + CH_ROWS - 1) / CH_ROWS), (unsigned)U), dim3(256), 0, st, d.T, d.begin, d.spk, d_choff,
                        ctx->frames64.p, ctx->frames32, ctx->FD, Dh, d_partial.p);
-    hipLaunchKernelGGL(cmvn_speaker_kernel, dim3((unsigned)S), dim3(128), 0, st, d_T, d_choff, d_lists.p, d_lists.p + o_list, d_partial.p, Dh, ctx->cmvn_n.p,
+    hipLaunchKernelGGL(cmvn_speaker_kernel, dim3((unsigned)S), dim3(128), 0, st, d.T, d_choff, d_lists.p, d_lists.p + o_list, d_partial.p, Dh, ctx->cmvn_n.p,
                        ctx->cmvn_sq.p);
     pcl_timer_end(ctx, "cmvn_stats");
     HIPCHK(ctx, hipGetLastError());
@@ -465,35 +441,29 @@ extern "C" int pcl_frames_cmvn(pcl_ctx *ctx, int U, const int32_t *T, const int6
     TRY(cmvn_check_ranges(ctx, who, U, T, frame_begin, &Tmax));
     TRY(cmvn_ready(ctx, who));
     if (S != ctx->cmvn_S) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: S = %d speakers, the resident statistics hold %d", who, S, ctx->cmvn_S);
-    TRY(cmvn_check_speakers(ctx, who, U, utt_speaker, S));
+    TRY(speakers_check(ctx, who, U, utt_speaker, S));
     if (norm_vars && !(var_floor > 0.0 && std::isfinite(var_floor))) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: var_floor = %g is not a finite number > 0", who, var_floor);
     if (min_count < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: min_count = %lld, need at least 1", who, (long long)min_count);
     const int Dh = ctx->cmvn_D, FD = ctx->FD;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::vector<long long> begin(frame_begin, frame_begin + U);
-    DevBuf<int> d_T, d_spk, d_status;
-    DevBuf<long long> d_begin;
+    DevSpans d;
+    DevBuf<int> d_status;
     DevBuf<double> d_ms;
-    TRY(d_T.alloc(ctx, (size_t)U));
-    TRY(d_spk.alloc(ctx, (size_t)U));
+    TRY(d.upload(ctx, U, T, frame_begin, utt_speaker));
     TRY(d_status.alloc(ctx, (size_t)S));
-    TRY(d_begin.alloc(ctx, (size_t)U));
     TRY(d_ms.alloc(ctx, (size_t)S * 2 * Dh));
-    HIPCHK(ctx, pcl_h2d(ctx, d_T, T, (size_t)U * sizeof(int32_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_spk, utt_speaker, (size_t)U * sizeof(int32_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), (size_t)U * sizeof(long long)));
     pcl_timer_begin(ctx, "cmvn_apply");
     hipLaunchKernelGGL(cmvn_decide_kernel, dim3((unsigned)S), dim3(64), 0, st, ctx->cmvn_n.p, ctx->cmvn_sq.p, Dh, (long long)min_count,
                        norm_vars ? var_floor : 0.0, d_status.p, d_ms.p);
     if (Tmax > 0) {
         if (ctx->frames64) {
             const unsigned gx = (unsigned)(((long long)Tmax * FD + 2) / 2 / 256 + 1);   // (a run of n elements meets at most n / G + 1 aligned groups)
-            hipLaunchKernelGGL(cmvn_apply_kernel<2>, dim3(gx, (unsigned)U), dim3(256), 0, st, d_T, d_begin, d_spk, d_status, d_ms, norm_vars, ctx->frames64.p,
+            hipLaunchKernelGGL(cmvn_apply_kernel<2>, dim3(gx, (unsigned)U), dim3(256), 0, st, d.T, d.begin, d.spk, d_status, d_ms, norm_vars, ctx->frames64.p,
                                ctx->frames32, FD, Dh);
         } else {
             const unsigned gx = (unsigned)(((long long)Tmax * FD + 4) / 4 / 256 + 1);
-            hipLaunchKernelGGL(cmvn_apply_kernel<4>, dim3(gx, (unsigned)U), dim3(256), 0, st, d_T, d_begin, d_spk, d_status, d_ms, norm_vars, (double *)nullptr,
+            hipLaunchKernelGGL(cmvn_apply_kernel<4>, dim3(gx, (unsigned)U), dim3(256), 0, st, d.T, d.begin, d.spk, d_status, d_ms, norm_vars, (double *)nullptr,
                                ctx->frames32, FD, Dh);
         }
     }

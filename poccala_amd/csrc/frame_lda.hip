@@ -19,6 +19,8 @@
 
 namespace {
 
+#include "frame_spans.h"                      // the checks and the upload of a call's utterances, the chunk plan
+
 constexpr int LDA_N_MAX = 128;                // order Ds + 1 of the statistics: 8 x 8 tiles of 16
 constexpr int KB = 32;                        // K-elements (rows) staged in LDS per step: 8 MFMA k-steps, two per wave
 constexpr long long LDA_CHUNK_DEFAULT = 1024; // rows per chunk: 300 chunks x 4 tile groups at 1024 x 300 frames
@@ -28,11 +30,7 @@ constexpr int PROJ_TF = 16;                   // frames per workgroup of the pro
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 // Chunk length in rows, env PCL_LDA_CHUNK, read on EVERY call (as PCL_MLLR_CHUNK is): tests force several chunks on a small input.
-long long lda_chunk() {
-    const char *e = getenv("PCL_LDA_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? std::min<long long>(v, 1 << 30) : LDA_CHUNK_DEFAULT;
-}
+long long lda_chunk() { return std::min<long long>(env_positive_ll("PCL_LDA_CHUNK", LDA_CHUNK_DEFAULT), 1 << 30); }
 bool lda_use_valu() {                         // env PCL_LDA_VALU=1 (read on every call): the float64 VALU form of the product (A/B, tools/lda_bench.py)
     const char *e = getenv("PCL_LDA_VALU");
     return e && atoi(e) != 0;
@@ -254,24 +252,10 @@ __global__ __launch_bounds__(256) void lda_project_kernel(const int *__restrict_
 
 // T / frame_begin of a call: inside the frame matrix, disjoint (a row has ONE utterance: its splice clamps are the utterance's)
 int lda_check_ranges(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, int *Tmax_out) {
-    if (U < 1 || U > 65535 || !T || !frame_begin) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: U = %d utterances (1 .. 65535), or a NULL argument", who, U);
-    if (!ctx->frames32 || ctx->F <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no frames loaded", who);
+    TRY(spans_args_check(ctx, who, U, T, frame_begin));           // (before the frames, as it always was here: the status of a call with both defects)
+    TRY(frames_loaded_check(ctx, who));
     if (ctx->F > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame matrix of %lld rows", who, (long long)ctx->F);
-    std::vector<std::pair<long long, long long>> spans;
-    int Tmax = 0;
-    for (int u = 0; u < U; ++u) {
-        if (T[u] < 0 || frame_begin[u] < 0 || frame_begin[u] + T[u] > ctx->F)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d covers rows [%lld, %lld) of a frame matrix of %lld rows", who, u, (long long)frame_begin[u],
-                     (long long)frame_begin[u] + T[u], (long long)ctx->F);
-        if (T[u] > 0) spans.emplace_back((long long)frame_begin[u], (long long)frame_begin[u] + T[u]);
-        Tmax = std::max(Tmax, (int)T[u]);
-    }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        if (spans[i].first < spans[i - 1].second)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the utterances overlap in the frame matrix at row %lld (a frame is spliced inside ONE utterance)", who, spans[i].first);
-    *Tmax_out = Tmax;
-    return PCL_OK;
+    return spans_check(ctx, who, "a frame is spliced inside ONE utterance", U, T, frame_begin, Tmax_out);
 }
 
 const char *lda_ready(pcl_ctx *ctx) {         // nullptr, or why the statistics cannot be used
@@ -329,24 +313,20 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const long long F = ctx->F;
-    std::vector<long long> begin(frame_begin, frame_begin + U);
-    DevBuf<int> d_T, d_sc, d_key, d_order, d_lists;
-    DevBuf<long long> d_begin;
+    DevSpans d;
+    DevBuf<int> d_sc, d_key, d_order, d_lists;
     DevBuf<int2> d_span;
     DevBuf<double> d_partial;
-    TRY(d_T.alloc(ctx, (size_t)U));
-    TRY(d_begin.alloc(ctx, (size_t)U));
+    TRY(d.upload(ctx, U, T, frame_begin, nullptr));
     TRY(d_key.alloc(ctx, (size_t)F));
     TRY(d_span.alloc(ctx, (size_t)F));
-    HIPCHK(ctx, pcl_h2d(ctx, d_T, T, (size_t)U * sizeof(int32_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), (size_t)U * sizeof(long long)));
     if (state_class) {
         TRY(d_sc.alloc(ctx, (size_t)J));
         HIPCHK(ctx, pcl_h2d(ctx, d_sc, state_class, (size_t)J * sizeof(int32_t)));
     }
     pcl_timer_begin(ctx, "lda_sort");                            // pcl_kernel_time groups: "lda_sort" (keys and counting sort), "lda_stats" (product and reduction)
     HIPCHK(ctx, hipMemsetAsync(d_key, 0xff, (size_t)F * sizeof(int), st));
-    hipLaunchKernelGGL(lda_key_kernel, dim3((unsigned)std::min(64, (Tmax + 255) / 256), (unsigned)U), dim3(256), 0, st, d_T, d_begin, d_src,
+    hipLaunchKernelGGL(lda_key_kernel, dim3((unsigned)std::min(64, (Tmax + 255) / 256), (unsigned)U), dim3(256), 0, st, d.T, d.begin, d_src,
                        state_class ? d_sc.p : nullptr, d_key, d_span);
     std::vector<int> counts;
     const int rc = pcl_count_sort_device(ctx, F, R, d_key, &counts, &d_order);
@@ -354,16 +334,8 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
     TRY(rc);
     // chunks of one class each, classes ascending
     const long long chunk = lda_chunk();
-    std::vector<int> cls_chunk0(R + 1, 0), chunk_v0, chunk_n;
-    long long V = 0;
-    for (int r = 0; r < R; ++r) {
-        for (long long v0 = V; v0 < V + counts[r]; v0 += chunk) {
-            chunk_v0.push_back((int)v0);
-            chunk_n.push_back((int)std::min(chunk, V + counts[r] - v0));
-        }
-        V += counts[r];
-        cls_chunk0[r + 1] = (int)chunk_v0.size();
-    }
+    std::vector<int> cls_chunk0, chunk_v0, chunk_n;
+    plan_chunks(counts, chunk, &cls_chunk0, &chunk_v0, &chunk_n);
     const int C = (int)chunk_v0.size();
     if (C == 0) return PCL_OK;
     const int NT = (n + 15) / 16, ntiles = NT * (NT + 1) / 2;
@@ -457,29 +429,24 @@ extern "C" int pcl_frames_splice_project(pcl_ctx *ctx, int U, const int32_t *T, 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t nn = (size_t)ctx->F * FDn;
-    std::vector<long long> begin(frame_begin, frame_begin + U);
     std::vector<double> At((size_t)Ds * D_out);
     for (int i = 0; i < D_out; ++i)
         for (int p = 0; p < Ds; ++p) At[(size_t)p * D_out + i] = A[(size_t)i * Ds + p];
     DevBuf<float> n32;
     DevBuf<double> n64, d_At, d_b;
-    DevBuf<int> d_T;
-    DevBuf<long long> d_begin;
+    DevSpans d;
     TRY(n32.alloc(ctx, nn));
     if (ctx->frames64) TRY(n64.alloc(ctx, nn));
     TRY(d_At.alloc(ctx, At.size()));
     TRY(d_b.alloc(ctx, (size_t)D_out));
-    TRY(d_T.alloc(ctx, (size_t)U));
-    TRY(d_begin.alloc(ctx, (size_t)U));
     HIPCHK(ctx, pcl_h2d(ctx, d_At, At.data(), At.size() * sizeof(double)));
     HIPCHK(ctx, pcl_h2d(ctx, d_b, b, (size_t)D_out * sizeof(double)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_T, T, (size_t)U * sizeof(int32_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, d_begin, begin.data(), (size_t)U * sizeof(long long)));
+    TRY(d.upload(ctx, U, T, frame_begin, nullptr));
     pcl_timer_begin(ctx, "lda_project");
     HIPCHK(ctx, hipMemsetAsync(n32, 0, nn * sizeof(float), st));  // rows of no utterance and the padding columns: zero
     if (n64) HIPCHK(ctx, hipMemsetAsync(n64, 0, nn * sizeof(double), st));
     if (Tmax > 0)
-        hipLaunchKernelGGL(lda_project_kernel, dim3((unsigned)((Tmax + PROJ_TF - 1) / PROJ_TF), (unsigned)U), dim3(256), 0, st, d_T, d_begin, ctx->frames64.p,
+        hipLaunchKernelGGL(lda_project_kernel, dim3((unsigned)((Tmax + PROJ_TF - 1) / PROJ_TF), (unsigned)U), dim3(256), 0, st, d.T, d.begin, ctx->frames64.p,
                            ctx->frames32, ctx->FD, D, left, Ds, d_At, d_b, D_out, FDn, n64.p, n32.p);
     pcl_timer_end(ctx, "lda_project");
     HIPCHK(ctx, hipGetLastError());

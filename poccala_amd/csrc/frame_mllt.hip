@@ -9,17 +9,21 @@
 // The apply needs no kernel of its own: pcl_frames_transform and pcl_model_transform_means take W = [0 | A].
 // The rule and every operation order are stated in include/poccala_hip.h; tests/_mllt_twin.py is its NumPy twin.  Everything is float64;
 // no floating-point atomics: two runs give the same bits.  Built with -ffp-contract=off.
-// This file defines PCL_FRAME_MLLT and includes frame_adapt.hip for the kernels the two rules share -- the frame reduction, the sweeps,
-// the inversion, the occupancy and pivot statuses -- whose MLLT = true instantiations are compiled HERE, so that the fMLLR kernels come
-// out as they did before there was a switch (hmm_decode_lm.hip does the same for the decoder).  The price: the small non-template kernels
-// of frame_adapt.hip and adapt_common.h this file also launches (beta, occupancy and pivot statuses) or does not use (gk_reduce, gk_solve,
-// gk_identity) are compiled a second time into this object, a few kilobytes of code; the apply kernel and the host side are left out.
+// The kernels the two rules share -- the frame reduction, the sweeps, the inversion, the occupancy and pivot statuses -- are
+// adapt_frames.h's; their MLLT = true instantiations are compiled HERE, the fMLLR ones in frame_adapt.hip.  The small kernels of
+// adapt_frames.h and adapt_common.h that are no templates are emitted into this object too, those this file launches (beta, occupancy
+// and pivot statuses) and those it does not (gk_reduce, gk_solve, gk_identity): a few kilobytes of code.
 // Every index a kernel forms is bounded by what the host validated: dimensions < Dhost <= 48, frame rows < F, virtual frames < V = the
 // frames of the call's kept utterances, kept states < J, mixtures < M, K-elements < 2 x (kept states x M).
-#define PCL_FRAME_MLLT 1
-#include "frame_adapt.hip"
+#include <math.h>
+
+#include "pcl_internal.h"
 
 namespace {
+
+#include "frame_spans.h"                      // env_positive_ll
+#include "adapt_common.h"
+#include "adapt_frames.h"
 
 static_assert(PCL_MLLT_OK == PCL_FMLLR_OK && PCL_MLLT_LOW_OCCUPANCY == PCL_FMLLR_LOW_OCCUPANCY &&
                   PCL_MLLT_NOT_POSITIVE_DEFINITE == PCL_FMLLR_NOT_POSITIVE_DEFINITE && PCL_MLLT_SINGULAR == PCL_FMLLR_SINGULAR,
@@ -34,11 +38,7 @@ constexpr double STAT_BIAS = 100.0;           // mean_acc holds sum gamma (o + b
 constexpr long long MLLT_FRAME_CHUNK_DEFAULT = 4096;
 
 // env PCL_MLLT_CHUNK, read on EVERY call (as PCL_MLLR_CHUNK is): K-elements per chunk of both GEMMs; 0 = not set
-long long mllt_chunk_env() {
-    const char *e = getenv("PCL_MLLT_CHUNK");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? std::min<long long>(v, 1 << 30) : 0;
-}
+long long mllt_chunk_env() { return std::min<long long>(env_positive_ll("PCL_MLLT_CHUNK", 0), 1 << 30); }
 
 // The frame side's operand source: K = the call's kept frames in batch order, chunk c = the virtual frames [c len, + n).  For feature
 // dimension i and row / column p of the padded grid:   a = x_t[p],   b = p_i(t) x_t[p]   (p < D; 0 beyond), so that sum a[p] b[q] = F_i[p][q]
@@ -151,22 +151,7 @@ __global__ __launch_bounds__(64) void mllt_factor_kernel(const double *__restric
     }
     for (int x = tid; x < n * n; x += 64) A[x / n][x % n] = G[(size_t)i * n * n + x];
     __syncthreads();
-    bool bad = false;
-    for (int j = 0; j < n; ++j) {
-        const double piv = A[j][j];
-        if (!(piv > 0.0 && piv < INFINITY)) {                     // (every thread reads the same value: uniform)
-            bad = true;
-            break;
-        }
-        const double d = sqrt(piv);
-        __syncthreads();
-        if (tid == j) A[j][j] = d;
-        if (tid > j && tid < n) A[tid][j] = A[tid][j] / d;
-        __syncthreads();
-        if (tid > j && tid < n)
-            for (int q = j + 1; q <= tid; ++q) A[tid][q] -= A[tid][j] * A[q][j];
-        __syncthreads();
-    }
+    const bool bad = chol_factor_lds(A, n, tid);
     if (tid == 0) pivot_bad[i] = bad ? 1 : 0;
     if (bad) return;
     for (int x = tid; x < n * n; x += 64) L_out[(size_t)i * n * n + x] = x % n <= x / n ? A[x / n][x % n] : 0.0;

@@ -15,6 +15,7 @@
 
 namespace {
 
+#include "frame_spans.h"                      // env_positive_ll
 #include "adapt_common.h"                     // the GEMM over an operand source, the chunk reduction, the solve: shared with frame_adapt.hip
 
 constexpr double STAT_BIAS = 100.0;           // mean_acc holds sum gamma (o + bias): pcl_launch_mstep_range passes the same constant
