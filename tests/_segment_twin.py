@@ -5,6 +5,8 @@ E1  loop body: expectation from the current parameters, maximization, the new pa
     Q - Q_prev > threshold (Q_prev = -inf at the start); the parameters of the step that fails the test are kept.
 E2  mean = sum gamma x / Gamma; variance = sum gamma (x - NEW mean)^2 / Gamma floored at c_covariance; weight = Gamma / n.
 E3  Q uses this iteration's gamma with the parameters after the M-step; closed form in `q_closed`.
+E4  (include/poccala_hip.h, pcl_seg_em; not the reference, which gives NaN there) a mixture no frame reaches, Gamma = 0: weight 0, its
+    mean and variance kept, nothing added to Q.  `maximization` needs the parameters the E-step used (`prev`) to keep them.
 The Gaussian is the reference's (util.gaussian_function, quirk Q1): constant -D/2 ln 2 pi - 1/2 sum(var).
 """
 import numpy as np
@@ -29,18 +31,25 @@ def expectation(x, mean, var, w, logdet=False):
     return np.exp(lg - lse)
 
 
-def maximization(x, gamma, c_covariance):
-    """-> mean, floored variance, weight, un-floored variance, Gamma"""
+def maximization(x, gamma, c_covariance, prev=None):
+    """-> mean, floored variance, weight, un-floored variance, Gamma.  prev = (mean, var) of the E-step: what a mixture with Gamma = 0
+    keeps (E4; its un-floored variance is reported as 0); without prev such a mixture gets the reference's NaN."""
     big = gamma.sum(0)
-    mean = gamma.T @ x / big[:, None]
-    s2 = np.einsum('im,imd->md', gamma, (x[:, None, :] - mean[None]) ** 2) / big[:, None]
-    return mean, np.maximum(s2, c_covariance), big / len(x), s2, big
+    dead = ~(big > 0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = gamma.T @ x / big[:, None]
+        s2 = np.einsum('im,imd->md', gamma, (x[:, None, :] - mean[None]) ** 2) / big[:, None]
+    var = np.maximum(s2, c_covariance)
+    if prev is not None and dead.any():
+        mean[dead], var[dead], s2[dead] = prev[0][dead], prev[1][dead], 0.0
+    return mean, var, big / len(x), s2, big
 
 
 def q_closed(big, w, var, s2, logdet=False):
     """E3: Q = sum_m Gamma_m [ln w_m - 1/2 sum_d (ln 2 pi + g(var) + s2 / var)], g(v) = v (quirk Q1) or ln v."""
     g = np.log(var) if logdet else var
-    return float((big * (np.log(w) - 0.5 * (LN2PI + g + s2 / var).sum(1))).sum())
+    live = big > 0                                              # E4: 0 ln 0 taken as 0
+    return float((big[live] * (np.log(w[live]) - 0.5 * (LN2PI + g + s2 / var).sum(1)[live])).sum())
 
 
 def q_literal(x, gamma, mean, var, w, logdet=False):
@@ -61,7 +70,7 @@ def em(x, mean, var, w, c_covariance=1e-3, threshold=1.28, max_iters=1000, logde
     q_old, q_seq = -np.inf, []
     for _ in range(max_iters):
         gamma = expectation(x, mean, var, w, logdet)
-        mean, var, w, s2, big = maximization(x, gamma, c_covariance)
+        mean, var, w, s2, big = maximization(x, gamma, c_covariance, prev=(mean, var))
         q_new = q_closed(big, w, var, s2, logdet)
         q_seq.append(q_new)
         if q_new - q_old > threshold:
