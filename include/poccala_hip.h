@@ -108,7 +108,7 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 /* GPU time of a kernel group since the last query, measured with HIP events recorded on the ctx
  * stream around every launch: which = "score" | "fb" | "viterbi" | "accumulate" | "allreduce" |
  * "mfcc" | "vad_dist" | "vad_osf" | "vad_select" | "vad_gather" | "moments" | "flat_fill" | "derive" (the derive pass of
- * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "fmllr" | "fmllr_frames" | "fmllr_gk" | "fmllr_solve" (pcl_fmllr_estimate and its kin, below) | "mllt" | "mllt_frames" | "mllt_gk" | "mllt_solve" (pcl_mllt_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16).
+ * pcl_model_upload / pcl_model_flat_start / pcl_model_mixup) | "mixup" (pcl_model_mixup's plan and fill) | "adapt" | "adapt_gk" | "adapt_solve" (pcl_mllr_estimate and its kin, below) | "fmllr" | "fmllr_frames" | "fmllr_gk" | "fmllr_solve" (pcl_fmllr_estimate and its kin, below) | "mllt" | "mllt_frames" | "mllt_gk" | "mllt_solve" (pcl_mllt_estimate and its kin, below) | "pcm_stage" | "pcm_h2d" (the front-end's transfer: see pcl_mfcc_pcm16) | "pitch_nccf" | "pitch_track" | "pitch_out" (pcl_pitch).
  * Returns the summed milliseconds and the number of launches, then resets the group. */
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches);
 /* The events behind pcl_kernel_time are recorded only while timing is on (default off, or env PCL_TIMERS=1): a
@@ -913,6 +913,65 @@ int pcl_frontend_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t
                        int nfft, int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin,
                        const double *mel_response, const double *dct_matrix, int simple_size, double alpha, double beta, int flags,
                        int32_t *T_out, int64_t *frame_begin_out, double *out_host, int64_t out_rows);
+
+/* ----------------------------------------------------------------- pitch and voicing features (csrc/pitch.hip)
+ * The unit inventory is toned (XIF_tone.csv): two finals that differ only in tone are different units, and the mel filters of the MFCC
+ * smooth away the harmonics that carry tone.  pcl_pitch gives three float64 columns per frame -- voicing, ln f0, delta ln f0 -- on the
+ * MFCC's frame grid, for U signals at once.  The reference has no pitch code; the rule is this project's (tests/_pitch_twin.py is its
+ * NumPy definition):
+ *   geometry  size = int(rate * sampletime), step = int(size * overlap), T = max(1, 1 + ceil((n - size) / step)), frame t starts at sample
+ *             t * step, samples beyond the signal are zero: the rows of pcl_mfcc (which refuses n < size; here that is one frame).
+ *             Lags are the integers Lmin = ceil(rate / f_max) .. Lmax = floor(rate / f_min), L = Lmax - Lmin + 1 of them.
+ *   P1  w = x[t*step : t*step + size + Lmax] minus the mean of its first `size` samples (the zero padding included in the subtraction);
+ *       the mean's sum is 64 partial sums, partial j = 0 + w[j] + w[j + 64] + ..., then 0 + partial 0 + partial 1 + ..., then / size
+ *   P2  a = w[0 : size], b_l = w[l : l + size]; p = a.b_l, e0 = a.a, el = b_l.b_l, each summed over the sample index in ascending order
+ *       from 0, one rounded multiplication and one rounded addition at a time (el directly for every lag, not from e_{l-1});
+ *       nccf_raw = p / sqrt(e0 * el), 0 where e0 * el == 0; nccf_bal = p / sqrt(e0 * el + ballast), 0 where that sum is 0 (ballast in
+ *       squared sample units, 7000 for int16 speech: it pulls quiet frames towards 0)
+ *   P3  c(t, l) = 1 - nccf_bal(t, l) * (1 - soft_min_f0 * l / rate)
+ *   P4  best(0, l) = c(0, l); best(t, l) = c(t, l) + min over l' of [best(t-1, l') + pf * (g[l] - g[l'])^2], ties to the smallest l';
+ *       the last frame takes the smallest l of its minimum and the back-pointers are followed.  g[n_lags] = ln(lag) is the CALLER's float64
+ *       table (as the mel and DCT tables are): the device only subtracts, multiplies and adds
+ *   P5  v = nccf_raw(t, l*); ln f0 = ln(rate / (l* + shift)), shift = 0.5 (y- - y+) / ((y- - 2 y0) + y+) from nccf_raw at l* - 1, l*, l* + 1,
+ *       clamped to +-0.5; no shift at the ends of the lag grid or where that denominator is >= 0; delta ln f0 = ((x[t+1] - x[t-1]) +
+ *       2 (x[t+2] - x[t-2])) / 10 with the frame indices clamped to the utterance's rows (the MFCC's +-2-frame rule, written as differences so
+ *       that a constant column gives exactly 0)
+ * Every step is one correctly rounded float64 operation in the order written (nothing contracted into an fma), nothing is summed with
+ * atomics: nccf_bal, nccf_raw, the lags and v are the twin's bits, ln f0 differs by the device's log alone.  Mean normalisation of ln f0
+ * is NOT part of the rule: pcl_frames_cmvn / pcl_frames_cmvn_sliding do it on resident columns.
+ * signal / sig_off as pcl_mfcc (sig_off[0] = 0).  Outputs (NULL pointers are skipped): out (out_rows, 3) = [v, ln f0, delta], lag
+ * (out_rows,) int32 in samples, nccf_bal / nccf_raw (out_rows, L); out_rows = total frames.  flags: PCL_PITCH_NCCF_IN = nccf_bal and
+ * nccf_raw are the CALLER's (P1-P2 skipped, signal may be NULL; sig_off still gives the rows).
+ * PCL_ERR_INVALID with a pcl_last_error text, before any launch: f_max > rate / 2, L > 1024, L < 2, Lmin < 1, n_lags != L, a negative or
+ * non-finite parameter, a window of more than 64 KiB (size + Lmax + 64 doubles), U outside 1 .. 65535, out_rows != the geometry's.
+ * pcl_kernel_time groups: "pitch_nccf" (P1-P2), "pitch_track" (P3-P4), "pitch_out" (P5).  Device buffers come from the pool and go back
+ * on every path.  Synchronous. */
+#define PCL_PITCH_NCCF_IN 1
+int pcl_pitch(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap, double f_min,
+              double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int flags, double *out, int32_t *lag,
+              double *nccf_bal, double *nccf_raw, int64_t out_rows);
+/* pcl_pitch on int16 PCM through pcl_mfcc_pcm16's staging: a sample becomes a double at the kernel's load, every output is bit-identical
+ * to pcl_pitch on (double)sample. */
+int pcl_pitch_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
+                    double f_min, double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int flags, double *out,
+                    int32_t *lag, double *nccf_bal, double *nccf_raw, int64_t out_rows);
+/* pcl_frontend with the three pitch columns behind the MFCC's: its arguments, then pcl_pitch's parameters.  The MFCC is computed, the
+ * detector runs on the MFCC columns ALONE (V2's distance does not see the pitch columns: T_out, frame_begin_out and the first
+ * rank * {1,2,3} columns are pcl_frontend's bit for bit), P1-P5 run on the same samples, and the survivors are gathered as resident rows
+ * of width rank * {1,2,3} + 3 (float32, padded to the device dimension; float64 too with PCL_FRONTEND_KEEP_F64): the pitch columns are those
+ * of the rows the detector kept (the delta was taken over ALL of the utterance's rows, before the detector).  out_host: NULL or out_rows x
+ * (rank * {1,2,3} + 3).  Every check -- pcl_frontend's, pcl_pitch's, width + 3 > 64 -- runs before the first launch: a failed call leaves the
+ * previous frame matrix in place.  Synchronous. */
+int pcl_frontend_pitch(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
+                       int nfft, int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin,
+                       const double *mel_response, const double *dct_matrix, int simple_size, double alpha, double beta, int flags, double f_min,
+                       double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int32_t *T_out,
+                       int64_t *frame_begin_out, double *out_host, int64_t out_rows);
+int pcl_frontend_pitch_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
+                             int nfft, int filterbanks, int rank, int mfcc_flags, const double *twiddle_cos, const double *twiddle_sin,
+                             const double *mel_response, const double *dct_matrix, int simple_size, double alpha, double beta, int flags,
+                             double f_min, double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags,
+                             int32_t *T_out, int64_t *frame_begin_out, double *out_host, int64_t out_rows);
 
 /* ----------------------------------------------------------------- multi-GPU (RCCL over xGMI)
  * Replaces the reference's file-based accumulator merge (LHMM.py:256-290, Clustering.py:314-367).

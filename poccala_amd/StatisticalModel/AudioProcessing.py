@@ -6,6 +6,8 @@ This is SURVEY.md section 8(f) rows 4 and 6, the steps BEFORE the hot path.  Mir
 data, params, mfcc(sampletime, overlap, nfft, cal_energy, d1, d2) (AudioProcessing.py:100-448); VAD(simple_size), init_mfcc,
 mel_distance, osf, detect, mfcc (:450-543; plotting is not supported).  Added: `mfcc_batch` / `vad_batch` for many utterances in one
 launch; `Engine.frontend` runs both and leaves the survivors resident on the device.  Recording / playback (pyaudio) are out of scope.
+`AudioProcessing.Pitch` / `pitch_batch` have no counterpart in the reference: voicing, ln f0 and its delta on the MFCC's frame grid
+(csrc/pitch.hip through `pcl_pitch`), the columns a toned unit inventory needs beside the cepstra.
 The reference's conventions are kept exactly (they are pinned by tests/golden/G10_mfcc.npz):
 the "Hamming window" is one factor per frame, the spectrum is the rFFT magnitude, every mel filter is two
 rising ramps, the DCT kernel is cos(pi (2k-1) j / 2N) * 2/sqrt(N), c0 is ln(sum of magnitudes).
@@ -16,7 +18,7 @@ import wave
 
 import numpy as np
 
-from .._lib import PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, all_int16, as_c, ptr
+from .._lib import PCL_PITCH_NCCF_IN, PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, all_int16, as_c, ptr
 from ..runtime import default_engine
 
 
@@ -83,6 +85,60 @@ def mfcc_tables(framerate, vec_num=13, nfft=512, filterbanks=26):
     n = np.arange(nfft)
     return (as_c(np.cos(2 * np.pi * n / nfft), np.float64), as_c(-np.sin(2 * np.pi * n / nfft), np.float64),
             as_c(mel_filter_matrix(framerate, nfft, filterbanks), np.float64), as_c(dct_basis(filterbanks, vec_num), np.float64))
+
+
+def frame_count_padded(n_samples, framerate, sampletime=0.025, overlap=0.5):
+    """frame_count, at least 1: the pitch rows of a signal shorter than one frame are one zero-padded frame."""
+    return max(1, frame_count(n_samples, framerate, sampletime, overlap))
+
+
+def pitch_lags(framerate, f_min=50.0, f_max=400.0):
+    """(Lmin, Lmax, g): the integer lag grid ceil(rate / f_max) .. floor(rate / f_min) of pcl_pitch and its float64 table g = ln(lag)."""
+    lmin, lmax = int(math.ceil(framerate / f_max)), int(math.floor(framerate / f_min))
+    return lmin, lmax, as_c(np.log(np.arange(lmin, max(lmax, lmin) + 1, dtype=np.float64)), np.float64)
+
+
+def pitch_batch(signals, framerate, sampletime=0.025, overlap=0.5, f_min=50.0, f_max=400.0, ballast=7000.0, soft_min_f0=10.0, pf=0.1,
+                details=False, nccf=None, engine=None):
+    """Pitch features of many signals in one call: list of (T_u, 3) float64 arrays [voicing, ln f0, delta ln f0] whose rows are the
+    MFCC's (mfcc_batch with the same sampletime / overlap).  When every signal is an np.int16 array the samples travel as int16
+    (pcl_pitch_pcm16) and give the same bits.  details=True: (rows, info) with info = dict(lag=[(T_u,) int32 lags in samples],
+    nccf_bal=[(T_u, L)], nccf_raw=[(T_u, L)], lag_min, lag_max).  nccf=(bal_list, raw_list): the correlations are the caller's
+    (PCL_PITCH_NCCF_IN; `signals` then only gives the lengths)."""
+    eng = engine or default_engine()
+    signals = list(signals)
+    pcm16 = all_int16(signals)
+    wire = np.int16 if pcm16 else np.float64
+    sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
+    off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    frames = [frame_count_padded(len(s), framerate, sampletime, overlap) for s in sigs]
+    rows = int(sum(frames))
+    lmin, lmax, g = pitch_lags(framerate, f_min, f_max)
+    L = len(g)
+    flat = as_c(np.concatenate(sigs), wire) if sigs else np.zeros(0, dtype=wire)
+    if flat.size == 0:
+        flat = np.zeros(1, dtype=wire)                  # (a pointer to hand over; sig_off says nothing of it is read)
+    out = np.empty((rows, 3))
+    lag = np.empty(rows, dtype=np.int32) if details else None
+    flags = 0
+    if nccf is not None:
+        flags = PCL_PITCH_NCCF_IN
+        bal = as_c(np.concatenate([np.asarray(b, dtype=np.float64) for b in nccf[0]]), np.float64)
+        raw = as_c(np.concatenate([np.asarray(r, dtype=np.float64) for r in nccf[1]]), np.float64)
+        if bal.shape != (rows, L) or raw.shape != (rows, L):
+            raise ValueError('pitch_batch: nccf arrays of shape %s / %s, the geometry gives (%d, %d)' % (bal.shape, raw.shape, rows, L))
+    else:
+        bal = np.empty((rows, L)) if details else None
+        raw = np.empty((rows, L)) if details else None
+    call = eng._lib.pcl_pitch_pcm16 if pcm16 else eng._lib.pcl_pitch
+    eng._check(call(eng._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap), float(f_min), float(f_max),
+                    float(ballast), float(soft_min_f0), float(pf), ptr(g), int(L), flags, ptr(out), ptr(lag), ptr(bal), ptr(raw),
+                    C.c_int64(rows)))
+    cuts = np.cumsum(frames)[:-1]
+    res = np.split(out, cuts)
+    if not details:
+        return res
+    return res, dict(lag=np.split(lag, cuts), nccf_bal=np.split(bal, cuts), nccf_raw=np.split(raw, cuts), lag_min=lmin, lag_max=lmax)
 
 
 def _vad_call(eng, mats, simple_size, alpha, beta, flags, want, dist=None, osf=None):
@@ -212,3 +268,31 @@ class AudioProcessing(object):
             if show_pic:
                 raise NotImplementedError('VAD.mfcc(show_pic=True): plotting is not supported')
             return vad_batch([self.__features()], self.__simple_size)[0]
+
+    class Pitch(object):
+        """Voicing, ln f0 and delta ln f0 of a signal on the MFCC's frame grid (no counterpart in the reference; rule P1-P5 of
+        include/poccala_hip.h at pcl_pitch): a normalised cross-correlation over the lags rate / f_max .. rate / f_min and a dynamic
+        programme over them, on the device.  Used like MFCC: init_audio / set_signal, then pitch()."""
+
+        def __init__(self, f_min=50.0, f_max=400.0):
+            self.__reader = AudioProcessing.MFCC()
+            self.__f_min, self.__f_max = f_min, f_max
+
+        @property
+        def data(self):
+            return self.__reader.data
+
+        @property
+        def params(self):
+            return self.__reader.params
+
+        def init_audio(self, wav=None, path=None):
+            self.__reader.init_audio(wav=wav, path=path)
+
+        def set_signal(self, samples, framerate):
+            self.__reader.set_signal(samples, framerate)
+
+        def pitch(self, sampletime=0.025, overlap=0.5, ballast=7000.0, soft_min_f0=10.0, pf=0.1):
+            """(T, 3) float64: [voicing in -1 .. 1, ln f0, delta ln f0], one row per MFCC row."""
+            return pitch_batch([self.__reader.data], self.params[2], sampletime, overlap, self.__f_min, self.__f_max, ballast, soft_min_f0,
+                               pf)[0]

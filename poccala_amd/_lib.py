@@ -17,6 +17,7 @@ PCL_ROW_ENTRY, PCL_ROW_EXIT = -1, -2
 PCL_MAX_PASS = 16
 PCL_VAD_DIST_IN, PCL_VAD_OSF_IN = 1, 2
 PCL_FRONTEND_NO_VAD, PCL_FRONTEND_KEEP_F64 = 1, 2
+PCL_PITCH_NCCF_IN = 1
 PCL_MLLR_OK, PCL_MLLR_LOW_OCCUPANCY, PCL_MLLR_FEW_MIXTURES, PCL_MLLR_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3
 PCL_CMVN_OK, PCL_CMVN_LOW_COUNT, PCL_CMVN_NOT_FINITE = 0, 1, 2
 SEG_GET = dict(counts=0, order=1, assign=2, seeds=3)
@@ -104,6 +105,12 @@ PROTOTYPES = {
     'pcl_vad': (_i, [_vp, _i, _vp, _vp, _i, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     'pcl_frontend': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),
     'pcl_frontend_pcm16': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _vp, _vp, _vp, C.c_int64]),
+    'pcl_pitch': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_int64]),
+    'pcl_pitch_pcm16': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _d, _d, _d, _d, _d, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_int64]),
+    'pcl_frontend_pitch': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _d, _d, _d, _d, _d, _vp, _i,
+                                _vp, _vp, _vp, C.c_int64]),
+    'pcl_frontend_pitch_pcm16': (_i, [_vp, _i, _vp, _vp, _i, _d, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _i, _d, _d, _d, _d, _d, _vp, _i,
+                                      _vp, _vp, _vp, C.c_int64]),
     'pcl_timing_enable': (_i, [_vp, _i]),
     'pcl_device_count': (_i, [C.POINTER(_i)]),
     'pcl_units_upload': (_i, [_vp, _i, _i, _vp, _vp]),

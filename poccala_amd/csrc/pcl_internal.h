@@ -14,6 +14,7 @@
 
 #include "../../include/poccala_hip.h"
 #include "pcl_own.h"
+#include "pitch_check.h"
 
 // ---------------------------------------------------------------- device-side descriptors
 // One scoring segment = one (utterance, emitting row): `len` consecutive frames starting at frame
@@ -663,6 +664,24 @@ int pcl_count_sort_device(pcl_ctx *ctx, long long F, int J, const int *d_key, st
 int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const void *signal, bool pcm16, const int64_t *sig_off, int framerate,
                     double sampletime, double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos,
                     const double *twiddle_sin, const double *mel_response, const double *dct_matrix, int64_t out_rows, DevBuf<double> *d_out,
-                    std::vector<long long> *row_off);
+                    std::vector<long long> *row_off, DevBuf<unsigned char> *d_sig = nullptr);
+// nsig samples (int16_t through the context's page-locked staging when pcm16, else double in one blocking copy) into d_sig, as
+// pcl_mfcc_device sends them.  Returns with the main stream behind the last copy; on a failure the caller drains ctx->pcm.stream before it
+// lets d_sig go.
+int pcl_signal_upload(pcl_ctx *ctx, const char *who, void *d_sig, const void *signal, bool pcm16, size_t nsig);
 void pcl_mfcc_release(pcl_ctx *ctx);          // the staging buffers, their events and stream, the cached tables (pcl_destroy, streams drained)
+// pitch.hip: the parameters of rule P1-P5 beside the geometry, and the device buffers of one call
+struct PitchArgs {
+    double f_min, f_max, ballast, soft_min_f0, pf;
+    const double *g;             // host: ln(lag) for the n_lags lags
+    int n_lags;
+};
+struct PitchWork {
+    DevBuf<long long> row_off, sig_off;
+    DevBuf<int> frame_utt, lagidx, lag;      // lagidx: the track's lag index (0 = Lmin) per row; lag: in samples, when asked for
+    DevBuf<double> g, bal, raw, out;         // bal / raw (rows, L); out (rows, 3) = [v, ln f0, delta ln f0]
+    DevBuf<short> bp;                        // (rows, L) back-pointers
+};
+int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, int rate, const PitchArgs &a, int U, const int64_t *sig_off,
+                     const std::vector<long long> &row_off, const void *d_sig, bool pcm16, bool nccf_in, bool want_lag, PitchWork *w);
 void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms);   // a host-clock entry of a timer group (only while timing is on)

@@ -167,7 +167,8 @@ class Engine(object):
         self._frames_key = key
 
     def frontend(self, signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nfft=512, filterbanks=26, cal_energy=True,
-                 d1=True, d2=True, vad=True, simple_size=16, alpha=0.5, beta=0.93, keep_f64=False, fetch=False):
+                 d1=True, d2=True, vad=True, simple_size=16, alpha=0.5, beta=0.93, keep_f64=False, fetch=False, pitch=False, f_min=50.,
+                 f_max=400., ballast=7000., soft_min_f0=10., pf=0.1):
         """PCM -> resident frames: MFCC (AudioProcessing.MFCC.mfcc), the voice-activity detector (AudioProcessing.VAD.mfcc) and the
         compaction of its survivors in one call, without the features leaving the device -- AcousticModel.__load_audio
         (AcousticModel.py:463-477) for a list of signals.  Afterwards the survivors are the current frame matrix, exactly as
@@ -179,8 +180,11 @@ class Engine(object):
         When EVERY signal is an np.int16 array (what a wav file holds, and what AudioProcessing.MFCC.init_audio reads) the samples are
         concatenated and sent as int16 (pcl_frontend_pcm16: a quarter of the bytes, page-locked staging, no float64 copy on the host)
         and become float64 in the kernel -- the same bits as the float64 route, which anything else takes (float arrays that hold
-        integers, mixed lists, Python lists): nothing is rounded silently."""
-        from .StatisticalModel.AudioProcessing import frame_count, mfcc_tables
+        integers, mixed lists, Python lists): nothing is rounded silently.
+        pitch=True (pcl_frontend_pitch): three more columns behind the MFCC's -- voicing, ln f0, delta ln f0 over f_min .. f_max Hz
+        (AudioProcessing.pitch_batch's, rule P1-P5) -- so the rows are vec_num * {1,2,3} + 3 wide.  The detector still sees the MFCC columns
+        alone: lens, begin and the MFCC columns are those of pitch=False bit for bit.  The default takes the call it always took."""
+        from .StatisticalModel.AudioProcessing import frame_count, mfcc_tables, pitch_lags
         signals = list(signals)
         pcm16 = all_int16(signals)
         wire = np.int16 if pcm16 else np.float64
@@ -193,6 +197,18 @@ class Engine(object):
         mflags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
         flags = (0 if vad else _lib.PCL_FRONTEND_NO_VAD) | (_lib.PCL_FRONTEND_KEEP_F64 if keep_f64 else 0)
         lens, begin = np.empty(len(sigs), dtype=np.int32), np.empty(len(sigs), dtype=np.int64)
+        if pitch:
+            dim += 3
+            _, _, g = pitch_lags(framerate, f_min, f_max)
+            out = np.empty((max(rows, 1), dim)) if fetch else None
+            call = self._lib.pcl_frontend_pitch_pcm16 if pcm16 else self._lib.pcl_frontend_pitch
+            self._check(call(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
+                             int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
+                             int(simple_size), float(alpha), float(beta), flags, float(f_min), float(f_max), float(ballast),
+                             float(soft_min_f0), float(pf), ptr(g), int(len(g)), ptr(lens), ptr(begin), ptr(out), C.c_int64(rows)))
+            self.F, self.FD = int(lens.sum()), dim
+            self._frames_key = None
+            return (lens, begin, out[:self.F].copy()) if fetch else (lens, begin)
         out = np.empty((max(rows, 1), dim)) if fetch else None
         call = self._lib.pcl_frontend_pcm16 if pcm16 else self._lib.pcl_frontend
         self._check(call(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
