@@ -18,7 +18,7 @@ import wave
 
 import numpy as np
 
-from .._lib import PCL_PITCH_NCCF_IN, PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, all_int16, as_c, ptr
+from .._lib import PCL_PITCH_NCCF_IN, PCL_VAD_DIST_IN, PCL_VAD_OSF_IN, as_c, pack_signals, ptr
 from ..runtime import default_engine
 
 
@@ -52,26 +52,26 @@ def dct_basis(filterbanks, rank):
     return (2 / filterbanks ** 0.5) * np.cos(np.pi * (2 * k - 1) * j / (2 * filterbanks))
 
 
+def mfcc_flags(cal_energy=True, d1=False, d2=False):
+    """The flag word of pcl_mfcc / pcl_frontend: 1 = c0 <- ln(energy), 2 = deltas, 4 = their deltas as well (only with d1)."""
+    return (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
+
+
+def mfcc_dim(vec_num, flags):
+    return vec_num * (3 if flags & 4 else 2 if flags & 2 else 1)
+
+
 def mfcc_batch(signals, framerate, vec_num=13, sampletime=0.025, overlap=0.5, nfft=512, filterbanks=26, cal_energy=True,
                d1=False, d2=False, engine=None):
     """MFCC matrices of many signals in one launch: list of (T_u, vec_num * {1,2,3}) float64 arrays.  When every signal is an np.int16
     array the samples travel as int16 (pcl_mfcc_pcm16) and give the same bits; anything else is sent as float64 (Engine.frontend's rule)."""
     eng = engine or default_engine()
-    signals = list(signals)
-    pcm16 = all_int16(signals)
-    wire = np.int16 if pcm16 else np.float64
-    sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    sigs, flat, off, pcm16 = pack_signals(signals)
     frames = [frame_count(len(s), framerate, sampletime, overlap) for s in sigs]
     rows = int(sum(frames))
-    dim = vec_num * (3 if (d1 and d2) else 2 if d1 else 1)
-    n = np.arange(nfft)
-    twc, tws = as_c(np.cos(2 * np.pi * n / nfft), np.float64), as_c(-np.sin(2 * np.pi * n / nfft), np.float64)
-    resp = as_c(mel_filter_matrix(framerate, nfft, filterbanks), np.float64)
-    dct = as_c(dct_basis(filterbanks, vec_num), np.float64)
-    flat = as_c(np.concatenate(sigs), wire)
-    out = np.empty((rows, dim))
-    flags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
+    flags = mfcc_flags(cal_energy, d1, d2)
+    twc, tws, resp, dct = mfcc_tables(framerate, vec_num, nfft, filterbanks)
+    out = np.empty((rows, mfcc_dim(vec_num, flags)))
     call = eng._lib.pcl_mfcc_pcm16 if pcm16 else eng._lib.pcl_mfcc
     eng._check(call(eng._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
                     int(nfft), int(filterbanks), int(vec_num), flags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
@@ -106,18 +106,13 @@ def pitch_batch(signals, framerate, sampletime=0.025, overlap=0.5, f_min=50.0, f
     nccf_bal=[(T_u, L)], nccf_raw=[(T_u, L)], lag_min, lag_max).  nccf=(bal_list, raw_list): the correlations are the caller's
     (PCL_PITCH_NCCF_IN; `signals` then only gives the lengths)."""
     eng = engine or default_engine()
-    signals = list(signals)
-    pcm16 = all_int16(signals)
-    wire = np.int16 if pcm16 else np.float64
-    sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    sigs, flat, off, pcm16 = pack_signals(signals, none_ok=True)
     frames = [frame_count_padded(len(s), framerate, sampletime, overlap) for s in sigs]
     rows = int(sum(frames))
     lmin, lmax, g = pitch_lags(framerate, f_min, f_max)
     L = len(g)
-    flat = as_c(np.concatenate(sigs), wire) if sigs else np.zeros(0, dtype=wire)
     if flat.size == 0:
-        flat = np.zeros(1, dtype=wire)                  # (a pointer to hand over; sig_off says nothing of it is read)
+        flat = np.zeros(1, dtype=flat.dtype)            # (a pointer to hand over; sig_off says nothing of it is read)
     out = np.empty((rows, 3))
     lag = np.empty(rows, dtype=np.int32) if details else None
     flags = 0

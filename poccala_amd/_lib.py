@@ -216,3 +216,17 @@ def all_int16(signals):
     sequence; no signal at all) takes the float64 entry points, as before there was a choice."""
     signals = list(signals) if not isinstance(signals, (list, tuple)) else signals
     return len(signals) > 0 and all(isinstance(s, np.ndarray) and s.dtype == np.int16 for s in signals)
+
+
+def pack_signals(signals, none_ok=False):
+    """What every front-end entry point is handed: (sigs, flat, off, pcm16) -- the signals as 1-D arrays of the wire type (np.int16 when
+    all_int16(signals), else np.float64), their concatenation, sig_off (U + 1,) int64, and the route.  No signal at all is a ValueError
+    before any call into the library, unless none_ok (pitch_batch, which lets the library refuse it): then `flat` is empty."""
+    signals = list(signals)
+    pcm16 = all_int16(signals)
+    wire = np.int16 if pcm16 else np.float64
+    sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
+    off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+    if none_ok and not sigs:
+        return sigs, np.zeros(0, dtype=wire), off, pcm16
+    return sigs, as_c(np.concatenate(sigs), wire), off, pcm16

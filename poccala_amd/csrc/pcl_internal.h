@@ -14,7 +14,7 @@
 
 #include "../../include/poccala_hip.h"
 #include "pcl_own.h"
-#include "pitch_check.h"
+#include "frontend_host.h"
 
 // ---------------------------------------------------------------- device-side descriptors
 // One scoring segment = one (utterance, emitting row): `len` consecutive frames starting at frame
@@ -415,6 +415,10 @@ static inline hipError_t pcl_h2d(pcl_ctx *ctx, void *dst, const void *src, size_
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
 }
+// Device -> host copy QUEUED on the main stream: the caller waits for the stream before it reads dst.
+static inline hipError_t pcl_d2h_queue(pcl_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+}
 // Descriptors into a buffer NO queued kernel can be reading (freshly allocated, or any buffer of a batch that has not launched
 // anything yet): a stream of their own, so that creating a batch in the middle of a stream of chunks does not wait for the
 // scoring kernel that happens to run on the main stream (28 ms per new batch in the C5 pipeline).  Complete at return.
@@ -658,30 +662,27 @@ int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int
 // pcl_seg_create's counting sort alone (gmm_segment.hip): d_key[f] in [0, J) or anything else = not kept -> counts (J, host) and the kept
 // rows key by key, each key in ascending row order (*d_order, sum counts entries).  Complete on return.
 int pcl_count_sort_device(pcl_ctx *ctx, long long F, int J, const int *d_key, std::vector<int> *counts, DevBuf<int> *d_order);
-// pcl_mfcc's device half (mfcc.hip): the (rows, dim) float64 feature matrix stays on the device (in *d_out: the caller's from then on),
-// complete on return; row_off[U + 1] = first row of every utterance.  `who` prefixes the error messages.  pcm16: `signal` is int16_t
-// samples, which travel through the context's page-locked staging; otherwise double, copied from the caller's memory as it is.
-int pcl_mfcc_device(pcl_ctx *ctx, const char *who, int U, const void *signal, bool pcm16, const int64_t *sig_off, int framerate,
-                    double sampletime, double overlap, int nfft, int nfilt, int rank, int flags, const double *twiddle_cos,
-                    const double *twiddle_sin, const double *mel_response, const double *dct_matrix, int64_t out_rows, DevBuf<double> *d_out,
-                    std::vector<long long> *row_off, DevBuf<unsigned char> *d_sig = nullptr);
-// nsig samples (int16_t through the context's page-locked staging when pcm16, else double in one blocking copy) into d_sig, as
-// pcl_mfcc_device sends them.  Returns with the main stream behind the last copy; on a failure the caller drains ctx->pcm.stream before it
-// lets d_sig go.
-int pcl_signal_upload(pcl_ctx *ctx, const char *who, void *d_sig, const void *signal, bool pcm16, size_t nsig);
+// The front-end's internal halves (the structs and the one frame geometry: frontend_host.h).  `who` prefixes the error messages.
+// mfcc.hip.  pcl_mfcc_check: the arguments, nfft and the frame kernel's LDS need against the device's grant, before anything is allocated.
+// pcl_mfcc_device: the (rows, dim) float64 feature matrix of rows `fr` (frame_rows, whole frames), left on the device in *d_out (the
+// caller's from then on), complete on return.  int16 samples travel through the context's page-locked staging, double ones are copied from
+// the caller's memory as they are; with d_sig the samples stay on the device too (pcl_frontend_pitch reads them again).
+int pcl_mfcc_check(pcl_ctx *ctx, const char *who, const SignalView &sig, const MfccSpec &m);
+int pcl_mfcc_device(pcl_ctx *ctx, const char *who, const SignalView &sig, const MfccSpec &m, const FrameRows &fr, DevBuf<double> *d_out,
+                    DevBuf<unsigned char> *d_sig = nullptr);
+// The samples into d_sig, as pcl_mfcc_device sends them.  Returns with the main stream behind the last copy; on a failure the caller drains
+// ctx->pcm.stream before it lets d_sig go.
+int pcl_signal_upload(pcl_ctx *ctx, const char *who, void *d_sig, const SignalView &sig);
 void pcl_mfcc_release(pcl_ctx *ctx);          // the staging buffers, their events and stream, the cached tables (pcl_destroy, streams drained)
-// pitch.hip: the parameters of rule P1-P5 beside the geometry, and the device buffers of one call
-struct PitchArgs {
-    double f_min, f_max, ballast, soft_min_f0, pf;
-    const double *g;             // host: ln(lag) for the n_lags lags
-    int n_lags;
-};
+// pitch.hip: the device buffers of one call, and what the caller wants of it
 struct PitchWork {
     DevBuf<long long> row_off, sig_off;
     DevBuf<int> frame_utt, lagidx, lag;      // lagidx: the track's lag index (0 = Lmin) per row; lag: in samples, when asked for
     DevBuf<double> g, bal, raw, out;         // bal / raw (rows, L); out (rows, 3) = [v, ln f0, delta ln f0]
     DevBuf<short> bp;                        // (rows, L) back-pointers
+    bool nccf_in = false;                    // bal / raw hold the caller's correlations (PCL_PITCH_NCCF_IN): d_sig is not read
+    bool want_lag = false;
 };
-int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, int rate, const PitchArgs &a, int U, const int64_t *sig_off,
-                     const std::vector<long long> &row_off, const void *d_sig, bool pcm16, bool nccf_in, bool want_lag, PitchWork *w);
+int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, const PitchArgs &a, const SignalView &sig, const FrameRows &fr,
+                     const void *d_sig, PitchWork *w);
 void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms);   // a host-clock entry of a timer group (only while timing is on)

@@ -26,6 +26,12 @@ int pcl_ctx_device(const pcl_ctx *ctx);
         hipError_t _e = (call);                                                                   \
         if (_e != hipSuccess) PCL_FAIL(ctx, PCL_ERR_HIP, "%s: %s", #call, hipGetErrorString(_e)); \
     } while (0)
+// ... with the entry point's name in front, where several entry points share the code
+#define HIPWHO(ctx, who, call)                                                                                   \
+    do {                                                                                                         \
+        hipError_t _e = (call);                                                                                  \
+        if (_e != hipSuccess) PCL_FAIL(ctx, PCL_ERR_HIP, "%s: %s: %s", who, #call, hipGetErrorString(_e));       \
+    } while (0)
 #define TRY(x)                    \
     do {                          \
         int _r = (x);             \

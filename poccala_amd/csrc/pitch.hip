@@ -165,10 +165,6 @@ __global__ __launch_bounds__(256) void pitch_delta_kernel(const long long *__res
     out[(size_t)row * 3 + 2] = ((at(t + 1) - at(t - 1)) + 2.0 * (at(t + 2) - at(t - 2))) / 10.0;
 }
 
-hipError_t d2h(pcl_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
-}
-
 // the signal of one stand-alone call on the device.  A failure path may leave the staging stream copying into `sig`: it is drained first.
 struct PitchSig {
     pcl_ctx *ctx;
@@ -179,41 +175,49 @@ struct PitchSig {
     }
 };
 
-int pitch_to_host(pcl_ctx *ctx, const char *who, int U, const void *signal, bool pcm16, const int64_t *sig_off, int framerate, double sampletime,
-                  double overlap, double f_min, double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int flags,
-                  double *out, int32_t *lag, double *nccf_bal, double *nccf_raw, int64_t out_rows) {
+// where a stand-alone call leaves its results on the host (each may be NULL); with PCL_PITCH_NCCF_IN nccf_bal / nccf_raw are its input
+struct PitchOut {
+    double *out;
+    int32_t *lag;
+    double *nccf_bal, *nccf_raw;
+    int64_t n_rows;
+};
+
+int pitch_to_host(pcl_ctx *ctx, const char *who, const SignalView &sig, const FrameSpec &f, const PitchArgs &a, int flags, const PitchOut &o) {
+    if (!ctx) return PCL_ERR_INVALID;
     const bool nccf_in = (flags & PCL_PITCH_NCCF_IN) != 0;
     if (flags & ~PCL_PITCH_NCCF_IN) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: unknown flags %d", who, flags);
     PitchGeom gm;
-    const PitchArgs a{f_min, f_max, ballast, soft_min_f0, pf, g, n_lags};
-    TRY(pitch_geometry_check(ctx, who, framerate, sampletime, overlap, f_min, f_max, ballast, soft_min_f0, pf, g, n_lags, &gm));
-    std::vector<long long> ro;
-    TRY(pitch_rows_check(ctx, who, U, sig_off, gm, false, &ro));
-    const long long rows = ro[U];
-    if (rows != out_rows) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: caller expects %lld frames, geometry gives %lld", who, (long long)out_rows, rows);
-    if (nccf_in && (!nccf_bal || !nccf_raw)) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: PCL_PITCH_NCCF_IN without nccf_bal and nccf_raw", who);
-    if (!nccf_in && !signal) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: NULL signal", who);
+    TRY(pitch_geometry_check(ctx, who, f, a, &gm));
+    FrameRows fr;
+    TRY(frame_rows(ctx, who, sig, gm, false, &fr.row_off));
+    const long long rows = fr.rows();
+    if (rows != o.n_rows) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: caller expects %lld frames, geometry gives %lld", who, (long long)o.n_rows, rows);
+    if (nccf_in && (!o.nccf_bal || !o.nccf_raw)) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: PCL_PITCH_NCCF_IN without nccf_bal and nccf_raw", who);
+    if (!nccf_in && !sig.samples) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: NULL signal", who);
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    fr.frame_utt = frame_utt_of(fr.row_off);
     const size_t nl = (size_t)rows * gm.L;
     std::optional<pcl_free_synced_scope> synced;                 // engaged once the main stream has been waited for: declared before the buffers
     PitchSig s(ctx);
     PitchWork w;
+    w.nccf_in = nccf_in;
+    w.want_lag = o.lag != nullptr;
     if (nccf_in) {
         TRY(w.bal.alloc(ctx, nl));
         TRY(w.raw.alloc(ctx, nl));
-        HIPCHK(ctx, pcl_h2d(ctx, w.bal, nccf_bal, nl * sizeof(double)));
-        HIPCHK(ctx, pcl_h2d(ctx, w.raw, nccf_raw, nl * sizeof(double)));
+        HIPCHK(ctx, pcl_h2d(ctx, w.bal, o.nccf_bal, nl * sizeof(double)));
+        HIPCHK(ctx, pcl_h2d(ctx, w.raw, o.nccf_raw, nl * sizeof(double)));
     } else {
-        const size_t nsig = (size_t)sig_off[U];
-        TRY(s.sig.alloc(ctx, nsig * (pcm16 ? sizeof(int16_t) : sizeof(double))));
-        TRY(pcl_signal_upload(ctx, who, s.sig, signal, pcm16, nsig));
+        TRY(s.sig.alloc(ctx, sig.total() * sig.sample_bytes()));
+        TRY(pcl_signal_upload(ctx, who, s.sig, sig));
     }
-    TRY(pcl_pitch_device(ctx, who, gm, framerate, a, U, sig_off, ro, s.sig, pcm16, nccf_in, lag != nullptr, &w));
+    TRY(pcl_pitch_device(ctx, who, gm, a, sig, fr, s.sig, &w));
     hipError_t e = hipSuccess;
-    if (out) e = d2h(ctx, out, w.out, (size_t)rows * 3 * sizeof(double));
-    if (e == hipSuccess && lag) e = d2h(ctx, lag, w.lag, (size_t)rows * sizeof(int));
-    if (e == hipSuccess && !nccf_in && nccf_bal) e = d2h(ctx, nccf_bal, w.bal, nl * sizeof(double));
-    if (e == hipSuccess && !nccf_in && nccf_raw) e = d2h(ctx, nccf_raw, w.raw, nl * sizeof(double));
+    if (o.out) e = pcl_d2h_queue(ctx, o.out, w.out, (size_t)rows * 3 * sizeof(double));
+    if (e == hipSuccess && o.lag) e = pcl_d2h_queue(ctx, o.lag, w.lag, (size_t)rows * sizeof(int));
+    if (e == hipSuccess && !nccf_in && o.nccf_bal) e = pcl_d2h_queue(ctx, o.nccf_bal, w.bal, nl * sizeof(double));
+    if (e == hipSuccess && !nccf_in && o.nccf_raw) e = pcl_d2h_queue(ctx, o.nccf_raw, w.raw, nl * sizeof(double));
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) PCL_FAIL(ctx, PCL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     synced.emplace();                                            // the kernels and copies are done (and every staged chunk they waited for)
@@ -223,16 +227,13 @@ int pitch_to_host(pcl_ctx *ctx, const char *who, int U, const void *signal, bool
 }  // namespace
 
 // P1-P5 queued on the main stream (NOT waited for): every buffer of the call is in *w and stays the caller's until it has waited.
-// d_sig: the concatenated samples on the device (int16_t when pcm16, else double; not read with nccf_in, when w->bal / w->raw hold the
-// caller's arrays).  The checks (pitch_check.h) are the caller's: gm and row_off come from them.
-int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, int rate, const PitchArgs &a, int U, const int64_t *sig_off,
-                     const std::vector<long long> &row_off, const void *d_sig, bool pcm16, bool nccf_in, bool want_lag, PitchWork *w) {
-    const long long rows = row_off[U];
-    const int L = gm.L;
-    std::vector<int> frame_utt((size_t)rows);
-    for (int u = 0; u < U; ++u)
-        for (long long r = row_off[u]; r < row_off[u + 1]; ++r) frame_utt[(size_t)r] = u;
-    std::vector<long long> so(sig_off, sig_off + U + 1);
+// d_sig: the concatenated samples on the device (int16_t when sig.pcm16, else double; not read with w->nccf_in, when w->bal / w->raw hold
+// the caller's arrays).  The checks (frontend_host.h) are the caller's: gm and fr come from them.
+int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, const PitchArgs &a, const SignalView &sig, const FrameRows &fr,
+                     const void *d_sig, PitchWork *w) {
+    const int U = sig.U, L = gm.L;
+    const long long rows = fr.rows();
+    const std::vector<long long> so(sig.sig_off, sig.sig_off + U + 1);
     TRY(w->row_off.alloc(ctx, (size_t)U + 1));
     TRY(w->sig_off.alloc(ctx, (size_t)U + 1));
     TRY(w->frame_utt.alloc(ctx, (size_t)rows));
@@ -240,21 +241,20 @@ int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, int rat
     TRY(w->out.alloc(ctx, (size_t)rows * 3));
     TRY(w->bp.alloc(ctx, (size_t)rows * L));
     TRY(w->lagidx.alloc(ctx, (size_t)rows));
-    if (want_lag) TRY(w->lag.alloc(ctx, (size_t)rows));
-    if (!nccf_in) {
+    if (w->want_lag) TRY(w->lag.alloc(ctx, (size_t)rows));
+    if (!w->nccf_in) {
         TRY(w->bal.alloc(ctx, (size_t)rows * L));
         TRY(w->raw.alloc(ctx, (size_t)rows * L));
     }
-#define PT(call) do { hipError_t _e = (call); if (_e != hipSuccess) PCL_FAIL(ctx, PCL_ERR_HIP, "%s: %s: %s", who, #call, hipGetErrorString(_e)); } while (0)
-    PT(pcl_h2d(ctx, w->row_off, row_off.data(), ((size_t)U + 1) * sizeof(long long)));
-    PT(pcl_h2d(ctx, w->sig_off, so.data(), ((size_t)U + 1) * sizeof(long long)));
-    PT(pcl_h2d(ctx, w->frame_utt, frame_utt.data(), (size_t)rows * sizeof(int)));
-    PT(pcl_h2d(ctx, w->g, a.g, (size_t)L * sizeof(double)));
+    HIPWHO(ctx, who, pcl_h2d(ctx, w->row_off, fr.row_off.data(), ((size_t)U + 1) * sizeof(long long)));
+    HIPWHO(ctx, who, pcl_h2d(ctx, w->sig_off, so.data(), ((size_t)U + 1) * sizeof(long long)));
+    HIPWHO(ctx, who, pcl_h2d(ctx, w->frame_utt, fr.frame_utt.data(), (size_t)rows * sizeof(int)));
+    HIPWHO(ctx, who, pcl_h2d(ctx, w->g, a.g, (size_t)L * sizeof(double)));
     const unsigned lanes = (unsigned)((L + 63) / 64 * 64);       // <= 1024 (PITCH_MAX_LAGS)
-    if (!nccf_in) {
+    if (!w->nccf_in) {
         const size_t shm = pitch_lds_bytes(gm);                  // <= 64 KiB (pitch_geometry_check)
         pcl_timer_begin(ctx, "pitch_nccf");
-        if (pcm16)
+        if (sig.pcm16)
             hipLaunchKernelGGL(pitch_nccf_kernel<int16_t>, dim3((unsigned)rows), dim3(lanes), shm, ctx->stream, (const int16_t *)d_sig, w->sig_off,
                                w->row_off, w->frame_utt, gm.size, gm.step, gm.Lmin, L, a.ballast, w->bal, w->raw);
         else
@@ -264,31 +264,28 @@ int pcl_pitch_device(pcl_ctx *ctx, const char *who, const PitchGeom &gm, int rat
     }
     pcl_timer_begin(ctx, "pitch_track");
     hipLaunchKernelGGL(pitch_track_kernel, dim3((unsigned)U), dim3(lanes), (size_t)3 * L * sizeof(double), ctx->stream, w->bal, w->row_off, w->g,
-                       gm.Lmin, L, (double)rate, a.soft_min_f0, a.pf, w->bp, w->lagidx);
+                       gm.Lmin, L, (double)gm.rate, a.soft_min_f0, a.pf, w->bp, w->lagidx);
     pcl_timer_end(ctx, "pitch_track");
     pcl_timer_begin(ctx, "pitch_out");
     const unsigned blocks = (unsigned)((rows + 255) / 256);
-    hipLaunchKernelGGL(pitch_out_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w->raw, w->lagidx, rows, gm.Lmin, L, (double)rate, w->out,
-                       want_lag ? w->lag.p : nullptr);
+    hipLaunchKernelGGL(pitch_out_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w->raw, w->lagidx, rows, gm.Lmin, L, (double)gm.rate, w->out,
+                       w->want_lag ? w->lag.p : nullptr);
     hipLaunchKernelGGL(pitch_delta_kernel, dim3(blocks), dim3(256), 0, ctx->stream, w->row_off, w->frame_utt, rows, w->out);
     pcl_timer_end(ctx, "pitch_out");
-    PT(hipGetLastError());
-#undef PT
+    HIPWHO(ctx, who, hipGetLastError());
     return PCL_OK;
 }
 
 extern "C" int pcl_pitch(pcl_ctx *ctx, int U, const double *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
                          double f_min, double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int flags,
                          double *out, int32_t *lag, double *nccf_bal, double *nccf_raw, int64_t out_rows) {
-    if (!ctx) return PCL_ERR_INVALID;
-    return pitch_to_host(ctx, "pcl_pitch", U, signal, false, sig_off, framerate, sampletime, overlap, f_min, f_max, ballast, soft_min_f0, pf, g, n_lags,
-                         flags, out, lag, nccf_bal, nccf_raw, out_rows);
+    return pitch_to_host(ctx, "pcl_pitch", SignalView{signal, false, U, sig_off}, FrameSpec{framerate, sampletime, overlap},
+                         PitchArgs{f_min, f_max, ballast, soft_min_f0, pf, g, n_lags}, flags, PitchOut{out, lag, nccf_bal, nccf_raw, out_rows});
 }
 
 extern "C" int pcl_pitch_pcm16(pcl_ctx *ctx, int U, const int16_t *signal, const int64_t *sig_off, int framerate, double sampletime, double overlap,
                                double f_min, double f_max, double ballast, double soft_min_f0, double pf, const double *g, int n_lags, int flags,
                                double *out, int32_t *lag, double *nccf_bal, double *nccf_raw, int64_t out_rows) {
-    if (!ctx) return PCL_ERR_INVALID;
-    return pitch_to_host(ctx, "pcl_pitch_pcm16", U, signal, true, sig_off, framerate, sampletime, overlap, f_min, f_max, ballast, soft_min_f0, pf, g,
-                         n_lags, flags, out, lag, nccf_bal, nccf_raw, out_rows);
+    return pitch_to_host(ctx, "pcl_pitch_pcm16", SignalView{signal, true, U, sig_off}, FrameSpec{framerate, sampletime, overlap},
+                         PitchArgs{f_min, f_max, ballast, soft_min_f0, pf, g, n_lags}, flags, PitchOut{out, lag, nccf_bal, nccf_raw, out_rows});
 }

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import GET, SEG_GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, all_int16, as_c, ptr
+from ._lib import GET, SEG_GET, PCL_F32, PCL_F64, PCL_MAX_PASS, PCL_ROW_ENTRY, PCL_ROW_EXIT, PoccalaHipError, as_c, ptr
 
 
 def device_count():
@@ -184,36 +184,23 @@ class Engine(object):
         pitch=True (pcl_frontend_pitch): three more columns behind the MFCC's -- voicing, ln f0, delta ln f0 over f_min .. f_max Hz
         (AudioProcessing.pitch_batch's, rule P1-P5) -- so the rows are vec_num * {1,2,3} + 3 wide.  The detector still sees the MFCC columns
         alone: lens, begin and the MFCC columns are those of pitch=False bit for bit.  The default takes the call it always took."""
-        from .StatisticalModel.AudioProcessing import frame_count, mfcc_tables, pitch_lags
-        signals = list(signals)
-        pcm16 = all_int16(signals)
-        wire = np.int16 if pcm16 else np.float64
-        sigs = [np.asarray(s, dtype=wire).reshape(-1) for s in signals]
-        off = np.concatenate([[0], np.cumsum([len(s) for s in sigs])]).astype(np.int64)
+        from .StatisticalModel.AudioProcessing import frame_count, mfcc_dim, mfcc_flags, mfcc_tables, pitch_lags
+        sigs, flat, off, pcm16 = _lib.pack_signals(signals)
         rows = int(sum(frame_count(len(s), framerate, sampletime, overlap) for s in sigs))
-        dim = vec_num * (3 if (d1 and d2) else 2 if d1 else 1)
-        twc, tws, resp, dct = mfcc_tables(framerate, vec_num, nfft, filterbanks)
-        flat = as_c(np.concatenate(sigs), wire)
-        mflags = (1 if cal_energy else 0) | (2 if d1 else 0) | (4 if (d1 and d2) else 0)
+        mflags = mfcc_flags(cal_energy, d1, d2)
+        dim = mfcc_dim(vec_num, mflags) + (3 if pitch else 0)
+        tables = mfcc_tables(framerate, vec_num, nfft, filterbanks)
         flags = (0 if vad else _lib.PCL_FRONTEND_NO_VAD) | (_lib.PCL_FRONTEND_KEEP_F64 if keep_f64 else 0)
         lens, begin = np.empty(len(sigs), dtype=np.int32), np.empty(len(sigs), dtype=np.int64)
-        if pitch:
-            dim += 3
-            _, _, g = pitch_lags(framerate, f_min, f_max)
-            out = np.empty((max(rows, 1), dim)) if fetch else None
-            call = self._lib.pcl_frontend_pitch_pcm16 if pcm16 else self._lib.pcl_frontend_pitch
-            self._check(call(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
-                             int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
-                             int(simple_size), float(alpha), float(beta), flags, float(f_min), float(f_max), float(ballast),
-                             float(soft_min_f0), float(pf), ptr(g), int(len(g)), ptr(lens), ptr(begin), ptr(out), C.c_int64(rows)))
-            self.F, self.FD = int(lens.sum()), dim
-            self._frames_key = None
-            return (lens, begin, out[:self.F].copy()) if fetch else (lens, begin)
         out = np.empty((max(rows, 1), dim)) if fetch else None
-        call = self._lib.pcl_frontend_pcm16 if pcm16 else self._lib.pcl_frontend
-        self._check(call(self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap),
-                         int(nfft), int(filterbanks), int(vec_num), mflags, ptr(twc), ptr(tws), ptr(resp), ptr(dct),
-                         int(simple_size), float(alpha), float(beta), flags, ptr(lens), ptr(begin), ptr(out), C.c_int64(rows)))
+        # the four entry points take the same arguments, the pitch ones theirs between the detector's and the outputs
+        args = [self._ctx, len(sigs), ptr(flat), ptr(off), int(framerate), float(sampletime), float(overlap), int(nfft), int(filterbanks),
+                int(vec_num), mflags] + [ptr(t) for t in tables] + [int(simple_size), float(alpha), float(beta), flags]
+        if pitch:
+            g = pitch_lags(framerate, f_min, f_max)[2]
+            args += [float(f_min), float(f_max), float(ballast), float(soft_min_f0), float(pf), ptr(g), int(len(g))]
+        call = getattr(self._lib, 'pcl_frontend' + ('_pitch' if pitch else '') + ('_pcm16' if pcm16 else ''))
+        self._check(call(*args, ptr(lens), ptr(begin), ptr(out), C.c_int64(rows)))
         self.F, self.FD = int(lens.sum()), dim
         self._frames_key = None
         return (lens, begin, out[:self.F].copy()) if fetch else (lens, begin)

@@ -13,7 +13,7 @@ U53 = 2.0 ** -53
 
 # ------------------------------------------------------------------ the kernel's index arithmetic, restated
 def kernel_geometry(rate, sampletime, overlap, nfft, nfilt):
-    """What pcl_mfcc_device and mfcc_frame_kernel derive from a call's arguments (mfcc.hip: `size`, `step`, `nbin`, `len`, `use_fft`,
+    """What FrameSpec::frame (frontend_host.h), mfcc_launch and mfcc_frame_kernel derive from a call's arguments (`size`, `step`, `nbin`, `len`, `use_fft`,
     `logn`, and the launch's dynamic LDS in bytes)."""
     size = int(rate * sampletime)
     step = int(size * overlap)

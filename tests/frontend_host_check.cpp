@@ -1,6 +1,7 @@
-// Stand-alone check of the host helpers of poccala_amd/csrc/pitch_check.h (pitch_geometry_check, pitch_frame_count, pitch_rows_check: the
-// argument and geometry checks the four pitch entry points share) against a stub context.  Built with the host sanitizers and run as its own
-// process by tests/test_pitch_host.py: exit status 0 and no sanitizer report = pass.  Every expected value is written out by hand.
+// Stand-alone check of the host helpers of poccala_amd/csrc/frontend_host.h (the argument structs, the one frame geometry, frame_rows in both
+// of its modes, frame_utt_of, pitch_geometry_check, pitch_frame_count: what the eight front-end entry points share) against a stub context.
+// Built with the host sanitizers and run as its own process by tests/test_frontend_host.py: exit status 0 and no sanitizer report = pass.
+// Every expected value is written out by hand.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,7 +22,7 @@ thread_local int pcl_tls_free_synced = 0;
 void *pcl_pool_alloc(int, size_t bytes) { return malloc(bytes ? bytes : 1); }
 void pcl_pool_free(void *p) { free(p); }
 
-#include "../poccala_amd/csrc/pitch_check.h"
+#include "../poccala_amd/csrc/frontend_host.h"
 
 #define CHECK(c)                                                        \
     do {                                                                \
@@ -38,7 +39,12 @@ static bool has(const char *text) { return ctx.err.find(text) != std::string::np
 static int geom(int rate, double f_min, double f_max, const double *g, int n_lags, PitchGeom *out, double sampletime = 0.025, double overlap = 0.5,
                 double ballast = 7000.0, double soft = 10.0, double pf = 0.1) {
     ctx.err.clear();
-    return pitch_geometry_check(&ctx, "who", rate, sampletime, overlap, f_min, f_max, ballast, soft, pf, g, n_lags, out);
+    return pitch_geometry_check(&ctx, "who", FrameSpec{rate, sampletime, overlap}, PitchArgs{f_min, f_max, ballast, soft, pf, g, n_lags}, out);
+}
+
+// frame_rows over U signals at offsets `off` (the samples themselves are never looked at)
+static int pitch_rows_check(pcl_ctx *c, const char *who, int U, const int64_t *off, const FrameGeom &g, bool whole_frame, std::vector<long long> *ro) {
+    return frame_rows(c, who, SignalView{nullptr, true, U, off}, g, whole_frame, ro);
 }
 
 int main() {
@@ -117,6 +123,59 @@ int main() {
         CHECK(pitch_rows_check(&ctx, "who", 1, huge, gm, false, &ro) == PCL_OK && ro[1] == 1 + (150000000000ll - 200 + 99) / 100);
         CHECK(pitch_rows_check(&ctx, "who", 2, huge, gm, false, &ro) == PCL_ERR_INVALID && has("more than 2^31 - 1 frames at signal 1"));
     }
-    printf("pitch_host_check: OK\n");
+    {   // whole frames (pcl_mfcc*, pcl_frontend*) at the one-frame edge: 8 kHz, 25 ms, half overlap -> 200 / 100
+        const FrameGeom fg = FrameSpec{8000, 0.025, 0.5}.frame();
+        CHECK(fg.size == 200 && fg.step == 100);
+        const FrameGeom odd = FrameSpec{11025, 0.025, 0.5}.frame();   // 275.625 -> 275, 137.5 -> 137: both truncated
+        CHECK(odd.size == 275 && odd.step == 137);
+        std::vector<long long> ro;
+        const int64_t edge[4] = {0, 200, 401, 702};                   // n = size, size + 1, size + step + 1
+        CHECK(pitch_rows_check(&ctx, "who", 3, edge, fg, true, &ro) == PCL_OK && (ro == std::vector<long long>{0, 1, 3, 6}));
+        CHECK(pitch_rows_check(&ctx, "who", 3, edge, fg, false, &ro) == PCL_OK && (ro == std::vector<long long>{0, 1, 3, 6}));   // the same rows in both modes
+        const int64_t shy[3] = {0, 200, 399};                         // n = size - 1, behind a good one
+        CHECK(pitch_rows_check(&ctx, "pcl_mfcc", 2, shy, fg, true, &ro) == PCL_ERR_INVALID);
+        CHECK(ctx.err == "pcl_mfcc: signal 1 has 199 samples, fewer than one frame (200)");
+        CHECK(pitch_rows_check(&ctx, "pcl_frontend_pcm16", 1, shy + 1, fg, true, &ro) == PCL_ERR_INVALID && ctx.err == "pcl_frontend_pcm16: sig_off[0] must be 0");
+        const int64_t lone[2] = {0, 199};
+        CHECK(pitch_rows_check(&ctx, "pcl_frontend_pcm16", 1, lone, fg, true, &ro) == PCL_ERR_INVALID);
+        CHECK(ctx.err == "pcl_frontend_pcm16: signal 0 has 199 samples, fewer than one frame (200)");
+        CHECK(pitch_rows_check(&ctx, "who", 1, lone, fg, false, &ro) == PCL_OK && (ro == std::vector<long long>{0, 1}));          // ... which the pitch rows pad
+        const int64_t back[3] = {0, 300, 200};                        // a negative length is "fewer than one frame" to the MFCC
+        CHECK(pitch_rows_check(&ctx, "who", 2, back, fg, true, &ro) == PCL_ERR_INVALID && ctx.err == "who: signal 1 has -100 samples, fewer than one frame (200)");
+        // a ragged batch of five: 200, 201, 300, 301 and 2400 samples -> 1, 2, 2, 3 and 1 + 2200 / 100 = 23 frames
+        const int64_t five[6] = {0, 200, 401, 701, 1002, 3402};
+        CHECK(pitch_rows_check(&ctx, "who", 5, five, fg, true, &ro) == PCL_OK && (ro == std::vector<long long>{0, 1, 3, 5, 8, 31}));
+        std::vector<int> want{0, 1, 1, 2, 2, 3, 3, 3};
+        want.insert(want.end(), 23, 4);
+        CHECK(frame_utt_of(ro) == want && want.size() == 31);
+        FrameRows fr;
+        fr.row_off = ro;
+        CHECK(fr.rows() == 31 && fr.longest() == 23);
+        CHECK(frame_utt_of(std::vector<long long>{0, 0, 2, 2}) == (std::vector<int>{1, 1}));     // utterances without rows (pcl_vad's callers) own none
+        // the limits of the pitch entry points do not reach the MFCC's rows: 65536 one-frame signals are 65536 rows
+        std::vector<int64_t> many(65537);
+        for (size_t u = 0; u < many.size(); ++u) many[u] = 200 * (int64_t)u;
+        CHECK(pitch_rows_check(&ctx, "who", 65536, many.data(), fg, true, &ro) == PCL_OK && ro.size() == 65537 && ro.back() == 65536);
+        CHECK(pitch_rows_check(&ctx, "who", 65536, many.data(), fg, false, &ro) == PCL_ERR_INVALID && has("65536 utterances, 1 .. 65535 per call"));
+    }
+    {   // the MFCC's width from its flags (1 = energy, 2 = deltas, 4 = their deltas), the signal's size on the wire
+        MfccSpec m{{16000, 0.025, 0.5}, 512, 26, 13, 1, nullptr, nullptr, nullptr, nullptr};
+        CHECK(m.dim() == 13 && m.frame().size == 400 && m.frame().step == 200 && !m.tables());
+        m.flags = 3;
+        CHECK(m.dim() == 26);
+        m.flags = 7;
+        CHECK(m.dim() == 39);
+        m.flags = 0;
+        CHECK(m.dim() == 13);
+        const double t[1] = {0.0};
+        m.twc = m.tws = m.resp = t;
+        CHECK(!m.tables());
+        m.dct = t;
+        CHECK(m.tables());
+        const int64_t off[3] = {0, 400, 1001};
+        const SignalView s16{nullptr, true, 2, off}, s64{nullptr, false, 2, off};
+        CHECK(s16.total() == 1001 && s16.total() * s16.sample_bytes() == 2002 && s64.total() * s64.sample_bytes() == 8008);
+    }
+    printf("frontend_host_check: OK\n");
     return 0;
 }

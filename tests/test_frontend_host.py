@@ -1,5 +1,5 @@
-"""The argument and geometry checks the four pitch entry points share (poccala_amd/csrc/pitch_check.h), without a GPU:
-tests/pitch_host_check.cpp is compiled against a stub context with the host's address and undefined-behaviour sanitizers and run as a
+"""The argument structs, the one frame geometry and the checks the eight front-end entry points share (poccala_amd/csrc/frontend_host.h),
+without a GPU: tests/frontend_host_check.cpp is compiled against a stub context with the host's address and undefined-behaviour sanitizers and run as a
 process of its own."""
 import os
 import shutil
@@ -11,17 +11,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 
 
-def test_pitch_checks_under_the_host_sanitizers(tmp_path):
+def test_frontend_host_checks_under_the_host_sanitizers(tmp_path):
     if not os.path.exists(HIPCC) and not shutil.which('hipcc'):
         pytest.fail('hipcc is needed to build the check (it is what builds the library)')
-    exe = str(tmp_path / 'pitch_host_check')
+    exe = str(tmp_path / 'frontend_host_check')
     cmd = [HIPCC if os.path.exists(HIPCC) else 'hipcc', '--offload-arch=gfx950', '-std=c++17', '-g', '-O1', '-fno-omit-frame-pointer',
            '-Xarch_host', '-fsanitize=address,undefined', '-Xarch_host', '-fno-sanitize-recover=undefined',
-           os.path.join(ROOT, 'tests', 'pitch_host_check.cpp'), '-o', exe]
+           os.path.join(ROOT, 'tests', 'frontend_host_check.cpp'), '-o', exe]
     build = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert build.returncode == 0, build.stdout + build.stderr
     env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
     run = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert 'pitch_host_check: OK' in run.stdout
+    assert 'frontend_host_check: OK' in run.stdout
     assert 'ERROR: AddressSanitizer' not in run.stderr and 'runtime error' not in run.stderr, run.stderr

@@ -336,3 +336,24 @@ def test_decode_batch_from_resident_frames(eng, lex):  # noqa: F811
         print(u, res[u][0], res[u][1])
         assert res[u][0] == words and same_bits(np.float64(res[u][1]), np.float64(score))
         assert res[u][2]['final'] == detail['final'] and res[u][2]['n_tokens'].tolist() == detail['n_tokens'].tolist()
+
+
+# ------------------------------------------------------------------ 9. the three halves cut the same rows
+def test_mfcc_frontend_and_pitch_rows_agree_at_the_frame_edges(eng):
+    """8 kHz: frame 200, step 100.  int16 signals of exactly one frame, one sample more (a second frame that is all padding but one
+    sample) and 501 samples (1 + ceil(301 / 100) = 5 frames, the last one padded): the MFCC alone, the front-end's MFCC columns without
+    and with the pitch columns, and the pitch columns against the stand-alone pitch call, byte for byte."""
+    from poccala_amd.StatisticalModel.AudioProcessing import mfcc_batch, pitch_batch
+    rng = np.random.default_rng(77)
+    sigs = [np.round(2500 * rng.standard_normal(n)).astype(np.int16) for n in (200, 201, 501)]
+    mats = mfcc_batch(sigs, 8000, d1=True, d2=True, engine=eng)
+    assert [m.shape for m in mats] == [(1, 39), (2, 39), (5, 39)]
+    want = np.concatenate(mats)
+    lens0, begin0, rows0 = eng.frontend(sigs, 8000, vad=False, fetch=True)
+    lens, begin, rows = eng.frontend(sigs, 8000, vad=False, pitch=True, fetch=True)
+    assert lens0.tolist() == lens.tolist() == [1, 2, 5] and begin0.tolist() == begin.tolist() == [0, 1, 3]
+    assert rows.shape == (8, 42)
+    assert same_bits(rows0, want)
+    assert same_bits(rows[:, :39], want)
+    assert same_bits(rows[:, 39:], np.concatenate(pitch_batch(sigs, 8000, engine=eng)))
+    assert np.isfinite(want[1:]).all() and np.isfinite(rows[:, 39:]).all()      # (the one-frame utterance's MFCC row is NaN everywhere, as in the reference)
