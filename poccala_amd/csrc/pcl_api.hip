@@ -26,10 +26,10 @@ void pcl_set_error(pcl_ctx *ctx, const char *msg) {
 // hipEventCreate per launch nor keep the events alive until the context dies.
 void pcl_timer_begin(pcl_ctx *ctx, const char *which) {
     if (!ctx->timing) return;
-    hipEvent_t a, b;
-    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-    hipEventRecord(a, ctx->stream);
-    ctx->timers[which].ev.push_back({a, b});
+    TimedEventPair p;
+    if (p.make() != hipSuccess) return;
+    hipEventRecord(p.first, ctx->stream);
+    ctx->timers[which].ev.push_back(std::move(p));
 }
 void pcl_timer_end(pcl_ctx *ctx, const char *which) {
     if (!ctx->timing) return;
@@ -42,18 +42,6 @@ void pcl_timer_host(pcl_ctx *ctx, const char *which, double ms) {
     auto &t = ctx->timers[which];
     t.host_ms += ms;
     ++t.host_n;
-}
-
-static void drop_timers(pcl_ctx *ctx) {
-    for (auto &kv : ctx->timers) {
-        kv.second.host_ms = 0.0;
-        kv.second.host_n = 0;
-        for (auto &p : kv.second.ev) {
-            hipEventDestroy(p.first);
-            hipEventDestroy(p.second);
-        }
-        kv.second.ev.clear();
-    }
 }
 
 // ================================================================ device memory pool
@@ -167,20 +155,9 @@ __global__ void desc_copy_kernel(DescCopyArgs a, const char *__restrict__ stage)
 }
 }  // namespace
 
-hipError_t pcl_desc_flush(pcl_ctx *ctx) {
-    ctx->desc_pin_used = 0;
-    if (ctx->desc_n == 0) return hipSuccess;
-    static_assert(PCL_DESC_MAX == 24, "pcl_ctx::desc_dst");
-    DescCopyArgs a;
-    a.n = ctx->desc_n;
-    for (int k = 0; k < ctx->desc_n; ++k) {
-        a.dst[k] = ctx->desc_dst[k];
-        a.off[k] = ctx->desc_off[k];
-        a.bytes[k] = ctx->desc_bytes[k];
-    }
-    ctx->desc_n = 0;
+hipError_t pcl_desc_launch(pcl_ctx *ctx, const DescCopyArgs &a, const char *pin) {
     void *dev_stage = nullptr;
-    hipError_t e = hipHostGetDevicePointer(&dev_stage, ctx->desc_pin, 0);
+    hipError_t e = hipHostGetDevicePointer(&dev_stage, const_cast<char *>(pin), 0);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(desc_copy_kernel, dim3(32, a.n), dim3(256), 0, ctx->stream_desc, a, (const char *)dev_stage);
     e = hipGetLastError();
@@ -217,11 +194,12 @@ static int ctx_setup(pcl_ctx *ctx) {
     if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->cus = prop.multiProcessorCount;
     // (compute units set aside for the second stream with hipExtStreamCreateWithCUMask were tried in round 4: 8 of 256 cost the scoring
     //  kernel 20 %, 16 cost 70 %, and the posterior kernel's in-loop span did not move -- it waits for registers, not for CUs)
-    HIPCHK(nullptr, hipStreamCreate(&ctx->stream));
-    HIPCHK(nullptr, hipStreamCreateWithPriority(&ctx->stream_dp, hipStreamDefault, -1));      // (priority 0 measured: no difference)
-    HIPCHK(nullptr, hipStreamCreate(&ctx->stream_aux));
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->stream_desc, hipStreamNonBlocking));
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&ctx->stream_d2h, hipStreamNonBlocking));
+    HIPCHK(nullptr, ctx->stream_main.make(StreamKind::Plain));
+    ctx->stream = ctx->stream_main;
+    HIPCHK(nullptr, ctx->stream_dp.make(StreamKind::HighPriority));                            // (priority 0 measured: no difference)
+    HIPCHK(nullptr, ctx->stream_aux.make(StreamKind::Plain));
+    HIPCHK(nullptr, ctx->stream_desc.make(StreamKind::NonBlocking));
+    HIPCHK(nullptr, ctx->stream_d2h.make(StreamKind::NonBlocking));
     // PCL_SCORE_VARIANT: 7 (default) = f32-class contraction on the f16 matrix pipe, 3 = strict f32 on the f32-input MFMA,
     // 1 = direct form on the VALU (the kernels states leave the matrix pipe for: fix-up, ill-conditioned models)
     const char *var = getenv("PCL_SCORE_VARIANT");
@@ -243,36 +221,17 @@ static int ctx_setup(pcl_ctx *ctx) {
     return PCL_OK;
 }
 
-// Everything a context holds goes, in this order: the communicator (collectives and the pipelined exchange run on the context's streams and
-// stream_comm; rounds 1-5 destroyed it first), the buried batches, events, memory, streams.  The caller has DRAINED the streams (pcl_destroy);
-// a context pcl_init gives up on has queued nothing.  Every handle may be null.
+// Everything a context holds goes.  Spelled out, in this order, are the steps whose order is a decision: the communicator (collectives and the
+// pipelined exchange run on the context's streams and stream_comm; rounds 1-5 destroyed it first), the buried batches, and zero_pending
+// (round 6, tools/lifecycle_stress.py: a context destroyed with an asynchronous pcl_stats_zero still un-joined had ev_zero destroyed here
+// and then synchronised on by free_model: a use of a dead event, SIGSEGV inside the runtime -- nothing may wait on an event from here on).
+// Everything else is given back by its owner when `delete ctx` destroys the members, the streams last (see pcl_ctx).  The caller has DRAINED
+// the streams (pcl_destroy); a context pcl_init gives up on has queued nothing.  Every handle may be null.
 static void ctx_teardown(pcl_ctx *ctx) {
     pcl_comm_destroy(ctx);
     pcl_batch_reap(ctx, true);
-    // (round 6, tools/lifecycle_stress.py: a context destroyed with an asynchronous pcl_stats_zero still un-joined -- zero_pending --
-    //  had ev_zero destroyed HERE and then synchronised on by free_model below: a use of a dead event, SIGSEGV inside the runtime.
-    //  The streams are drained: nothing is pending any more, and the handles are cleared as they go.)
     ctx->zero_pending = false;
-    ctx->ev_zero.destroy();
-    ctx->ev_zero_src.destroy();
-    if (ctx->desc_pin) hipHostFree(ctx->desc_pin);
-    ctx->desc_pin = nullptr;
-    drop_timers(ctx);                                            // (the per-chunk events of the staging stream's "pcm_h2d" group among them)
-    pcl_mfcc_release(ctx);                                       // drained: no copy reads the staging buffers, no event is waited for
-    free_model(ctx);
-    pcl_lda_release(ctx);
-    pcl_cmvn_release(ctx);
-    pcl_units_release(ctx);
-    release_frames32(ctx);
-    ctx->frames64.release();
-    ctx->d_softplus.release();
-    ctx->frames_slot[0].release();
-    ctx->frames_slot[1].release();
-    ctx->ev_stage.destroy();
-    ctx->ev_slot_free.destroy();
-    for (hipStream_t s : {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_desc, ctx->stream_d2h})
-        if (s) hipStreamDestroy(s);
-    delete ctx;                                                  // (nothing is left for the members' destructors to give back)
+    delete ctx;
 }
 
 int pcl_init(int device, pcl_ctx **out) {
@@ -304,8 +263,7 @@ int pcl_destroy(pcl_ctx *ctx) {
     // of one drained later only in the sense that its wait completes; nothing new is queued, so the second round returns at once and
     // is there for the reader), THEN ctx_teardown.  No member of the context gives anything back before this point.
     for (int round = 0; round < 2; ++round) {
-        hipStream_t all[] = {ctx->stream, ctx->stream_dp, ctx->stream_aux, ctx->stream_d2h, ctx->stream_desc, ctx->stream_comm, ctx->pcm.stream};
-        for (hipStream_t s : all)
+        for (hipStream_t s : ctx->streams())
             if (s) hipStreamSynchronize(s);
     }
     ctx_teardown(ctx);
@@ -314,10 +272,16 @@ int pcl_destroy(pcl_ctx *ctx) {
 
 const char *pcl_last_error(pcl_ctx *ctx) { return ctx ? ctx->err.c_str() : g_init_error.c_str(); }
 
-int pcl_sync(pcl_ctx *ctx) {
-    if (!ctx) return PCL_ERR_INVALID;
+// the two streams kernels are timed on
+static int sync_main_and_dp(pcl_ctx *ctx) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));
+    return PCL_OK;
+}
+
+int pcl_sync(pcl_ctx *ctx) {
+    if (!ctx) return PCL_ERR_INVALID;
+    TRY(sync_main_and_dp(ctx));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream_aux));
     if (ctx->stream_d2h) HIPCHK(ctx, hipStreamSynchronize(ctx->stream_d2h));
     pcl_batch_reap(ctx, false);
@@ -351,17 +315,15 @@ int pcl_device_info(pcl_ctx *ctx, char *name, int cap, int *cus, size_t *hbm_byt
 
 int pcl_timing_enable(pcl_ctx *ctx, int on) {
     if (!ctx) return PCL_ERR_INVALID;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));
-    if (!on) drop_timers(ctx);
+    TRY(sync_main_and_dp(ctx));
+    if (!on) ctx->timers.clear();                                // (every group's event pairs and host-clock entries)
     ctx->timing = on != 0;
     return PCL_OK;
 }
 
 int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launches) {
     if (!ctx || !which) return PCL_ERR_INVALID;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));
+    TRY(sync_main_and_dp(ctx));
     float tot = 0.f;
     int n = 0;
     auto it = ctx->timers.find(which);
@@ -372,8 +334,6 @@ int pcl_kernel_time(pcl_ctx *ctx, const char *which, float *total_ms, int *launc
                 tot += ms;
                 ++n;
             }
-            hipEventDestroy(p.first);
-            hipEventDestroy(p.second);
         }
         it->second.ev.clear();
         tot += (float)it->second.host_ms;

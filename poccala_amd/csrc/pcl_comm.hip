@@ -510,7 +510,7 @@ int pipe_issue_chunk(pcl_ctx *ctx, int c) {
 
 int pcl_pipe_begin(pcl_ctx *ctx, double c_covariance, int payload, int n_chunks) {
     if (ctx->pipe_active) PCL_FAIL(ctx, PCL_ERR_STATE, "pipelined exchange: already open");
-    if (!ctx->stream_comm) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->stream_comm, hipStreamNonBlocking));
+    HIPCHK(ctx, ctx->stream_comm.make(StreamKind::NonBlocking));
     const int K = std::max(1, std::min(n_chunks, std::min(ctx->J, 64)));
     while ((int)ctx->pipe_ev.size() < K) {
         LazyEvent e;
@@ -575,11 +575,8 @@ int pcl_pipe_finish(pcl_ctx *ctx, int update_transitions) {
 void pcl_pipe_release(pcl_ctx *ctx) {
     ctx->pipe_ev.clear();
     ctx->pipe_done.destroy();
-    if (ctx->stream_comm) {
-        hipStreamSynchronize(ctx->stream_comm);
-        hipStreamDestroy(ctx->stream_comm);
-    }
-    ctx->stream_comm = nullptr;
+    if (ctx->stream_comm) hipStreamSynchronize(ctx->stream_comm);
+    ctx->stream_comm.destroy();
     ctx->pipe_active = false;
 }
 

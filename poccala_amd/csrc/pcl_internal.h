@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 
 #include <map>
 #include <string>
@@ -14,6 +15,7 @@
 
 #include "../../include/poccala_hip.h"
 #include "pcl_own.h"
+#include "pcl_desc.h"
 #include "frontend_host.h"
 
 // ---------------------------------------------------------------- device-side descriptors
@@ -61,18 +63,17 @@ struct ActiveFrame {
 
 // ---------------------------------------------------------------- host-side objects
 struct KernelTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    std::vector<TimedEventPair> ev;
     double host_ms = 0.0;   // groups measured on the host clock ("pcm_stage", the float64 route's blocking "pcm_h2d"): added to the events' sum
     int host_n = 0;
 };
 
 // The int16 PCM route of the front-end (mfcc.hip): two page-locked staging buffers of one chunk each and the stream their H2D copies run
-// on, beside the host's memcpy of the next chunk.  Made on the first int16 call, kept with the context, released by pcl_destroy after it
-// has drained `stream`.  ev[s] = the last copy that read pin[s] is done.
+// on, beside the host's memcpy of the next chunk.  Made on the first int16 call, kept with the context, gone with it after pcl_destroy
+// has drained `stream` (declared first: destroyed after the buffers and events that were used on it).  ev[s] = the last copy that read pin[s] is done.
 struct PcmStage {
-    hipStream_t stream = nullptr;
-    int16_t *pin[2] = {nullptr, nullptr};
-    size_t cap = 0;                          // samples per buffer
+    Stream stream;                           // StreamKind::NonBlocking
+    PinBuf<int16_t> pin[2];                  // one chunk of samples each
     LazyEvent ev[2];
 };
 // The four host-built MFCC tables (twiddle cos | sin | mel response | DCT basis) in ONE device block, kept with the context: `host` is the
@@ -159,10 +160,25 @@ struct LexiconDev {
     DevBuf<int> lm_col, lm_node_word_ptr, lm_node_word_ids;
 };
 
-struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
+// The context's own streams (the int16 front-end's staging stream lives with its buffers, PcmStage::stream; pcl_ctx::streams() lists all seven).
+struct CtxStreams {
+    Stream stream_main;          // the owner of the main stream; launchers read the VIEW pcl_ctx::stream, which pcl_stream_scope redirects
+    Stream stream_dp;            // HighPriority: forward-backward runs here, beside the next batch's scoring on the main stream
+    Stream stream_aux;           // the accumulate pass's tile-image producer runs here, beside its consumer on the main stream
+    Stream stream_desc;          // NonBlocking: descriptor uploads of batches that have nothing in flight (pcl_h2d_fresh)
+    Stream stream_d2h;           // NonBlocking: pcl_batch_fetch_async, results travel to the host beside the next step's kernels
+    Stream stream_comm;          // NonBlocking, made by the first pcl_pipe_begin: the pipelined exchange (pcl_comm.hip)
+};
+
+// TEARDOWN ORDER.  `delete ctx` (ctx_teardown, pcl_api.hip) destroys the members below in reverse order of declaration and then the base
+// structs in reverse order, and every one of them gives back what it owns.  One thing in that order is relied upon: CtxStreams is the FIRST
+// base, so the streams outlive every buffer, event, timer and staging area of the context (PcmStage keeps the same order for its own
+// stream).  Nothing else depends on the order: pcl_destroy has drained every stream before, and the steps whose order IS a decision
+// (communicator, buried batches, zero_pending) are spelled out in ctx_teardown.
+struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev {
     int device = 0;
     AccScratch acc;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;      // VIEW of stream_main, or of the stream an open pcl_stream_scope has put in its place
     std::string err;
     int cus = 0;
     // model (device)
@@ -172,10 +188,6 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     int fmllr_S = 0;             // speakers of fmllr_Gk / fmllr_beta / fmllr_W
     int Mpad32 = 0;              // M rounded up to a multiple of 32
     int layouts_valid = 0;             // PCL_LAYOUT_* derived for the current model (the f64 rows are derived on first use)
-    hipStream_t stream_dp = nullptr;   // forward-backward runs here, beside the next batch's scoring on `stream`
-    hipStream_t stream_aux = nullptr;  // the accumulate pass's tile-image producer runs here, beside its consumer on `stream`
-    hipStream_t stream_desc = nullptr; // descriptor uploads of batches that have nothing in flight (pcl_h2d_fresh)
-    hipStream_t stream_d2h = nullptr;  // pcl_batch_fetch_async: results travel to the host beside the next step's kernels
     bool dp_async = true;              // env PCL_DP_STREAM=0: everything on one stream
     int score_wgs_per_cu = 0;    // pcl_score_occupancy: 2 = the matrix-pipe scoring kernel leaves a third of each CU to kernels beside it
     int score_variant = 0;       // 7 = two-piece f16 split on the matrix pipe (default), 3 = f32-input MFMA (strict f32), 1 = direct form on the VALU
@@ -256,7 +268,6 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     DevBuf<float> payload32;                         // f32 staging of the statistics / parameters (payload = PCL_F32)
     // pipelined exchange (pcl_comm.hip): state chunks go through reduce-scatter -> M-step -> all-gather -> derive on stream_comm
     // as soon as the accumulate pass has queued the last kernel that touches them
-    hipStream_t stream_comm = nullptr;
     std::vector<LazyEvent> pipe_ev;
     LazyEvent pipe_done;
     bool pipe_active = false;
@@ -269,20 +280,11 @@ struct pcl_ctx : ModelDev, CoarseDev, UnitsDev, LexiconDev {
     // step k runs): pcl_batch_destroy returns at once; the memory goes back to the pool when the batch's OWN last work on every
     // stream has completed (its events: ev_mark / ev_dp / ev_fetch; pcl_batch_reap on the next create / destroy, pcl_sync, pcl_destroy).
     std::vector<struct pcl_batch *> graves;
-    // Descriptor uploads of a batch under construction (pcl_desc_group): the arrays are packed into ONE page-locked staging buffer and
-    // queued as asynchronous copies on stream_desc, with one wait at the end of the group -- pcl_batch_create_labels made 16 separate
-    // synchronous copies from pageable memory (5.3 ms of host time per 1024-utterance batch beside a busy GPU, tools/fresh_batch_probe.py).
-    // The copy itself is a KERNEL on stream_desc that reads the staging buffer over PCIe, not hipMemcpyAsync: the copy engines serve
-    // their queue in order, and in a pipeline that also moves frames up and results down the descriptors sat behind the NEXT step's
-    // frame upload, which waits for its slot's last reader -- 15 ms per pcl_batch_create_labels (bench.py pcie_inclusive_loop).
-    char *desc_pin = nullptr;
-    size_t desc_pin_cap = 0, desc_pin_used = 0;
-    int desc_group = 0;          // > 0: inside a group, pcl_h2d_fresh stages and does not wait
-    void *desc_dst[24];          // the staged entries of the open group (PCL_DESC_MAX)
-    unsigned long long desc_off[24], desc_bytes[24];
-    int desc_n = 0;
+    DescStager<> desc;           // descriptor uploads of a batch under construction (pcl_desc_group; pcl_desc.h)
     PcmStage pcm;
     MfccTables mfcc_tab;
+    // Every stream of the context, made or not (null): the ONE list behind pcl_destroy's drain.
+    std::array<hipStream_t, 7> streams() const { return {stream_main, stream_dp, stream_aux, stream_d2h, stream_desc, stream_comm, pcm.stream}; }
 };
 
 // Decoder state of a batch (hmm_decode.hip): token buffers, node -> token map, scratch, results; re-made as a group when a call needs more room
@@ -422,50 +424,15 @@ static inline hipError_t pcl_d2h_queue(pcl_ctx *ctx, void *dst, const void *src,
 // Descriptors into a buffer NO queued kernel can be reading (freshly allocated, or any buffer of a batch that has not launched
 // anything yet): a stream of their own, so that creating a batch in the middle of a stream of chunks does not wait for the
 // scoring kernel that happens to run on the main stream (28 ms per new batch in the C5 pipeline).  Complete at return.
-// One launch copies every staged array of a descriptor group from the page-locked staging buffer (the kernel reads host memory
-// over PCIe) to its device array: pcl_api.hip.  entries: (dst, offset into the staging buffer, bytes).
-constexpr int PCL_DESC_MAX = 24;
-struct DescCopyArgs {
-    void *dst[PCL_DESC_MAX];
-    unsigned long long off[PCL_DESC_MAX], bytes[PCL_DESC_MAX];
-    int n;
-};
-hipError_t pcl_desc_flush(pcl_ctx *ctx);      // launch the pending entries on stream_desc and wait for them
-
+// Inside a pcl_desc_group the array is staged (pcl_desc.h) and copied with the group's other arrays by ONE launch at its end.
+hipError_t pcl_desc_launch(pcl_ctx *ctx, const DescCopyArgs &a, const char *pin);   // pcl_api.hip: copy the entries on stream_desc and wait for them
+static inline auto pcl_desc_flusher(pcl_ctx *ctx) {
+    return [ctx](const DescCopyArgs &a, const char *pin) { return pcl_desc_launch(ctx, a, pin); };
+}
 static inline hipError_t pcl_h2d_fresh(pcl_ctx *ctx, void *dst, const void *src, size_t bytes) {
     if (!bytes) return hipSuccess;
     if (!ctx->stream_desc) return pcl_h2d(ctx, dst, src, bytes);
-    if (ctx->desc_group > 0) {                                       // inside a pcl_desc_group: staged, copied by ONE kernel at its end
-        const size_t need = (bytes + 255) & ~(size_t)255;
-        if (ctx->desc_pin_used + need > ctx->desc_pin_cap || ctx->desc_n == PCL_DESC_MAX) {
-            hipError_t e = pcl_desc_flush(ctx);                      // what is staged so far has to land before the buffer is reused
-            if (e != hipSuccess) return e;
-            if (need > ctx->desc_pin_cap) {
-                if (ctx->desc_pin) (void)hipHostFree(ctx->desc_pin);
-                ctx->desc_pin = nullptr;
-                ctx->desc_pin_cap = 0;
-                const size_t cap = std::max<size_t>((size_t)16 << 20, need * 2);
-                e = hipHostMalloc((void **)&ctx->desc_pin, cap, hipHostMallocDefault);
-                if (e != hipSuccess) return e;
-                ctx->desc_pin_cap = cap;
-            }
-        }
-        memcpy(ctx->desc_pin + ctx->desc_pin_used, src, bytes);
-        // ONE kernel copies all pending entries side by side: two entries with the same destination would race.  A later upload of an array
-        // replaces the earlier one (pcl_batch_create_labels uploads the utterance descriptors twice: before and after the transition
-        // offsets are known -- when the first version won, every utterance read utterance 0's transitions: wrong results as soon as the
-        // unit matrices differ, tests/test_gpu_sweep.py::test_the_queueing_knobs_do_not_move_a_bit)
-#ifndef PCL_DESC_RACE_REPRO                                            // (a build WITH this macro restores the bug: what the sweep tests must catch)
-        for (int k = 0; k < ctx->desc_n; ++k)
-            if (ctx->desc_dst[k] == dst) ctx->desc_bytes[k] = 0;
-#endif
-        ctx->desc_dst[ctx->desc_n] = dst;
-        ctx->desc_off[ctx->desc_n] = ctx->desc_pin_used;
-        ctx->desc_bytes[ctx->desc_n] = bytes;
-        ++ctx->desc_n;
-        ctx->desc_pin_used += need;
-        return hipSuccess;
-    }
+    if (ctx->desc.group > 0) return ctx->desc.stage(dst, src, bytes, pcl_desc_flusher(ctx));
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream_desc);
     return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream_desc);
 }
@@ -474,12 +441,11 @@ static inline hipError_t pcl_h2d_fresh(pcl_ctx *ctx, void *dst, const void *src,
 struct pcl_desc_group {
     pcl_ctx *ctx;
     bool open;
-    explicit pcl_desc_group(pcl_ctx *c) : ctx(c), open(true) { ++ctx->desc_group; }
+    explicit pcl_desc_group(pcl_ctx *c) : ctx(c), open(true) { ctx->desc.enter(); }
     hipError_t finish() {
         if (!open) return hipSuccess;
         open = false;
-        if (--ctx->desc_group > 0) return hipSuccess;
-        return pcl_desc_flush(ctx);
+        return ctx->desc.leave(pcl_desc_flusher(ctx));
     }
     ~pcl_desc_group() { (void)finish(); }
 };
@@ -568,13 +534,13 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
 void pcl_fmllr_release(pcl_ctx *ctx);                // the fMLLR statistics and estimate (a frame matrix of another dimension)
 int pcl_launch_mllt_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_keep);        // frame_mllt.hip, behind pcl_batch_accumulate_mllt's checks
 void pcl_mllt_release(pcl_ctx *ctx);                 // the MLLT statistics (a frame matrix of another dimension)
-void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate scratch (pcl_destroy, pcl_model_upload)
+void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate scratch (pcl_model_upload)
 // frame_lda.hip, behind the checks of pcl_lda_accumulate / pcl_batch_accumulate_lda: d_src (rows of the frame matrix, on the device) = the
 // class of every row, or with state_class (host, J entries) its owner state; -1 = not kept
 int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src,
                               const int32_t *state_class, int J);
-void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (pcl_destroy)
-void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; pcl_destroy)
+void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (the next pcl_lda_zero)
+void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; the next pcl_cmvn_zero)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);
@@ -673,7 +639,6 @@ int pcl_mfcc_device(pcl_ctx *ctx, const char *who, const SignalView &sig, const 
 // The samples into d_sig, as pcl_mfcc_device sends them.  Returns with the main stream behind the last copy; on a failure the caller drains
 // ctx->pcm.stream before it lets d_sig go.
 int pcl_signal_upload(pcl_ctx *ctx, const char *who, void *d_sig, const SignalView &sig);
-void pcl_mfcc_release(pcl_ctx *ctx);          // the staging buffers, their events and stream, the cached tables (pcl_destroy, streams drained)
 // pitch.hip: the device buffers of one call, and what the caller wants of it
 struct PitchWork {
     DevBuf<long long> row_off, sig_off;

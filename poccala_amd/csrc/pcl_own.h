@@ -1,4 +1,5 @@
-// Ownership of device resources: the error macros, the one owning device buffer and the one lazily created event of libpoccala_hip.so.
+// Ownership of device resources: the error macros, the one owning device buffer, and the one owning handle behind the events, streams and
+// page-locked buffers of libpoccala_hip.so.
 // Needs only the declarations below (the pool, the error sink, the context's device ordinal), so that tests/test_devbuf_host.py can compile
 // the types against a malloc-backed stub pool.
 #pragma once
@@ -98,26 +99,86 @@ struct DevBuf {
     }
 };
 
-// An event without timing, created on first use (most batches never fetch, most contexts never stage): make() before the first record.
-// Reads as a plain hipEvent_t (nullptr until made).
-struct LazyEvent {
-    hipEvent_t ev = nullptr;
-    LazyEvent() = default;
-    LazyEvent(LazyEvent &&o) noexcept : ev(std::exchange(o.ev, nullptr)) {}
-    LazyEvent &operator=(LazyEvent &&o) noexcept {
+// THE owner of anything else the runtime hands out: a handle and the function that gives it back.  Ops has `static hipError_t create(H *)` (for
+// make(), where a handle is made without arguments) and `static void destroy(H)`.  Move-only, reads as the plain handle, null (H{}) until made
+// and after a move or a destroy().  tests/devbuf_host_check.cpp instantiates it with counting stubs.
+template <typename H, typename Ops>
+struct Owned {
+    H h{};
+    Owned() = default;
+    Owned(Owned &&o) noexcept : h(std::exchange(o.h, H{})) {}
+    Owned &operator=(Owned &&o) noexcept {
         if (this != &o) {
             destroy();
-            ev = std::exchange(o.ev, nullptr);
+            h = std::exchange(o.h, H{});
         }
         return *this;
     }
-    LazyEvent(const LazyEvent &) = delete;
-    LazyEvent &operator=(const LazyEvent &) = delete;
-    ~LazyEvent() { destroy(); }
-    operator hipEvent_t() const { return ev; }
-    hipError_t make() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { destroy(); }
+    operator H() const { return h; }
+    hipError_t make() { return h ? hipSuccess : Ops::create(&h); }   // on first use: a second make() keeps what is there
     void destroy() {
-        if (ev) (void)hipEventDestroy(ev);
-        ev = nullptr;
+        if (h) Ops::destroy(h);
+        h = H{};
+    }
+};
+// Two of them made as a pair or not at all.
+template <typename H, typename Ops>
+struct OwnedPair {
+    Owned<H, Ops> first, second;
+    hipError_t make() {
+        hipError_t e = first.make();
+        if (e == hipSuccess && (e = second.make()) != hipSuccess) first.destroy();
+        return e;
+    }
+};
+
+template <unsigned Flags>
+struct EventOps {
+    static hipError_t create(hipEvent_t *e) { return hipEventCreateWithFlags(e, Flags); }
+    static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+// An event without timing, created on first use (most batches never fetch, most contexts never stage): make() before the first record.
+using LazyEvent = Owned<hipEvent_t, EventOps<hipEventDisableTiming>>;
+// The two timing events around one launch of a KernelTimer group.
+using TimedEventPair = OwnedPair<hipEvent_t, EventOps<hipEventDefault>>;
+
+// A stream in one of the three flavours the runtime uses, chosen where it is made.
+enum class StreamKind { Plain, HighPriority, NonBlocking };
+struct StreamOps {
+    static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+struct Stream : Owned<hipStream_t, StreamOps> {
+    hipError_t make(StreamKind k) {
+        if (h) return hipSuccess;
+        if (k == StreamKind::HighPriority) return hipStreamCreateWithPriority(&h, hipStreamDefault, -1);
+        return k == StreamKind::NonBlocking ? hipStreamCreateWithFlags(&h, hipStreamNonBlocking) : hipStreamCreate(&h);
+    }
+};
+
+// Page-locked host memory: a pointer and a capacity in elements, as DevBuf.  reserve grows only and copies nothing; a failed allocation
+// leaves the buffer empty.  (Memory the CALLER owns -- pcl_host_alloc / pcl_host_free -- does not come through here.)
+struct PinBlock {
+    void *p = nullptr;
+    size_t cap = 0;
+    explicit operator bool() const { return p != nullptr; }
+};
+struct PinOps {
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void destroy(PinBlock b) { (void)hipHostFree(b.p); }
+};
+template <typename T, typename Ops = PinOps>
+struct PinBuf : Owned<PinBlock, Ops> {
+    operator T *() const { return static_cast<T *>(this->h.p); }
+    size_t cap() const { return this->h.cap; }
+    hipError_t reserve(size_t n) {
+        if (n <= this->h.cap) return hipSuccess;
+        this->destroy();
+        void *p = nullptr;
+        const hipError_t e = Ops::alloc(&p, n * sizeof(T));
+        if (e == hipSuccess) this->h = PinBlock{p, n};
+        return e;
     }
 };

@@ -1,5 +1,6 @@
-"""The owning device buffer of the host runtime (poccala_amd/csrc/pcl_own.h), without a GPU: tests/devbuf_host_check.cpp is compiled
-against a malloc-backed stub pool with the host's address and undefined-behaviour sanitizers and run as a process of its own."""
+"""The owning types of the host runtime (poccala_amd/csrc/pcl_own.h: device buffer, handle, handle pair, page-locked buffer) and the
+descriptor stager's bookkeeping (pcl_desc.h), without a GPU: tests/devbuf_host_check.cpp is compiled against malloc-backed counting stubs
+with the host's address and undefined-behaviour sanitizers and run as a process of its own."""
 import os
 import shutil
 import subprocess

@@ -114,3 +114,19 @@ def test_contexts_torn_down_with_everything_in_flight():
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     d = json.loads(p.stdout.strip().splitlines()[-1])
     assert d['ok'] and d['iterations'] == 40 and d['fetches_checked'] > 0 and len(d['teardown_modes']) == 4, d
+
+
+def test_a_context_with_every_lazy_member_gives_everything_back():
+    """tests/_teardown_walk.py in a subprocess (trouble ends the child, not the suite): twice a context torn down with timer event pairs
+    read and unread, the int16 front-end's staging stream and buffers, a used descriptor stager and a host communicator alive, then a
+    context destroyed at once.  Every call returned PCL_OK (the child asserts it), the pool's handed-out blocks are back where they were
+    after each context, and the second round took nothing new from the device."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', '_teardown_walk.py')], cwd=ROOT, capture_output=True, text=True,
+                       timeout=120, env=dict(os.environ, PCL_DESTROY_SYNC='1'))
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    first, second, bare = d['after']
+    for after in (first, second, bare):
+        assert after['handed_out_blocks'] == d['before']['handed_out_blocks'] and after['handed_out_bytes'] == d['before']['handed_out_bytes'], d
+    assert first['device_allocs'] > d['before']['device_allocs']
+    assert second['device_allocs'] == first['device_allocs'] and bare['device_allocs'] == second['device_allocs'], d
