@@ -342,8 +342,8 @@ __global__ __launch_bounds__(WG, MINW) void gmm_accumulate_kernel(
 // supplies the k-pair (frame row(r), frame row(r)+4) with the mixture on the lane -- no data movement
 // between the two products.  The frame tile Xe (32 frames x 80 features) is staged once in LDS by the
 // workgroup and read by MFMA (1) frame-major and by MFMA (2) feature-major (stride 97: conflict free).
-// A wave owns one 32-mixture tile of one state: its 40 parameter registers and its 48 moment
-// accumulators stay resident while the workgroup walks the state's frame list.
+// A wave owns one 32-mixture tile of one state: its 40 parameter registers and its moment
+// accumulators (16x16x4 form: one set per 16-frame half of a tile) stay resident while the workgroup walks the state's frame list.
 // Flush: cov = S2 - 2 d S1 + d^2 S0, mean = S1 + (c + bias) S0 with d = mu - c, in float64.
 // ------------------------------------------------------------------------------------------------
 typedef float f16v __attribute__((ext_vector_type(16)));
@@ -410,12 +410,18 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
         }
     }
     f16v S[T16 ? 1 : NCT];
-    f4x S16[T16 ? 2 : 1][T16 ? NCT16 : 1];
+    // T16: one set of moment accumulators per 16-frame half of the tile (ft), added in float64 at the flush.  A running f32 sum is rounded
+    // at every MFMA of its chain; when a mixture's frames sit far from the state's centre and close together, S2, S1 and S0 cancel in the
+    // flush and those roundings are what is left of cov_acc.  Two chains of half the length over half the mass halve that error (the
+    // `scale` case of tests/_acc16_cases.py was 1.0044 of its bound with one chain), and they are independent for the scheduler.
+    f4x S16[T16 ? 2 : 1][T16 ? 2 : 1][T16 ? NCT16 : 1];
     if constexpr (T16) {
 #pragma unroll
-        for (int ms = 0; ms < 2; ++ms)
+        for (int ft = 0; ft < 2; ++ft)
 #pragma unroll
-            for (int ct = 0; ct < NCT16; ++ct) S16[ms][ct] = f4x{0.f, 0.f, 0.f, 0.f};
+            for (int ms = 0; ms < 2; ++ms)
+#pragma unroll
+                for (int ct = 0; ct < NCT16; ++ct) S16[ft][ms][ct] = f4x{0.f, 0.f, 0.f, 0.f};
     } else {
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct)
@@ -527,8 +533,8 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
 #pragma unroll
                         for (int ct = 0; ct < NCT16; ++ct) {
                             const float bx = x[fr * XSTR + ct * 16 + l15];
-                            S16[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(d1[ft][0][r], bx, S16[0][ct], 0, 0, 0);
-                            S16[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(d1[ft][1][r], bx, S16[1][ct], 0, 0, 0);
+                            S16[ft][0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(d1[ft][0][r], bx, S16[ft][0][ct], 0, 0, 0);
+                            S16[ft][1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(d1[ft][1][r], bx, S16[ft][1][ct], 0, 0, 0);
                         }
                     }
             } else {
@@ -559,16 +565,15 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
     }
 
     // ---- flush: lane = feature column, register = mixture row; cov = S2 - 2 d S1 + d^2 S0, mean = S1 + (c + bias) S0
-    auto flush_one = [&](int m, int cidx, float s0, float s1, float s2v) {
+    auto flush_one = [&](int m, int cidx, double S0, double S1, double S2) {
         if (m < M && !(cidx & 1) && cidx < 2 * D) {
             const int d = cidx >> 1;
             const size_t o = ((size_t)j * Mpad + m) * D + d;
             const double c = (double)cen[d], dl = means64[o] - c;
-            const double S0 = (double)s0, S1 = (double)s1, S2 = (double)s2v;
             st_mean[o] += S1 + (c + bias) * S0;                            // Clustering.py:669-672
             st_cov[o] += fmax(S2 - 2.0 * dl * S1 + dl * dl * S0, 0.0);     // Clustering.py:674-678 (never negative: gmm_accumulate_f16.hip)
         }
-        if (m < M && cidx == 2 * D) st_acc[(size_t)j * Mpad + m] += (double)s2v;   // Clustering.py:665
+        if (m < M && cidx == 2 * D) st_acc[(size_t)j * Mpad + m] += S2;             // Clustering.py:665
     };
     if (live) {
         if constexpr (T16) {
@@ -577,11 +582,12 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = mt * 32 + ms * 16 + 4 * (lane >> 4) + r;
-                    const float s0 = __shfl(S16[ms][(2 * D) >> 4][r], (lane & 48) + ((2 * D) & 15), 64);
+                    const int src0 = (lane & 48) + ((2 * D) & 15);
+                    const double s0 = (double)__shfl(S16[0][ms][(2 * D) >> 4][r], src0, 64) + (double)__shfl(S16[1][ms][(2 * D) >> 4][r], src0, 64);
 #pragma unroll
                     for (int ct = 0; ct < NCT16; ++ct) {
-                        const float s1 = __shfl_xor(S16[ms][ct][r], 1, 64);
-                        flush_one(m, ct * 16 + (lane & 15), s0, s1, S16[ms][ct][r]);
+                        const double s1 = (double)__shfl_xor(S16[0][ms][ct][r], 1, 64) + (double)__shfl_xor(S16[1][ms][ct][r], 1, 64);
+                        flush_one(m, ct * 16 + (lane & 15), s0, s1, (double)S16[0][ms][ct][r] + (double)S16[1][ms][ct][r]);
                     }
                 }
         } else {
@@ -592,7 +598,7 @@ __global__ __launch_bounds__(AW * 64, 2) void gmm_accumulate_mfma_kernel(
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
                     const float s1 = __shfl_xor(S[ct][r], 1, 64);                      // odd neighbour: x' column of the same d
-                    flush_one(m, ct * 32 + col, s0, s1, S[ct][r]);
+                    flush_one(m, ct * 32 + col, (double)s0, (double)s1, (double)S[ct][r]);
                 }
             }
         }
