@@ -62,6 +62,11 @@ typedef enum {
 /* pcl_model_upload flags */
 #define PCL_MODEL_Q1_SUMVAR 0 /* reference constant: -D/2 ln2pi - 1/2 sum(var)   (util.py:29, quirk Q1) */
 #define PCL_MODEL_LOGDET 1    /* textbook constant:  -D/2 ln2pi - 1/2 sum(ln var) (opt-in, not parity)  */
+/* The flag belongs to the RESIDENT MODEL, not to a call: only pcl_model_upload and the flat starts (pcl_model_flat_start,
+ * pcl_flat_start) set it, and everything that rewrites the resident model afterwards keeps it -- pcl_mstep, pcl_em_exchange and
+ * pcl_batch_accumulate_exchange (state ranges re-derived on their own), pcl_model_mixup, pcl_model_transform_means, pcl_mstep_map and
+ * the re-upload after pcl_seg_kmeans.  Scoring, the accumulate pass and segmental EM all read it from there; uploading the same arrays
+ * with the other flag is a new model (tests/test_gpu_logdet.py). */
 
 /* row kinds in pcl_batch_set_states: >=0 is a GMM state id */
 #define PCL_ROW_ENTRY (-1) /* VirtualState(1.): ln 1 = 0   (AcousticModel.py:218,1039-1043) */
