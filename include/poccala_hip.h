@@ -798,6 +798,72 @@ int pcl_frames_cmvn(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_
 int pcl_frames_cmvn_sliding(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, int window, int min_window, int center,
                             int norm_vars, double var_floor);
 
+/* ----------------------------------------------------------------- phonetic decision tree (row f16): context statistics, tied states
+ * The first half of monophone -> context-dependent (csrc/tree_cluster.hip): per-context single-Gaussian statistics from an alignment, trees
+ * grown top-down over phonetic questions, the tied-state map, and a one-Gaussian-per-leaf seed model that pcl_model_mixup and the E-step
+ * then grow.  Not in the reference; tests/_tree_twin.py is the rule's NumPy twin.  Everything is float64, one rounding per operation; no
+ * floating-point atomics: two runs give the same bits.
+ *
+ * ROWS.  The caller lists the E distinct contexts it saw: event_ctx (E, 3) int32 = (left, centre, right), unit ids 0 .. n_units - 1, the
+ * value n_units = no neighbour (utterance edge); the centre is a unit.  P = S - 2 state positions; statistics row r = e P + k, R = E P.
+ * Per row   n = its frames (int64)    s_d = sum x_d    q_d = sum x_d x_d   (x_d x_d rounded, then added)
+ * pcl_tree_zero makes (and clears) them for R rows at the dimension D of the CURRENT frame matrix: ONE block of 8 R (2 D + 1) bytes from
+ * the context's pool, at most 2^32; freed by pcl_destroy and by the next pcl_tree_zero.  They are additive over calls.
+ *
+ * ACCUMULATE.  pcl_tree_accumulate: frame_row (F,) int32, the statistics row of every row of the frame matrix, or -1; utterance u occupies
+ * the rows [frame_begin[u], + T[u]), the utterances must not overlap, rows outside every utterance are not counted.
+ * pcl_batch_accumulate_tree: a label-built batch after pcl_batch_viterbi -- everything pcl_batch_align_segments needs and checks, its drop
+ * rule and its slices; label_event (sum of the label lengths,) int32 = the event of every label position, or -1 = the position's frames
+ * are skipped.  A frame whose path row belongs to label position i (entry row -> 0, rows 1 .. P L -> (row - 1) / P, exit row -> L - 1)
+ * and whose slice in pcl_batch_align_segments' owner map is k goes to row label_event[i] P + k.  The owner map stays on the device.
+ * x is read from the float64 copy when the context holds one, else the float32 rows are widened, as in pcl_frames_moments.
+ * Order: the kept frame rows are counting-sorted by statistics row, stably; a statistics row's frames, in ascending frame row, are cut into
+ * chunks of PCL_TREE_CHUNK (env, read on every call; default 256); a chunk's frames are added in ascending order from 0; the chunks'
+ * sums are added onto the resident sum in chunk order.  One group of lanes per chunk, one 16-byte load per frame and lane.
+ *
+ * LIKELIHOOD of a pooled set (n, s, q), n > 0, d ascending:
+ *     m_d = s_d / n      v_d = max(q_d / n - m_d m_d, var_floor)      L = -0.5 n (D c + sum_d ln v_d),  c = 1 + ln 2 pi = 2.8378770664093453
+ * L = 0 for n = 0.
+ *
+ * QUESTIONS.  q_member (Q, n_units + 1) uint8: unit sets, the edge symbol a member like any other.  Candidate c = pos Q + qi, pos 0 left,
+ * 1 centre, 2 right; an event answers yes iff q_member[qi][event_ctx[e][pos]].  ROOTS.  root_of (n_units P,) int32 in [0, R0) maps
+ * (centre, k) to its root; row (e, k) starts in root root_of[centre(e) P + k]; nodes 0 .. R0 - 1 are the roots.
+ *
+ * GROWTH.  For a leaf and a candidate, the yes-set is the leaf's rows whose event answers yes, the no-set the rest; either side's (n, s, q)
+ * is the sum of its rows in ascending row order from +0.0, the same for every candidate.  gain = (L_yes + L_no) - L_leaf, L_leaf from the
+ * sum of all the leaf's rows in ascending order.  A candidate is valid iff n_yes >= min_count, n_no >= min_count and gain >= min_gain.
+ * Each step splits the (leaf, candidate) of largest gain among all current leaves; ties go to the lowest node id, then the lowest c.
+ * Split number t (from 0) creates the nodes R0 + 2 t (no) and R0 + 2 t + 1 (yes).  Growth stops when no candidate is valid or the leaves
+ * number max_leaves (>= R0).  Tied-state ids are the leaves in ascending node id, 0 .. J_t - 1.  Rows with n = 0 follow their answers.
+ * One workgroup per (leaf, 8 candidates) walks the leaf's rows once; the gains and the arg-max of a leaf run on the device, the choice
+ * among the leaves and the stable partition of the chosen leaf's row list on the host.
+ *
+ * OUTPUTS (NULLs are skipped; capacity N <= R0 + 2 (max_leaves - R0)): node_cand (N,) c or -1 at leaves; node_child (N, 2) (no, yes) or
+ * -1; node_state (N,) tied id or -1; node_n (N,) int64; split_gain ((N - R0) / 2,) in split order; row_state (R,); the leaves' sums
+ * leaf_n (J_t,) int64, leaf_s, leaf_q (J_t, D).  *n_nodes_out = N, *n_states_out = J_t.
+ * INSTALL (install != 0).  The resident model becomes (J_t, 1, D): mean = s / n, var = v as above, weight 1, written into the float64
+ * master copy, then everything pcl_model_upload runs after its copy (pcl_model_flat_start's path and flags).  A leaf with n = 0:
+ * PCL_ERR_INVALID naming the node, before anything is written; the model in place stays.  Unit transitions, frames and the tree
+ * statistics are untouched.
+ * pcl_tree_stats_upload REPLACES the resident statistics (externally merged sums; tests drive the build with exact values).
+ * pcl_tree_stats_shape: *R and *D of the resident statistics, the sizes a download needs; 0 and 0 when there are none (no refusal).
+ *
+ * PCL_ERR_STATE: no frames or no statistics; the frame matrix changed its width since pcl_tree_zero; the batch conditions of
+ * pcl_batch_align_segments.  PCL_ERR_INVALID: R < 1 or 8 R (2 D + 1) > 2^32; a row or event id outside [-1, R) / [-1, E); E P != R; a
+ * context id outside [0, n_units] or a centre = n_units; root_of outside [0, R0) or a root nobody maps to; Q < 1 or 3 Q > 4096;
+ * max_leaves < R0; min_gain negative or not finite; var_floor <= 0; min_count < 1; uploaded statistics not finite or n < 0; overlapping
+ * utterances.  All checked before anything is changed.  pcl_kernel_time groups: "tree_sort", "tree_stats", "tree_build".  Synchronous. */
+int pcl_tree_zero(pcl_ctx *ctx, int R);
+int pcl_tree_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *frame_row /* F, -1 = skip */);
+int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event /* sum L_u, -1 = skip */);
+int pcl_tree_stats_shape(pcl_ctx *ctx, int32_t *R, int32_t *D);
+int pcl_tree_stats_download(pcl_ctx *ctx, int64_t *n /* R or NULL */, double *s /* R*D or NULL */, double *q /* R*D or NULL */);
+int pcl_tree_stats_upload(pcl_ctx *ctx, const int64_t *n /* R */, const double *s /* R*D */, const double *q /* R*D */);
+int pcl_tree_build(pcl_ctx *ctx, int E, int P, const int32_t *event_ctx /* E*3 */, int n_units, int Q, const uint8_t *q_member /* Q*(n_units+1) */,
+                   int R0, const int32_t *root_of /* n_units*P */, int64_t min_count, double min_gain, int max_leaves, double var_floor, int install,
+                   int flags, int32_t *node_cand, int32_t *node_child, int32_t *node_state, int64_t *node_n, double *split_gain,
+                   int32_t *row_state, int64_t *leaf_n, double *leaf_s, double *leaf_q, int32_t *n_nodes_out, int32_t *n_states_out);
+
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /
  * (2 var_jmd) (about 5e-7 * cond nats).  States with cond[j] > *cond_max (default 96, env PCL_MFMA_COND_MAX) are scored

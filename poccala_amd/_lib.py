@@ -93,6 +93,14 @@ PROTOTYPES = {
     'pcl_cmvn_stats_download': (_i, [_vp, _vp, _vp, _vp]),
     'pcl_frames_cmvn': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _d, C.c_int64, _vp]),
     'pcl_frames_cmvn_sliding': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _d]),
+    'pcl_tree_zero': (_i, [_vp, _i]),
+    'pcl_tree_accumulate': (_i, [_vp, _i, _vp, _vp, _vp]),
+    'pcl_batch_accumulate_tree': (_i, [_vp, _vp]),
+    'pcl_tree_stats_shape': (_i, [_vp, _vp, _vp]),
+    'pcl_tree_stats_download': (_i, [_vp, _vp, _vp, _vp]),
+    'pcl_tree_stats_upload': (_i, [_vp, _vp, _vp, _vp]),
+    'pcl_tree_build': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, C.c_int64, _d, _i, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                            _vp, _vp]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

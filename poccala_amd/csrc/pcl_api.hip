@@ -1323,6 +1323,63 @@ int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
     return rc;
 }
 
+// Decision-tree context statistics from the batch's Viterbi paths (tree_cluster.hip): the owner map pcl_batch_align_segments makes and the
+// statistics row of every frame stay on the device
+int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    const char *who = "pcl_batch_accumulate_tree";
+    TRY(pcl_tree_accumulate_ready(ctx, who));
+    TRY(align_precheck(b, who));
+    const int P = ctx->S - 2;
+    if (ctx->tree_R % P != 0)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the statistics hold %d rows, no multiple of the inventory's %d emitting states per unit", who, ctx->tree_R, P);
+    const int E = ctx->tree_R / P;
+    if (!label_event) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: label_event is NULL", who);
+    for (size_t i = 0; i < b->labels.size(); ++i)
+        if (label_event[i] < -1 || label_event[i] >= E)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: label_event[%zu] = %d is neither -1 nor an event in [0, %d)", who, i, (int)label_event[i], E);
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const long long F = ctx->F;
+    TRY(align_labels_up(b));
+    DevBuf<int32_t> d_state, d_drop, d_row, d_event;
+    auto align = [&]() -> int {
+        TRY(d_state.alloc(ctx, (size_t)F));
+        TRY(d_row.alloc(ctx, (size_t)F));
+        TRY(d_drop.alloc(ctx, (size_t)b->U));
+        TRY(d_event.alloc(ctx, b->labels.size()));
+        HIPCHK(ctx, pcl_h2d(ctx, d_event, label_event, b->labels.size() * sizeof(int32_t)));
+        HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(d_row, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
+        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, P, d_state, d_drop));
+        TRY(pcl_launch_tree_label_rows(ctx, b, d_event, P, d_state, d_row));
+        HIPCHK(ctx, pcl_batch_mark(b));
+        return PCL_OK;
+    };
+    int rc = align();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) {      // (on every path: the frees below rely on it)
+        pcl_set_error(ctx, "pcl_batch_accumulate_tree: HIP error");
+        rc = PCL_ERR_HIP;
+    }
+    if (rc == PCL_OK) {
+        std::vector<int32_t> T(b->U);
+        std::vector<int64_t> begin(b->U);
+        for (int u = 0; u < b->U; ++u) {
+            T[u] = b->utt[u].T;
+            begin[u] = b->utt[u].frame0;
+        }
+        rc = pcl_launch_tree_accumulate(ctx, who, b->U, T.data(), begin.data(), d_row);   // (waits for its kernels)
+        if (rc != PCL_OK) (void)hipStreamSynchronize(ctx->stream);  // ... unless it gave up half-way
+    }
+    pcl_free_synced_scope done;
+    d_state.release();
+    d_drop.release();
+    d_row.release();
+    d_event.release();
+    return rc;
+}
+
 int pcl_batch_get(pcl_batch *b, int what, void *host) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;

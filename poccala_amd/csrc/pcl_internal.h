@@ -234,6 +234,10 @@ struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev {
     DevBuf<long long> cmvn_n;
     DevBuf<double> cmvn_sq;
     int cmvn_S = 0, cmvn_D = 0;
+    // Decision-tree context statistics (tree_cluster.hip): ONE block [n (tree_R) int64 | s (tree_R, tree_D) | q (tree_R, tree_D)]; tree_D = the
+    // frame dimension pcl_tree_zero saw.  Freed by pcl_destroy and by the next pcl_tree_zero.
+    DevBuf<double> tree_stats;
+    int tree_R = 0, tree_D = 0;
     // streaming: two frame slots (grow only); pcl_frames_stage copies the next chunk into the slot that is not current on stream_aux,
     // pcl_frames_swap makes it current
     DevBuf<float> frames_slot[2];
@@ -541,6 +545,15 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
                               const int32_t *state_class, int J);
 void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (the next pcl_lda_zero)
 void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; the next pcl_cmvn_zero)
+// tree_cluster.hip, for pcl_batch_accumulate_tree (pcl_api.hip).  pcl_tree_accumulate_ready: statistics made, frames loaded, at the statistics'
+// width.  pcl_launch_tree_label_rows: the batch's owner map (d_frame_state, unit * P + slice) and the caller's label position -> event list
+// (d_label_event, on the device) -> the statistics row of every frame (d_frame_row, set to -1 before); queued on ctx->stream.
+// pcl_launch_tree_accumulate: behind the checks of both accumulate entries; d_src (rows of the frame matrix, on the device) = the
+// statistics row of every frame row in [-1, R); waits for its kernels.
+int pcl_tree_accumulate_ready(pcl_ctx *ctx, const char *who);
+int pcl_launch_tree_label_rows(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_label_event, int P, const int32_t *d_frame_state, int32_t *d_frame_row);
+int pcl_launch_tree_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src);
+void pcl_tree_release(pcl_ctx *ctx);                 // the tree statistics (the next pcl_tree_zero)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);

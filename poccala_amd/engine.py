@@ -655,6 +655,77 @@ class Engine(object):
         self.FD = int(A.shape[0])
         self._frames_key = None                      # the resident frames are no longer what was uploaded
 
+    # ------------------------------------------------------------------ phonetic decision tree: context statistics, tied states
+    def tree_zero(self, n_rows):
+        """Make (and clear) the context's decision-tree statistics for n_rows = E * P rows at the dimension of the resident frames
+        (pcl_tree_zero): per row the frames n, sum x and sum x^2."""
+        self._check(self._lib.pcl_tree_zero(self._ctx, int(n_rows)))
+
+    def _tree_shape(self):
+        """(R, D) of the context's decision-tree statistics (pcl_tree_stats_shape), (0, 0) when it holds none: asked of the context, so
+        that a pcl_tree_zero made through the C-ABI on it is seen."""
+        R, D = C.c_int32(), C.c_int32()
+        self._check(self._lib.pcl_tree_stats_shape(self._ctx, C.byref(R), C.byref(D)))
+        return int(R.value), int(D.value)
+
+    def tree_accumulate(self, T, frame_begin, frame_row):
+        """Add the rows [frame_begin[u], + T[u]) of the resident frames to the statistics (pcl_tree_accumulate): frame_row (F,) int32, the
+        statistics row in [0, n_rows) of every row of the frame matrix, -1 = skip the row."""
+        T, fb = self._utt_ranges(T, frame_begin)
+        rows = as_c(frame_row, np.int32).reshape(-1)
+        if fb is None or rows.shape != (int(self.F),):
+            raise ValueError('frame_begin is needed and frame_row must hold one row per frame row (F = %d), got %s' % (self.F, rows.shape))
+        self._check(self._lib.pcl_tree_accumulate(self._ctx, T.size, ptr(T), ptr(fb), ptr(rows)))
+
+    def tree_stats(self):
+        """(n (R,) int64, s (R, D), q (R, D)): what tree_accumulate / Batch.accumulate_tree have summed since tree_zero."""
+        R, D = self._tree_shape()
+        n, s, q = np.empty(max(R, 1), dtype=np.int64), np.empty((max(R, 1), max(D, 1))), np.empty((max(R, 1), max(D, 1)))
+        self._check(self._lib.pcl_tree_stats_download(self._ctx, ptr(n), ptr(s), ptr(q)))
+        return n[:R], s[:R, :D], q[:R, :D]
+
+    def tree_stats_load(self, n, s, q):
+        """Replace the resident statistics (pcl_tree_stats_upload): n (R,) int64, s and q (R, D), the shapes of the last tree_zero."""
+        R, D = self._tree_shape()
+        n, s, q = as_c(n, np.int64).reshape(-1), as_c(s, np.float64), as_c(q, np.float64)
+        if n.shape != (R,) or s.shape != (R, D) or q.shape != (R, D):
+            raise ValueError('the statistics are n (%d,), s and q (%d, %d), got %s, %s, %s' % (R, R, D, n.shape, s.shape, q.shape))
+        self._check(self._lib.pcl_tree_stats_upload(self._ctx, ptr(n), ptr(s), ptr(q)))
+
+    def tree_build(self, event_ctx, P, n_units, q_member, root_of, n_roots=None, min_count=1, min_gain=0.0, max_leaves=None, var_floor=1e-4,
+                   install=False, logdet=False):
+        """Grow the trees over the resident statistics (pcl_tree_build; the rule: include/poccala_hip.h) and return the ContextTree.Tree.
+        event_ctx (E, 3) int32, q_member (Q, n_units + 1) uint8, root_of (n_units * P,) int32.  install=True: the resident model becomes
+        the (J_t, 1, D) one-Gaussian-per-leaf model, as flat_start_model would have left it."""
+        from .AcousticModel.ContextTree import Tree
+        ec = as_c(event_ctx, np.int32).reshape(-1, 3)
+        qm = as_c(q_member, np.uint8)
+        ro = as_c(root_of, np.int32).reshape(-1)
+        P, n_units = int(P), int(n_units)
+        if qm.ndim != 2 or qm.shape[1] != n_units + 1 or ro.shape != (n_units * P,):
+            raise ValueError('q_member must be (Q, %d) and root_of (%d,), got %s and %s' % (n_units + 1, n_units * P, qm.shape, ro.shape))
+        E, Q = int(ec.shape[0]), int(qm.shape[0])
+        R, D = E * P, self._tree_shape()[1]
+        R0 = int(ro.max()) + 1 if n_roots is None else int(n_roots)
+        ml = max(R0, R) if max_leaves is None else min(int(max_leaves), max(R0, R, 1))
+        cap = max(R0 + 2 * max(ml - R0, 0), 1)
+        node_cand, node_child, node_state = np.empty(cap, dtype=np.int32), np.empty((cap, 2), dtype=np.int32), np.empty(cap, dtype=np.int32)
+        node_n, gain, row_state = np.empty(cap, dtype=np.int64), np.empty(cap), np.empty(max(R, 1), dtype=np.int32)
+        leaf_n, leaf_s, leaf_q = np.empty(cap, dtype=np.int64), np.empty((cap, max(D, 1))), np.empty((cap, max(D, 1)))
+        nn, ns = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        self._check(self._lib.pcl_tree_build(self._ctx, E, P, ptr(ec), n_units, Q, ptr(qm), R0, ptr(ro), int(min_count), float(min_gain), ml,
+                                             float(var_floor), 1 if install else 0, 1 if logdet else 0, ptr(node_cand), ptr(node_child),
+                                             ptr(node_state), ptr(node_n), ptr(gain), ptr(row_state), ptr(leaf_n), ptr(leaf_s), ptr(leaf_q),
+                                             ptr(nn), ptr(ns)))
+        N, Jt = int(nn[0]), int(ns[0])
+        if install:
+            self.J, self.M, self.D = Jt, 1, D
+            self._model_key = None
+        return Tree(P, n_units, node_cand=node_cand[:N].copy(), node_child=node_child[:N].copy(), node_state=node_state[:N].copy(),
+                    node_n=node_n[:N].copy(), split_gain=gain[:(N - R0) // 2].copy(), row_state=row_state[:R].copy(), event_ctx=ec, q_member=qm,
+                    root_of=ro, leaf_n=leaf_n[:Jt].copy(), leaf_s=leaf_s.reshape(-1)[:Jt * D].reshape(Jt, D).copy(),
+                    leaf_q=leaf_q.reshape(-1)[:Jt * D].reshape(Jt, D).copy())
+
     # ------------------------------------------------------------------ CMVN: mean and variance normalisation of the resident frames
     def cmvn_zero(self, n_speakers):
         """Make (and clear) the context's CMVN statistics for n_speakers speakers at the dimension of the resident frames (pcl_cmvn_zero)."""
@@ -987,6 +1058,17 @@ class Batch(object):
                 raise ValueError('state_class must hold one class per model state (J = %d), got %s' % (self.eng.J, sc.shape))
         self._check(self._lib.pcl_batch_accumulate_lda(self._b, ptr(sc)))
 
+    def accumulate_tree(self, label_event):
+        """Decision-tree context statistics from this batch's Viterbi paths (pcl_batch_accumulate_tree) into the sums of the last
+        Engine.tree_zero: a frame at label position i, slice k (align_segments' slices and drop rule) counts for row
+        label_event[i] * P + k; label_event (sum of the label lengths,) int32, -1 = skip the position's frames
+        (ContextTree.triphone_events makes it).  Label-built batches only; needs score() and viterbi().  The owner map stays on the device."""
+        le = as_c(label_event, np.int32).reshape(-1)
+        labels = getattr(self, 'labels', None)        # (a host-built batch has none: the library refuses it)
+        if labels is not None and le.shape != labels.shape:
+            raise ValueError('label_event must hold one event per label position (%d), got %s' % (labels.size, le.shape))
+        self._check(self._lib.pcl_batch_accumulate_tree(self._b, ptr(le)))
+
     def accumulate_hmm(self):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
         self._check(self._lib.pcl_batch_accumulate_hmm(self._b))
@@ -1286,21 +1368,30 @@ def embedded_row_states(unit_state_ids, s=5):
     return np.concatenate([[PCL_ROW_ENTRY], ids, [PCL_ROW_EXIT]]).astype(np.int32)
 
 
-def make_sentence_batch(engine, unit_ids, T, frame_begin, unit_trans, s=5):
+def make_sentence_batch(engine, unit_ids, T, frame_begin, unit_trans, s=5, unit_state_ids=None):
     """Build the batch for a list of labels.  unit_ids[u]: sequence of unit indices (label of
     utterance u); unit i owns GMM states i*(S-2) .. i*(S-2)+S-3 of the uploaded model and the
-    transition matrix unit_trans[i] (S,S).  Returns (batch, N)."""
+    transition matrix unit_trans[i] (S,S).  unit_state_ids[u]: the (L_u, S-2) GMM state ids of the
+    label's emitting rows in place of unit*(S-2) + k -- tied states (ContextTree.Tree.unit_state_ids).
+    Returns (batch, N)."""
     e = s - 2
     n = np.array([e * len(l) + 2 for l in unit_ids], dtype=np.int32)
+    if unit_state_ids is not None and len(unit_state_ids) != len(unit_ids):
+        raise ValueError('unit_state_ids must hold one (L, %d) array per utterance' % e)
     b = engine.batch(n, T, frame_begin)
     log_a, log_pi, rows = [], [], []
     with np.errstate(divide='ignore'):
-        for lab in unit_ids:
+        for u, lab in enumerate(unit_ids):
             lab = np.asarray(lab, dtype=np.int64)
             a, pi = embedded_structure(len(lab), [unit_trans[i] for i in lab], s)
             log_a.append(np.log(a))
             log_pi.append(np.log(pi))
-            rows.append(embedded_row_states(lab[:, None] * e + np.arange(e)[None, :], s))
+            ids = lab[:, None] * e + np.arange(e)[None, :]
+            if unit_state_ids is not None:
+                ids = np.asarray(unit_state_ids[u])
+                if ids.shape != (len(lab), e):
+                    raise ValueError('unit_state_ids[%d] must be (%d, %d), got %s' % (u, len(lab), e, ids.shape))
+            rows.append(embedded_row_states(ids, s))
     b.set_transitions(log_a, log_pi)
     b.set_states(rows)
     return b, n

@@ -1,0 +1,153 @@
+"""NumPy twin of the decision-tree rule (row f16; include/poccala_hip.h states it, csrc/tree_cluster.hip runs it on the device).
+
+Statistics: per row n, s = sum x, q = sum x x as SEQUENTIAL float64 sums in ascending frame-row order, onto what is there.
+Build: the greedy rule.  A side's (n, s, q) is the sum of its rows in ascending row order from +0.0 (adding +0.0 for the rows of the other
+side leaves the bits, so the masked walk below IS that sum); L = -0.5 n (D c + sum_d ln v_d) with d ascending, c = 1 + ln 2 pi as the
+double 2.8378770664093453.  Every decision is recorded with what the GPU tests need to know that it can be compared: the winner's gain,
+B = 0.5 sum over (yes, no, leaf) of n (D c + sum_d |ln v_d|), the best gain among the valid candidates of a DIFFERENT partition
+(another leaf, or another unordered {yes, no} of the same leaf -- a candidate of the same partition has the winner's gain bit for bit on
+either side, and the tie rules decide), and the smallest |gain - min_gain| / B over the count-valid candidates."""
+import numpy as np
+
+C1 = 2.8378770664093453
+
+
+def zero(R, D):
+    return dict(n=np.zeros(R, dtype=np.int64), s=np.zeros((R, D)), q=np.zeros((R, D)), sabs=np.zeros((R, D)), qabs=np.zeros((R, D)))
+
+
+def accumulate(st, frames, T, begin, frame_row):
+    """frames (F, D) as the context holds them (float32 rows are widened); sabs / qabs: the sums of |x| and x x of the bounds."""
+    frames = np.asarray(frames)
+    frame_row = np.asarray(frame_row)
+    inside = np.zeros(frames.shape[0], dtype=bool)
+    for t, b in zip(T, begin):
+        inside[int(b):int(b) + int(t)] = True
+    out = {k: v.copy() for k, v in st.items()}
+    for r in np.unique(frame_row[inside & (frame_row >= 0)]):
+        x = frames[np.flatnonzero(inside & (frame_row == r))].astype(np.float64)
+        out['n'][r] += x.shape[0]
+        out['s'][r] = np.cumsum(np.vstack([out['s'][r][None], x]), axis=0)[-1]
+        out['q'][r] = np.cumsum(np.vstack([out['q'][r][None], x * x]), axis=0)[-1]
+        out['sabs'][r] += np.abs(x).sum(axis=0)
+        out['qabs'][r] += (x * x).sum(axis=0)
+    return out
+
+
+def loglike(n, sq, var_floor):
+    """n (K,), sq (K, 2 D) -> (L (K,), B-term n (D c + sum |ln v|) (K,), v (K, D))"""
+    D = sq.shape[1] // 2
+    nn = np.where(n > 0, n, 1).astype(np.float64)[:, None]
+    m = sq[:, :D] / nn
+    v = np.maximum(sq[:, D:] / nn - m * m, var_floor)
+    acc, aabs = np.zeros(len(n)), np.zeros(len(n))
+    for d in range(D):
+        lv = np.log(v[:, d])
+        acc = acc + lv
+        aabs = aabs + np.abs(lv)
+    nf = n.astype(np.float64)
+    L = np.where(n > 0, -0.5 * nf * (float(D) * C1 + acc), 0.0)
+    return L, np.where(n > 0, nf * (float(D) * C1 + aabs), 0.0), v
+
+
+def answers(event_ctx, P, q_member):
+    """(3 Q, R) bool: candidate c = pos Q + qi of row r = e P + k"""
+    event_ctx, q_member = np.asarray(event_ctx), np.asarray(q_member)
+    a = np.concatenate([q_member[:, event_ctx[:, pos]] for pos in range(3)], axis=0) != 0      # (3 Q, E)
+    return np.repeat(a, P, axis=1)
+
+
+def _eval_leaf(rows, n, X, ans, min_count, var_floor):
+    A = ans[:, rows]
+    NC = A.shape[0]
+    yes, no, tot = np.zeros((NC, X.shape[1])), np.zeros((NC, X.shape[1])), np.zeros((1, X.shape[1]))
+    cy = np.zeros(NC, dtype=np.int64)
+    for k, r in enumerate(rows):
+        on = A[:, k:k + 1]
+        yes = yes + np.where(on, X[r][None, :], 0.0)
+        no = no + np.where(on, 0.0, X[r][None, :])
+        tot = tot + X[r][None, :]
+        cy += np.where(A[:, k], n[r], 0)
+    nt = int(n[rows].sum()) if len(rows) else 0
+    cn = nt - cy
+    Ly, By, _ = loglike(cy, yes, var_floor)
+    Ln, Bn, _ = loglike(cn, no, var_floor)
+    Ll, Bl, _ = loglike(np.array([nt], dtype=np.int64), tot, var_floor)
+    gain = (Ly + Ln) - Ll[0]
+    keys = []
+    for c in range(NC):
+        a = A[c].tobytes()
+        keys.append(min(a, (~A[c]).tobytes()))
+    return dict(gain=gain, B=0.5 * (By + Bn + Bl[0]), cv=(cy >= min_count) & (cn >= min_count), cy=cy, cn=cn, nt=nt, tot=tot[0], keys=keys)
+
+
+def build(n, s, q, event_ctx, P, n_units, q_member, R0, root_of, min_count=1, min_gain=0.0, max_leaves=None, var_floor=1e-4):
+    n, X = np.asarray(n, dtype=np.int64), np.concatenate([np.asarray(s, dtype=np.float64), np.asarray(q, dtype=np.float64)], axis=1)
+    event_ctx, root_of = np.asarray(event_ctx), np.asarray(root_of)
+    R, D = X.shape[0], X.shape[1] // 2
+    ML = max(R0, R) if max_leaves is None else min(int(max_leaves), max(R0, R))
+    ans = answers(event_ctx, P, q_member)
+    row_root = root_of[event_ctx[np.arange(R) // P, 1] * P + np.arange(R) % P]
+    rows_of = [np.flatnonzero(row_root == i) for i in range(R0)]
+    cand, child = [-1] * R0, [[-1, -1] for _ in range(R0)]
+    ev = [_eval_leaf(rows_of[i], n, X, ans, min_count, var_floor) for i in range(R0)]
+    leaves, gains, decisions = list(range(R0)), [], []
+    while True:
+        pool = []                                                 # (gain, node, c) of every valid candidate, and the threshold margins
+        thr = np.inf
+        for i in sorted(leaves):
+            e = ev[i]
+            if e['cv'].any():
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    thr = min(thr, float(np.min(np.abs(e['gain'][e['cv']] - min_gain) / e['B'][e['cv']])))
+            for c in np.flatnonzero(e['cv'] & (e['gain'] >= min_gain)):
+                pool.append((float(e['gain'][c]), i, int(c)))
+        if len(leaves) >= ML:
+            break
+        if not pool:
+            decisions.append(dict(kind='stop', thr=thr))
+            break
+        best = max(pool, key=lambda x: (x[0], -x[1], -x[2]))
+        g, p, c = best
+        key = ev[p]['keys'][c]
+        others = [x[0] for x in pool if not (x[1] == p and ev[p]['keys'][x[2]] == key)]
+        other = max(others) if others else -np.inf
+        B = float(ev[p]['B'][c])
+        decisions.append(dict(kind='split', node=p, cand=c, gain=g, B=B, other=other, sep=(g - other) / B if B > 0 else np.inf, thr=thr))
+        A = ans[c, rows_of[p]]
+        id_no = len(cand)
+        cand[p], child[p] = c, [id_no, id_no + 1]
+        gains.append(g)
+        for side in (~A, A):
+            cand.append(-1)
+            child.append([-1, -1])
+            rows_of.append(rows_of[p][side])
+            ev.append(_eval_leaf(rows_of[-1], n, X, ans, min_count, var_floor))
+        leaves.remove(p)
+        leaves += [id_no, id_no + 1]
+    N = len(cand)
+    state = np.full(N, -1, dtype=np.int32)
+    leaf_ids = [i for i in range(N) if cand[i] < 0]
+    state[leaf_ids] = np.arange(len(leaf_ids), dtype=np.int32)
+    row_state = np.full(R, -1, dtype=np.int32)
+    for i in leaf_ids:
+        row_state[rows_of[i]] = state[i]
+    leaf_n = np.array([ev[i]['nt'] for i in leaf_ids], dtype=np.int64)
+    leaf_sq = np.array([ev[i]['tot'] for i in leaf_ids]).reshape(len(leaf_ids), 2 * D)
+    return dict(node_cand=np.array(cand, dtype=np.int32), node_child=np.array(child, dtype=np.int32).reshape(N, 2), node_state=state,
+                node_n=np.array([ev[i]['nt'] for i in range(N)], dtype=np.int64), split_gain=np.array(gains, dtype=np.float64), row_state=row_state,
+                leaf_n=leaf_n, leaf_s=leaf_sq[:, :D].copy(), leaf_q=leaf_sq[:, D:].copy(), decisions=decisions,
+                gain_B=np.array([d['B'] for d in decisions if d['kind'] == 'split']))
+
+
+def seed_model(t, var_floor):
+    """The (J_t, 1, D) model of the install: mean = s / n, var = max(q / n - m m, var_floor), weight 1"""
+    nn = t['leaf_n'].astype(np.float64)[:, None]
+    m = t['leaf_s'] / nn
+    v = np.maximum(t['leaf_q'] / nn - m * m, var_floor)
+    return m[:, None, :], v[:, None, :], np.ones((len(nn), 1))
+
+
+def as_tree(t, P, n_units, event_ctx, q_member, root_of):
+    from poccala_amd.AcousticModel.ContextTree import Tree
+    return Tree(P, n_units, event_ctx=event_ctx, q_member=q_member, root_of=root_of, **{f: t[f] for f in Tree.FIELDS if f in t})
