@@ -99,6 +99,110 @@ def build_cases():
     return c
 
 
+BIG = 2 ** 23                                                     # big_counts' factor
+
+
+def _mirror(case, src=0, dst=1):
+    """The rows of centre dst become bit-identical copies of centre src's (same left and right neighbour, same position): with separate
+    roots the two centres' roots hold equal rows in equal order, and every question about a neighbour splits them alike."""
+    ev, P = case['event_ctx'], case['P']
+    at = {tuple(e): i for i, e in enumerate(ev.tolist())}
+    for i, (l, c, r) in enumerate(ev.tolist()):
+        if c == dst:
+            j = at[(l, src, r)]
+            for k in ('n', 's', 'q'):
+                case[k][i * P:(i + 1) * P] = case[k][j * P:(j + 1) * P]
+    return case
+
+
+def edge_cases():
+    """name -> case: the build's edges (tests/test_gpu_tree_edges.py runs them, tests/test_tree_twin.py holds them to the separation
+    condition like the others).  The seeds were chosen on the CPU so that the condition holds; the twin alone decides that."""
+    c = {}
+    # the evaluation kernel gives a lane to each column of [s | q]: D = 64 fills all 128, D = 1 leaves 2 columns for 17 sums, D = 39 is the
+    # front-end's width.  d14 / d40 / d49 are the first widths behind a device width (13, 39, 48): the install pads them to 26, 47 and 64.
+    c['wide64'] = make(21, n_units=3, P=2, D=64, max_leaves=6 + 4)
+    c['d1'] = make(22, n_units=3, P=1, D=1, max_leaves=3 + 4)
+    c['d39'] = make(23, n_units=3, P=2, D=39, max_leaves=6 + 4)
+    c['d14'] = make(24, n_units=3, P=1, D=14, max_leaves=3 + 4)
+    c['d40'] = make(25, n_units=3, P=2, D=40, max_leaves=6 + 3)
+    c['d49'] = make(26, n_units=3, P=1, D=49, max_leaves=3 + 4)
+    # 24 candidates: exactly three groups of 8, no ragged last group
+    c['q8_full_groups'] = make(27, shared_root=True, centre_shift=2.0, sets=[{0}, {1}, {2}, {3}, {4}, {0, 1}, {1, 2, 4}, {0, 3}], max_leaves=2 + 14)
+    # set 8 = set 0 and set 7 = the complement of set 1: of one position, candidates c and c + 8 (the duplicate) lie in adjacent groups,
+    # and so do c + 1 and c + 7 (the complement) for the centre and the right neighbour.  The later group's equal gain must not win.
+    c['dup_across_groups'] = make(28, shared_root=True, centre_shift=4.0, sets=[{1, 2, 4}, {0, 1}, {0}, {1}, {3}, {4}, {2}, {2, 3, 4}, {1, 2, 4}],
+                                  max_leaves=2 + 10)
+    # the largest Q the build accepts: 4095 candidates in 512 groups, the last one ragged; 7 symbols, so most sets come many times
+    c['q1365'] = make(29, n_units=6, P=1, D=2, sets=_rand_sets(32, 1365, 6), keep=np.arange(0, 294, 12), shared_root=True, max_leaves=1 + 3)
+    # centres 0 and 1 hold bit-identical rows under separate roots: their bests tie exactly, the lowest node id goes first.  Built to an
+    # odd and to an even number of leaves, so that one of the two stops between a leaf and its mirror image.
+    c['mirror_roots_even'] = _mirror(make(30, n_units=3, P=1, max_leaves=3 + 5))
+    c['mirror_roots_odd'] = _mirror(make(30, n_units=3, P=1, max_leaves=3 + 6))
+    # counts beyond 32 bits: 'min_count' with n, s, q and min_count times 2^23.  A power of two scales every sum, every n and every
+    # likelihood exactly (s / n and q / n keep their bits, L = -0.5 n (...) and the gains scale by 2^23 without a rounding), so the
+    # twin's decisions, their sep and thr are those of 'min_count', and the case is separated because that one is.  The root holds
+    # 1232 frames there: 2^20 would leave every count below 2^32; 2^23 puts the root at 1.0e10, both children beyond 2^32 and min_count
+    # (3.4e9) beyond 2^31, so that a count or a threshold cut to 32 bits anywhere changes the tree.
+    base = build_cases()['min_count']
+    c['big_counts'] = dict(base, n=base['n'] * BIG, s=base['s'] * float(BIG), q=base['q'] * float(BIG), min_count=base['min_count'] * BIG)
+    return c
+
+
+# ------------------------------------------------------------------ statistics at the kernels' edges
+DEVICE_DIMS = (13, 26, 39, 47, 48, 64)                            # the row strides the device holds a frame matrix at (pcl_api.hip, device_dim)
+WIDTH_DIMS = (1, 12, 13, 14, 26, 27, 37, 39, 40, 45, 47, 48, 49, 63, 64)
+
+
+def tail_load_dims(G):
+    """The widths D at which tree_partial_kernel's element-by-element load runs for the LAST frame row: lane g loads the G columns from
+    d0 = G g when d0 < D, in one piece iff (F - 1) FD + d0 + G <= F FD, that is d0 + G <= FD, FD the device width of D."""
+    out = []
+    for D in range(1, 65):
+        FD = min(x for x in DEVICE_DIMS if x >= D)
+        if any(d0 + G > FD for d0 in range(0, D, G)):
+            out.append(D)
+    return out
+
+
+def order_case(D=13):
+    """Gaussian frames whose sums tell one summation order from another: F = 2 * 2048 + 37 rows (three tiles of the counting sort), R = 9,
+    two utterances that cover frame rows 0 and F - 1 with a gap between them (whose rows name a statistics row and must not count), the
+    rows on either side of both tile edges in the same statistics row, row 0 with more than half of the frames, some rows -1."""
+    rng = np.random.default_rng(2048)
+    F, R = 2 * 2048 + 37, 9
+    frames = rng.standard_normal((F, D)) * 3 + 1
+    T, begin = np.array([2100, F - 2150], dtype=np.int32), np.array([0, 2150], dtype=np.int64)
+    frame_row = rng.integers(-1, R, size=F).astype(np.int32)
+    frame_row[rng.integers(0, F, size=F)] = 0
+    frame_row[[2047, 2048]] = 3
+    frame_row[[4095, 4096]] = 5
+    frame_row[0], frame_row[F - 1] = 7, 8
+    return frames, T, begin, frame_row, R
+
+
+def width_case(D):
+    """Grid frames, F = 64, one utterance over all of them; the last two frame rows are kept and go to different statistics rows"""
+    rng = np.random.default_rng(300 + D)
+    F, R = 64, 7
+    frames = np.clip(np.round(rng.standard_normal((F, D)) * 2 * GRID) / GRID, -7.984375, 7.984375)
+    frame_row = rng.integers(-1, R, size=F).astype(np.int32)
+    frame_row[F - 2], frame_row[F - 1] = 2, 5
+    return frames, np.array([F], dtype=np.int32), np.array([0], dtype=np.int64), frame_row, R
+
+
+def long_case(T):
+    """Grid frames at D = 2, one utterance of T frames from frame row 3 on, R = 5; the frames t = 16382 .. 16386 of the utterance (the
+    key kernel's grid is 64 x 256 = 16384 threads an utterance: t = 16384 is the first frame of its second step) go to distinct rows."""
+    rng = np.random.default_rng(400 + T % 1000)
+    F, R, D, b = T + 5, 5, 2, 3
+    frames = np.clip(np.round(rng.standard_normal((F, D)) * 2 * GRID) / GRID, -7.984375, 7.984375)
+    frame_row = rng.integers(-1, R, size=F).astype(np.int32)
+    t = np.arange(16382, min(16387, T))
+    frame_row[b + t] = t % R
+    return frames, np.array([T], dtype=np.int32), np.array([b], dtype=np.int64), frame_row, R
+
+
 def frames_case(D, seed=0):
     """Grid frames for the exact statistics tests under PCL_TREE_CHUNK=4: R = 65 rows; rows 0..5 hold 0, 1, 3, 4, 5 and 9 frames (chunk - 1,
     chunk, chunk + 1, two chunks and one), the rest share what is left; some frames map to -1; rows in front of, between and behind the

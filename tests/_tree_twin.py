@@ -6,10 +6,14 @@ side leaves the bits, so the masked walk below IS that sum); L = -0.5 n (D c + s
 double 2.8378770664093453.  Every decision is recorded with what the GPU tests need to know that it can be compared: the winner's gain,
 B = 0.5 sum over (yes, no, leaf) of n (D c + sum_d |ln v_d|), the best gain among the valid candidates of a DIFFERENT partition
 (another leaf, or another unordered {yes, no} of the same leaf -- a candidate of the same partition has the winner's gain bit for bit on
-either side, and the tie rules decide), and the smallest |gain - min_gain| / B over the count-valid candidates."""
+either side, and the tie rules decide), and the smallest |gain - min_gain| / B over the count-valid candidates.  A candidate of ANOTHER
+leaf is the same partition too when that leaf's rows are bit-identical copies of the winner's, in the same order, and answer alike:
+xleaf_ties counts those, later_group_ties the equals of the winner's own leaf that sit in a later group of GROUP candidates.
+accumulate is the sequential sum and the bounds' |x| sums; accumulate_ordered is the order the device is held to bit for bit."""
 import numpy as np
 
 C1 = 2.8378770664093453
+GROUP = 8                                                         # candidates per evaluation workgroup (csrc/tree_cluster.hip, CG)
 
 
 def zero(R, D):
@@ -31,6 +35,54 @@ def accumulate(st, frames, T, begin, frame_row):
         out['q'][r] = np.cumsum(np.vstack([out['q'][r][None], x * x]), axis=0)[-1]
         out['sabs'][r] += np.abs(x).sum(axis=0)
         out['qabs'][r] += (x * x).sum(axis=0)
+    return out
+
+
+def _exact_fma(a, x):
+    """fl(a + x x) with ONE rounding, entry by entry: what a contracted multiply-add would give (the order tests' own sanity check)"""
+    from fractions import Fraction
+    return np.array([float(Fraction(float(ai)) + Fraction(float(xi)) * Fraction(float(xi))) for ai, xi in zip(a, x)])
+
+
+def accumulate_ordered(st, frames, T, begin, frame_row, chunk, wrong=None):
+    """The header's order (include/poccala_hip.h, ACCUMULATE, "Order:"), literally: per statistics row the kept frame rows in ascending
+    order, cut into runs of `chunk`; a run's s and q are sequential float64 sums from +0.0 in ascending frame row, x x formed (and
+    rounded) first; the runs' sums are added one by one, in run order, onto the value in st.  float32 frames are widened first.
+    Returns n, s, q (a dict, so that a second call can go on from it).
+    wrong: None, or one of the orders the device must NOT compute -- the CPU tests use them to show that an input tells the orders
+    apart: 'runs_reversed' (the runs added onto st last first), 'frames_reversed' (a run summed in descending frame row), 'unstable'
+    (a row's kept frames swapped pair by pair before the cut, as a scatter that ranks equal keys the wrong way round would leave
+    them), 'fused' (q + x x rounded once)."""
+    frames = np.asarray(frames)
+    frame_row = np.asarray(frame_row)
+    chunk = int(chunk)
+    assert chunk >= 1 and wrong in (None, 'runs_reversed', 'frames_reversed', 'unstable', 'fused')
+    inside = np.zeros(frames.shape[0], dtype=bool)
+    for t, b in zip(T, begin):
+        inside[int(b):int(b) + int(t)] = True
+    out = {k: np.array(st[k], copy=True) for k in ('n', 's', 'q')}
+    D = frames.shape[1]
+    for r in np.unique(frame_row[inside & (frame_row >= 0)]):
+        idx = np.flatnonzero(inside & (frame_row == r))            # ascending: the stable sort's order
+        if wrong == 'unstable':
+            m = len(idx) // 2 * 2
+            idx[:m] = idx[:m].reshape(-1, 2)[:, ::-1].reshape(-1)
+        runs = [idx[a:a + chunk] for a in range(0, len(idx), chunk)]
+        parts = []
+        for run in runs:
+            x = frames[run[::-1] if wrong == 'frames_reversed' else run].astype(np.float64)
+            s = np.cumsum(np.vstack([np.zeros((1, D)), x]), axis=0)[-1]
+            if wrong == 'fused':
+                q = np.zeros(D)
+                for row in x:
+                    q = _exact_fma(q, row)
+            else:
+                q = np.cumsum(np.vstack([np.zeros((1, D)), x * x]), axis=0)[-1]
+            parts.append((s, q))
+        out['n'][r] += len(idx)
+        for s, q in (parts[::-1] if wrong == 'runs_reversed' else parts):
+            out['s'][r] = out['s'][r] + s
+            out['q'][r] = out['q'][r] + q
     return out
 
 
@@ -78,7 +130,11 @@ def _eval_leaf(rows, n, X, ans, min_count, var_floor):
     for c in range(NC):
         a = A[c].tobytes()
         keys.append(min(a, (~A[c]).tobytes()))
-    return dict(gain=gain, B=0.5 * (By + Bn + Bl[0]), cv=(cy >= min_count) & (cn >= min_count), cy=cy, cn=cn, nt=nt, tot=tot[0], keys=keys)
+    # what the leaf's sums are made of, in order: the rows' (n, s, q) bit for bit -- two leaves of equal sig whose candidates give equal
+    # keys walk the same additions, on the device too
+    rows = np.asarray(rows, dtype=np.int64)
+    sig = (len(rows), np.ascontiguousarray(n[rows]).tobytes(), np.ascontiguousarray(X[rows]).tobytes())
+    return dict(gain=gain, B=0.5 * (By + Bn + Bl[0]), cv=(cy >= min_count) & (cn >= min_count), cy=cy, cn=cn, nt=nt, tot=tot[0], keys=keys, sig=sig)
 
 
 def build(n, s, q, event_ctx, P, n_units, q_member, R0, root_of, min_count=1, min_gain=0.0, max_leaves=None, var_floor=1e-4):
@@ -109,11 +165,18 @@ def build(n, s, q, event_ctx, P, n_units, q_member, R0, root_of, min_count=1, mi
             break
         best = max(pool, key=lambda x: (x[0], -x[1], -x[2]))
         g, p, c = best
-        key = ev[p]['keys'][c]
-        others = [x[0] for x in pool if not (x[1] == p and ev[p]['keys'][x[2]] == key)]
+        key, sig = ev[p]['keys'][c], ev[p]['sig']
+        # the same decision: the winner's partition asked of the winner's leaf, or of ANOTHER leaf whose rows are bit-identical copies
+        # in the same order (then every sum, likelihood and gain is the winner's bit for bit, and the tie rules decide)
+        same = [x for x in pool if ev[x[1]]['keys'][x[2]] == key and (x[1] == p or ev[x[1]]['sig'] == sig)]
+        assert all(x[0] == g for x in same)
+        same_ids = {(x[1], x[2]) for x in same}
+        others = [x[0] for x in pool if (x[1], x[2]) not in same_ids]
         other = max(others) if others else -np.inf
         B = float(ev[p]['B'][c])
-        decisions.append(dict(kind='split', node=p, cand=c, gain=g, B=B, other=other, sep=(g - other) / B if B > 0 else np.inf, thr=thr))
+        decisions.append(dict(kind='split', node=p, cand=c, gain=g, B=B, other=other, sep=(g - other) / B if B > 0 else np.inf, thr=thr,
+                              xleaf_ties=sum(1 for x in same if x[1] != p),
+                              later_group_ties=sum(1 for x in same if x[1] == p and x[2] // GROUP > c // GROUP)))
         A = ans[c, rows_of[p]]
         id_no = len(cand)
         cand[p], child[p] = c, [id_no, id_no + 1]

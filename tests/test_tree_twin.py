@@ -2,7 +2,9 @@
 poccala_amd/AcousticModel/ContextTree.py, make_sentence_batch's unit_state_ids argument, the C-ABI names, and -- for every build case
 tests/test_gpu_tree.py runs -- the separation condition: at every decision every candidate of a different partition lies at least
 1e-9 B below the winner, and no count-valid candidate lies within 1e-9 B of min_gain.  A case that is not separated FAILS here: no
-decision is left uncompared on the device."""
+decision is left uncompared on the device.  The same for the cases of tests/test_gpu_tree_edges.py, and that each of them reaches the
+edge it is named after: an equal candidate in a later group, leaves that tie exactly, counts beyond 2^32, the widths at which the
+statistics kernel loads a frame's tail element by element, and an input whose sums tell the stated summation order from others."""
 import os
 
 import numpy as np
@@ -12,7 +14,8 @@ import _tree_cases as tc
 import _tree_twin as tw
 
 SEP = 1e-9
-CASES = tc.build_cases()
+EDGE = tc.edge_cases()                                            # tests/test_gpu_tree_edges.py runs these
+CASES = dict(tc.build_cases(), **EDGE)
 _BUILT = {}
 
 
@@ -99,6 +102,129 @@ def test_edge_cases_do_what_their_names_say():
     assert behind == {1, 2, 4, 6}
     assert all(cnd % Qd not in behind for cnd in d['node_cand'] if cnd >= 0)
     assert CASES['q1']['q_member'].shape[0] == 1 and CASES['q65']['q_member'].shape[0] == 65 and CASES['one_unit']['n_units'] == 1
+
+
+def test_edge_build_cases_reach_their_edges():
+    for name, D in (('wide64', 64), ('d1', 1), ('d39', 39), ('d14', 14), ('d40', 40), ('d49', 49)):
+        c = EDGE[name]
+        assert c['D'] == D and c['n_units'] == 3 and c['P'] in (1, 2) and c['max_leaves'] <= c['R0'] + 4 and len(built(name)['split_gain']) >= 3
+    assert 3 * EDGE['q8_full_groups']['q_member'].shape[0] == 3 * tw.GROUP                 # three full groups
+    assert {cnd // tw.GROUP for cnd in built('q8_full_groups')['node_cand'] if cnd >= 0} >= {0, 1}
+    # duplicate and complement one group apart: a winner with an equal in a LATER group, of either kind
+    cd = EDGE['dup_across_groups']
+    qd = cd['q_member'] != 0
+    assert len(qd) == 9 and (qd[8] == qd[0]).all() and (qd[7] != qd[1]).all()
+    later = [d for d in built('dup_across_groups')['decisions'] if d['kind'] == 'split' and d['later_group_ties'] > 0]
+    print('dup_across_groups: winners with an equal in a later group: %s' % [d['cand'] for d in later])
+    assert {d['cand'] % 9 for d in later} >= {0, 1}                                          # set 0's duplicate, set 1's complement
+    assert all(d['cand'] % 9 not in (7, 8) for d in built('dup_across_groups')['decisions'] if d['kind'] == 'split')
+    cq = EDGE['q1365']
+    assert cq['q_member'].shape == (1365, 7) and 22 <= len(cq['event_ctx']) <= 26 and cq['max_leaves'] == cq['R0'] + 3
+    assert len(built('q1365')['split_gain']) == 3 and any(d['later_group_ties'] > 0 for d in built('q1365')['decisions'])
+    # mirrored centres: exact ties between leaves, at the roots and after the first split; one of the two builds stops inside a tie
+    last = []
+    for name in ('mirror_roots_even', 'mirror_roots_odd'):
+        c, t = EDGE[name], built(name)
+        ev, P = c['event_ctx'], c['P']
+        r0, r1 = np.flatnonzero(ev[:, 1] == 0), np.flatnonzero(ev[:, 1] == 1)
+        assert c['root_of'][0] != c['root_of'][P] and all(c[k][r0].tobytes() == c[k][r1].tobytes() for k in ('n', 's', 'q'))
+        ties = [i for i, d in enumerate(t['decisions']) if d['kind'] == 'split' and d['xleaf_ties'] > 0]
+        print('%s: decisions with an equal in another leaf: %s' % (name, ties))
+        assert len(ties) >= 2 and max(ties) > 0                   # behind the first split the leaves are no longer listed in node order
+        for i in ties:                                            # the lowest node id won
+            d = t['decisions'][i]
+            assert all(t['decisions'][k]['node'] > d['node'] for k in range(i + 1, len(t['decisions'])) if t['decisions'][k].get('gain') == d['gain'])
+        last.append(t['decisions'][-1]['xleaf_ties'])
+    assert EDGE['mirror_roots_even']['max_leaves'] % 2 == 0 and EDGE['mirror_roots_odd']['max_leaves'] % 2 == 1
+    assert min(last) == 0 < max(last)                             # one stops between a leaf and its mirror image, the other behind both
+    # big_counts IS min_count times 2^23: the same decisions, sep and thr to the bit, the gains scaled exactly, counts beyond 2^32
+    b, m, cb = built('big_counts'), built('min_count'), EDGE['big_counts']
+    assert b['node_n'].max() > 2 ** 32 and cb['min_count'] > 2 ** 31 and np.array_equal(b['node_n'], m['node_n'] * tc.BIG)
+    assert np.array_equal(b['node_cand'], m['node_cand']) and np.array_equal(b['split_gain'], m['split_gain'] * tc.BIG)
+    assert len(b['decisions']) == len(m['decisions'])
+    for x, y in zip(b['decisions'], m['decisions']):
+        assert x['thr'] == y['thr'] and x.get('sep') == y.get('sep') and x.get('cand') == y.get('cand')
+
+
+def test_ordered_twin_is_the_sequential_one_where_orders_agree():
+    """accumulate_ordered against accumulate: bit for bit on the grid (every order is exact there), within accumulate's first-order bound
+    (n - 1) 2^-53 sum |x| on Gaussian frames, for several chunk lengths and over two calls."""
+    frames, T, begin, frame_row, R = tc.frames_case(13)
+    st = tw.accumulate(tw.zero(R, 13), frames, T, begin, frame_row)
+    for chunk in (1, 4, 7, 256):
+        o = tw.accumulate_ordered(tw.zero(R, 13), frames, T, begin, frame_row, chunk)
+        two = tw.accumulate_ordered(tw.accumulate_ordered(tw.zero(R, 13), frames, T[:2], begin[:2], frame_row, chunk), frames, T[2:], begin[2:], frame_row, chunk)
+        for k in ('n', 's', 'q'):
+            assert o[k].dtype == st[k].dtype and o[k].tobytes() == st[k].tobytes() == two[k].tobytes(), (chunk, k)
+    o32 = tw.accumulate_ordered(tw.zero(R, 13), frames.astype(np.float32), T, begin, frame_row, 4)      # widened first
+    assert all(o32[k].tobytes() == st[k].tobytes() for k in ('n', 's', 'q'))
+    frames, T, begin, frame_row, R = tc.order_case()
+    D = frames.shape[1]
+    st = tw.accumulate(tw.zero(R, D), frames, T, begin, frame_row)
+    for chunk in (1, 7, 256):
+        o = tw.accumulate_ordered(tw.zero(R, D), frames, T, begin, frame_row, chunk)
+        assert np.array_equal(o['n'], st['n'])
+        for k in ('s', 'q'):
+            bound = np.maximum(st['n'] - 1, 0)[:, None] * 2.0 ** -53 * st[k + 'abs']
+            worst = float(np.max(np.abs(o[k] - st[k]) / bound))
+            print('ordered twin, chunk %d: %s worst difference / bound = %.3e, %d entries differ' % (chunk, k, worst, (o[k] != st[k]).sum()))
+            assert worst <= 1.0
+
+
+def test_order_case_tells_the_orders_apart():
+    """The input of the GPU order test (tests/test_gpu_tree_edges.py) has what the issue asks of it, and its sums DO depend on the order:
+    every wrong order differs from the stated one in at least one byte, in float64 and in float32, at every chunk length the GPU test
+    runs.  Entries of q that differ out of 117, chunk 7, float64 / float32 input: runs added last first 77 / 83, a run summed in
+    descending frame row 44 / 11, a row's frames swapped pair by pair (a scatter that is not stable) 83 / 68, q + x x rounded once (a
+    contracted multiply-add) 19 / none: a float32 value's square is exact in float64, so only float64 frames can show a contraction,
+    and float32 values' plain sums are exact in any order here, so for them only q tells the orders apart."""
+    frames, T, begin, frame_row, R = tc.order_case()
+    F, D = frames.shape
+    assert F == 2 * 2048 + 37 and R == 9 and len(T) == 2
+    assert begin[0] == 0 and begin[1] + T[1] == F and begin[0] + T[0] < begin[1]             # rows 0 and F - 1 are inside, a gap between
+    assert frame_row[2047] == frame_row[2048] >= 0 and frame_row[4095] == frame_row[4096] >= 0
+    assert frame_row[0] >= 0 and frame_row[F - 1] >= 0 and (frame_row[begin[0] + T[0]:begin[1]] >= 0).any() and (frame_row == -1).any()
+    right = tw.accumulate_ordered(tw.zero(R, D), frames, T, begin, frame_row, 7)
+    assert right['n'][0] > F // 2 and (right['n'] > 0).all()
+    for fr, kind in ((frames, 'f64'), (frames.astype(np.float32), 'f32')):
+        for chunk in (1, 7, 256):
+            ok = tw.accumulate_ordered(tw.zero(R, D), fr, T, begin, frame_row, chunk)
+            # (at chunk 1 a run holds one frame: nothing inside it to reverse)
+            for wrong in ('runs_reversed', 'unstable', 'fused') + (('frames_reversed',) if chunk > 1 else ()):
+                if wrong == 'fused' and (kind, chunk) != ('f64', 7):
+                    continue                                      # (the exact multiply-add runs entry by entry in Python: once)
+                bad = tw.accumulate_ordered(tw.zero(R, D), fr, T, begin, frame_row, chunk, wrong=wrong)
+                ds, dq = int((bad['s'] != ok['s']).sum()), int((bad['q'] != ok['q']).sum())
+                print('order case %s chunk %d, %s: s differs in %d, q in %d of %d entries' % (kind, chunk, wrong, ds, dq, ok['q'].size))
+                # (float32 frames widened: 24-bit values, whose sums over a few thousand frames are exact in any order and whose squares
+                # are exact products -- there only q tells the orders apart, and a contracted multiply-add shows in float64 frames alone)
+                assert np.array_equal(bad['n'], ok['n']) and dq > 0 and (ds > 0 or wrong == 'fused' or kind == 'f32')
+    # chunk lengths give different sums too: the knob is not a no-op on this input
+    assert right['s'].tobytes() != tw.accumulate_ordered(tw.zero(R, D), frames, T, begin, frame_row, 256)['s'].tobytes()
+
+
+def test_statistics_edge_cases_reach_their_edges():
+    """The widths at which the statistics kernel's element-by-element load runs (csrc/tree_cluster.hip, tree_partial_kernel): lane g
+    loads the G columns from d0 = G g (d0 < D) of frame row f in one piece iff f FD + d0 + G <= F FD; for the last row that is
+    d0 + G <= FD, FD the device width.  float32 (G = 4): FD = 13 has d0 = 12 (D = 13), FD = 26 has d0 = 24 (D = 25, 26), FD = 39 has
+    d0 = 36 (D = 37 .. 39), FD = 47 has d0 = 44 (D = 45 .. 47); 48 and 64 are multiples of 4.  float64 (G = 2): the odd widths, d0 = FD - 1:
+    D = 13, 39, 47."""
+    assert tc.tail_load_dims(4) == [13, 25, 26, 37, 38, 39, 45, 46, 47] and tc.tail_load_dims(2) == [13, 39, 47]
+    assert [d for d in tc.WIDTH_DIMS if d in tc.tail_load_dims(4)] == [13, 26, 37, 39, 45, 47]
+    assert [d for d in tc.WIDTH_DIMS if d in tc.tail_load_dims(2)] == [13, 39, 47]
+    assert {min(x for x in tc.DEVICE_DIMS if x >= d) for d in tc.WIDTH_DIMS} == set(tc.DEVICE_DIMS)
+    api = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'poccala_amd', 'csrc', 'pcl_api.hip')).read()
+    assert 'const int pipe[] = {13, 26, 39, 47};' in api and 'const int opts[] = {48, 64};' in api
+    for D in tc.WIDTH_DIMS:
+        frames, T, begin, frame_row, R = tc.width_case(D)
+        F = len(frames)
+        assert F == 64 and T.tolist() == [F] and begin.tolist() == [0] and 0 <= frame_row[F - 1] != frame_row[F - 2] >= 0
+        assert np.array_equal(frames.astype(np.float32).astype(np.float64), frames)
+    for T in (16384, 16385, 40000):
+        frames, Tu, begin, frame_row, R = tc.long_case(T)
+        assert Tu.tolist() == [T] and frames.shape == (T + 5, 2) and R == 5
+        around = frame_row[begin[0] + np.arange(16382, min(16387, T))]
+        assert len(set(around.tolist())) == len(around) and (around >= 0).all()
 
 
 def test_twin_statistics_are_additive_and_sequential():
