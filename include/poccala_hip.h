@@ -864,6 +864,56 @@ int pcl_tree_build(pcl_ctx *ctx, int E, int P, const int32_t *event_ctx /* E*3 *
                    int flags, int32_t *node_cand, int32_t *node_child, int32_t *node_state, int64_t *node_n, double *split_gain,
                    int32_t *row_state, int64_t *leaf_n, double *leaf_s, double *leaf_q, int32_t *n_nodes_out, int32_t *n_states_out);
 
+/* ----------------------------------------------------------------- resident tying, label-built batches over tied states (row f17)
+ * The second half of monophone -> context-dependent (csrc/tying.hip): the trees of a build stay on the device, one kernel maps every label
+ * position of a corpus to its tied states, and the batch made from them is a label-built batch for every entry point that asks for one.
+ * Not in the reference; tests/_tied_twin.py is the NumPy twin.  Integer work only: equal inputs give equal bytes.
+ *
+ * TYING.  pcl_tying_upload takes the arrays a build returned, with the meaning of the tree section above: q_member (Q, n_units + 1) uint8,
+ * candidate c = pos Q + qi, n_units = the utterance-edge symbol; node_cand (N,), node_child (N, 2) = (no, yes), node_state (N,); the nodes
+ * 0 .. R0 - 1 are the roots, root_of (n_units P,) maps (centre, k) to its root; J_t tied states.  Checked, in this order, before anything
+ * resident changes (PCL_ERR_INVALID unless stated): a unit inventory is resident (PCL_ERR_STATE); P = S - 2 of the inventory; n_units is the
+ * inventory's; 1 <= Q, 3 Q <= 4096; 1 <= R0 <= N; 1 <= J_t <= N; per node in ascending id -- a leaf (cand = -1) has children (-1, -1) and a
+ * state in [0, J_t) no earlier leaf names; an inner node has 0 <= cand < 3 Q, both children in (node, N) and state -1 -- the leaves number J_t;
+ * root_of in [0, R0).  pcl_tree_build creates children after their parent, so a built tree passes, and a walk, which only ever moves to a
+ * larger node id, ends.  The upload REPLACES a resident tying as a whole; pcl_tying_drop removes it (no refusal when there is none);
+ * pcl_destroy and a pcl_units_upload of another (n_units, S) free it too.  On the device: one 16-byte record (cand, no, yes, state) per node
+ * in global memory -- a step of a walk is one load -- and q_member as a bit table of ceil((n_units + 1) / 32) words per question, staged in
+ * LDS by every workgroup when it is at most 16 KiB.
+ *
+ * WALK of (left, centre, right) at state position k: node = root_of[centre P + k]; while node_cand[node] = c >= 0: pos = c / Q, qi = c mod Q,
+ * node = node_child[node][q_member[qi][context[pos]]]; the result is node_state[node].  ContextTree.Tree.lookup is the same walk.
+ * pcl_tying_lookup: ctx3 (n, 3) int32 contexts, seen in training or not -> state_out (n, P) int32.  PCL_ERR_STATE without a resident
+ * tying; PCL_ERR_INVALID for n < 1, a centre outside [0, n_units) or a neighbour outside [0, n_units], before anything runs.
+ *
+ * BATCH.  pcl_batch_create_labels_tied: the arguments, the N_u = P L_u + 2 rows, the banded transitions of the centre units, the uniform
+ * pi and the unit -> occurrence lists of pcl_batch_create_labels, and its refusals under its own name; PCL_ERR_STATE without a resident
+ * tying, for a tying of another inventory shape, or when the model's J is not the tying's J_t.  Label position i of utterance u has the context
+ * (labels[i - 1], labels[i], labels[i + 1]) with n_units in place of a neighbour beyond either end (ContextTree.triphone_events); one
+ * workgroup per utterance, its lanes striding the (i, k) pairs, walks once per pair and writes pos_state (sum L, P) and the row -> state
+ * map: entry row, row 1 + i P + k -> pos_state[i][k], exit row.  pos_state stays with the batch: a later pcl_tying_upload or
+ * pcl_tying_drop does not change a batch that exists.  The map comes back to the host once (sum N int32) for the scoring work lists.
+ *
+ * LABEL-BASED CALLS on a tied batch.  Where pcl_batch_align_segments and the calls that share its checks demand J = n_units (S - 2) of a
+ * monophone batch, they demand J = the batch's J_t of a tied one (PCL_ERR_INVALID); every other check is unchanged.
+ * pcl_batch_align_segments: the owner of a kept frame t is pos_state[i(t)][k(t)], i(t) = the label position of the frame's path row by the
+ * rule of pcl_batch_accumulate_tree above, k(t) = the slice the monophone owner map gives the same labels and path (runs of equal units,
+ * adjacent equal units merged); the drop rule is unchanged; the pcl_seg holds J_t lists.  pcl_batch_accumulate_lda: the class of a frame is
+ * that owner, or state_class[owner] (J_t entries).  pcl_batch_accumulate_tree: rows label_event[i(t)] P + k(t), as for a monophone batch.
+ * pcl_batch_accumulate_hmm, pcl_mstep_transitions, pcl_batch_refresh_transitions: transitions are per centre unit, the calls do on a tied
+ * batch what they do on a monophone one; the refresh refuses (PCL_ERR_STATE) when J is no longer the batch's J_t or the inventory no
+ * longer fits the batch's labels and rows.
+ * pcl_batch_get_states: the device copies of a batch's row -> state map (row_state, sum N int32; any batch that has one) and of a tied
+ * batch's pos_state (sum L * P int32; PCL_ERR_STATE for any other batch); NULLs are skipped.
+ * pcl_kernel_time groups: "tying" (the batch's walks), "tying_lookup", "tying_owner".  Synchronous. */
+int pcl_tying_upload(pcl_ctx *ctx, int n_units, int P, int Q, const uint8_t *q_member /* Q*(n_units+1) */, int N, const int32_t *node_cand /* N */,
+                     const int32_t *node_child /* N*2 */, const int32_t *node_state /* N */, int R0, const int32_t *root_of /* n_units*P */, int J_t);
+int pcl_tying_drop(pcl_ctx *ctx);
+int pcl_tying_lookup(pcl_ctx *ctx, int n, const int32_t *ctx3 /* n*3 */, int32_t *state_out /* n*P */);
+int pcl_batch_get_states(pcl_batch *b, int32_t *row_state /* sum N or NULL */, int32_t *pos_state /* sum L * P or NULL */);
+int pcl_batch_create_labels_tied(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T,
+                                 const int64_t *frame_begin, const double *logpi, pcl_batch **out);
+
 /* Numerical guard of the f32 matrix-core path.  The MFMA kernels evaluate the Gaussian exponent in a form expanded
  * around a per-state centre c_j; its f32 rounding error grows with cond[j] = max_m log2(e) * sum_d (mu_jmd - c_jd)^2 /
  * (2 var_jmd) (about 5e-7 * cond nats).  States with cond[j] > *cond_max (default 96, env PCL_MFMA_COND_MAX) are scored

@@ -79,6 +79,18 @@ class Tree(object):
                 out[i, k] = self.lookup(left, c, right, k)
         return out
 
+    @property
+    def n_roots(self):
+        """R0: the nodes 0 .. R0 - 1 are the roots (every root has a (centre, k) that maps to it)."""
+        return int(self.root_of.max()) + 1
+
+    def tying_arrays(self):
+        """What Engine.load_tying hands to pcl_tying_upload, C-contiguous: (q_member uint8 (Q, n_units + 1), node_cand, node_child (N, 2),
+        node_state, root_of int32)."""
+        return (np.ascontiguousarray(self.q_member, dtype=np.uint8), np.ascontiguousarray(self.node_cand, dtype=np.int32),
+                np.ascontiguousarray(self.node_child, dtype=np.int32).reshape(-1, 2), np.ascontiguousarray(self.node_state, dtype=np.int32),
+                np.ascontiguousarray(self.root_of, dtype=np.int32).reshape(-1))
+
     def save(self, path):
         """One .npz holding arrays only."""
         np.savez(path, P=np.int64(self.P), n_units=np.int64(self.n_units), **{f: getattr(self, f) for f in self.FIELDS})

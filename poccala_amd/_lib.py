@@ -101,6 +101,11 @@ PROTOTYPES = {
     'pcl_tree_stats_upload': (_i, [_vp, _vp, _vp, _vp]),
     'pcl_tree_build': (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, C.c_int64, _d, _i, _d, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp, _vp]),
+    'pcl_tying_upload': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i]),
+    'pcl_tying_drop': (_i, [_vp]),
+    'pcl_tying_lookup': (_i, [_vp, _i, _vp, _vp]),
+    'pcl_batch_get_states': (_i, [_vp, _vp, _vp]),
+    'pcl_batch_create_labels_tied': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     'pcl_model_conditioning': (_i, [_vp, _vp, _vp]),
     'pcl_model_split_info': (_i, [_vp, _vp, _vp]),
     'pcl_coarse_counter': (_i, [_vp, _vp, _i]),

@@ -231,6 +231,7 @@ int pcl_units_upload(pcl_ctx *ctx, int n_units, int S, const double *trans, cons
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // an inventory of the same shape keeps a resident pronunciation tree (its unit ids stay valid): only the transitions change
     const bool keep_tree = ctx->lex_nodes && n_units == ctx->n_units && S == ctx->S;
+    if (n_units != ctx->n_units || S != ctx->S) pcl_tying_release(ctx);   // a resident tying names units and state positions of the old inventory
     if (keep_tree) units_free(ctx);
     else pcl_units_release(ctx);
     const size_t n = (size_t)n_units * S * S;
@@ -262,25 +263,36 @@ int pcl_units_download(pcl_ctx *ctx, double *trans) {
     return PCL_OK;
 }
 
-int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T,
-                            const int64_t *frame_begin, const double *logpi, pcl_batch **out) {
+}  // extern "C"
+
+// Both label-built batches: `tied` = over the tied states of the resident tying (pcl_batch_create_labels_tied), else row -> unit * (S-2) + k.
+// They differ in the model they accept and in who fills the row -> state map; the sentence HMMs (build_sentences) and the occurrence lists
+// depend on the centre units only.
+static int create_labels(pcl_ctx *ctx, const char *who, bool tied, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T,
+                         const int64_t *frame_begin, const double *logpi, pcl_batch **out) {
     if (!ctx || !out) return PCL_ERR_INVALID;
     *out = nullptr;
-    if (!ctx->n_units) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_create_labels: pcl_units_upload first");
-    if (ctx->J == 0) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_create_labels: pcl_model_upload first");
+    if (!ctx->n_units) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: pcl_units_upload first", who);
+    if (ctx->J == 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: pcl_model_upload first", who);
     const int S = ctx->S, e = S - 2;
-    if (ctx->J != ctx->n_units * e)
-        PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_create_labels: the model has %d GMM states, %d units x %d emitting states need %d", ctx->J, ctx->n_units, e, ctx->n_units * e);
-    if (U <= 0 || !label_len || !labels || !T || !frame_begin) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels: bad arguments (U=%d)", U);
+    if (tied) {
+        if (!ctx->ty_N) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no resident tying: pcl_tying_upload first", who);
+        if (ctx->ty_P != e || ctx->ty_units != ctx->n_units)
+            PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the resident tying is for %d units x %d state positions, the inventory has %d x %d", who, ctx->ty_units, ctx->ty_P,
+                     ctx->n_units, e);
+        if (ctx->J != ctx->ty_Jt) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the model has %d GMM states, the resident tying %d tied states", who, ctx->J, ctx->ty_Jt);
+    } else if (ctx->J != ctx->n_units * e)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the model has %d GMM states, %d units x %d emitting states need %d", who, ctx->J, ctx->n_units, e, ctx->n_units * e);
+    if (U <= 0 || !label_len || !labels || !T || !frame_begin) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: bad arguments (U=%d)", who, U);
     std::vector<int32_t> N(U);
     size_t tot = 0;
     for (int u = 0; u < U; ++u) {
-        if (label_len[u] < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels: utterance %d has an empty label", u);
+        if (label_len[u] < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has an empty label", who, u);
         N[u] = e * label_len[u] + 2;                               // AcousticModel.py:966
         tot += label_len[u];
     }
     for (size_t i = 0; i < tot; ++i)
-        if (labels[i] < 0 || labels[i] >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels: unit id %d outside [0,%d)", labels[i], ctx->n_units);
+        if (labels[i] < 0 || labels[i] >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: unit id %d outside [0,%d)", who, labels[i], ctx->n_units);
     pcl_batch *b = nullptr;
     TRY(pcl_batch_create(ctx, U, N.data(), T, frame_begin, &b));
     pcl_desc_group uploads(ctx);                                   // every descriptor array below: staged, one wait at the end
@@ -304,7 +316,8 @@ int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const
         row_state[d.vec_off + d.N - 1] = PCL_ROW_EXIT;
         for (int p = 0; p < label_len[u]; ++p) {
             const int unit = labels[lo + p];
-            for (int k = 0; k < e; ++k) row_state[d.vec_off + 1 + p * e + k] = unit * e + k;
+            if (!tied)
+                for (int k = 0; k < e; ++k) row_state[d.vec_off + 1 + p * e + k] = unit * e + k;
             const int q = fillp[unit]++;
             occ_utt[q] = u;
             occ_row0[q] = 1 + p * e;
@@ -313,6 +326,11 @@ int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const
     }
     b->n_occ = (int)tot;
     auto fill = [&]() -> int {                                     // (the batch is the caller's only once all of it has worked)
+        if (tied) {                                                // the walks write the map; it comes back ONCE, for the bookkeeping below
+            TRY(pcl_launch_tied_label_states(ctx, b, row_state.data()));
+            b->tied = true;
+            b->tied_J = ctx->ty_Jt;
+        }
         TRY(pcl_batch_set_states_impl(b, row_state.data()));
         TRY(build_sentences(b));
         TRY(b->occ_ptr.alloc(ctx, occ_ptr.size()));
@@ -346,11 +364,33 @@ int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const
     return PCL_OK;
 }
 
+// has the inventory kept the shape a tied batch's sentences were laid out for?  (a monophone batch: J == n_units (S-2) says so)
+static bool tied_inventory_fits(const pcl_batch *b) {
+    const pcl_ctx *ctx = b->ctx;
+    if (ctx->J != b->tied_J || b->label_max >= ctx->n_units) return false;
+    for (int u = 0; u < b->U; ++u)
+        if (b->utt[u].N != (ctx->S - 2) * b->label_len[u] + 2) return false;
+    return true;
+}
+
+extern "C" {
+
+int pcl_batch_create_labels(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T,
+                            const int64_t *frame_begin, const double *logpi, pcl_batch **out) {
+    return create_labels(ctx, "pcl_batch_create_labels", false, U, label_len, labels, T, frame_begin, logpi, out);
+}
+
+int pcl_batch_create_labels_tied(pcl_ctx *ctx, int U, const int32_t *label_len, const int32_t *labels, const int32_t *T,
+                                 const int64_t *frame_begin, const double *logpi, pcl_batch **out) {
+    return create_labels(ctx, "pcl_batch_create_labels_tied", true, U, label_len, labels, T, frame_begin, logpi, out);
+}
+
 int pcl_batch_refresh_transitions(pcl_batch *b) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
     if (!b->from_labels) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_refresh_transitions: the batch was not created from labels");
-    if (ctx->J != ctx->n_units * (ctx->S - 2) || ctx->J != b->model_J) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_refresh_transitions: the unit inventory changed since the batch was created");
+    if ((b->tied ? !tied_inventory_fits(b) : ctx->J != ctx->n_units * (ctx->S - 2)) || ctx->J != b->model_J)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_refresh_transitions: the unit inventory changed since the batch was created");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));

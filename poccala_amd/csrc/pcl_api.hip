@@ -1203,7 +1203,10 @@ static int align_precheck(pcl_batch *b, const char *who) {
     if (!b->from_labels) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch was not created from labels (pcl_batch_create_labels)", who);
     if (!b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: run pcl_batch_viterbi first", who);
     const int e = ctx->S - 2;
-    if (ctx->n_units < 1 || e < 1 || ctx->J != ctx->n_units * e)
+    if (b->tied) {                                    // owners are the tied states the batch was made with (pcl_batch_create_labels_tied)
+        if (ctx->n_units < 1 || e < 1 || ctx->J != b->tied_J)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the model has %d GMM states, the batch was made over %d tied states", who, ctx->J, b->tied_J);
+    } else if (ctx->n_units < 1 || e < 1 || ctx->J != ctx->n_units * e)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the model has %d GMM states, %d units x %d emitting states need %d", who, ctx->J, ctx->n_units, e, ctx->n_units * e);
     if (b->label_max >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch names unit %d, the inventory now has %d units", who, b->label_max, ctx->n_units);
     for (int u = 0; u < b->U; ++u)
@@ -1263,6 +1266,7 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
         TRY(d_drop.alloc(ctx, (size_t)b->U));
         HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
         TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, e, d_state, d_drop));
+        if (b->tied) TRY(pcl_launch_tied_owner(ctx, b, e, d_state));            // unit * P + slice -> the position's tied state of that slice
         if (frame_state_out) HIPCHK(ctx, hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         if (dropped_out) HIPCHK(ctx, hipMemcpyAsync(dropped_out, d_drop, (size_t)b->U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, pcl_batch_mark(b));
@@ -1299,6 +1303,7 @@ int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
         TRY(d_drop.alloc(ctx, (size_t)b->U));
         HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
         TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, ctx->S - 2, d_state, d_drop));
+        if (b->tied) TRY(pcl_launch_tied_owner(ctx, b, ctx->S - 2, d_state));
         HIPCHK(ctx, pcl_batch_mark(b));
         return PCL_OK;
     };

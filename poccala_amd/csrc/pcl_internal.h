@@ -160,6 +160,14 @@ struct LexiconDev {
     DevBuf<int> lm_col, lm_node_word_ptr, lm_node_word_ids;
 };
 
+// Resident tying (tying.hip): a decision tree's node arrays in the layouts the walk reads.  Replaced as a whole by pcl_tying_upload, gone with
+// pcl_tying_drop, with an inventory of another shape, and with the context.
+struct TyingDev {
+    DevBuf<int4> ty_nodes;                        // [ty_N] (cand, no, yes, state): one 16-byte load per step of a walk
+    DevBuf<unsigned int> ty_qbits;                // [ty_Q][ty_W] bit u of row qi = q_member[qi][u]
+    DevBuf<int> ty_root;                          // [n_units * P] root_of
+};
+
 // The context's own streams (the int16 front-end's staging stream lives with its buffers, PcmStage::stream; pcl_ctx::streams() lists all seven).
 struct CtxStreams {
     Stream stream_main;          // the owner of the main stream; launchers read the VIEW pcl_ctx::stream, which pcl_stream_scope redirects
@@ -175,7 +183,7 @@ struct CtxStreams {
 // base, so the streams outlive every buffer, event, timer and staging area of the context (PcmStage keeps the same order for its own
 // stream).  Nothing else depends on the order: pcl_destroy has drained every stream before, and the steps whose order IS a decision
 // (communicator, buried batches, zero_pending) are spelled out in ctx_teardown.
-struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev {
+struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev, TyingDev {
     int device = 0;
     AccScratch acc;
     hipStream_t stream = nullptr;      // VIEW of stream_main, or of the stream an open pcl_stream_scope has put in its place
@@ -263,6 +271,8 @@ struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev {
     int lex_nodes = 0, lex_nroots = 0;
     std::vector<int> lex_word_host;                  // node_word as uploaded: pcl_lm_upload checks its node -> word lists against it
     int lm_W = 0;                                    // words of the resident language model (0: none)
+    // resident tying (TyingDev): ty_N = 0 means none
+    int ty_N = 0, ty_Q = 0, ty_W = 0, ty_R0 = 0, ty_Jt = 0, ty_P = 0, ty_units = 0;
     // multi-GPU (pcl_comm.hip): RCCL communicator, or the host-callback rehearsal transport
     void *comm = nullptr;
     int rank = 0, nranks = 1;
@@ -380,6 +390,11 @@ struct pcl_batch : BatchDecodeDev {
     DevBuf<int32_t> d_labels;             // the labels on the device and the U + 1 offsets into them: uploaded by the first
     DevBuf<int> d_label_off;              // pcl_batch_align_segments of the batch, kept for the next
     int label_max = 0, label_len_max = 0;    // largest unit id / longest label of the batch
+    // ... over tied states (pcl_batch_create_labels_tied): the tied state of every (label position, state position), written by the walk
+    // when the batch was made and the batch's own from then on -- a later pcl_tying_upload / pcl_tying_drop does not reach it
+    bool tied = false;
+    int tied_J = 0;                          // J_t of the tying the batch was made with
+    DevBuf<int32_t> pos_state;               // [sum L][P]
 };
 
 // ---------------------------------------------------------------- scaled linear-domain forward-backward (hmm_fb_linear.hip)
@@ -554,6 +569,15 @@ int pcl_tree_accumulate_ready(pcl_ctx *ctx, const char *who);
 int pcl_launch_tree_label_rows(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_label_event, int P, const int32_t *d_frame_state, int32_t *d_frame_row);
 int pcl_launch_tree_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src);
 void pcl_tree_release(pcl_ctx *ctx);                 // the tree statistics (the next pcl_tree_zero)
+// tying.hip.  pcl_launch_tied_label_states, for pcl_batch_create_labels_tied (hmm_units.hip): the batch's labels and their offsets go to the
+// device (d_labels / d_label_off), one walk per (label position, k) of the resident tying fills b->pos_state and the row -> state map, which
+// comes back to the host (row_state, sum N entries) for pcl_batch_set_states_impl's bookkeeping.  Complete on return.
+// pcl_launch_tied_owner, for the label-based entry points (pcl_api.hip): d_frame_state holds pcl_launch_align_segments' owner map of the
+// batch (unit * P + slice, -1 = not kept); every kept frame's entry becomes pos_state[i * P + slice], i = the label position of its path row.
+// Queued on ctx->stream.
+int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state);
+int pcl_launch_tied_owner(pcl_ctx *ctx, pcl_batch *b, int P, int32_t *d_frame_state);
+void pcl_tying_release(pcl_ctx *ctx);                // the resident tying
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);

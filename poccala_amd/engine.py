@@ -392,9 +392,40 @@ class Engine(object):
         self._check(self._lib.pcl_units_download(self._ctx, ptr(t)))
         return t
 
-    def label_batch(self, unit_ids, T, frame_begin):
-        """Sentence HMMs of a list of labels (AcousticModel.embedded for every utterance at once, in the library)."""
-        return Batch(self, None, T, frame_begin, unit_ids=unit_ids)
+    def label_batch(self, unit_ids, T, frame_begin, tied=False):
+        """Sentence HMMs of a list of labels (AcousticModel.embedded for every utterance at once, in the library).  tied=True: over the
+        tied states of the resident tying (load_tying; pcl_batch_create_labels_tied) -- the model has the tying's J_t states, every label
+        position's states come from a walk of the tree on the device, and the batch is a label-built batch for accumulate_hmm,
+        refresh_transitions, align_segments, accumulate_tree and accumulate_lda."""
+        return Batch(self, None, T, frame_begin, unit_ids=unit_ids, tied=tied)
+
+    def load_tying(self, tree, n_states=None, n_roots=None):
+        """Make a ContextTree.Tree's node arrays the resident tying (pcl_tying_upload), in place of the one before.  The unit inventory
+        (load_units) must be the tree's: n_units units of P + 2 states.  n_states / n_roots: J_t and R0 where they are not the tree's own
+        count of leaves and largest root."""
+        qm, cand, child, state, root_of = tree.tying_arrays()
+        jt = int(tree.n_states if n_states is None else n_states)
+        if qm.ndim != 2 or qm.shape[1] != tree.n_units + 1 or child.shape != (cand.size, 2) or state.shape != cand.shape \
+                or root_of.shape != (tree.n_units * tree.P,):
+            raise ValueError('the tree\'s arrays do not fit together: q_member %s, node_cand %s, node_child %s, node_state %s, root_of %s'
+                             % (qm.shape, cand.shape, child.shape, state.shape, root_of.shape))
+        self._check(self._lib.pcl_tying_upload(self._ctx, tree.n_units, tree.P, int(qm.shape[0]), ptr(qm), int(cand.size), ptr(cand), ptr(child),
+                                               ptr(state), int(tree.n_roots if n_roots is None else n_roots), ptr(root_of), jt))
+        self.tying_P, self.tying_J = int(tree.P), jt
+
+    def drop_tying(self):
+        """Remove the resident tying (pcl_tying_drop).  Batches made over it keep their states."""
+        self._check(self._lib.pcl_tying_drop(self._ctx))
+        self.tying_P = self.tying_J = 0
+
+    def tying_lookup(self, ctx3):
+        """Tied states of arbitrary contexts, seen in training or not (pcl_tying_lookup; the device form of Tree.lookup): ctx3 (n, 3) int32
+        = (left, centre, right) with n_units for "no neighbour" -> (n, P) int32."""
+        c = as_c(ctx3, np.int32).reshape(-1, 3)
+        P = int(getattr(self, 'tying_P', 0)) or max(int(getattr(self, 'S', 2)) - 2, 1)   # (without a tying the library refuses)
+        out = np.empty((max(c.shape[0], 1), P), dtype=np.int32)
+        self._check(self._lib.pcl_tying_lookup(self._ctx, int(c.shape[0]), ptr(c), ptr(out)))
+        return out[:c.shape[0]]
 
     def load_lexicon(self, tree):
         """The flat pronunciation tree of Lexicon.PronunciationLexicon.compile (units = ids of the loaded inventory)."""
@@ -911,13 +942,13 @@ class Batch(object):
     """U sentence HMMs.  N[u] states, T[u] frames; matrices cross the boundary in the reference's
     (N,T) float64 layout, one array per utterance."""
 
-    def __init__(self, engine, N, T, frame_begin=None, unit_ids=None):
+    def __init__(self, engine, N, T, frame_begin=None, unit_ids=None, tied=False):
         self.eng = engine
         self._lib = engine._lib
         self.T = as_c(T, np.int32).reshape(-1)
         self._b = C.c_void_p()
         if unit_ids is not None:
-            # label-built: N_u = (S-2) L_u + 2 (AcousticModel.py:966); structure built by pcl_batch_create_labels
+            # label-built: N_u = (S-2) L_u + 2 (AcousticModel.py:966); structure built by pcl_batch_create_labels (tied: ..._labels_tied)
             if isinstance(unit_ids, np.ndarray) and unit_ids.ndim == 2:      # equal-length labels as one (U, L) array: no per-utterance Python
                 lens = np.full(unit_ids.shape[0], unit_ids.shape[1], dtype=np.int32)
                 flat = np.ascontiguousarray(unit_ids, dtype=np.int32).reshape(-1)
@@ -931,16 +962,19 @@ class Batch(object):
             fb = as_c(frame_begin, np.int64).reshape(-1)
             logpi = np.ascontiguousarray(np.log(1.0 / self.N.astype(np.float64)))     # np.log(np.ones(N) / N), AcousticModel.py:1005
             self.label_len, self.labels = lens, flat
-            engine._check(self._lib.pcl_batch_create_labels(engine._ctx, self.U, ptr(lens), ptr(flat), ptr(self.T), ptr(fb),
-                                                            ptr(logpi), C.byref(self._b)))
+            create = self._lib.pcl_batch_create_labels_tied if tied else self._lib.pcl_batch_create_labels
+            engine._check(create(engine._ctx, self.U, ptr(lens), ptr(flat), ptr(self.T), ptr(fb), ptr(logpi), C.byref(self._b)))
         else:
             self.N = as_c(N, np.int32).reshape(-1)
             if self.N.shape != self.T.shape or self.N.size == 0:
                 raise ValueError('N and T must be equal-length, non-empty')
+            if tied:
+                raise ValueError('tied=True needs labels (unit_ids)')
             self.U = int(self.N.size)
             fb = None if frame_begin is None else as_c(frame_begin, np.int64).reshape(-1)
             engine._check(self._lib.pcl_batch_create(engine._ctx, self.U, ptr(self.N), ptr(self.T), ptr(fb),
                                                      C.byref(self._b)))
+        self.tied = bool(tied)
         engine._batches.add(self)
         self._frame_begin = None if frame_begin is None else fb.copy()
         self._fetch_slots = set()                     # engine result slots with un-waited copies of this batch (fetch_async)
@@ -1215,6 +1249,21 @@ class Batch(object):
         seg = Segments(self.eng, None, self.eng.J, handle=h)
         dropped = np.flatnonzero(flags).tolist()
         return (seg, dropped, state[:self.eng.F]) if want_map else (seg, dropped)
+
+    def row_states(self):
+        """The row -> GMM state map as the device holds it (pcl_batch_get_states): one (N_u,) int32 array per utterance, entry and exit
+        rows PCL_ROW_ENTRY / PCL_ROW_EXIT."""
+        flat = np.empty(int(self._n_off[-1]), dtype=np.int32)
+        self._check(self._lib.pcl_batch_get_states(self._b, ptr(flat), None))
+        return [flat[self._n_off[u]:self._n_off[u + 1]] for u in range(self.U)]
+
+    def pos_states(self):
+        """A tied batch's (L_u, P) tied states per utterance: what the walks of the resident tying gave every label position."""
+        P = int(self.eng.S) - 2
+        flat = np.empty(int(self.labels.size) * P, dtype=np.int32)
+        self._check(self._lib.pcl_batch_get_states(self._b, None, ptr(flat)))
+        off = np.concatenate([[0], np.cumsum(self.label_len)]) * P
+        return [flat[off[u]:off[u + 1]].reshape(-1, P) for u in range(self.U)]
 
     def get(self, what):
         """List of per-utterance arrays (or a (U,...) array for per-utterance scalars)."""
