@@ -37,7 +37,9 @@
 // 15.1 (more B-operand registers, more LDS fragment traffic: this kernel reads each of the 2 KS8 fragments of an m-tile once,
 // 10 ds_read_b128 at D = 39, not once per pass) -> the m-tile loop scheduled by hand (process(), profiles/r19_score_schedule.txt):
 // 14.8 -> 14.2 ms per step, results bit for bit -> the double buffer made a ring, two m-tiles per stage and barrier
-// (profiles/r22_score_ring.txt): 14.03 -> 13.73 ms per step on one device, 13.63 -> 13.20 on another, results bit for bit.
+// (profiles/r22_score_ring.txt): 14.03 -> 13.73 ms per step on one device, 13.63 -> 13.20 on another, results bit for bit -> one
+// frame tile's chain at a time, the last tile's log-sum-exp carried under the next m-tile's first chain (process_carry(),
+// PCL_SPLIT16_CARRY; profiles/r28_score_carry.txt), results bit for bit.
 #include <stdlib.h>
 
 #include "pcl_internal.h"
@@ -66,6 +68,11 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 #ifndef PCL_SPLIT16_MTS
 #define PCL_SPLIT16_MTS 2     // m-tiles staged per workgroup barrier
 #endif
+// The order of one m-tile in the KS8 <= 5 kernels (NT = 2): 1 = one frame tile's MFMA chain at a time, the other tile's log-sum-exp in
+// its gaps, the last tile's carried under the first chain of the next m-tile (process_carry()); 0 = the order of rounds 19-22 (process()).
+#ifndef PCL_SPLIT16_CARRY
+#define PCL_SPLIT16_CARRY 1
+#endif
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
 // The ring of the D-dimensional kernel.  D = 47 (KS8 = 6: 12 KB per m-tile, the rolled DMA loop) keeps the double buffer.
@@ -75,7 +82,14 @@ struct Ring {
     static constexpr int R = KS8 > 5 ? 2 : PCL_SPLIT16_RING;
     static constexpr int MTS = KS8 > 5 ? 1 : PCL_SPLIT16_MTS;
     static constexpr int STAGE_CH = MTS * 2 * KS8;                              // 1-KiB chunks per stage
-    static constexpr size_t LDS = (size_t)R * STAGE_CH * 64 * 16 + 16;          // static LDS per workgroup: the ring and s_ovf
+#ifdef PCL_DIAG_NOLSE
+    static constexpr bool CARRY = false;
+#else
+    static constexpr bool CARRY = PCL_SPLIT16_CARRY && KS8 <= 5 && PCL_SPLIT16_NT == 2;
+#endif
+    // (the carried order parks each lane's output indices in LDS over the m-tile loop: the registers go to the held fragments)
+    static constexpr size_t STASH = CARRY ? (size_t)WG * PCL_SPLIT16_NT * sizeof(long long) : 0;
+    static constexpr size_t LDS = (size_t)R * STAGE_CH * 64 * 16 + 16 + STASH;  // static LDS per workgroup: the ring, s_ovf, the parked indices
     static_assert(R >= 2 && MTS >= 1, "a ring has at least two stages");
     static_assert(3 * LDS <= (160u << 10), "three workgroups per CU: the ring does not fit a third of the 160 KB of LDS");
     static_assert(LDS <= (56u << 10), "pcl_score_occupancy(ctx, 2) pads a workgroup to 56 KB");
@@ -115,10 +129,14 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
     __syncthreads();
     const int vend = segs[tile.seg_hi - 1].vstart + segs[tile.seg_hi - 1].len;
     const bool wave_active = tile.vstart + wave * NT * 32 < vend;
+    const int wave_u = Ring<D>::CARRY ? __builtin_amdgcn_readfirstlane(wave) : 0;      // (on the scalar unit ahead of the branch, for the same reason as below)
     if (n_mtiles == 0) {                    // not one mixture of the state on the pipe: ln 0 for every frame (the coarse pass adds the rest), no flag
         if (wave_active) {
             for (int c = 0; c < NT; ++c) {
-                const int v = tile.vstart + (wave * NT + c) * 32 + col;
+                int v = tile.vstart + (wave * NT + c) * 32 + col;
+                // (the carried order: this path's frame index from a lane counted afresh, or the compiler keeps its pieces over the m-tile loop)
+                if constexpr (Ring<D>::CARRY)
+                    v = tile.vstart + (wave_u * NT + c) * 32 + ((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 31);
                 if (v < vend && half == 0) {
                     int lo = tile.seg0;
                     const int hi = tile.seg_hi - 1;
@@ -193,11 +211,20 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 
     // a ring of R stages of MTS m-tiles each: one workgroup barrier per MTS x 32 mixtures
     constexpr int R = Ring<D>::R, MTS = Ring<D>::MTS;
+    constexpr bool CARRY = Ring<D>::CARRY && NT == PCL_SPLIT16_NT;
     __shared__ __attribute__((aligned(16))) uint4 abuf[R][MTS * CH * 64];
     const uint4 *pstate = pm + (size_t)tile.state * nmt_max * (CH * 64);
     // every wave issues its share of the stage's 1-KiB chunks: the chunk index is wave-uniform, so it is kept on the scalar unit
     // (readfirstlane) and the 2-3 trips are unrolled -- as a loop over threadIdx.x >> 6 each trip cost ~5 VALU instructions
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    // (the carried order holds ten fragments, two accumulators and the sums over the whole m-tile: the output indices, needed again only
+    //  behind the loop, wait in LDS, each lane's own slots and -1 for a frame past the end, addressed by what the loop keeps anyway, so
+    //  that the D = 39 kernel keeps 168 registers without scratch)
+    __shared__ long long s_oidx[Ring<D>::CARRY ? NT : 1][Ring<D>::CARRY ? WG : 1];
+    if constexpr (Ring<D>::CARRY) {
+#pragma unroll
+        for (int c = 0; c < NT; ++c) s_oidx[c][wave_s * 64 + lane] = valid[c] ? oidx[c] : -1;
+    }
     auto dma = [&](int buf, int stage) {
         const uint4 *src = pstate + (size_t)stage * (MTS * CH * 64);
         const int nch = min(MTS, n_mtiles - stage * MTS) * CH;
@@ -233,6 +260,58 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 #else
 #define SSTAMP(k)
 #endif
+    // The carried order's log-sum-exp of one frame tile's accumulator: the 32 operations of process()'s lse_op and the same pairwise
+    // tree -- P(r) = e[r] + e[r + 8], Q(r) = P(r) + P(r + 4), R(r) = Q(r) + Q(r + 2), S = R(0) + R(1), sm + S -- walked depth first, so
+    // that five partial sums are live instead of nine: every add has the operands it has there, so every sum is that one bit for bit.
+    // (Those four registers are what keeps all 2 KS8 fragments, both accumulators and the sums of the D = 39 kernel within 168.)
+    // LSE_WALK[k] = {kind, dst, src}: kind 0: t[dst] = exp2(a[src]), 1: t[dst] += t[src], 2: sn = sm[c] + t[0].
+    auto lse_step = [&](const f16v &a, float (&t)[5], float &sn, int c, int k) {
+        constexpr signed char LSE_WALK[32][3] = {
+            {0, 0, 0}, {0, 1, 8},  {1, 0, 1}, {0, 1, 4}, {0, 2, 12}, {1, 1, 2}, {1, 0, 1},                   // Q(0)
+            {0, 1, 2}, {0, 2, 10}, {1, 1, 2}, {0, 2, 6}, {0, 3, 14}, {1, 2, 3}, {1, 1, 2}, {1, 0, 1},        // Q(2), R(0)
+            {0, 1, 1}, {0, 2, 9},  {1, 1, 2}, {0, 2, 5}, {0, 3, 13}, {1, 2, 3}, {1, 1, 2},                   // Q(1)
+            {0, 2, 3}, {0, 3, 11}, {1, 2, 3}, {0, 3, 7}, {0, 4, 15}, {1, 3, 4}, {1, 2, 3}, {1, 1, 2},        // Q(3), R(1)
+            {1, 0, 1}, {2, 0, 0}};                                                                           // S, sm + S
+        const int kind = LSE_WALK[k][0], dst = LSE_WALK[k][1], src = LSE_WALK[k][2];
+        if (kind == 0) t[dst] = __builtin_amdgcn_exp2f(a[src]);
+        else if (kind == 1) t[dst] += t[src];
+        else sn = sm[c] + t[0];
+    };
+    // frame tile c's accumulator a of one m-tile and the sum sn = sm[c] + (its 16 exponentials) go into sm[c]; on the wave-uniform slow
+    // path the reference moves first, and with it the spare slot of xb[c] that every later MFMA chain of tile c subtracts
+    // (the statements are those at the end of process(), where the comments are; that copy stays as it is so that PCL_SPLIT16_CARRY=0 and
+    //  the D = 47 kernel compile to the code they had)
+    auto settle = [&](f16v &a, int c, float sn) {
+        if (__any(!inited[c]) | __any(!(sn < 3.0e38f))) {
+            float gm = a[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) gm = __builtin_fmaxf(gm, a[r]);
+            const float gp = __builtin_fmaxf(gm, __shfl_xor(gm, 32, 64));
+            float s = sm[c];
+            const bool first = !inited[c];
+            if ((first || gp > 0.f) && gp > -5.0e4f) {
+                const _Float16 r1 = (_Float16)__builtin_fminf(__builtin_fmaxf(-(ref[c] + gp), -FMAXH), FMAXH);
+                const float nref = -(float)r1, dl = nref - ref[c];
+                ref_ovf |= __builtin_fabsf(nref) > 5.0e4f;
+#ifdef PCL_LSE_FLUSH_REPRO                                    // mutation build (tests are expected to FAIL on it)
+                s = first ? 0.f : s * __builtin_amdgcn_exp2f(-dl);
+#else
+                const float hs = __builtin_amdgcn_exp2f(-0.5f * dl);
+                s = first ? 0.f : (s * hs) * hs;
+#endif
+                inited[c] = true;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) a[r] -= dl;
+                ref[c] = nref;
+                if (half) xb[c][0][SC][JC] = r1;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s += __builtin_amdgcn_exp2f(a[r]);
+            sm[c] = s;
+        } else {
+            sm[c] = sn;
+        }
+    };
     auto process = [&](int mt) {
         const uint4 *ab = &abuf[(unsigned)(mt / MTS) % R][(mt % MTS) * (CH * 64)];
         f16v acc[NT];
@@ -393,6 +472,82 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
         }
         SSTAMP(2)
     };
+    // The carried order (PCL_SPLIT16_CARRY, KS8 <= 5, NT = 2).  One frame tile's whole chain at a time -- a2x1 s0.., a1x2 s0.., a1x1 s0.. on
+    // one accumulator, the first MFMA on C = 0 -- with the OTHER tile's 32 log-sum-exp operations in its gaps:
+    //   chain(0) of m-tile k      beside it the log-sum-exp of tile 1 of m-tile k - 1, read from cacc[1], which nothing has overwritten yet;
+    //                             behind it settle(1) of m-tile k - 1, so xb[1] is final before chain(1) reads it
+    //   chain(1) of m-tile k      its first MFMA (C = 0) frees the old cacc[1]; beside it the log-sum-exp of tile 0 of m-tile k;
+    //                             behind it settle(0) of m-tile k, before chain(0) of m-tile k + 1
+    // sm, ref, inited and xb[c] move at the same points relative to the MFMAs that read xb[c] as in process(), and every sum keeps its
+    // order: the results are process()'s bit for bit.  The first m-tile has nothing to carry: cacc[1] starts as a tile of log zeros, which
+    // settles to what is there already (sm = 0 + 16 exp2(-6e4) = 0, no reference taken) -- under a test of mt the compiler sinks the whole
+    // log-sum-exp out of chain(0)'s gaps into the branch.  The last m-tile leaves tile 1 to carry_tail() behind the stage loop, the one tail
+    // per workgroup.  cacc[1] lives across the stage loop's wait and barrier -- registers only.  All 2 KS8 fragments are read under
+    // chain(0) and held for chain(1).
+    f16v cacc[2];
+    if constexpr (CARRY) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cacc[1][r] = -FMAXH;
+    }
+    auto process_carry = [&](int mt) {
+        const uint4 *ab = &abuf[(unsigned)(mt / MTS) % R][(mt % MTS) * (CH * 64)];
+        auto frag = [&](int pa, int s) { return *reinterpret_cast<const h8v *>(&ab[(pa * KS8 + s) * 64 + lane]); };
+        h8v af[2 * KS8];                               // in the order of first use: the a2 set, then the a1 set
+        auto rd = [&](int f) { af[f] = frag(f < KS8 ? 1 : 0, f % KS8); };
+        float t[5], snew;
+        rd(0);
+        rd(1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            int k = 0;
+#pragma unroll
+            for (int g = 0; g < 3 * KS8; ++g) {
+                const int s = g % KS8;
+                const h8v &a = af[g < KS8 ? s : KS8 + s];
+                const h8v &x = xb[c][g >= KS8 && g < 2 * KS8 ? 1 : 0][s];
+                if (g == 0) {
+                    f16v zero;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+                    cacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, x, zero, 0, 0, 0);
+                } else {
+                    cacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, x, cacc[c], 0, 0, 0);
+                }
+                if (g == 0) {
+                    // the chain starts before anything waits for the other chain's last MFMA; behind chain(0)'s first MFMA the rest of
+                    // the reads: the wait of the first two is the one exposed round trip
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (c == 0) {
+#pragma unroll
+                        for (int f = 2; f < 2 * KS8; ++f) rd(f);
+                    }
+                }
+                // three operations of the other tile's log-sum-exp per gap (the gap of the fragment reads takes none)
+                if (c == 1 || g > 0) {
+#pragma unroll
+                    for (int q = 0; q < 3 && k < 32; ++q, ++k) lse_step(cacc[1 - c], t, snew, 1 - c, k);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (; k < 32; ++k) lse_step(cacc[1 - c], t, snew, 1 - c, k);       // (KS8 = 2: six gaps hold 18 of the 32)
+            __builtin_amdgcn_sched_barrier(0);
+            if (c == 0) {
+                settle(cacc[1], 1, snew);
+            } else {
+                SSTAMP(1)
+                settle(cacc[0], 0, snew);
+                SSTAMP(2)
+            }
+        }
+    };
+    auto carry_tail = [&]() {                          // tile 1 of the last m-tile
+        float t[5], snew;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) lse_step(cacc[1], t, snew, 1, k);
+        settle(cacc[1], 1, snew);
+    };
     // The ring.  Stage st + R - 1 is issued right behind the barrier of stage st, which proves all four waves done with stage st - 1, whose
     // buffer it takes: R - 1 stages ahead of its use, so its DMA has (R - 1) x MTS m-tile periods to land.  With R = 2 (the default) nothing
     // younger is in flight at the wait: vmcnt(0) and the plain barrier.  With R > 2 a wave waits for ITS pieces of the oldest stage only:
@@ -429,8 +584,13 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
         if (st + R - 1 < n_stages) dma((unsigned)(st + R - 1) % R, st + R - 1);
         if (wave_active) {
             const int mend = min(n_mtiles, (st + 1) * MTS);
-            for (int mt = st * MTS; mt < mend; ++mt) process(mt);
+            for (int mt = st * MTS; mt < mend; ++mt) {
+                if constexpr (CARRY) process_carry(mt); else process(mt);
+            }
         }
+    }
+    if constexpr (CARRY) {
+        if (wave_active) carry_tail();
     }
 #ifdef PCL_SPLIT_STAMPS
     if (blockIdx.x == 800 && lane == 0)
@@ -448,6 +608,11 @@ __global__ __launch_bounds__(WG, PCL_SPLIT16_MINW * 256 / WG > 0 ? PCL_SPLIT16_M
 #pragma unroll
     for (int c = 0; c < NT; ++c) {
         const double S = (double)sm[c] + (double)__shfl_xor(sm[c], 32, 64);
+        if constexpr (Ring<D>::CARRY) {
+            // (the lane counted afresh: an address the compiler shares with the store's is one more register held over the loop)
+            oidx[c] = s_oidx[c][wave_s * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))];
+            valid[c] = oidx[c] >= 0;
+        }
         if (valid[c] && half == 0) out[oidx[c]] = (S > 0) ? LN2 * ((double)ref[c] + k0 + ::log2(S)) : -INFINITY;
     }
     if (__any(ref_ovf) && lane == 0) s_ovf = 1;
