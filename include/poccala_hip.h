@@ -290,6 +290,36 @@ int pcl_lm_upload(pcl_ctx *ctx, int W, const double *uni, const double *bow, con
 int pcl_batch_decode_lm(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit,
                         double logpi_two_units);
 int pcl_batch_decode_get_words(pcl_batch *b, int32_t *hist_word);
+/* TIED STATES IN THE DECODER.  A model over the tied states of a decision tree (tying section below: pcl_tree_build(install) ->
+ * pcl_tying_upload -> EM over pcl_batch_create_labels_tied batches) has J_t states reached through a tree walk, not n_units (S - 2) states
+ * at unit (S - 2) + k.  pcl_lexicon_tie runs that walk (pcl_tying_lookup's) once for every (node, unit slot j, state position k) of the
+ * resident lexicon, under the resident tying, and keeps the result beside the lexicon: node_state (n_nodes, 2 P) int32, P = S - 2.
+ * node_ctx (n_nodes, 2, 3) int32 = (left, centre, right) of unit slot j of node i, in the tying section's conventions: unit ids
+ * 0 .. n_units - 1, n_units = no or unknown neighbour.  Slot 1 of a one-unit node is ignored on input and its node_state entries are -1.
+ * THE DEFAULT CONTEXT RULE (PronunciationLexicon.node_contexts on the host; a caller who knows better passes its own node_ctx):
+ *   inside a node            the neighbour is the node's other unit
+ *   left of the first unit   the LAST unit of the parent node (unique in a prefix tree); n_units for a first-character node
+ *   right of the last unit   ALWAYS n_units: the children differ, the tree is not copied per right context, and the edge symbol is a
+ *                            member of a question like any other unit
+ * Consequence: a context across a syllable boundary to the right is answered as "edge", while training labels see the next syllable's
+ * first unit there (labels[i + 1], pcl_batch_create_labels_tied: unchanged); cross-word contexts are unknown on both sides.
+ * Snapshot, as for tied batches: a later pcl_tying_upload / pcl_tying_drop does not change the kept states; whatever drops the lexicon
+ * (a new pcl_lexicon_upload, a pcl_units_upload of another shape) drops them; pcl_lexicon_untie removes them (no refusal when there are
+ * none); they remember the J_t they were made under.  Checked before anything resident changes: PCL_ERR_STATE without a resident lexicon
+ * or tying; PCL_ERR_INVALID, the text naming node and slot, for a centre that is not node_units[i][j], a neighbour outside [0, n_units],
+ * or a tying whose P is not the inventory's S - 2.  pcl_lexicon_states: the kept node_state; PCL_ERR_STATE when the lexicon is not tied.
+ * pcl_kernel_time group: "lexicon_tie".  Synchronous.
+ * pcl_batch_decode_tied = pcl_batch_decode (lm = 0) or pcl_batch_decode_lm (lm != 0) with ONE difference: the emission row of state
+ * position k of unit slot j of a token at node n is 1 + node_state[n][j P + k] of an all-state batch of J_t + 2 rows (entry, states
+ * 0 .. J_t - 1, exit).  Transitions stay per centre unit; pi, D1 - D6, pruning, transfer and history are untouched; results through
+ * pcl_batch_decode_get (and pcl_batch_decode_get_words after lm != 0).  The kernels' TIED = true instantiations; PCL_DEC_GENERAL=1 still
+ * forces the general one.  PCL_ERR_STATE: the lexicon is not tied, the resident model's J is not the J_t it was tied under, lm != 0
+ * without a language model; PCL_ERR_INVALID: the batch is not an all-state batch of J_t + 2 rows. */
+int pcl_lexicon_tie(pcl_ctx *ctx, const int32_t *node_ctx /* n_nodes * 2 * 3 */);
+int pcl_lexicon_untie(pcl_ctx *ctx);
+int pcl_lexicon_states(pcl_ctx *ctx, int32_t *node_state /* n_nodes * 2 * P */);
+int pcl_batch_decode_tied(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit,
+                          double logpi_two_units, int lm);
 
 /* Copy a result to a caller buffer (layouts in pcl_get_what). */
 int pcl_batch_get(pcl_batch *b, int what, void *host);

@@ -24,13 +24,18 @@ from .runtime import default_engine
 beam = 0.85          # Decoder.py:34
 
 
-def load_inventory(engine, unit_names, means, variances, weights, unit_trans, lexicon):
+def load_inventory(engine, unit_names, means, variances, weights, unit_trans, lexicon, tying=None):
     """Upload what the decoder needs: the GMM states (unit-major, S-2 per unit), the unit transition matrices and the
-    pronunciation tree compiled against `unit_names` (Lexicon.PronunciationLexicon).  Returns the compiled tree."""
+    pronunciation tree compiled against `unit_names` (Lexicon.PronunciationLexicon).  Returns the compiled tree.
+    tying: a ContextTree.Tree -- the GMM states are then its J_t tied states; the tree becomes the resident tying and the pronunciation
+    tree is tied under it with the default contexts (Engine.tie_lexicon), for decode_batch / decode_stream(tied=True)."""
     engine.load_model(means, variances, weights)
     engine.load_units(np.asarray(unit_trans))
     tree = lexicon.compile({u: i for i, u in enumerate(unit_names)})
     engine.load_lexicon(tree)
+    if tying is not None:
+        engine.load_tying(tying)
+        engine.tie_lexicon()
     return tree
 
 
@@ -80,13 +85,15 @@ def _report(res, tree):
 
 
 def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096, lm=None, lm_scale=1.0,
-                 word_penalty=0.0):
+                 word_penalty=0.0, tied=False):
     """data_list: MFCC matrices (T_u, D), which are uploaded -- or the (lens, begin) of frames already resident (Engine.frontend /
     load_audio_batch(fetch=False)), the form AcousticModel's batch helpers take: nothing is uploaded, PCM goes to words without a host
     round trip.  Scores every GMM state for every frame (the decoder has no label) and runs the token passing.  Returns per utterance
     (words, score, detail); on the resident route an utterance of length 0 (the detector kept no frame) is left out of the batch and
     reported as ([], -inf, None).  lm: a LanguageModel.Ngram -- compiled with lm_scale / word_penalty, uploaded, and applied at word
-    ends (D6); every word then comes back as one string instead of the node's list of homophones."""
+    ends (D6); every word then comes back as one string instead of the node's list of homophones.  tied: the loaded model is one over
+    tied states and the tree was tied under its tying (load_inventory(tying=...)): the all-state batch has J_t + 2 rows and the token
+    passing reads each node's tied states."""
     engine = engine or default_engine()
     compiled = load_language_model(engine, tree, lm, lm_scale, word_penalty) if lm is not None else None
     report = (lambda res: _report_lm(res, tree, compiled)) if lm is not None else (lambda res: _report(res, tree))
@@ -97,7 +104,7 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
         if len(keep):
             b = engine.all_state_batch(lens[keep], begin[keep])
             b.score(precision)
-            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None)
+            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
             b.close()
             for u, r in zip(keep, report(res)):
                 out[u] = r
@@ -107,13 +114,13 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
     engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
     b = engine.all_state_batch(lens, begin)
     b.score(precision)
-    res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None)
+    res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
     b.close()
     return report(res)
 
 
 def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096, lm=None, lm_scale=1.0,
-                  word_penalty=0.0):
+                  word_penalty=0.0, tied=False):
     """The streaming form (BASELINE config 5: a corpus that is fed chunk by chunk).  `chunks` yields lists of (T_u, D)
     float32 MFCC matrices; for every chunk, in order, decode_batch's result list is yielded.  Three legs overlap:
       copy stream    frames of chunk k+1 travel into the frame slot that is not being scored (Engine.stage_frames)
@@ -122,7 +129,7 @@ def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, cand
     and the host packs chunk k+2 into page-locked memory meanwhile.  Batches are kept for the last few chunk shapes (the
     lengths of a chunk's utterances) and reused in rotation; a new shape costs a batch creation, which takes its buffers from
     the library's device-memory pool and copies its descriptors on the main stream -- it does not wait for the decoder
-    running on the second stream."""
+    running on the second stream.  tied: as in decode_batch (the all-state batches have the loaded model's J_t + 2 rows)."""
     engine = engine or default_engine()
     bm = beam if beam_ is None else beam_
     compiled = load_language_model(engine, tree, lm, lm_scale, word_penalty) if lm is not None else None   # (lm: as in decode_batch)
@@ -187,7 +194,7 @@ def decode_stream(chunks, tree, engine=None, precision=PCL_F32, beam_=None, cand
             layout = pack(nxt)                                     # host packing + H2D of chunk 1 beside the GPU work
         k = 0
         while b is not None:
-            b.decode_launch(bm, 8, candidate, max_tokens, lm is not None)   # decode(k): second stream, behind score(k)
+            b.decode_launch(bm, 8, candidate, max_tokens, lm is not None, tied)   # decode(k): second stream, behind score(k)
             inflight.append(b)
             b = None
             if nxt is not None:

@@ -9,6 +9,8 @@ pickled tree (:30-39; the reference's `lexicon_ch_small.pkl` and word lists are 
 
 `compile` flattens the tree for pcl_lexicon_upload: one node per reading below the initial level, its units (the
 reading split at the comma: initial + final, or a lone final), its children and whether words end there.
+`node_contexts` gives every unit of every node of that flat tree its (left, centre, right) context for a decoder over tied
+states (pcl_lexicon_tie): the default rule, in this one place.
 """
 import os
 import pickle
@@ -18,7 +20,37 @@ import numpy as np
 from .PinYin import PinYin
 
 
+def node_contexts(tree, n_units):
+    """The default context of every unit slot of the flat tree `compile` returned: (n_nodes, 2, 3) int32 = (left, centre, right), unit ids
+    of the inventory, n_units = no or unknown neighbour (the edge symbol of ContextTree).
+      inside a node            the neighbour is the node's other unit
+      left of the first unit   the last unit of the parent node (unique in a prefix tree); n_units for a first-character node
+      right of the last unit   always n_units: the children differ and the tree is not copied per right context
+    Slot 1 of a one-unit node is (n_units, -1, n_units): pcl_lexicon_tie ignores it."""
+    n_units = int(n_units)
+    nu = np.asarray(tree['node_units'], dtype=np.int64).reshape(-1, 2)
+    nn = np.asarray(tree['node_nunits'], dtype=np.int64).reshape(-1)
+    n = len(nn)
+    parent = np.full(n, -1, dtype=np.int64)
+    cp, ci = np.asarray(tree['child_ptr'], dtype=np.int64), np.asarray(tree['child_idx'], dtype=np.int64)
+    for i in range(n):
+        parent[ci[cp[i]:cp[i + 1]]] = i
+    out = np.empty((n, 2, 3), dtype=np.int32)
+    out[:, :, 0] = out[:, :, 2] = n_units
+    out[:, :, 1] = -1
+    for i in range(n):
+        left = n_units if parent[i] < 0 else nu[parent[i], nn[parent[i]] - 1]
+        if nn[i] == 1:
+            out[i, 0] = (left, nu[i, 0], n_units)
+        else:
+            out[i, 0] = (left, nu[i, 0], nu[i, 1])
+            out[i, 1] = (nu[i, 0], nu[i, 1], n_units)
+    return out
+
+
 class PronunciationLexicon(object):
+    node_contexts = staticmethod(node_contexts)
+
     def __init__(self):
         self.__lexicon = {}
         self.__lexicon_size = 0

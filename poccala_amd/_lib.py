@@ -140,6 +140,10 @@ PROTOTYPES = {
     'pcl_lm_upload': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'pcl_batch_decode_lm': (_i, [_vp, _d, _i, _i, _i, _d, _d]),
     'pcl_batch_decode_get_words': (_i, [_vp, _vp]),
+    'pcl_lexicon_tie': (_i, [_vp, _vp]),
+    'pcl_lexicon_untie': (_i, [_vp]),
+    'pcl_lexicon_states': (_i, [_vp, _vp]),
+    'pcl_batch_decode_tied': (_i, [_vp, _d, _i, _i, _i, _d, _d, _i]),
     'pcl_comm_init_host': (_i, [_vp, _i, _i, _vp, _vp]),
     'pcl_comm_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     'pcl_em_exchange': (_i, [_vp, _d, _i, _i]),

@@ -59,14 +59,18 @@ struct LaneCtx {
 
 // One step of one token by its 8 lanes (they sit in one wave and run in lockstep).  FIRST: p = ln pi + B[:,t]
 // (Decoder.py:270); else the max recursion (:278-283).  best = max_j p_j and fin (D1) come back on every lane.
-template <bool FIRST>
-__device__ __forceinline__ void token_step(const LaneCtx &c, const double *lt, const double *Bs, int up, double pold, int sub, double &pj,
-                                           double &best, int &fin) {
+// TIED: the lane's emission row is 1 + sid, its entry of the node's tied states (DecTie::gen), instead of 1 + unit e + k.
+template <bool FIRST, bool TIED>
+__device__ __forceinline__ void token_step(const LaneCtx &c, const double *lt, const double *Bs, int up, [[maybe_unused]] int sid, double pold, int sub,
+                                           double &pj, double &best, int &fin) {
     const int u0 = up & 0xffff, u1 = (int)((unsigned int)up >> 16);
     const int nu = (u1 == 0xffff) ? 1 : 2, N = c.e * nu + 2;
     double bj = -INFINITY;
     if (sub == 0) bj = 0.0;                                        // entry VirtualState: ln 1 (AcousticModel.py:218)
-    else if (sub < N - 1) bj = Bs[1 + (c.mypos ? u1 : u0) * c.e + c.myk];    // (exit VirtualState: ln 0, :219)
+    else if (sub < N - 1) {                                        // (exit VirtualState: ln 0, :219)
+        if constexpr (TIED) bj = Bs[1 + sid];
+        else bj = Bs[1 + (c.mypos ? u1 : u0) * c.e + c.myk];
+    }
     pj = -INFINITY;
     if (FIRST) {
         if (sub < N) pj = (nu == 1 ? c.lpi1 : c.lpi2) + bj;
@@ -96,13 +100,20 @@ __device__ __forceinline__ void token_step(const LaneCtx &c, const double *lt, c
 // tokens [lo, hi) take a step, two per 8-lane group and pass, software-pipelined over the passes: while pass k computes,
 // the old p of pass k+1 and the indices of pass k+2 are on their way (the old p of token i sits at src[i] of the other p
 // buffer: the compaction at the end of a frame only writes that map).
-struct StepIn {
+struct StepTied {
+    int nd[2], st[2];               // TIED: the token's node (with the indices) and the lane's tied state (with the old p)
+};
+struct StepUntied {};
+template <bool TIED>
+struct StepIn : std::conditional_t<TIED, StepTied, StepUntied> {
     int up[2], at[2];
     double sc[2];
 };
-template <bool FIRST>
+template <bool FIRST, bool TIED>
 __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, const double *Bs, int lo, int hi, const int *up, const double *pin,
-                                           const int *src, double *p, double *sc, int *flag, int tk8, int sub) {
+                                           const int *src, double *p, double *sc, int *flag, int tk8, int sub, [[maybe_unused]] const int *nd,
+                                           [[maybe_unused]] const int *tie) {
+    using StepIn = StepIn<TIED>;
     auto fetch = [&](int i0, StepIn &in) {                         // indices, unit pairs, scores of the pass that starts at i0
 #pragma unroll
         for (int x = 0; x < 2; ++x) {
@@ -111,11 +122,16 @@ __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, c
             in.up[x] = ok ? up[i] : (int)0xffff0000;
             in.at[x] = (!FIRST && ok) ? src[i] : 0;
             in.sc[x] = (ok && sub == 0) ? sc[i] : 0.0;
+            if constexpr (TIED) in.nd[x] = ok ? nd[i] : 0;
         }
     };
-    auto fetch_p = [&](int i0, const StepIn &in, double (&po)[2]) {
+    auto fetch_p = [&](int i0, StepIn &in, double (&po)[2]) {
 #pragma unroll
-        for (int x = 0; x < 2; ++x) po[x] = (!FIRST && i0 + tk8 + x * TG < hi) ? pin[(size_t)in.at[x] * NS + sub] : 0.0;
+        for (int x = 0; x < 2; ++x) {
+            po[x] = (!FIRST && i0 + tk8 + x * TG < hi) ? pin[(size_t)in.at[x] * NS + sub] : 0.0;
+            // (lanes 1 .. 2 e of a token; -1 in the second slot of a one-unit node, which token_step does not use; a pass without a token: node 0)
+            if constexpr (TIED) in.st[x] = (sub >= 1 && sub <= 2 * c.e) ? tie[(size_t)in.nd[x] * (2 * c.e) + sub - 1] : 0;
+        }
     };
     if (lo >= hi) return;
     StepIn in0, in1, in2;
@@ -131,7 +147,9 @@ __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, c
             const int i = i0 + tk8 + x * TG;
             double pj, best;
             int fin;
-            token_step<FIRST>(c, lt, Bs, in0.up[x], po0[x], sub, pj, best, fin);
+            int sid = 0;
+            if constexpr (TIED) sid = in0.st[x];
+            token_step<FIRST, TIED>(c, lt, Bs, in0.up[x], sid, po0[x], sub, pj, best, fin);
             if (i < hi) {
                 p[(size_t)i * NS + sub] = pj;
                 if (sub == 0) {
@@ -161,8 +179,11 @@ __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, c
 // pcl_batch_decode's kernel and does not read `lm`.  As for the left-to-right kernel, the LM = true instantiations are compiled in a
 // translation unit of their own (hmm_decode_lm.hip defines PCL_DEC_LM and includes this file), so the LM = false ones come out as they
 // did before there was a switch.
-template <bool TLDS, int KMAX, bool LM>
-__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a, DecLmArg<LM> lm) {
+// TIED (compile time): a lane's emission row comes from its node's tied states (pcl_batch_decode_tied; DecTie, hmm_decode_common.h),
+// gathered in the step by the token's node id; TIED = false reads nothing of `tie`.  The TIED = true instantiations (with and without LM)
+// have a translation unit of their own too: hmm_decode_tied.hip defines PCL_DEC_TIED and includes this file.
+template <bool TLDS, int KMAX, bool LM, bool TIED>
+__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a, DecLmArg<LM> lm, DecTieArg<TIED> tie) {
     extern __shared__ double dyn[];
     __shared__ int seg_l[SEG_LDS + 1];
     __shared__ unsigned int hist256[256];                          // pruning: the occupancy map, then the radix histogram
@@ -220,6 +241,8 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         const int u1 = (a.node_nunits[node] == 2) ? a.node_units[2 * node + 1] : 0xffff;
         return u0 | (u1 << 16);
     };
+    [[maybe_unused]] const int *tie_gen = nullptr;
+    if constexpr (TIED) tie_gen = tie.gen;
     STAMP_BEGIN
 
     // ---- frame 0: every first-character node starts (D3)
@@ -236,7 +259,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
     if (TLDS)
         for (int k = tid; k < Nb; k += DW) Bs_l[k] = B[k];
     __syncthreads();
-    step_range<true>(c, lt, TLDS ? Bs_l : B, 0, n, upb[0], nullptr, nullptr, pb[0], scb[0], flag, tk8, sub);
+    step_range<true, TIED>(c, lt, TLDS ? Bs_l : B, 0, n, upb[0], nullptr, nullptr, pb[0], scb[0], flag, tk8, sub, ndb[0], tie_gen);
     for (int i = tid; i < n; i += DW) src[i] = i;
     __syncthreads();
     if (tid == 0) a.trace[(size_t)u * a.Tmax] = n;
@@ -254,7 +277,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         const double *Bs = TLDS ? Bs_l : Bf;
         const int C = ((n + DW - 1) / DW) * 64, w0 = wave * C;     // this frame's ownership of the old tokens
         // ---- (1) every live token takes its step
-        step_range<false>(c, lt, Bs, 0, n, up, pin, src, p, sc, flag, tk8, sub);
+        step_range<false, TIED>(c, lt, Bs, 0, n, up, pin, src, p, sc, flag, tk8, sub, nd, tie_gen);
         __syncthreads();
         STAMP(0)
         // ---- (2) donors = finished tokens.  The best finished word-end token (earliest on ties) re-seeds the first
@@ -417,7 +440,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         if (created > cap - n) ovf = 1;
         STAMP(2)
         // the new tokens take their first step at once (Decoder.py:138-139)
-        step_range<true>(c, lt, Bs, n, n + n_new, up, nullptr, nullptr, p, sc, flag, tk8, sub);
+        step_range<true, TIED>(c, lt, Bs, n, n + n_new, up, nullptr, nullptr, p, sc, flag, tk8, sub, nd, tie_gen);
         STAMP(3)
         // ---- (4) pruning over the tokens that were alive before the frame and did not finish (Decoder.py:159-167): the four steps
         //      of hmm_decode_common.h; the radix histogram is the occupancy map's 256 words
@@ -510,7 +533,39 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
     STAMP_END(a.stamps)
 }
 
-#ifndef PCL_DEC_LM
+// The launch of one (LM, TIED) pair of instantiations, for the three translation units that hold them.
+template <bool LM, bool TIED>
+int dec_launch_kernel(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie) {
+    // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
+    const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)n_rows) * sizeof(double);
+    const bool tlds = table_bytes <= 44u * 1024u;
+    const int cap = a.cap;
+#define PCL_DEC_LAUNCH(K)                                                                                                                  \
+    do {                                                                                                                                   \
+        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K, LM, TIED>), dim3(U), dim3(DW), table_bytes, ctx->stream, a, lma, tie);   \
+        else hipLaunchKernelGGL((hmm_decode_kernel<false, K, LM, TIED>), dim3(U), dim3(DW), 0, ctx->stream, a, lma, tie);                  \
+    } while (0)
+    if (cap <= DW) PCL_DEC_LAUNCH(1);
+    else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
+    else if (cap <= 4 * DW) PCL_DEC_LAUNCH(4);
+    else if (cap <= 8 * DW) PCL_DEC_LAUNCH(8);
+    else PCL_DEC_LAUNCH(16);
+#undef PCL_DEC_LAUNCH
+    static_assert(PCL_DEC_MAX_KEYS_PER_LANE == 16, "the largest KMAX instantiated above");
+    return PCL_OK;
+}
+
+#if defined(PCL_DEC_TIED)
+}  // namespace
+int pcl_decode_general_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie) {
+    return lm ? dec_launch_kernel<true, true>(ctx, a, U, n_rows, *lm, tie) : dec_launch_kernel<false, true>(ctx, a, U, n_rows, DecNoLm{}, tie);
+}
+#elif defined(PCL_DEC_LM)
+}  // namespace
+int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
+    return dec_launch_kernel<true, false>(ctx, a, U, n_rows, lma, DecNoTie{});
+}
+#else
 // ---- host side of pcl_batch_decode
 
 // The decoder's workspace, described ONCE: the element counts of the batch's allocations and the offset of every array in them.
@@ -562,9 +617,13 @@ DecLayout dec_layout(int U, int cap, int candidate, int Tmax, bool use_lr) {
     return l;
 }
 
-int dec_validate(const pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens) {
+// tied: pcl_batch_decode_tied -- the rows are those of the J_t tied states the lexicon was tied under, and so must the resident model's be
+int dec_validate(const pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, bool tied) {
     pcl_ctx *ctx = b->ctx;
     if (!ctx->lex_nodes) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: pcl_lexicon_upload first");
+    if (tied && !ctx->lex_tie_Jt) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_tied: the lexicon is not tied (pcl_lexicon_tie first)");
+    if (tied && ctx->J != ctx->lex_tie_Jt)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_tied: the resident model has %d states, the lexicon was tied under J_t = %d", ctx->J, ctx->lex_tie_Jt);
     if (!b->have_B) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: no emissions (pcl_batch_score first)");
     if (!(beam > 0.0 && beam <= 1.0) || min_distinct < 1 || candidate < 1 || max_tokens < 1)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: beam %g, min_distinct %d, candidate %d, max_tokens %d", beam, min_distinct, candidate, max_tokens);
@@ -573,11 +632,13 @@ int dec_validate(const pcl_batch *b, double beam, int min_distinct, int candidat
     if (max_tokens > PCL_DEC_MAX_KEYS_PER_LANE * DW)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode: max_tokens %d > %d (a lane keeps the sort keys of its tokens in registers)", max_tokens, PCL_DEC_MAX_KEYS_PER_LANE * DW);
     // the emission rows must be [entry, state 0 .. J-1, exit]: the all-state matrix
-    const int J = ctx->n_units * (ctx->S - 2);
+    const int J = tied ? ctx->lex_tie_Jt : ctx->n_units * (ctx->S - 2);
     for (int u = 0; u < b->U; ++u) {
         const UttDesc &d = b->utt[u];
         bool ok = d.N == J + 2 && (int)b->row_state.size() >= d.vec_off + d.N;
         for (int n = 0; ok && n < d.N; ++n) ok = b->row_state[d.vec_off + n] == (n == 0 ? PCL_ROW_ENTRY : n == d.N - 1 ? PCL_ROW_EXIT : n - 1);
+        if (!ok && tied)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode_tied: utterance %d is not an all-state batch of J_t + 2 = %d rows (entry, 0..%d, exit)", u, J + 2, J - 1);
         if (!ok) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: utterance %d is not an all-state batch (rows entry, 0..%d, exit)", u, J - 1);
     }
     return PCL_OK;
@@ -657,33 +718,8 @@ DecArgs dec_fill_args(const pcl_batch *b, const DecLayout &l, double beam, int m
 
 int dec_launch_general(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm) {
     if (lm) return pcl_decode_general_launch_lm(ctx, a, U, n_rows, *lm);     // (hmm_decode_lm.hip)
-    constexpr bool LM = false;
-    const DecNoLm lma;
-#else
-}  // namespace
-int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
-    constexpr bool LM = true;
-#endif
-    // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
-    const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)n_rows) * sizeof(double);
-    const bool tlds = table_bytes <= 44u * 1024u;
-    const int cap = a.cap;
-#define PCL_DEC_LAUNCH(K)                                                                                                      \
-    do {                                                                                                                       \
-        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K, LM>), dim3(U), dim3(DW), table_bytes, ctx->stream, a, lma);  \
-        else hipLaunchKernelGGL((hmm_decode_kernel<false, K, LM>), dim3(U), dim3(DW), 0, ctx->stream, a, lma);                 \
-    } while (0)
-    if (cap <= DW) PCL_DEC_LAUNCH(1);
-    else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
-    else if (cap <= 4 * DW) PCL_DEC_LAUNCH(4);
-    else if (cap <= 8 * DW) PCL_DEC_LAUNCH(8);
-    else PCL_DEC_LAUNCH(16);
-#undef PCL_DEC_LAUNCH
-    static_assert(PCL_DEC_MAX_KEYS_PER_LANE == 16, "the largest KMAX instantiated above");
-    return PCL_OK;
+    return dec_launch_kernel<false, false>(ctx, a, U, n_rows, DecNoLm{}, DecNoTie{});
 }
-
-#ifndef PCL_DEC_LM
 
 #ifdef PCL_DEC_STAMPS
 int dec_print_stamps(pcl_ctx *ctx, DevBuf<long long> &d_stamps) {
@@ -702,6 +738,9 @@ void pcl_lexicon_release(pcl_ctx *ctx) {
     static_cast<LexiconDev &>(*ctx) = {};                // (the language model's tables with it)
     ctx->lex_nodes = ctx->lex_nroots = 0;
     ctx->lex_word_host.clear();
+    ctx->lex_units_host.clear();
+    ctx->lex_nunits_host.clear();
+    ctx->lex_tie_Jt = ctx->lex_tie_P = 0;                // (the tied states went with LexiconDev)
     ctx->lm_W = 0;
 }
 
@@ -764,6 +803,8 @@ int pcl_lexicon_upload(pcl_ctx *ctx, int n_nodes, const int32_t *node_units, con
     ctx->lex_nodes = n_nodes;
     ctx->lex_nroots = n_roots;
     ctx->lex_word_host.assign(node_word, node_word + n_nodes);
+    ctx->lex_units_host.assign(node_units, node_units + 2 * (size_t)n_nodes);
+    ctx->lex_nunits_host.assign(node_nunits, node_nunits + n_nodes);
     return PCL_OK;
 }
 
@@ -822,12 +863,15 @@ int pcl_lm_upload(pcl_ctx *ctx, int W, const double *uni, const double *bow, con
     return PCL_OK;
 }
 
-// pcl_batch_decode (with_lm = false: the LM = false kernels, nothing of the language model is touched) and pcl_batch_decode_lm
-static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, bool with_lm) {
+// pcl_batch_decode (with_lm = false: the LM = false kernels, nothing of the language model is touched), pcl_batch_decode_lm, and
+// pcl_batch_decode_tied (tied: the TIED = true kernels of either)
+static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, bool with_lm,
+                   bool tied = false) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
-    TRY(dec_validate(b, beam, min_distinct, candidate, max_tokens));
-    if (with_lm && !ctx->lm_W) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_lm: no language model (pcl_lm_upload after pcl_lexicon_upload)");
+    TRY(dec_validate(b, beam, min_distinct, candidate, max_tokens, tied));
+    if (with_lm && !ctx->lm_W)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no language model (pcl_lm_upload after pcl_lexicon_upload)", tied ? "pcl_batch_decode_tied" : "pcl_batch_decode_lm");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (b->dp_pending) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_dp, 0));
@@ -836,11 +880,11 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
     // Like the forward-backward recursion, the decoder does no matrix work and is latency / bandwidth bound: it runs on
     // the second stream, beside the scoring of the next chunk on the main one (every later call on this batch joins it).
     auto launch = [&]() -> int {                                               // (on ctx->stream: the second stream when dp_async)
-        const int cap = max_tokens, U = b->U, n_rows = ctx->n_units * (ctx->S - 2) + 2;
+        const int cap = max_tokens, U = b->U, n_rows = (tied ? ctx->lex_tie_Jt : ctx->n_units * (ctx->S - 2)) + 2;
         // left-to-right units (every model the reference builds): one lane per token, hmm_decode_lr.hip; PCL_DEC_GENERAL=1 keeps
         // the general kernel (the parity tests run both against the restatement)
         const char *force_general = getenv("PCL_DEC_GENERAL");
-        const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, n_rows, cap, b->Tmax);
+        const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, n_rows, cap, b->Tmax, tied);
         const DecLayout l = dec_layout(U, cap, candidate, b->Tmax, use_lr);
         TRY(dec_ensure_workspace(b, l, cap, candidate));
         DecArgs a = dec_fill_args(b, l, beam, min_distinct, candidate, cap, logpi_one_unit, logpi_two_units);
@@ -858,7 +902,10 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
         a.stamps = d_stamps;
 #endif
         pcl_timer_begin(ctx, "decode");
-        const int rc = use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows, with_lm ? &lm : nullptr) : dec_launch_general(ctx, a, U, n_rows, with_lm ? &lm : nullptr);
+        const DecLm *lmp = with_lm ? &lm : nullptr;
+        const DecTie tie{ctx->lex_tie_lr, ctx->lex_tie_gen};
+        const int rc = tied ? (use_lr ? pcl_decode_lr_launch_tied(ctx, a, U, n_rows, lmp, tie) : pcl_decode_general_launch_tied(ctx, a, U, n_rows, lmp, tie))
+                            : (use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows, lmp) : dec_launch_general(ctx, a, U, n_rows, lmp));
         pcl_timer_end(ctx, "decode");
         TRY(rc);
         HIPCHK(ctx, hipGetLastError());
@@ -886,11 +933,15 @@ int pcl_batch_decode_lm(pcl_batch *b, double beam, int min_distinct, int candida
     return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, true);
 }
 
+int pcl_batch_decode_tied(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, int lm) {
+    return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, lm != 0, true);
+}
+
 // the chosen words of the history entries, on the stream the decoder ran on (before or after pcl_batch_decode_get)
 int pcl_batch_decode_get_words(pcl_batch *b, int32_t *hist_word) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
-    if (!b->have_dec || !b->dec_has_words) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_get_words: run pcl_batch_decode_lm first");
+    if (!b->have_dec || !b->dec_has_words) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_get_words: run pcl_batch_decode_lm (or pcl_batch_decode_tied with lm) first");
     if (!hist_word) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode_get_words: hist_word is NULL");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = b->dp_pending ? ctx->stream_dp : ctx->stream;
@@ -930,4 +981,4 @@ int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *
 }
 
 }  // extern "C"
-#endif  // PCL_DEC_LM
+#endif  // the kernel-only translation units (PCL_DEC_LM, PCL_DEC_TIED)

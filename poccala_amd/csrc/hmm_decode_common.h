@@ -50,6 +50,18 @@ struct DecNoLm {};                  // what the LM = false kernels take in its p
 template <bool LM>
 using DecLmArg = std::conditional_t<LM, DecLm, DecNoLm>;
 
+// The lexicon's tied states (pcl_lexicon_tie; tying.hip) for the TIED = true instantiations of the two kernels (pcl_batch_decode_tied): the
+// emission row of state position k of unit slot j of a token at node n is 1 + node_state[n][j P + k] instead of 1 + unit (S - 2) + k.  Like
+// DecLm a kernel argument of its own: DecArgs and the TIED = false kernels stay what they were.  Both forms are indexed by the node id the
+// step has at hand anyway (one gather per token and step; DESIGN.md says what carrying the ids in the token arrays would cost instead).
+struct DecTie {
+    const int4 *lr;                 // [n_nodes] six 16-bit ids (s0 | s1 << 16, s2 | s3 << 16, s4 | s5 << 16, 0); a one-unit node repeats slot 0 in slot 1
+    const int *gen;                 // [n_nodes][2 P] int32, -1 in slot 1 of a one-unit node: lane `sub` of a token reads entry sub - 1
+};
+struct DecNoTie {};
+template <bool TIED>
+using DecTieArg = std::conditional_t<TIED, DecTie, DecNoTie>;
+
 constexpr int PCL_DEC_N_STAMP = 8;
 // A lane keeps the sort keys of the old tokens it owns in registers through the pruning phase, at most this many: a kernel of NT
 // threads takes cap <= 16 NT tokens per utterance.  The general kernel's 16 x 1024 is what pcl_batch_decode accepts; the
@@ -454,7 +466,11 @@ __device__ __forceinline__ int pcl_transfer(int n, int candidate, const double *
 
 // hmm_decode_lr.hip: true when every unit matrix is left-to-right (row 0 reaches state 1 only, an emitting state itself and
 // its successor only) and S = 5 -- then the fast kernel gives the general kernel's bits and pcl_decode_lr_launch runs it.
-bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max);
+// tied: n_rows = J_t + 2 (the two staged emission rows), and the state ids must fit DecTie::lr's 16 bits.
+bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max, bool tied = false);
 int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm = nullptr);   // lm: the LM = true instantiation ...
 int pcl_decode_lr_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lm);           // ... which hmm_decode_lr_lm.hip holds
 int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lm);      // the general kernel's, hmm_decode_lm.hip
+// the TIED = true instantiations, with (lm) and without (nullptr) the language model: hmm_decode_lr_tied.hip, hmm_decode_tied.hip
+int pcl_decode_lr_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie);
+int pcl_decode_general_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie);

@@ -60,13 +60,27 @@ constexpr size_t POOL_BYTES = LIST_BYTES > SEL_BYTES ? LIST_BYTES : SEL_BYTES;
 // One step of one token by one lane.  first: p = ln pi + B[:,t] (Decoder.py:270); else the max recursion (:278-283) in the
 // general kernel's operand order (predecessor i ascending: the state before, then the state itself).  best = max_j p_j,
 // fin (D1) <=> the FIRST argmax is the last emitting state.
-__device__ __forceinline__ void lr_step(const double *tab, const double *Bs, int up, bool first, bool fresh, double lpi1, double lpi2,
-                                        const double (&po)[NE], double (&pn)[NE], double &best, int &fin) {
+// TIED: the six emission rows are 1 + the node's tied states (st = DecTie::lr[node]: a one-unit node repeats its first three, as b1 = b0
+// does below); the transitions stay the centre units' (up).
+template <bool TIED>
+__device__ __forceinline__ void lr_step(const double *tab, const double *Bs, int up, [[maybe_unused]] const int4 &st, bool first, bool fresh,
+                                        double lpi1, double lpi2, const double (&po)[NE], double (&pn)[NE], double &best, int &fin) {
     const int u0 = up & 0xffff, u1r = (int)((unsigned int)up >> 16);
     const bool two = u1r != 0xffff;
     const int u1 = two ? u1r : u0;
     const double *t0 = tab + u0 * TS, *t1 = tab + u1 * TS;
-    const double *b0 = Bs + 1 + u0 * E, *b1 = Bs + 1 + u1 * E;
+    [[maybe_unused]] const double *c0 = Bs + 1 + u0 * E, *c1 = Bs + 1 + u1 * E;
+    [[maybe_unused]] const double *r = Bs + 1;
+    struct Row {                                                   // b[k]: the emission of state position k of a unit slot
+        const double *c, *r;
+        unsigned int i0, i1, i2;
+        __device__ __forceinline__ double operator[](int k) const {
+            if constexpr (TIED) return r[k == 0 ? i0 : k == 1 ? i1 : i2];
+            else return c[k];
+        }
+    };
+    const Row b0{c0, r, (unsigned int)st.x & 0xffffu, (unsigned int)st.x >> 16, (unsigned int)st.y & 0xffffu};
+    const Row b1{c1, r, (unsigned int)st.y >> 16, (unsigned int)st.z & 0xffffu, (unsigned int)st.z >> 16};
     const double lpi = two ? lpi2 : lpi1;
     const double ninf = -INFINITY;
     if (first) {
@@ -110,8 +124,12 @@ __device__ __forceinline__ void lr_step(const double *tab, const double *Bs, int
 // units -- this file for LM = false; hmm_decode_lr_lm.hip defines PCL_DECLR_LM and includes this file for LM = true: with both in one
 // module the compiler schedules and allocates the LM = false kernels differently (same source, 4 more spilled registers at KMAX = 16,
 // 40.8 -> 43.5 ms per C5 shard), alone they come out instruction for instruction as before there was a switch.
-template <int KMAX, bool LM>
-__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP, DecLmArg<LM> lm) {
+// TIED (compile time): the emission rows of a token are those of its node's tied states (pcl_batch_decode_tied; DecTie, hmm_decode_common.h),
+// gathered from the per-node table by the node id each phase has at hand.  TIED = false reads nothing of `tie`.  For the same reason as
+// above the TIED = true instantiations (with and without LM) have a translation unit of their own: hmm_decode_lr_tied.hip defines
+// PCL_DECLR_TIED and includes this file.
+template <int KMAX, bool LM, bool TIED>
+__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP, DecLmArg<LM> lm, DecTieArg<TIED> tie) {
     extern __shared__ double dyn[];                                // unit table [n_units][TS] | two emission rows [NbP]
     // one pool, two tenants: the donor lists (phases A - C) and the pruning select's histogram + candidates (phase E)
     __shared__ __attribute__((aligned(16))) unsigned char pool[POOL_BYTES];
@@ -181,7 +199,9 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         const int4 info = ninfo[node];
         double po[NE] = {0, 0, 0, 0, 0, 0}, pn[NE], best;
         int fin;
-        lr_step(tab, Bsl, info.w, true, false, lpi1, lpi2, po, pn, best, fin);
+        int4 st = make_int4(0, 0, 0, 0);
+        if constexpr (TIED) st = tie.lr[node];
+        lr_step<TIED>(tab, Bsl, info.w, st, true, false, lpi1, lpi2, po, pn, best, fin);
 #pragma unroll
         for (int j = 0; j < NE; ++j) pb(0)[(size_t)j * cap + i] = pn[j];
         scb(0)[i] = 0.0 + best;
@@ -256,6 +276,11 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                         mu[g] = ok ? up_o[s] : (int)0xffff0000;
                         so[g] = ok ? sc_o[s] : 0.0;
                     }
+                    [[maybe_unused]] int4 ms[G];                   // TIED: the nodes' tied states (a lane without a token reads node 0's)
+                    if constexpr (TIED) {
+#pragma unroll
+                        for (int g = 0; g < G; ++g) ms[g] = tie.lr[mn[g]];
+                    }
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
                         if ((kb + g) * 64 < C) {                   // (wave-uniform)
@@ -263,7 +288,9 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                             const bool ok = i < n;
                             double pn[NE], best;
                             int fin;
-                            lr_step(tab, Bs, mu[g], false, srcv[kb + g] < 0, lpi1, lpi2, po[g], pn, best, fin);
+                            int4 st = make_int4(0, 0, 0, 0);
+                            if constexpr (TIED) st = ms[g];
+                            lr_step<TIED>(tab, Bs, mu[g], st, false, srcv[kb + g] < 0, lpi1, lpi2, po[g], pn, best, fin);
                             const double sn = so[g] + best;        // score += max_j p_j (Decoder.py:285)
                             if (ok) {
 #pragma unroll
@@ -407,6 +434,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         int created = 0;
         for (int qc = 0; qc < Q; qc += PMAX * LW) {
             int child[PMAX], dh[PMAX], sidx[PMAX], upn[PMAX];
+            [[maybe_unused]] int4 stn[PMAX];
             double ds[PMAX];
             bool val[PMAX];
 #pragma unroll
@@ -463,6 +491,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                 const int sv = val[x] ? slot[child[x]] : -1;       // this frame's stamp, or the node has no live token
                 sidx[x] = (sv >= 0 && (sv >> SLOT_BITS) == t) ? (sv & ((1 << SLOT_BITS) - 1)) : -1;
                 upn[x] = val[x] ? ninfo[child[x]].w : 0;
+                if constexpr (TIED) stn[x] = tie.lr[child[x]];         // (child = 0 without a pair)
             }
             unsigned long long nmask[PMAX];
 #pragma unroll
@@ -486,7 +515,9 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                     if (pos < cap) {                               // (slots n .. cap-1 of the current buffers)
                         double po[NE] = {0, 0, 0, 0, 0, 0}, pn[NE], best;
                         int fin;
-                        lr_step(tab, Bs, upn[x], true, false, lpi1, lpi2, po, pn, best, fin);
+                        int4 st = make_int4(0, 0, 0, 0);
+                        if constexpr (TIED) st = stn[x];
+                        lr_step<TIED>(tab, Bs, upn[x], st, true, false, lpi1, lpi2, po, pn, best, fin);
 #pragma unroll
                         for (int j = 0; j < NE; ++j) p[(size_t)j * cap + pos] = pn[j];
                         sc[pos] = ds[x] + best;
@@ -593,13 +624,38 @@ size_t lr_dyn_bytes(const pcl_ctx *ctx, int n_rows) {
     return ((size_t)((ctx->n_units * TS + 1) & ~1) + 2 * (size_t)NbP) * sizeof(double);
 }
 
+template <bool LM, bool TIED>
+int lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie) {
+    const int cap = a.cap, NbP = (n_rows + 1) & ~1;
+    const size_t dyn = lr_dyn_bytes(ctx, n_rows);
+#define PCL_DECLR_LAUNCH(K)                                                                                                             \
+    do {                                                                                                                                \
+        if (dyn + LR_STATIC_LDS > 64u * 1024u)                                                                                          \
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K, LM, TIED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+        hipLaunchKernelGGL((hmm_decode_lr_kernel<K, LM, TIED>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP, lma, tie);                 \
+    } while (0)
+    if (cap <= 8 * LW) PCL_DECLR_LAUNCH(8);
+    else PCL_DECLR_LAUNCH(16);
+#undef PCL_DECLR_LAUNCH
+    return PCL_OK;
+}
+
 }  // namespace
 
-#ifndef PCL_DECLR_LM
-bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max) {
+#if defined(PCL_DECLR_TIED)
+int pcl_decode_lr_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie) {
+    return lm ? lr_launch<true, true>(ctx, a, U, n_rows, *lm, tie) : lr_launch<false, true>(ctx, a, U, n_rows, DecNoLm{}, tie);
+}
+#elif defined(PCL_DECLR_LM)
+int pcl_decode_lr_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
+    return lr_launch<true, false>(ctx, a, U, n_rows, lma, DecNoTie{});
+}
+#else
+bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max, bool tied) {
     if (ctx->S != 5 || cap > PCL_DEC_MAX_KEYS_PER_LANE * LW || cap > (1 << SLOT_BITS)) return false;
     if (t_max >= (1 << (31 - SLOT_BITS))) return false;            // (the frame stamp of the node -> token map: utterances of up to 131071 frames)
     if (lr_dyn_bytes(ctx, n_rows) + LR_STATIC_LDS > LR_LDS_BUDGET) return false;
+    if (tied && n_rows - 2 > 0x10000) return false;                // (DecTie::lr packs a state id into 16 bits)
     const double *lt = ctx->unit_logtrans.data();
     for (int u = 0; u < ctx->n_units; ++u)
         for (int r = 0; r <= E; ++r)                                // (the exit row takes no part in a sentence HMM)
@@ -612,22 +668,6 @@ bool pcl_decode_lr_applicable(const pcl_ctx *ctx, int n_rows, int cap, int t_max
 
 int pcl_decode_lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm) {
     if (lm) return pcl_decode_lr_launch_lm(ctx, a, U, n_rows, *lm);           // (hmm_decode_lr_lm.hip)
-    constexpr bool LM = false;
-    const DecNoLm lma;
-#else
-int pcl_decode_lr_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm &lma) {
-    constexpr bool LM = true;
-#endif
-    const int cap = a.cap, NbP = (n_rows + 1) & ~1;
-    const size_t dyn = lr_dyn_bytes(ctx, n_rows);
-#define PCL_DECLR_LAUNCH(K)                                                                                                       \
-    do {                                                                                                                          \
-        if (dyn + LR_STATIC_LDS > 64u * 1024u)                                                                                    \
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K, LM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-        hipLaunchKernelGGL((hmm_decode_lr_kernel<K, LM>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP, lma);                      \
-    } while (0)
-    if (cap <= 8 * LW) PCL_DECLR_LAUNCH(8);
-    else PCL_DECLR_LAUNCH(16);
-#undef PCL_DECLR_LAUNCH
-    return PCL_OK;
+    return lr_launch<false, false>(ctx, a, U, n_rows, DecNoLm{}, DecNoTie{});
 }
+#endif

@@ -158,6 +158,10 @@ struct LexiconDev {
     DevBuf<double> lm_uni, lm_bow, lm_val;
     DevBuf<long long> lm_row_ptr;
     DevBuf<int> lm_col, lm_node_word_ptr, lm_node_word_ids;
+    // the nodes' tied states (pcl_lexicon_tie, tying.hip; DecTie, hmm_decode_common.h): a snapshot of the walks under the tying that was
+    // resident then, gone with the tree or with pcl_lexicon_untie
+    DevBuf<int> lex_tie_gen;                      // [lex_nodes][2 P] int32, -1 in slot 1 of a one-unit node: node_state as pcl_lexicon_states returns it
+    DevBuf<int4> lex_tie_lr;                      // [lex_nodes] the same ids, 16 bits each, for the left-to-right kernel
 };
 
 // Resident tying (tying.hip): a decision tree's node arrays in the layouts the walk reads.  Replaced as a whole by pcl_tying_upload, gone with
@@ -270,6 +274,8 @@ struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev, TyingDev
     // pronunciation tree for the decoder (LexiconDev)
     int lex_nodes = 0, lex_nroots = 0;
     std::vector<int> lex_word_host;                  // node_word as uploaded: pcl_lm_upload checks its node -> word lists against it
+    std::vector<int> lex_units_host, lex_nunits_host;   // node_units (n, 2) / node_nunits as uploaded: pcl_lexicon_tie checks the centres against them
+    int lex_tie_Jt = 0, lex_tie_P = 0;               // J_t and P of the tying the lexicon was tied under (0: not tied)
     int lm_W = 0;                                    // words of the resident language model (0: none)
     // resident tying (TyingDev): ty_N = 0 means none
     int ty_N = 0, ty_Q = 0, ty_W = 0, ty_R0 = 0, ty_Jt = 0, ty_P = 0, ty_units = 0;
@@ -578,6 +584,7 @@ void pcl_tree_release(pcl_ctx *ctx);                 // the tree statistics (the
 int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state);
 int pcl_launch_tied_owner(pcl_ctx *ctx, pcl_batch *b, int P, int32_t *d_frame_state);
 void pcl_tying_release(pcl_ctx *ctx);                // the resident tying
+void pcl_lexicon_untie_release(pcl_ctx *ctx);        // the lexicon's tied states (tying.hip)
 int pcl_launch_transpose(pcl_ctx *ctx, pcl_batch *b, const double *src, double *dst, int to_time_major);
 int pcl_score_tile_frames(int D, int precision);
 int pcl_launch_score_mfma(pcl_ctx *ctx, pcl_batch *b, const ScoreTile *tiles, int n_tiles);

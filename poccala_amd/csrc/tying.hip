@@ -97,6 +97,45 @@ __global__ __launch_bounds__(256) void tied_owner_kernel(const UttDesc *__restri
     }
 }
 
+// pcl_lexicon_tie: one thread per (lexicon node, unit slot, state position) runs the walk of tying_lookup_kernel on the node's context
+// node_ctx (n_nodes, 2, 3); slot 1 of a one-unit node gets -1.  gen (n_nodes, 2 P) is what pcl_lexicon_states returns and the general decode
+// kernel reads.
+template <bool LDS>
+__global__ __launch_bounds__(256) void lexicon_tie_kernel(const int4 *__restrict__ nodes, const unsigned int *__restrict__ qbits, const int *__restrict__ root_of,
+                                                          int P, int Q, int W, int n_nodes, const int32_t *__restrict__ node_ctx,
+                                                          const int *__restrict__ node_nunits, int *__restrict__ gen) {
+    const unsigned int *qb = tying_qbits<LDS>(qbits, Q * W);
+    const long long n_items = (long long)n_nodes * 2 * P;
+    for (long long w = blockIdx.x * 256LL + threadIdx.x; w < n_items; w += gridDim.x * 256LL) {
+        const long long slot = w / P;                              // node * 2 + j
+        const int k = (int)(w - slot * P), j = (int)(slot & 1);
+        int st = -1;
+        if (j < node_nunits[slot >> 1]) {
+            const int l = node_ctx[3 * slot], c = node_ctx[3 * slot + 1], r = node_ctx[3 * slot + 2];
+            st = tying_walk(nodes, qb, Q, W, root_of[c * P + k], l, c, r);
+        }
+        gen[w] = st;
+    }
+}
+
+// ... and the same ids as the left-to-right decode kernel reads them (DecTie::lr; P = 3 there): six 16-bit fields per node, a one-unit
+// node repeats slot 0 in slot 1 (the kernel reads both and drops the second).  Zero for another P: that kernel does not apply then.
+__global__ __launch_bounds__(256) void lexicon_tie_pack_kernel(int n_nodes, int P, const int *__restrict__ gen, int4 *__restrict__ lr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_nodes) return;
+    int4 v = make_int4(0, 0, 0, 0);
+    if (P == 3) {
+        unsigned int s[6];
+#pragma unroll
+        for (int x = 0; x < 6; ++x) {
+            const int a = gen[(size_t)i * 6 + x];
+            s[x] = (unsigned int)(a >= 0 ? a : gen[(size_t)i * 6 + x - 3]) & 0xffffu;
+        }
+        v = make_int4((int)(s[0] | s[1] << 16), (int)(s[2] | s[3] << 16), (int)(s[4] | s[5] << 16), 0);
+    }
+    lr[i] = v;
+}
+
 size_t qbits_shm(const pcl_ctx *ctx) {
     const size_t bytes = (size_t)ctx->ty_Q * ctx->ty_W * sizeof(unsigned int);
     return bytes <= (size_t)TY_QBITS_LDS ? bytes : 0;
@@ -107,6 +146,12 @@ size_t qbits_shm(const pcl_ctx *ctx) {
 void pcl_tying_release(pcl_ctx *ctx) {
     static_cast<TyingDev &>(*ctx) = {};
     ctx->ty_N = ctx->ty_Q = ctx->ty_W = ctx->ty_R0 = ctx->ty_Jt = ctx->ty_P = ctx->ty_units = 0;
+}
+
+void pcl_lexicon_untie_release(pcl_ctx *ctx) {
+    ctx->lex_tie_gen.release();
+    ctx->lex_tie_lr.release();
+    ctx->lex_tie_Jt = ctx->lex_tie_P = 0;
 }
 
 int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state) {
@@ -201,6 +246,86 @@ int pcl_batch_get_states(pcl_batch *b, int32_t *row_state, int32_t *pos_state) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (row_state) HIPCHK(ctx, pcl_d2h_queue(ctx, row_state, b->d_row_state, (size_t)b->sumN * sizeof(int32_t)));
     if (pos_state) HIPCHK(ctx, pcl_d2h_queue(ctx, pos_state, b->pos_state, b->pos_state.cap * sizeof(int32_t)));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PCL_OK;
+}
+
+int pcl_lexicon_tie(pcl_ctx *ctx, const int32_t *node_ctx) {
+    if (!ctx) return PCL_ERR_INVALID;
+    const char *who = "pcl_lexicon_tie";
+    if (!ctx->lex_nodes) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no resident lexicon: pcl_lexicon_upload first", who);
+    if (!ctx->ty_N) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no resident tying: pcl_tying_upload first", who);
+    if (!node_ctx) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: node_ctx is NULL", who);
+    const int nu = ctx->ty_units, P = ctx->ty_P, n_nodes = ctx->lex_nodes;
+    if (P != ctx->S - 2 || nu != ctx->n_units)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the tying has %d units of P = %d state positions, the unit inventory %d units of %d emitting states", who, nu, P,
+                 ctx->n_units, ctx->S - 2);
+    for (int i = 0; i < n_nodes; ++i)
+        for (int j = 0; j < ctx->lex_nunits_host[i]; ++j) {
+            const int32_t *c = node_ctx + 3 * (2 * (size_t)i + j);
+            if (c[1] != ctx->lex_units_host[2 * (size_t)i + j])
+                PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: node %d slot %d: centre %d is not the node's unit %d", who, i, j, c[1], ctx->lex_units_host[2 * (size_t)i + j]);
+            if (c[0] < 0 || c[0] > nu || c[2] < 0 || c[2] > nu)
+                PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: node %d slot %d: neighbours (%d, %d) outside [0,%d]", who, i, j, c[0], c[2], nu);
+        }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));             // (a decoder may still be reading the old states on the second stream)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // the new states are complete on the device before the resident ones are touched
+    DevBuf<int32_t> d_ctx;
+    DevBuf<int> gen;
+    DevBuf<int4> lr;
+    const size_t items = (size_t)n_nodes * 2 * P;
+    auto run = [&]() -> int {
+        TRY(d_ctx.alloc(ctx, (size_t)n_nodes * 6));
+        TRY(gen.alloc(ctx, items));
+        TRY(lr.alloc(ctx, (size_t)n_nodes));
+        HIPCHK(ctx, hipMemcpyAsync(d_ctx, node_ctx, (size_t)n_nodes * 6 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        const unsigned grid = (unsigned)std::min<size_t>((items + 255) / 256, 1024);
+        const size_t shm = qbits_shm(ctx);
+        pcl_timer_begin(ctx, "lexicon_tie");
+        if (shm)
+            hipLaunchKernelGGL(lexicon_tie_kernel<true>, dim3(grid), dim3(256), shm, ctx->stream, ctx->ty_nodes.p, ctx->ty_qbits.p, ctx->ty_root.p, P, ctx->ty_Q,
+                               ctx->ty_W, n_nodes, d_ctx.p, ctx->lex_nunits.p, gen.p);
+        else
+            hipLaunchKernelGGL(lexicon_tie_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, ctx->ty_nodes.p, ctx->ty_qbits.p, ctx->ty_root.p, P, ctx->ty_Q,
+                               ctx->ty_W, n_nodes, d_ctx.p, ctx->lex_nunits.p, gen.p);
+        hipLaunchKernelGGL(lexicon_tie_pack_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, ctx->stream, n_nodes, P, gen.p, lr.p);
+        pcl_timer_end(ctx, "lexicon_tie");
+        HIPCHK(ctx, hipGetLastError());
+        return PCL_OK;
+    };
+    int rc = run();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PCL_OK) {      // (on every path: the frees below rely on it)
+        pcl_set_error(ctx, "pcl_lexicon_tie: HIP error");
+        rc = PCL_ERR_HIP;
+    }
+    pcl_free_synced_scope done;
+    d_ctx.release();
+    if (rc != PCL_OK) return rc;
+    ctx->lex_tie_gen = std::move(gen);
+    ctx->lex_tie_lr = std::move(lr);
+    ctx->lex_tie_Jt = ctx->ty_Jt;
+    ctx->lex_tie_P = P;
+    return PCL_OK;
+}
+
+int pcl_lexicon_untie(pcl_ctx *ctx) {
+    if (!ctx) return PCL_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream_dp));             // (a tied decode may still be reading them)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    pcl_lexicon_untie_release(ctx);
+    return PCL_OK;
+}
+
+int pcl_lexicon_states(pcl_ctx *ctx, int32_t *node_state) {
+    if (!ctx) return PCL_ERR_INVALID;
+    const char *who = "pcl_lexicon_states";
+    if (!ctx->lex_nodes || !ctx->lex_tie_Jt) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the lexicon is not tied (pcl_lexicon_tie first)", who);
+    if (!node_state) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: node_state is NULL", who);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, pcl_d2h_queue(ctx, node_state, ctx->lex_tie_gen, (size_t)ctx->lex_nodes * 2 * ctx->lex_tie_P * sizeof(int32_t)));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }

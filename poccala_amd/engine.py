@@ -439,6 +439,34 @@ class Engine(object):
         ro = as_c(tree['roots'], np.int32)
         self._check(self._lib.pcl_lexicon_upload(self._ctx, len(nn), ptr(nu), ptr(nn), ptr(cp), ptr(ci), ptr(nw), len(ro), ptr(ro)))
         self.n_nodes = len(nn)
+        self._lex_tree = dict(node_units=nu.copy(), node_nunits=nn.copy(), child_ptr=cp.copy(), child_idx=ci[:int(cp[-1])].copy())
+
+    def tie_lexicon(self, node_ctx=None):
+        """Tied states of every (node, unit slot, state position) of the loaded pronunciation tree under the resident tying (load_tying;
+        pcl_lexicon_tie), kept beside the tree for Batch.decode(tied=True): a snapshot, as for tied batches.  node_ctx (n_nodes, 2, 3)
+        int32 = (left, centre, right); None: the default rule, PronunciationLexicon.node_contexts of the tree load_lexicon took."""
+        if node_ctx is None:
+            from .Lexicon.PronunciationLexicon import node_contexts
+            tree = getattr(self, '_lex_tree', None)
+            if tree is None:
+                raise ValueError('tie_lexicon: no pronunciation tree (load_lexicon first)')
+            node_ctx = node_contexts(tree, self.n_units)
+        c = as_c(node_ctx, np.int32)
+        if c.shape != (getattr(self, 'n_nodes', 0), 2, 3):
+            raise ValueError('node_ctx must be (n_nodes, 2, 3) = (%d, 2, 3), got %r' % (getattr(self, 'n_nodes', 0), c.shape))
+        self._check(self._lib.pcl_lexicon_tie(self._ctx, ptr(c)))
+        self._lex_tie_P = int(self.tying_P)
+
+    def untie_lexicon(self):
+        """Remove the tree's tied states (pcl_lexicon_untie); nothing happens when there are none."""
+        self._check(self._lib.pcl_lexicon_untie(self._ctx))
+
+    def lexicon_states(self):
+        """The kept tied states (pcl_lexicon_states): (n_nodes, 2 P) int32, -1 in the second slot of a one-unit node."""
+        P = int(getattr(self, '_lex_tie_P', 0)) or max(int(getattr(self, 'S', 2)) - 2, 1)   # (not tied: the library refuses)
+        out = np.empty((max(int(getattr(self, 'n_nodes', 0)), 1), 2 * P), dtype=np.int32)
+        self._check(self._lib.pcl_lexicon_states(self._ctx, ptr(out)))
+        return out[:self.n_nodes]
 
     def load_language_model(self, compiled):
         """The tables of LanguageModel.Ngram.compile (pre-scaled, ARPA-shaped; rule D6 in include/poccala_hip.h) for the loaded tree:
@@ -1107,20 +1135,24 @@ class Batch(object):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
         self._check(self._lib.pcl_batch_accumulate_hmm(self._b))
 
-    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False):
+    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False):
         """Token passing over the loaded pronunciation tree (Decoder.py:91-167, 250-288) for every utterance of an all-state
         batch.  Returns a list (one dict per utterance): final = [(node, score, hist)] best first, history = [(prev, node)],
         n_tokens (T,) live tokens after every frame, overflow.  lm=True: with the loaded language model at word ends
-        (Engine.load_language_model); history entries are then (prev, node, chosen word id)."""
-        self.decode_launch(beam, min_distinct, candidate, max_tokens, lm)
+        (Engine.load_language_model); history entries are then (prev, node, chosen word id).  tied=True: the emission rows are the
+        tied states Engine.tie_lexicon kept for the tree (pcl_batch_decode_tied): the model and the batch's rows are the tying's J_t states."""
+        self.decode_launch(beam, min_distinct, candidate, max_tokens, lm, tied)
         return self.decode_results()
 
-    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False):
+    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False):
         """Queue the token passing (on the library's second stream, behind this batch's scoring) and return at once."""
         e = self.eng.S - 2
         lp = np.log(np.array([1.0 / (e + 2), 1.0 / (2 * e + 2)]))               # np.log(np.ones(N) / N), AcousticModel.py:1005
-        launch = self._lib.pcl_batch_decode_lm if lm else self._lib.pcl_batch_decode
-        self._check(launch(self._b, float(beam), int(min_distinct), int(candidate), int(max_tokens), float(lp[0]), float(lp[1])))
+        args = (self._b, float(beam), int(min_distinct), int(candidate), int(max_tokens), float(lp[0]), float(lp[1]))
+        if tied:
+            self._check(self._lib.pcl_batch_decode_tied(*(args + (1 if lm else 0,))))
+        else:
+            self._check((self._lib.pcl_batch_decode_lm if lm else self._lib.pcl_batch_decode)(*args))
         self._dec_candidate, self._dec_lm = int(candidate), bool(lm)
 
     def decode_fetch(self):
