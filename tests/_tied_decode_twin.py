@@ -35,15 +35,24 @@ def identity_tree(n_units, P):
     return make_tree(P, n_units, np.zeros((1, n_units + 1), dtype=np.uint8), np.full(n, -1), np.full((n, 2), -1), np.arange(n), np.arange(n))
 
 
-def random_tree(n_units, P, seed, odd_states):
+def random_tree(n_units, P, seed, odd_states, wide=False):
     """A hand-grown tying: units 0 and 1 share their roots (a state shared across units), questions on the left, centre and right
-    neighbour up to three levels deep, two of the four questions hold the edge symbol n_units.  odd_states: the parity of J_t."""
+    neighbour up to three levels deep, two of the four questions hold the edge symbol n_units.  odd_states: the parity of J_t.
+    wide (n_units >= 33: two words of the bit table per question, the edge symbol in word 1): every question has members on both
+    sides of unit 32 -- units 31 and 32 answer the first differently from each other, and unit 5 answers the last as the edge does, which
+    is what a walk that reads word 0 for the edge symbol's bit would see."""
     rng = np.random.default_rng(seed)
     q = np.zeros((4, n_units + 1), dtype=np.uint8)
     q[0, [0, 1, 2]] = 1
     q[1, [3, 4, n_units]] = 1
     q[2, list(range(1, n_units, 2))] = 1
     q[3, n_units] = 1
+    if wide:
+        assert n_units >= 33
+        q[0, 32] = 1
+        q[1, 32] = 1
+        q[2, 32:n_units] = 1 - q[2, 32:n_units]                    # odd units below 32, even ones from 32 on
+        q[3, 5] = 1
     Q = 4
     root_of = np.zeros(n_units * P, dtype=np.int32)
     for u in range(n_units):
@@ -73,10 +82,10 @@ def random_tree(n_units, P, seed, odd_states):
     return make_tree(P, n_units, q, cand, child, state, root_of)
 
 
-def make_lexicon(n_units, seed, n_nodes=40):
+def make_lexicon(n_units, seed, n_nodes=40, pin=()):
     """A flat pronunciation tree in PronunciationLexicon.compile's form: about n_nodes nodes of one and two units, depth >= 3, words at
     every leaf and some inner nodes (a few with two homophones), and pairs of nodes that spell the same units under parents whose last
-    units differ."""
+    units differ.  pin: up to five units; the i-th is the first unit of root i, whatever the draws give."""
     rng = np.random.default_rng(seed)
     units, parent, kids, depth = [], [], [], []
 
@@ -91,8 +100,10 @@ def make_lexicon(n_units, seed, n_nodes=40):
 
     def spell():
         return [int(x) for x in rng.integers(n_units, size=int(rng.integers(1, 3)))]
-    for _ in range(5):
+    for i in range(5):
         add(-1, spell())
+        if i < len(pin):
+            units[i][0] = int(pin[i])
     chain = 0
     for _ in range(3):                                             # a depth-3 chain, whatever the draws below do
         chain = add(chain, spell())
@@ -120,6 +131,12 @@ def make_lexicon(n_units, seed, n_nodes=40):
     return dict(node_units=np.array(units, dtype=np.int32), node_nunits=nu, node_parent=np.array(parent, dtype=np.int32), child_ptr=child_ptr,
                 child_idx=np.array([c for k in kids for c in k], dtype=np.int32), node_word=np.array(word, dtype=np.int32),
                 roots=np.array([i for i in range(n) if parent[i] < 0], dtype=np.int32), names=['n%d' % i for i in range(n)], words=words, dropped=[])
+
+
+def wide_fixture(P=3):
+    """(lexicon, tying) over 33 units: roots that begin with units 32 and 31 (the two sides of the word boundary), 5 (which answers the
+    last question as the edge symbol does) and 0 and 1 (the units that share their roots)."""
+    return make_lexicon(33, 3, pin=(32, 31, 5, 0, 1)), random_tree(33, P, seed=5, odd_states=True, wide=True)
 
 
 def node_states(lex, tying, node_ctx=None):

@@ -1,7 +1,8 @@
 """NumPy twin of the resident tying and of label-built batches over tied states (row f17; csrc/tying.hip), and the trees and corpora the
 tests share.  Built from ContextTree.Tree.lookup (the walk), tests/_realign_twin.py (row -> position, runs, slices, the drop rule) and
 tests/_tree_twin.py (the statistics).  Integer work only: every comparison against it is for equality.  tests/test_tied_twin.py proves on
-the CPU that every tree and corpus below reaches the edge it claims; tests/test_gpu_tied_batches.py runs them on the device."""
+the CPU that every tree and corpus below reaches the edge it claims; tests/test_gpu_tied_batches.py runs them on the device, and
+tests/test_gpu_tying_wide.py the inventories of 31 to 96 units, whose questions take up to four words of the bit table."""
 import numpy as np
 
 import _realign_twin as rt
@@ -70,6 +71,195 @@ def chain(P, n_units=N_UNITS, Q=CHAIN_Q, seed=7):
         state[node] = nstate
         nstate += 1
     return _tree(P, n_units, qm, cand, child, state, np.tile(np.arange(P), n_units))
+
+
+# ------------------------------------------------------------------ wide inventories: more than one table word per question
+def words(n_units):
+    """tying_words of tying_check.h, restated: 32-bit words per question, bit u of a row for u in [0, n_units]"""
+    return (n_units + 1 + 31) // 32
+
+
+def wide_follower(k, n_units):
+    """chain_follower for an inventory of 65 .. 127 units (W = 3 or 4).  The first stands between two utterance edges (the last word of a
+    row), the second has its left neighbour at bit 31 of word 1, the third at bit 0 of word 2; between them their neighbours and centres
+    lie in every word (at 96 units: words 3 1 3, 1 0 0, 2 2 2)."""
+    assert 65 <= n_units <= 127
+    return [(n_units, 40, n_units), (63, 5, 31), (64, min(70, n_units - 1), min(95, n_units - 1))][k % 3]
+
+
+def followers(tree):
+    """The chain followers of a chain() or wide_chain() tree, one per state position"""
+    f = wide_follower if getattr(tree, 'wide', False) else chain_follower
+    return [f(k, tree.n_units) for k in range(tree.P)]
+
+
+def wide_chain(P, n_units=96, Q=1024, n_levels=72, seed=11):
+    """The chain tree over a large question set: one root per state position, n_levels levels below each.  The candidates of a chain are
+    drawn without replacement from all 3 Q and always hold 3 Q - 1, question Q - 1 (the last table row) and question 0 at each of the
+    three positions (those six in the last six levels).  wide_follower(k) stays on chain k to its last level, so the first follower reads
+    the table's last word there, as a neighbour at the utterance edge.  The rows are random bits, so a unit and its aliases u +- 32 k
+    disagree on about half of the questions, with two exceptions: the edge symbol is a member of question Q - 1 (the table's last word
+    is not zero), and for every level a unit is made to agree with the follower on the levels above that ask the same position and to
+    disagree on this one -- the follower with that unit in that position leaves the chain exactly there, so every leaf has a context
+    (about 300 of the Q (n_units + 1) bits per chain and position are set for it)."""
+    rng = np.random.default_rng(seed)
+    qm = rng.integers(0, 2, size=(Q, n_units + 1)).astype(np.uint8)
+    qm[Q - 1, n_units] = 1
+    fol = [wide_follower(k, n_units) for k in range(P)]
+    keep = sorted({u for f in fol for u in f})                     # the followers' own bits are never touched
+    must = [pos * Q + qi for pos in range(3) for qi in (0, Q - 1)]
+    assert 3 * Q - 1 in must
+    rest = np.setdiff1d(np.arange(3 * Q), must)
+    fixed = {}
+    perms = []
+    for k in range(P):
+        # (the six candidates every chain shares come last: above them they would tie the made units of all chains to each other)
+        perm = np.concatenate([rng.choice(rest, size=n_levels - len(must), replace=False), rng.permutation(must)])
+        perms.append(perm)
+        for pos in range(3):
+            qs = [int(c) % Q for c in perm if int(c) // Q == pos]  # the questions this chain asks about this position, in level order
+            f = fol[k][pos]
+            free = [int(u) for u in rng.permutation(n_units + (pos != 1)) if u not in keep]
+            for j, qj in enumerate(qs):
+                want = [(q, int(qm[q, f])) for q in qs[:j]] + [(qj, 1 - int(qm[qj, f]))]
+                u = next(u for u in free if all(fixed.get((q, u), v) == v for q, v in want))
+                free.remove(u)
+                for q, v in want:
+                    qm[q, u] = v
+                    fixed[(q, u)] = v
+    assert ((qm.sum(axis=1) > 0) & (qm.sum(axis=1) <= n_units)).all()
+    cand, child, state = [-1] * P, [[-1, -1] for _ in range(P)], [-1] * P
+    nstate = 0
+    for k in range(P):
+        node = k
+        for c in perms[k]:
+            pos, qi = divmod(int(c), Q)
+            go = int(qm[qi, fol[k][pos]])
+            a, b = len(cand), len(cand) + 1
+            cand += [-1, -1]
+            child += [[-1, -1], [-1, -1]]
+            state += [nstate, -1]
+            nstate += 1
+            cand[node] = int(c)
+            child[node] = [a, b] if go == 1 else [b, a]
+            node = b
+        state[node] = nstate
+        nstate += 1
+    tree = _tree(P, n_units, qm, cand, child, state, np.tile(np.arange(P), n_units))
+    tree.wide = True
+    return tree
+
+
+def walk_all(tree, k, ctx3=None):
+    """The leaf NODE of every context's walk from position k's root, all walks at once (the contexts still walking shrink level by
+    level).  Used to FIND contexts, never as the reference: that is Tree.lookup."""
+    ctx = all_contexts_array(tree.n_units) if ctx3 is None else np.asarray(ctx3)
+    node = tree.root_of[ctx[:, 1] * tree.P + k].astype(np.int64)
+    live = np.flatnonzero(tree.node_cand[node] >= 0)
+    while len(live):
+        c = tree.node_cand[node[live]]
+        yes = tree.q_member[c % tree.Q, ctx[live, c // tree.Q]]
+        node[live] = tree.node_child[node[live], yes]
+        live = live[tree.node_cand[node[live]] >= 0]
+    return node
+
+
+def all_contexts_array(n_units):
+    """all_contexts, without the Python loop"""
+    l, c, r = np.meshgrid(np.arange(n_units + 1), np.arange(n_units), np.arange(n_units + 1), indexing='ij')
+    return np.stack([l.reshape(-1), c.reshape(-1), r.reshape(-1)], axis=1).astype(np.int32)
+
+
+def leaf_witnesses(tree):
+    """One context for every (state position, leaf) that any context of the inventory reaches"""
+    ctx = all_contexts_array(tree.n_units)
+    out = []
+    for k in range(tree.P):
+        _, first = np.unique(walk_all(tree, k, ctx), return_index=True)
+        out.append(ctx[first])
+    return np.concatenate(out)
+
+
+BOUNDARY_UNITS = (0, 31, 32, 63, 64, 95, 96)
+
+
+def context_sample(tree, n=4000, seed=5):
+    """(about n, 3) int32: the followers, every unit once in each of the three positions, every pair of BOUNDARY_UNITS and the edge
+    symbol as (left, right), a witness of every reachable leaf, and random contexts up to n."""
+    rng = np.random.default_rng(seed)
+    nu = tree.n_units
+    rows = [tuple(f) for f in followers(tree)]
+    for u in range(nu + 1):
+        rows.append((u, int(rng.integers(nu)), int(rng.integers(nu + 1))))
+        rows.append((int(rng.integers(nu + 1)), int(rng.integers(nu)), u))
+        if u < nu:
+            rows.append((int(rng.integers(nu + 1)), u, int(rng.integers(nu + 1))))
+    edge = sorted({u for u in BOUNDARY_UNITS + (nu,) if u <= nu})
+    rows += [(l, int(rng.integers(nu)), r) for l in edge for r in edge]
+    rows += [tuple(int(x) for x in w) for w in leaf_witnesses(tree)]
+    while len(rows) < n:
+        rows.append((int(rng.integers(nu + 1)), int(rng.integers(nu)), int(rng.integers(nu + 1))))
+    return np.array(rows, dtype=np.int32)
+
+
+def packed(tree):
+    """tying_pack's bit table, restated: Q W words as Python ints, bit u & 31 of word qi W + (u >> 5) = q_member[qi, u]"""
+    W = words(tree.n_units)
+    qb = [0] * (tree.Q * W)
+    for qi, u in zip(*np.nonzero(tree.q_member)):
+        qb[int(qi) * W + (int(u) >> 5)] |= 1 << (int(u) & 31)
+    return qb
+
+
+BROKEN = {1: 'the word index dropped: word qi W, bit u & 31', 2: 'stride W - 1, as if W = ceil(n_units / 32)', 3: 'stride 1',
+          4: 'words at index >= 4096 read as 0: a staging copy that stops at the LDS limit', 5: 'the last word Q W - 1 reads as 0: a copy one short'}
+LDS_WORDS = 4096                                                   # TY_QBITS_LDS / 4 of csrc/tying.hip
+
+
+def table_walk(tree, qb, left, centre, right, k, mistake=0, reads=None):
+    """tying_walk over the packed table in plain Python; mistake 1 .. 5: one of BROKEN, 0: none (then it is Tree.lookup).  reads: a set
+    that takes (qi, u, answer) of every step."""
+    W, Q = words(tree.n_units), tree.Q
+    ctx, node = (left, centre, right), int(tree.root_of[centre * tree.P + k])
+    while tree.node_cand[node] >= 0:
+        pos, qi = divmod(int(tree.node_cand[node]), Q)
+        u = ctx[pos]
+        at = qi * W if mistake == 1 else qi * (W - 1) + (u >> 5) if mistake == 2 else qi + (u >> 5) if mistake == 3 else qi * W + (u >> 5)
+        word = 0 if (mistake == 4 and at >= LDS_WORDS) or (mistake == 5 and at == Q * W - 1) else qb[at]
+        yes = (word >> (u & 31)) & 1
+        if reads is not None:
+            reads.add((qi, u, yes))
+        node = int(tree.node_child[node, yes])
+    return int(tree.node_state[node])
+
+
+def table_walk_all(tree, ctx3, mistake=0, reads=None):
+    qb = packed(tree)
+    return np.array([[table_walk(tree, qb, l, c, r, k, mistake, reads) for k in range(tree.P)] for l, c, r in np.asarray(ctx3).tolist()],
+                    dtype=np.int32).reshape(-1, tree.P)
+
+
+def applicable_mistakes(n_units, Q):
+    """The BROKEN walks that read another bit than tying_walk somewhere in a (n_units, Q) table"""
+    W = words(n_units)
+    return ([1, 2, 3] if W >= 2 else []) + ([4] if Q * W > LDS_WORDS else []) + ([5] if Q * W == LDS_WORDS else [])
+
+
+DEVICE_CASES = [(31, 24), (32, 24), (63, 24), (64, 24), (95, 24), (96, 1024), (96, 1025)]
+_cases = {}
+
+
+def device_case(n_units, Q, P):
+    """(tree, sample, states of the sample by Tree.lookup) of one case the device runs; made once, shared, not to be written to"""
+    key = (n_units, Q, P)
+    if key not in _cases:
+        tree = chain(P, n_units=n_units) if Q == CHAIN_Q else wide_chain(P, n_units=n_units, Q=Q)
+        sample = context_sample(tree)
+        want = lookup_all(tree, sample)
+        sample.setflags(write=False)
+        want.setflags(write=False)
+        _cases[key] = (tree, sample, want)
+    return _cases[key]
 
 
 def build_case(P, seed=41):

@@ -80,6 +80,46 @@ def test_identity_tying_expansion_reproduces_the_oracle_exactly():
         assert got == want and t0 == t1 and i0 == i1               # (float scores compared with ==: the same bits)
 
 
+def test_wide_tying_and_lexicons_reach_the_second_word():
+    """What tests/test_gpu_tying_wide.py ties and decodes: a 33-unit tying whose questions have members on both sides of unit 32 and
+    whose edge symbol is bit 1 of word 1, under a lexicon that spells units 31 and 32; a 96-unit lexicon with units in every word.
+    Each walk that misreads the table (tests/_tied_twin.py BROKEN) gives some node of the lexicon another state."""
+    import _tied_twin as tw
+    n_units = 33
+    lex, tying = tt.wide_fixture(P)
+    assert tying.n_units == n_units and tying.n_states % 2 == 1 and tw.words(n_units) == 2 and (n_units >> 5, n_units & 31) == (1, 1)
+    qm = tying.q_member
+    assert qm.shape == (4, 34) and all(qm[q, :32].any() and qm[q, 32:].any() and not qm[q].all() for q in range(4))
+    assert qm[0, 31] != qm[0, 32] and qm[3, 5] == qm[3, n_units] == 1 and qm[3].sum() == 2
+    narrow = tt.random_tree(n_units, P, seed=5, odd_states=True)
+    assert np.array_equal(narrow.node_cand, tying.node_cand) and not narrow.q_member[0, 32:].any()    # the same tree; only the questions' members differ
+    assert lex['node_units'][:5, 0].tolist() == [32, 31, 5, 0, 1] and np.array_equal(tt.make_lexicon(6, 3, pin=())['node_units'], tt.make_lexicon(6, 3)['node_units'])
+    states = tt.node_states(lex, tying)
+    assert all(tt.not_vacuous(lex, tying, states).values()), tt.not_vacuous(lex, tying, states)
+    ctx = node_contexts(lex, n_units)
+    slots = np.array([ctx[i, j] for i in range(len(ctx)) for j in range(int(lex['node_nunits'][i]))], dtype=np.int32)
+    assert (slots[:, 2] == n_units).any() and (slots[:, :2] == 32).any()
+    want = tw.lookup_all(tying, slots)
+    assert np.array_equal(tw.table_walk_all(tying, slots), want)
+    for m in (1, 2, 3):
+        n = int((tw.table_walk_all(tying, slots, m) != want).any(axis=1).sum())
+        print('33-unit tying, broken walk %d: %d of %d lexicon slots get another state' % (m, n, len(slots)))
+        assert n >= 1
+    # the 96-unit lexicon of the lexicon test
+    big = tt.make_lexicon(96, 3, pin=(95, 64, 32, 31))
+    used = big['node_units'][big['node_units'] >= 0]
+    n = len(big['node_nunits'])
+    assert 35 <= n <= 45 and set(big['node_nunits'].tolist()) == {1, 2}
+    assert {0, 1, 2} <= set((used >> 5).tolist()) and 95 in used and used.max() == 95
+    tree = tw.device_case(96, 1025, P)[0]
+    slots = np.array([c for i, cc in enumerate(node_contexts(big, 96)) for c in cc[:int(big['node_nunits'][i])]], dtype=np.int32)
+    want = tw.lookup_all(tree, slots)
+    for m in (1, 2, 3):
+        k = int((tw.table_walk_all(tree, slots, m) != want).any(axis=1).sum())
+        print('96-unit lexicon under the (96, 1025) chain, broken walk %d: %d of %d slots get another state' % (m, k, len(slots)))
+        assert k >= 1
+
+
 @pytest.mark.parametrize('odd', [False, True])
 def test_expansion_is_the_stated_gather_and_the_fixture_is_not_vacuous(odd):
     lex, trans, rng = problem(3)

@@ -100,6 +100,37 @@ int main() {
                     for (int k = 0; k < 2; ++k)
                         CHECK(tying_walk_host(nodes.data(), qbits.data(), w.Q, 2, w.root_of[c * 2 + k], l, c, r) == plain_walk(w, l, c, r, k));
     }
+    // 31, 32 and 96 units: the edge symbol at bit 31 of the only word, alone in the second word, alone in the fourth.  Every pair of
+    // neighbours around centres at the word boundaries; root 0 asks the left neighbour about question Q - 1, the table's last row.
+    for (int nu : {31, 32, 96}) {
+        Tree w = good();
+        w.n_units = nu;
+        w.qm.assign((size_t)w.Q * (nu + 1), 0);
+        for (int q = 0; q < w.Q; ++q)
+            for (int u = 0; u <= nu; ++u) w.qm[(size_t)q * (nu + 1) + u] = (uint8_t)(((q * 11 + u * 5) % 7) < 3);
+        w.qm[(size_t)(w.Q - 1) * (nu + 1) + nu] = 1;               // the edge symbol answers the last question: the last word is not zero
+        w.root_of.assign((size_t)nu * 2, 0);
+        for (int i = 0; i < nu * 2; ++i) w.root_of[i] = i % 2;
+        CHECK(tying_validate(w.arrays(), msg, sizeof(msg)));
+        tying_pack(w.arrays(), &nodes, &qbits);
+        const int Ww = tying_words(nu);
+        CHECK(Ww == (nu == 31 ? 1 : nu == 32 ? 2 : 4));
+        CHECK(qbits.size() == (size_t)w.Q * Ww && qbits.back() != 0);
+        if (nu != 31) CHECK(qbits.back() == 1u);                   // ... the edge symbol's bit and nothing beside it
+        int walks = 0, edge_yes = 0;
+        for (int c : {0, 30, 31, 32, 64, 95})
+            if (c < nu)
+                for (int l = 0; l <= nu; ++l)
+                    for (int r = 0; r <= nu; ++r)
+                        for (int k = 0; k < 2; ++k) {
+                            const int want = plain_walk(w, l, c, r, k);
+                            CHECK(tying_walk_host(nodes.data(), qbits.data(), w.Q, Ww, w.root_of[c * 2 + k], l, c, r) == want);
+                            ++walks;
+                            edge_yes += k == 0 && l == nu && want != 0;     // (state 0 is root 0's "no" leaf)
+                        }
+        CHECK(edge_yes > 0);
+        printf("  %d units: W = %d, %zu words, last word %#x, %d walks\n", nu, Ww, qbits.size(), qbits.back(), walks);
+    }
     // roots only
     {
         Tree r;
