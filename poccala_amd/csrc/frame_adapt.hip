@@ -130,7 +130,7 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
     const int S = ctx->fmllr_S, U = b->U, Dh = ctx->Dhost;
     TRY(speakers_check(ctx, who, U, utt_speaker, S));
     for (int u = 0; u < U; ++u)
-        if (utt_speaker[u] >= 0 && b->utt[u].frame0 < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has no frames (the batch was made without frame_begin)", who, u);
+        if (utt_speaker[u] >= 0 && b->shape.utt[u].frame0 < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has no frames (the batch was made without frame_begin)", who, u);
     // virtual frame order: speakers ascending, a speaker's utterances in batch order; a speaker's frames cut into chunks
     const long long chunk = std::min<long long>(mllr_chunk(), 1 << 30);
     std::vector<int> vbase(U, -1), spk_v0(S + 1, 0), spk_frames(S, 0), spk_chunk0, chunk_v0, chunk_n;
@@ -140,7 +140,7 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
         for (int u = 0; u < U; ++u)
             if (utt_speaker[u] == s) {
                 vbase[u] = (int)V;
-                V += b->utt[u].T;
+                V += b->shape.utt[u].T;
             }
         spk_frames[s] = (int)(V - spk_v0[s]);
     }
@@ -173,7 +173,7 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
     pcl_timer_begin(ctx, "fmllr");                               // the whole call's kernels; "fmllr_frames" / "fmllr_gk": its two halves
     pcl_timer_begin(ctx, "fmllr_frames");
     {
-        const unsigned tiles = (unsigned)((b->Tmax + FT - 1) / FT);
+        const unsigned tiles = (unsigned)((b->shape.Tmax + FT - 1) / FT);
 #define FRAMES_CASE(DP, NH)                                                                                                                              \
     hipLaunchKernelGGL((fmllr_frames_kernel<DP, NH, false>), dim3(tiles, (unsigned)U, NH), dim3(256), 0, st, b->d_utt, b->d_row_state, d_lists, b->Bt, b->lgam, ctx->frames64, ctx->frames32, \
                        ctx->FD, ctx->params64, ctx->row, ctx->w64, ctx->M, ctx->Mpad, Dh, d_P, d_Q, d_B, d_vrow, MlltKeep<false>{})

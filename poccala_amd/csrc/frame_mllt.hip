@@ -222,9 +222,9 @@ int pcl_launch_mllt_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_ke
     long long V = 0;
     for (int u = 0; u < U; ++u) {
         if (utt_keep && utt_keep[u] == 0) continue;
-        if (b->utt[u].frame0 < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has no frames (the batch was made without frame_begin)", who, u);
+        if (b->shape.utt[u].frame0 < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has no frames (the batch was made without frame_begin)", who, u);
         lists[u] = (int)V;
-        V += b->utt[u].T;                                         // (V <= sum T < 2^31: pcl_batch_create)
+        V += b->shape.utt[u].T;                                         // (V <= sum T < 2^31: pcl_batch_create)
     }
     if (V == 0) return PCL_OK;
     lists[U] = 0;
@@ -248,7 +248,7 @@ int pcl_launch_mllt_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_ke
     pcl_timer_begin(ctx, "mllt");                                // the whole call's kernels; "mllt_frames" / "mllt_gk": its two halves
     pcl_timer_begin(ctx, "mllt_frames");
     {
-        const unsigned tiles = (unsigned)((b->Tmax + FT - 1) / FT);
+        const unsigned tiles = (unsigned)((b->shape.Tmax + FT - 1) / FT);
         const MlltKeep<true> mk{ctx->mllt_keep.p};
 #define FRAMES_CASE(DP)                                                                                                                                  \
     hipLaunchKernelGGL((fmllr_frames_kernel<DP, 1, true>), dim3(tiles, (unsigned)U, 1), dim3(256), 0, st, b->d_utt, b->d_row_state, d_lists, b->Bt, b->lgam, ctx->frames64, \

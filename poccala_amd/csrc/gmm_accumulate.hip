@@ -677,10 +677,10 @@ struct AccPass {
 // room for this batch: every list at its worst case (every frame of every state survives)
 int reserve_scratch(pcl_ctx *ctx, const pcl_batch *b) {
     AccScratch &a = ctx->acc;
-    const size_t nseg = (size_t)b->n_segs + 1, ns = b->work_states.size();
+    const size_t nseg = (size_t)b->plan.n_segs + 1, ns = b->plan.work_states.size();
     size_t frames = 0;
     for (size_t k = 0; k < ns; ++k) {
-        const ScoreSeg &last = b->segs[b->state_seg_hi[k] - 1];
+        const ScoreSeg &last = b->plan.segs[b->plan.state_seg_hi[k] - 1];
         frames += (size_t)last.vstart + last.len;
     }
     TRY(a.cnt.reserve(ctx, nseg));
@@ -693,16 +693,16 @@ int reserve_scratch(pcl_ctx *ctx, const pcl_batch *b) {
 // MFMA mode: well-conditioned states first (MFMA kernel), then the ill-conditioned ones (direct-form VALU kernel)
 int order_states(pcl_ctx *ctx, pcl_batch *b, bool mfma, AccPass &p) {
     AccScratch &a = ctx->acc;
-    const size_t ns = b->work_states.size();
+    const size_t ns = b->plan.work_states.size();
     b->acc_ws.clear(); b->acc_lo.clear(); b->acc_hi.clear(); b->acc_split.clear();
     for (int pass = 0; pass < 2; ++pass)
         for (size_t k = 0; k < ns; ++k) {
-            const bool bad = mfma && pcl_state_acc_uses_valu(ctx, b->work_states[k]);
+            const bool bad = mfma && pcl_state_acc_uses_valu(ctx, b->plan.work_states[k]);
             if (bad != (pass == 1)) continue;
-            b->acc_ws.push_back(b->work_states[k]);
-            b->acc_lo.push_back(b->state_seg_lo[k]);
-            b->acc_hi.push_back(b->state_seg_hi[k]);
-            const int sp = (mfma && pass == 0 && pcl_state_acc_is_split(ctx, b->work_states[k])) ? 1 : 0;
+            b->acc_ws.push_back(b->plan.work_states[k]);
+            b->acc_lo.push_back(b->plan.state_seg_lo[k]);
+            b->acc_hi.push_back(b->plan.state_seg_hi[k]);
+            const int sp = (mfma && pass == 0 && pcl_state_acc_is_split(ctx, b->plan.work_states[k])) ? 1 : 0;
             b->acc_split.push_back(sp);
             p.n_split += sp;
             p.n_good += pass == 0;
@@ -724,15 +724,15 @@ void build_active_lists(pcl_ctx *ctx, pcl_batch *b, int precision) {
     const double LN2 = 0.693147180559945309417232121458;
     const double thr = std::max(precision == PCL_F64 ? -1076.0 : -150.0, ctx->acc_prune_log2) * LN2;
     const int wpb = 4;
-    dim3 gseg((b->n_segs + wpb - 1) / wpb);
+    dim3 gseg((b->plan.n_segs + wpb - 1) / wpb);
     static const bool rows_on = !(getenv("PCL_ACC_ROWS") && atoi(getenv("PCL_ACC_ROWS")) == 0);      // 0: a wave per segment (rounds 1-3), A/B
     const bool by_rows = rows_on && b->U <= 65535 && b->d_seg_of_row;                                // (grid.y = utterances)
-    const dim3 grows((b->max_N + 8 * ROWS_WPB - 1) / (8 * ROWS_WPB), (unsigned)b->U);
+    const dim3 grows((b->plan.max_N + 8 * ROWS_WPB - 1) / (8 * ROWS_WPB), (unsigned)b->U);
     if (by_rows) hipLaunchKernelGGL(acc_count_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, thr, a.cnt.p);
-    else hipLaunchKernelGGL(acc_count_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, thr, a.cnt.p);
-    hipLaunchKernelGGL(acc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, a.cnt.p, b->n_segs, a.off.p);
+    else hipLaunchKernelGGL(acc_count_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->plan.n_segs, b->lgam, thr, a.cnt.p);
+    hipLaunchKernelGGL(acc_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, a.cnt.p, b->plan.n_segs, a.off.p);
     if (by_rows) hipLaunchKernelGGL(acc_fill_rows_kernel, grows, dim3(64 * ROWS_WPB), 0, ctx->stream, b->d_utt, b->d_seg_of_row, b->lgam, b->Bt, thr, a.off.p, a.list.p);
-    else hipLaunchKernelGGL(acc_fill_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->n_segs, b->lgam, b->Bt, thr, a.off.p, a.list.p);
+    else hipLaunchKernelGGL(acc_fill_kernel, gseg, dim3(64 * wpb), 0, ctx->stream, b->d_segs, b->plan.n_segs, b->lgam, b->Bt, thr, a.off.p, a.list.p);
 }
 
 // f16 route, 1: the two image buffer sets, and the groups of states whose tile images fit one.  Grouped by the ACTUAL tile counts: the scan
@@ -740,7 +740,7 @@ void build_active_lists(pcl_ctx *ctx, pcl_batch *b, int precision) {
 // sizing the groups for the worst case made eight half-empty launches, each with its parameter prologue and statistics flush, out of one
 int size_groups(pcl_ctx *ctx, const pcl_batch *b, AccPass &p) {
     AccScratch &a = ctx->acc;
-    std::vector<long long> off_h((size_t)b->n_segs + 1);
+    std::vector<long long> off_h((size_t)b->plan.n_segs + 1);
     HIPCHK(ctx, hipMemcpyAsync(off_h.data(), a.off.p, off_h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<int> wtiles(p.n_good);
@@ -866,8 +866,8 @@ int run_direct(pcl_ctx *ctx, int precision, int first, int count) {
 void pcl_accumulate_release(pcl_ctx *ctx) { ctx->acc = {}; }
 
 int pcl_launch_accumulate(pcl_ctx *ctx, pcl_batch *b, int precision) {
-    if (b->n_segs == 0) return PCL_OK;
-    const int route = pcl_route(ctx, precision, ctx->D), ns = (int)b->work_states.size();
+    if (b->plan.n_segs == 0) return PCL_OK;
+    const int route = pcl_route(ctx, precision, ctx->D), ns = (int)b->plan.work_states.size();
     AccPass p;
     TRY(reserve_scratch(ctx, b));
     TRY(order_states(ctx, b, route != PCL_ROUTE_DIRECT, p));

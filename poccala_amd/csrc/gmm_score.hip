@@ -501,8 +501,8 @@ __global__ void dup_rows_kernel(const DupRow *__restrict__ dups, int n, double *
 }  // namespace
 
 int pcl_launch_dup_rows(pcl_ctx *ctx, pcl_batch *b) {
-    if (b->dups.empty()) return PCL_OK;
-    hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)b->dups.size()), dim3(256), 0, ctx->stream, b->d_dups, (int)b->dups.size(), b->Bt);
+    if (b->plan.dups.empty()) return PCL_OK;
+    hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)b->plan.dups.size()), dim3(256), 0, ctx->stream, b->d_dups, (int)b->plan.dups.size(), b->Bt);
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
 }

@@ -761,10 +761,10 @@ int pcl_seg_em(pcl_seg *seg, double c_covariance, double q_threshold, int max_it
                 }
             TRY(pcl_batch_create(ctx, (int)N.size(), N.data(), T.data(), begin.data(), &b));
             TRY(pcl_batch_set_states(b, rows.data()));
-            TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
+            TRY(b->lgam.alloc(ctx, (size_t)b->shape.sumNT));
             {
-                hipLaunchKernelGGL(seg_posterior_kernel, dim3((unsigned)std::min<long long>(4096, (b->sumNT + 255) / 256)), dim3(256), 0, ctx->stream, b->lgam,
-                                   b->sumNT);
+                hipLaunchKernelGGL(seg_posterior_kernel, dim3((unsigned)std::min<long long>(4096, (b->shape.sumNT + 255) / 256)), dim3(256), 0, ctx->stream, b->lgam,
+                                   b->shape.sumNT);
                 HIPCHK(ctx, hipGetLastError());
                 b->have_post = true;
             }

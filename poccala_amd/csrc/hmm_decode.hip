@@ -634,9 +634,9 @@ int dec_validate(const pcl_batch *b, double beam, int min_distinct, int candidat
     // the emission rows must be [entry, state 0 .. J-1, exit]: the all-state matrix
     const int J = tied ? ctx->lex_tie_Jt : ctx->n_units * (ctx->S - 2);
     for (int u = 0; u < b->U; ++u) {
-        const UttDesc &d = b->utt[u];
-        bool ok = d.N == J + 2 && (int)b->row_state.size() >= d.vec_off + d.N;
-        for (int n = 0; ok && n < d.N; ++n) ok = b->row_state[d.vec_off + n] == (n == 0 ? PCL_ROW_ENTRY : n == d.N - 1 ? PCL_ROW_EXIT : n - 1);
+        const UttDesc &d = b->shape.utt[u];
+        bool ok = d.N == J + 2 && (int)b->plan.row_state.size() >= d.vec_off + d.N;
+        for (int n = 0; ok && n < d.N; ++n) ok = b->plan.row_state[d.vec_off + n] == (n == 0 ? PCL_ROW_ENTRY : n == d.N - 1 ? PCL_ROW_EXIT : n - 1);
         if (!ok && tied)
             PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode_tied: utterance %d is not an all-state batch of J_t + 2 = %d rows (entry, 0..%d, exit)", u, J + 2, J - 1);
         if (!ok) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode: utterance %d is not an all-state batch (rows entry, 0..%d, exit)", u, J - 1);
@@ -684,7 +684,7 @@ DecArgs dec_fill_args(const pcl_batch *b, const DecLayout &l, double beam, int m
     a.cap = cap;
     a.candidate = candidate;
     a.min_distinct = min_distinct;
-    a.Tmax = b->Tmax;
+    a.Tmax = b->shape.Tmax;
     a.beam = beam;
     a.lpi1 = lpi1;
     a.lpi2 = lpi2;
@@ -884,13 +884,13 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
         // left-to-right units (every model the reference builds): one lane per token, hmm_decode_lr.hip; PCL_DEC_GENERAL=1 keeps
         // the general kernel (the parity tests run both against the restatement)
         const char *force_general = getenv("PCL_DEC_GENERAL");
-        const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, n_rows, cap, b->Tmax, tied);
-        const DecLayout l = dec_layout(U, cap, candidate, b->Tmax, use_lr);
+        const bool use_lr = !(force_general && atoi(force_general)) && pcl_decode_lr_applicable(ctx, n_rows, cap, b->shape.Tmax, tied);
+        const DecLayout l = dec_layout(U, cap, candidate, b->shape.Tmax, use_lr);
         TRY(dec_ensure_workspace(b, l, cap, candidate));
         DecArgs a = dec_fill_args(b, l, beam, min_distinct, candidate, cap, logpi_one_unit, logpi_two_units);
         DecLm lm = {};
         if (with_lm) {
-            const size_t n_word = (size_t)U * b->Tmax;
+            const size_t n_word = (size_t)U * b->shape.Tmax;
             if (!b->dec_word || b->dec_word.cap < n_word) TRY(b->dec_word.alloc(ctx, n_word));
             HIPCHK(ctx, hipMemsetAsync(b->dec_word, 0, n_word * sizeof(int), ctx->stream));
             lm = DecLm{ctx->lm_uni, ctx->lm_bow, ctx->lm_row_ptr, ctx->lm_col, ctx->lm_val, ctx->lm_node_word_ptr, ctx->lm_node_word_ids, b->dec_word};
@@ -945,7 +945,7 @@ int pcl_batch_decode_get_words(pcl_batch *b, int32_t *hist_word) {
     if (!hist_word) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_decode_get_words: hist_word is NULL");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = b->dp_pending ? ctx->stream_dp : ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(hist_word, b->dec_word, (size_t)b->U * b->Tmax * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hist_word, b->dec_word, (size_t)b->U * b->shape.Tmax * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     return PCL_OK;
 }
@@ -956,8 +956,8 @@ int pcl_batch_decode_get(pcl_batch *b, int32_t *n_final, int32_t *node, double *
     pcl_ctx *ctx = b->ctx;
     if (!b->have_dec) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_decode_get: run pcl_batch_decode first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t U = (size_t)b->U, c = (size_t)b->dec_cand, Tm = (size_t)b->Tmax;
-    const DecLayout l = dec_layout(b->U, b->dec_cap, b->dec_cand, b->Tmax, false);   // (the results sit alike for both kernels)
+    const size_t U = (size_t)b->U, c = (size_t)b->dec_cand, Tm = (size_t)b->shape.Tmax;
+    const DecLayout l = dec_layout(b->U, b->dec_cap, b->dec_cand, b->shape.Tmax, false);   // (the results sit alike for both kernels)
     const int *r = b->dec_int;
     // the results come down on the stream the decoder ran on, and only that stream is waited for: the scoring of the next
     // chunk, queued on the main stream meanwhile, keeps running

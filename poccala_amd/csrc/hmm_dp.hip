@@ -886,15 +886,15 @@ bool pcl_fb_linear_enabled() {
 
 int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshold) {
     if (!b->Bp) {
-        TRY(b->Bp.alloc(ctx, (size_t)b->sumNT));
-        TRY(b->alpha_e.alloc(ctx, (size_t)b->sumNT));
-        TRY(b->beta_e.alloc(ctx, (size_t)b->sumNT));
+        TRY(b->Bp.alloc(ctx, (size_t)b->shape.sumNT));
+        TRY(b->alpha_e.alloc(ctx, (size_t)b->shape.sumNT));
+        TRY(b->beta_e.alloc(ctx, (size_t)b->shape.sumNT));
         TRY(b->fb_kmax.alloc(ctx, (size_t)PCL_FB_KREC * b->U));
         TRY(b->fb_dump.alloc(ctx, (size_t)128));                  // where the posterior kernel's lanes beyond N "store"
     }
     hipLaunchKernelGGL(hmm_emis_pack_kernel, dim3(PACK_BLOCKS, b->U), dim3(256), 0, ctx->stream, b->d_utt, b->Bt, b->Bp, b->fb_kmax, b->row_ptr, b->csr_val,
                        b->logpi);
-    const int NPc = (b->Nmax + 63) / 64 * 64;
+    const int NPc = (b->shape.Nmax + 63) / 64 * 64;
     if (NPc > 64) {
 #define LAUNCH_CM(W)                                                                                                                             \
     hipLaunchKernelGGL((hmm_fblm_kernel<W>), dim3(b->U), dim3(128 * W), 0, ctx->stream, b->d_utt, b->Bp, b->fb_kmax, b->row_ptr, b->col_idx, b->csr_val, \
@@ -912,7 +912,7 @@ int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshol
 }
 
 int pcl_launch_fb_linear_post(pcl_ctx *ctx, pcl_batch *b) {
-    const int NPp = (b->Nmax + 63) / 64 * 64;
+    const int NPp = (b->shape.Nmax + 63) / 64 * 64;
     if (!b->fb_part_m) {
         TRY(b->fb_part_m.alloc(ctx, (size_t)b->U * 3 * POSTL_W * NPp));
         TRY(b->fb_part_e.alloc(ctx, (size_t)b->U * 3 * POSTL_W * NPp));
@@ -964,8 +964,8 @@ __global__ void one_frame_kernel(const UttDesc *__restrict__ utts, double *__res
 }  // namespace
 
 int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshold) {
-    const int NP = (b->Nmax + 63) / 64 * 64;
-    if (NP > 64 * MAXW) PCL_FAIL(ctx, PCL_ERR_INVALID, "HMM with %d states exceeds the %d-state limit", b->Nmax, 64 * MAXW);
+    const int NP = (b->shape.Nmax + 63) / 64 * 64;
+    if (NP > 64 * MAXW) PCL_FAIL(ctx, PCL_ERR_INVALID, "HMM with %d states exceeds the %d-state limit", b->shape.Nmax, 64 * MAXW);
     const size_t shm = (size_t)3 * NP * sizeof(double);
     if (!ctx->d_softplus) {                                      // (f, s) of log1p(exp(-d)) at d = k / 32, host libm
         std::vector<double> tab(2 * SP_N);
@@ -981,11 +981,11 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
     pcl_timer_begin(ctx, "fb");
     static const bool one_wave = getenv("PCL_FB_ONE_WAVE") && atoi(getenv("PCL_FB_ONE_WAVE")) != 0;      // A/B: the round-1 kernel
     b->fb_linear = false;
-    if (b->max_indeg <= 2 && b->max_outdeg <= 2 && NP == 64 && !one_wave) {
+    if (b->trans.max_indeg <= 2 && b->trans.max_outdeg <= 2 && NP == 64 && !one_wave) {
         // left-to-right sentence HMMs (everything AcousticModel.embedded builds): the scaled linear-domain chain (hmm_fb_linear.inc),
         // whose kernels run the log-domain bodies for the utterances that do not fit its int32 exponents (usually none); any other
         // structure, or PCL_FB_LINEAR=0: the log-domain kernels
-        if (b->left_right && pcl_fb_linear_enabled()) {
+        if (b->trans.left_right && pcl_fb_linear_enabled()) {
             TRY(pcl_launch_fb_linear(ctx, b, fix_pi, threshold));
             TRY(pcl_launch_fb_linear_post(ctx, b));
             b->fb_linear = true;
@@ -996,10 +996,10 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
             hipLaunchKernelGGL(hmm_post_kernel, dim3(b->U), dim3(64 * POST_W), 0, ctx->stream, b->d_utt, b->Bt, b->row_ptr, b->col_idx, b->csr_val,
                                b->alpha, b->beta, b->lgam, b->ksai, b->gamma_out, b->logp);
         }
-    } else if (b->max_indeg <= 2 && b->max_outdeg <= 2) {
+    } else if (b->trans.max_indeg <= 2 && b->trans.max_outdeg <= 2) {
         // more than 64 states (a label of 21 units has 65): left-to-right HMMs of up to 256 states run the scaled chain spread over
         // several waves (hmm_fb_linear_mw.inc); the log-domain kernel behind it takes the utterances outside the exponent range
-        const bool lin = b->left_right && NP <= 256 && pcl_fb_linear_enabled();
+        const bool lin = b->trans.left_right && NP <= 256 && pcl_fb_linear_enabled();
         if (lin) {
             TRY(pcl_launch_fb_linear(ctx, b, fix_pi, threshold));
             TRY(pcl_launch_fb_linear_post(ctx, b));
@@ -1015,7 +1015,7 @@ int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double t
     // A one-frame utterance: LHMM.baulm_welch raises on it (the sum over t < T - 1 of LHMM.py:424-445 is empty: ValueError, golden G15), so
     // under the reference's workers it adds nothing to any accumulator.  Here: ln P(O), alpha and beta are what one frame gives, the
     // posteriors are ln 0 -- the accumulate passes (GMM statistics and per-unit transitions) then skip the utterance as a whole.
-    if (b->has_one_frame) hipLaunchKernelGGL(one_frame_kernel, dim3(b->U), dim3(64), 0, ctx->stream, b->d_utt, b->lgam);
+    if (b->shape.has_one_frame) hipLaunchKernelGGL(one_frame_kernel, dim3(b->U), dim3(64), 0, ctx->stream, b->d_utt, b->lgam);
     pcl_timer_end(ctx, "fb");
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;
@@ -1121,8 +1121,8 @@ __global__ void hmm_align_segments_kernel(const UttDesc *__restrict__ utts, cons
 }
 
 int pcl_launch_regroup(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_row_unit, int gmm_num, int32_t *d_frame_unit, int32_t *d_frame_k) {
-    const size_t shm = (size_t)2 * b->Tmax * sizeof(int);
-    if (shm > 64 * 1024) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_regroup: utterances of %d frames exceed the 8192-frame limit", b->Tmax);
+    const size_t shm = (size_t)2 * b->shape.Tmax * sizeof(int);
+    if (shm > 64 * 1024) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_regroup: utterances of %d frames exceed the 8192-frame limit", b->shape.Tmax);
     pcl_timer_begin(ctx, "regroup");
     hipLaunchKernelGGL(hmm_regroup_kernel, dim3(b->U), dim3(64), shm, ctx->stream, b->d_utt, b->path, d_row_unit, gmm_num, d_frame_unit,
                        d_frame_k);
@@ -1132,10 +1132,10 @@ int pcl_launch_regroup(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_row_unit, in
 }
 
 int pcl_launch_align_segments(pcl_ctx *ctx, pcl_batch *b, int Lmax, int gmm_num, int32_t *d_frame_state, int32_t *d_dropped) {
-    const size_t shm = ((size_t)2 * b->Tmax + (size_t)2 * Lmax) * sizeof(int);
+    const size_t shm = ((size_t)2 * b->shape.Tmax + (size_t)2 * Lmax) * sizeof(int);
     if (shm > 64 * 1024)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_align_segments: utterances of %d frames and %d label units exceed the 8192-frame limit (2 T + 2 L <= 16384)",
-                 b->Tmax, Lmax);
+                 b->shape.Tmax, Lmax);
     pcl_timer_begin(ctx, "align_segments");
     hipLaunchKernelGGL(hmm_align_segments_kernel, dim3(b->U), dim3(64), shm, ctx->stream, b->d_utt, b->path, b->d_labels, b->d_label_off, gmm_num,
                        d_frame_state, d_dropped);
@@ -1145,9 +1145,9 @@ int pcl_launch_align_segments(pcl_ctx *ctx, pcl_batch *b, int Lmax, int gmm_num,
 }
 
 int pcl_launch_viterbi(pcl_ctx *ctx, pcl_batch *b, int end_state_back) {
-    const int NP = (b->Nmax + 63) / 64 * 64;
-    if (NP > 64 * MAXW) PCL_FAIL(ctx, PCL_ERR_INVALID, "HMM with %d states exceeds the %d-state limit", b->Nmax, 64 * MAXW);
-    if (b->Nmax > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "too many states for 16-bit back-pointers");
+    const int NP = (b->shape.Nmax + 63) / 64 * 64;
+    if (NP > 64 * MAXW) PCL_FAIL(ctx, PCL_ERR_INVALID, "HMM with %d states exceeds the %d-state limit", b->shape.Nmax, 64 * MAXW);
+    if (b->shape.Nmax > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "too many states for 16-bit back-pointers");
     const size_t shm = (size_t)2 * NP * sizeof(double);
     pcl_timer_begin(ctx, "viterbi");
     hipLaunchKernelGGL(hmm_viterbi_kernel, dim3(b->U), dim3(NP), shm, ctx->stream, b->d_utt, b->Bt, b->col_ptr,

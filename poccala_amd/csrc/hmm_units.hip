@@ -169,58 +169,11 @@ int pcl_launch_trans_mstep(pcl_ctx *ctx) {
 // (AcousticModel.embedded: embedded_transmat :979-989, embedded_pi :1003-1006).
 static int build_sentences(pcl_batch *b) {
     pcl_ctx *ctx = b->ctx;
-    const int S = ctx->S, e = S - 2;
-    std::vector<int> row_ptr((size_t)b->sumN + b->U), col_ptr((size_t)b->sumN + b->U);
-    std::vector<int> col_idx, row_idx;
-    std::vector<double> csr_val, csc_val, logpi((size_t)b->sumN);
-    b->max_outdeg = b->max_indeg = 0;
-    size_t lo = 0;
-    std::vector<int> indeg, fillp;
-    for (int u = 0; u < b->U; ++u) {
-        UttDesc &d = b->utt[u];
-        const int N = d.N, L = b->label_len[u];
-        const int32_t *lab = b->labels.data() + lo;
-        lo += L;
-        d.nnz_off = (int)col_idx.size();
-        const size_t base = col_idx.size();
-        int cnt = 0;
-        for (int i = 0; i < N; ++i) {
-            row_ptr[d.ptr_off + i] = cnt;
-            if (i < N - 1) {                                     // the exit row has no successors
-                // row 0: unit 0's entry row at columns 0..S-1; row 1 + p e + k: row 1 + k of unit lab[p] at columns p e + c
-                const int p = (i == 0) ? 0 : (i - 1) / e, r = (i == 0) ? 0 : 1 + (i - 1) % e;
-                const double *row = ctx->unit_logtrans.data() + ((size_t)lab[p] * S + r) * S;
-                for (int c = 0; c < S; ++c)
-                    if (!(row[c] == -INFINITY)) {
-                        col_idx.push_back(p * e + c);
-                        csr_val.push_back(row[c]);
-                        ++cnt;
-                    }
-            }
-            b->max_outdeg = std::max(b->max_outdeg, cnt - row_ptr[d.ptr_off + i]);
-        }
-        row_ptr[d.ptr_off + N] = cnt;
-        // CSC by a counting sort of the CSR entries: sources come out in ascending order
-        indeg.assign(N + 1, 0);
-        for (int k = 0; k < cnt; ++k) ++indeg[col_idx[base + k] + 1];
-        for (int j = 0; j < N; ++j) {
-            b->max_indeg = std::max(b->max_indeg, indeg[j + 1]);
-            indeg[j + 1] += indeg[j];
-        }
-        for (int j = 0; j <= N; ++j) col_ptr[d.ptr_off + j] = indeg[j];
-        fillp.assign(indeg.begin(), indeg.end() - 1);
-        row_idx.resize(base + cnt);
-        csc_val.resize(base + cnt);
-        for (int i = 0; i < N; ++i)
-            for (int k = row_ptr[d.ptr_off + i]; k < row_ptr[d.ptr_off + i + 1]; ++k) {
-                const int j = col_idx[base + k], q = fillp[j]++;
-                row_idx[base + q] = i;
-                csc_val[base + q] = csr_val[base + k];
-            }
-        for (int i = 0; i < N; ++i) logpi[d.vec_off + i] = b->logpi_u[u];
-        if (col_idx.size() > 0x7fffffffULL) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels: too many transitions");
-    }
-    return pcl_batch_upload_sparse(b, row_ptr, col_idx, csr_val, col_ptr, row_idx, csc_val, logpi.data());
+    SparseTrans t;
+    TRY(plan_sparse_trans(ctx, "pcl_batch_create_labels", b->shape.utt, label_trans_rows(b->shape.utt, b->lab, ctx->unit_logtrans.data(), ctx->S), &t));
+    std::vector<double> logpi((size_t)b->shape.sumN);
+    for (int u = 0; u < b->U; ++u) std::fill_n(logpi.begin() + b->shape.utt[u].vec_off, b->shape.utt[u].N, b->logpi_u[u]);
+    return pcl_batch_upload_sparse(b, t, logpi.data());
 }
 
 extern "C" {
@@ -284,61 +237,30 @@ static int create_labels(pcl_ctx *ctx, const char *who, bool tied, int U, const 
     } else if (ctx->J != ctx->n_units * e)
         PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the model has %d GMM states, %d units x %d emitting states need %d", who, ctx->J, ctx->n_units, e, ctx->n_units * e);
     if (U <= 0 || !label_len || !labels || !T || !frame_begin) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: bad arguments (U=%d)", who, U);
-    std::vector<int32_t> N(U);
-    size_t tot = 0;
-    for (int u = 0; u < U; ++u) {
-        if (label_len[u] < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has an empty label", who, u);
-        N[u] = e * label_len[u] + 2;                               // AcousticModel.py:966
-        tot += label_len[u];
-    }
-    for (size_t i = 0; i < tot; ++i)
-        if (labels[i] < 0 || labels[i] >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: unit id %d outside [0,%d)", who, labels[i], ctx->n_units);
+    LabelPlan lab;
+    TRY(plan_labels(ctx, who, U, label_len, labels, e, ctx->n_units, &lab));
     pcl_batch *b = nullptr;
-    TRY(pcl_batch_create(ctx, U, N.data(), T, frame_begin, &b));
+    TRY(pcl_batch_create(ctx, U, lab.N.data(), T, frame_begin, &b));
     pcl_desc_group uploads(ctx);                                   // every descriptor array below: staged, one wait at the end
     b->from_labels = true;
-    b->label_len.assign(label_len, label_len + U);
-    b->labels.assign(labels, labels + tot);
-    b->label_max = *std::max_element(labels, labels + tot);
-    b->label_len_max = *std::max_element(label_len, label_len + U);
+    b->lab = std::move(lab);
     b->logpi_u.resize(U);
-    for (int u = 0; u < U; ++u) b->logpi_u[u] = logpi ? logpi[u] : log(1.0 / N[u]);
-    // row -> GMM state (embedded_prob, AcousticModel.py:990-1001) and unit -> occurrences
-    std::vector<int32_t> row_state((size_t)b->sumN);
-    std::vector<int> occ_ptr(ctx->n_units + 1, 0);
-    for (size_t i = 0; i < tot; ++i) ++occ_ptr[labels[i] + 1];
-    for (int k = 0; k < ctx->n_units; ++k) occ_ptr[k + 1] += occ_ptr[k];
-    std::vector<int> occ_utt(tot), occ_row0(tot), fillp(occ_ptr.begin(), occ_ptr.end() - 1);
-    size_t lo = 0;
-    for (int u = 0; u < U; ++u) {
-        const UttDesc &d = b->utt[u];
-        row_state[d.vec_off] = PCL_ROW_ENTRY;
-        row_state[d.vec_off + d.N - 1] = PCL_ROW_EXIT;
-        for (int p = 0; p < label_len[u]; ++p) {
-            const int unit = labels[lo + p];
-            if (!tied)
-                for (int k = 0; k < e; ++k) row_state[d.vec_off + 1 + p * e + k] = unit * e + k;
-            const int q = fillp[unit]++;
-            occ_utt[q] = u;
-            occ_row0[q] = 1 + p * e;
-        }
-        lo += label_len[u];
-    }
-    b->n_occ = (int)tot;
+    for (int u = 0; u < U; ++u) b->logpi_u[u] = logpi ? logpi[u] : log(1.0 / b->lab.N[u]);
+    const size_t tot = b->lab.labels.size();
     auto fill = [&]() -> int {                                     // (the batch is the caller's only once all of it has worked)
         if (tied) {                                                // the walks write the map; it comes back ONCE, for the bookkeeping below
-            TRY(pcl_launch_tied_label_states(ctx, b, row_state.data()));
+            TRY(pcl_launch_tied_label_states(ctx, b, b->lab.row_state.data()));
             b->tied = true;
             b->tied_J = ctx->ty_Jt;
         }
-        TRY(pcl_batch_set_states_impl(b, row_state.data()));
+        TRY(pcl_batch_set_states_impl(b, b->lab.row_state.data()));
         TRY(build_sentences(b));
-        TRY(b->occ_ptr.alloc(ctx, occ_ptr.size()));
+        TRY(b->occ_ptr.alloc(ctx, b->lab.occ_ptr.size()));
         TRY(b->occ_utt.alloc(ctx, tot));
         TRY(b->occ_row0.alloc(ctx, tot));
-        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_ptr, occ_ptr.data(), occ_ptr.size() * sizeof(int)));
-        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_utt, occ_utt.data(), tot * sizeof(int)));
-        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_row0, occ_row0.data(), tot * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_ptr, b->lab.occ_ptr.data(), b->lab.occ_ptr.size() * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_utt, b->lab.occ_utt.data(), tot * sizeof(int)));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->occ_row0, b->lab.occ_row0.data(), tot * sizeof(int)));
         HIPCHK(ctx, uploads.finish());
         if (ctx->stream_desc && pcl_fewer_markers()) {
             // the constant entry / exit rows of the emission matrix (AcousticModel.py:218-219), here instead of in front of the batch's first
@@ -367,9 +289,9 @@ static int create_labels(pcl_ctx *ctx, const char *who, bool tied, int U, const 
 // has the inventory kept the shape a tied batch's sentences were laid out for?  (a monophone batch: J == n_units (S-2) says so)
 static bool tied_inventory_fits(const pcl_batch *b) {
     const pcl_ctx *ctx = b->ctx;
-    if (ctx->J != b->tied_J || b->label_max >= ctx->n_units) return false;
+    if (ctx->J != b->tied_J || b->lab.label_max >= ctx->n_units) return false;
     for (int u = 0; u < b->U; ++u)
-        if (b->utt[u].N != (ctx->S - 2) * b->label_len[u] + 2) return false;
+        if (b->shape.utt[u].N != (ctx->S - 2) * b->lab.label_len[u] + 2) return false;
     return true;
 }
 
@@ -403,7 +325,7 @@ int pcl_batch_accumulate_hmm(pcl_batch *b) {
     pcl_ctx *ctx = b->ctx;
     if (!b->from_labels) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_accumulate_hmm: the batch was not created from labels (pcl_batch_create_labels)");
     if (!b->have_fb) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_accumulate_hmm: run pcl_batch_forward_backward first");
-    if (!ctx->hmm_ksai || (int)b->label_len.size() != b->U) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_accumulate_hmm: no units uploaded");
+    if (!ctx->hmm_ksai || (int)b->lab.label_len.size() != b->U) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_accumulate_hmm: no units uploaded");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (b->dp_pending) {                                           // the recursion ran on the second stream
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_dp, 0));

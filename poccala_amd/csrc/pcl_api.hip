@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 
@@ -588,69 +589,21 @@ int pcl_host_free(pcl_ctx *ctx, void *ptr) {
 int pcl_batch_create(pcl_ctx *ctx, int U, const int32_t *N, const int32_t *T, const int64_t *frame_begin, pcl_batch **out) {
     if (!ctx || !out) return PCL_ERR_INVALID;
     *out = nullptr;
-    if (U <= 0 || !N || !T) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: bad arguments (U=%d)", U);
-    // several kernels index the utterance with the grid's second dimension (HIP: at most 65535): say so here instead of failing a launch later
-    if (U > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: %d utterances in one batch, at most 65535 (split the batch)", U);
+    BatchShape shape;
+    TRY(plan_batch_shape(ctx, U, N, T, frame_begin, ctx->F, &shape));
     HIPCHK(ctx, hipSetDevice(ctx->device));
     pcl_batch_reap(ctx, false);                              // destroyed batches the GPU has finished with: their blocks first
-    pcl_batch *b = new pcl_batch();
+    std::unique_ptr<pcl_batch> b(new pcl_batch());           // (a failed allocation below gives back what the batch holds by then: nothing was launched on it)
     b->ctx = ctx;
     b->U = U;
-    b->utt.resize(U);
-    long long bo = 0, mo = 0, vo = 0, po = 0, to = 0;
-    for (int u = 0; u < U; ++u) {
-        if (N[u] < 1 || T[u] < 1) {
-            delete b;
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: utterance %d has N=%d T=%d", u, N[u], T[u]);
-        }
-        if (frame_begin && (frame_begin[u] < 0 || frame_begin[u] + T[u] > ctx->F)) {
-            delete b;
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: utterance %d frames [%lld,%lld) outside the uploaded %lld frames", u,
-                     (long long)frame_begin[u], (long long)frame_begin[u] + T[u], (long long)ctx->F);
-        }
-        UttDesc &d = b->utt[u];
-        d.b_off = bo;
-        d.mat_off = mo;
-        d.frame0 = frame_begin ? frame_begin[u] : -1;
-        if (frame_begin) b->max_frame_end = std::max(b->max_frame_end, (long long)frame_begin[u] + T[u]);
-        d.T = T[u];
-        d.N = N[u];
-        d.vec_off = (int)vo;
-        d.ptr_off = (int)po;
-        d.nnz_off = 0;
-        d.path_off = (int)to;
-        bo += (long long)N[u] * T[u];
-        mo += (long long)N[u] * N[u];
-        vo += N[u];
-        po += N[u] + 1;
-        to += T[u];
-        b->Nmax = std::max(b->Nmax, (int)N[u]);
-        b->Tmax = std::max(b->Tmax, (int)T[u]);
-        if (T[u] == 1) b->has_one_frame = true;
-    }
-    b->sumNT = bo;
-    b->sumNN = mo;
-    b->sumN = vo;
-    b->sumT = to;
-    if (vo > 0x7fffffffLL || to > 0x7fffffffLL) {
-        delete b;
-        PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create: batch too large");
-    }
-    auto alloc = [&]() -> int {
-        TRY(b->d_utt.alloc(ctx, (size_t)U));
-        TRY(b->Bt.alloc(ctx, (size_t)bo));
-        TRY(b->logpi.alloc(ctx, (size_t)vo));
-        TRY(b->d_row_state.alloc(ctx, (size_t)vo));
-        return PCL_OK;
-    };
-    const int r = alloc();
-    if (r != PCL_OK) {
-        pcl_batch_destroy(b);
-        return r;
-    }
+    b->shape = std::move(shape);
+    TRY(b->d_utt.alloc(ctx, (size_t)U));
+    TRY(b->Bt.alloc(ctx, (size_t)b->shape.sumNT));
+    TRY(b->logpi.alloc(ctx, (size_t)b->shape.sumN));
+    TRY(b->d_row_state.alloc(ctx, (size_t)b->shape.sumN));
     b->counted = true;
     ++ctx->live_batches;
-    *out = b;
+    *out = b.release();
     return PCL_OK;
 }
 
@@ -704,31 +657,14 @@ int pcl_batch_destroy(pcl_batch *b) {
     return PCL_OK;
 }
 
-// Upload the sparse transition structure of every utterance (CSR successors / CSC predecessors, both with ascending
-// indices; entries with ln A = -inf are not stored) and ln pi.  row_ptr / col_ptr: sumN + U entries (N_u + 1 per
-// utterance, local offsets); the UttDesc nnz_off fields must already be set.
-int pcl_batch_upload_sparse(pcl_batch *b, const std::vector<int> &row_ptr, const std::vector<int> &col_idx,
-                            const std::vector<double> &csr_val, const std::vector<int> &col_ptr,
-                            const std::vector<int> &row_idx, const std::vector<double> &csc_val, const double *logpi) {
+// Upload the sparse transition structure of every utterance (SparseTrans, batch_plan.h; the UttDesc nnz_off fields are set) and ln pi.
+int pcl_batch_upload_sparse(pcl_batch *b, const SparseTrans &t, const double *logpi) {
     pcl_ctx *ctx = b->ctx;
-    b->nnz = (long long)col_idx.size();
-    // left to right: state i is entered from i - 1 and from itself only (what AcousticModel.embedded builds, AcousticModel.py:979-989)
-    b->left_right = true;
-    for (int u = 0; u < b->U && b->left_right; ++u) {
-        const UttDesc &d = b->utt[u];
-        for (int i = 0; i < d.N && b->left_right; ++i)
-            for (int k = row_ptr[d.ptr_off + i]; k < row_ptr[d.ptr_off + i + 1]; ++k) {
-                const int j = col_idx[(size_t)d.nnz_off + k];
-                if (j != i && j != i + 1) {
-                    b->left_right = false;
-                    break;
-                }
-            }
-    }
+    b->trans = t.shape;
     b->row_ptr.release(); b->col_idx.release(); b->csr_val.release();
     b->col_ptr.release(); b->row_idx.release(); b->csc_val.release();
     b->xi_m.release(); b->xi_s.release(); b->nz_tmp.release();
-    const size_t nz = (size_t)b->nnz, np = row_ptr.size();
+    const size_t nz = (size_t)t.shape.nnz, np = t.row_ptr.size();
     TRY(b->row_ptr.alloc(ctx, np));
     TRY(b->col_ptr.alloc(ctx, np));
     TRY(b->col_idx.alloc(ctx, nz));
@@ -739,16 +675,16 @@ int pcl_batch_upload_sparse(pcl_batch *b, const std::vector<int> &row_ptr, const
     TRY(b->xi_s.alloc(ctx, nz));
     // (a batch that has launched nothing: its buffers are fresh, the copies need not queue behind the main stream's kernels)
     auto up = b->launched ? pcl_h2d : pcl_h2d_fresh;
-    HIPCHK(ctx, up(ctx, b->row_ptr, row_ptr.data(), np * sizeof(int)));
-    HIPCHK(ctx, up(ctx, b->col_ptr, col_ptr.data(), np * sizeof(int)));
+    HIPCHK(ctx, up(ctx, b->row_ptr, t.row_ptr.data(), np * sizeof(int)));
+    HIPCHK(ctx, up(ctx, b->col_ptr, t.col_ptr.data(), np * sizeof(int)));
     if (nz) {
-        HIPCHK(ctx, up(ctx, b->col_idx, col_idx.data(), nz * sizeof(int)));
-        HIPCHK(ctx, up(ctx, b->row_idx, row_idx.data(), nz * sizeof(int)));
-        HIPCHK(ctx, up(ctx, b->csr_val, csr_val.data(), nz * sizeof(double)));
-        HIPCHK(ctx, up(ctx, b->csc_val, csc_val.data(), nz * sizeof(double)));
+        HIPCHK(ctx, up(ctx, b->col_idx, t.col_idx.data(), nz * sizeof(int)));
+        HIPCHK(ctx, up(ctx, b->row_idx, t.row_idx.data(), nz * sizeof(int)));
+        HIPCHK(ctx, up(ctx, b->csr_val, t.csr_val.data(), nz * sizeof(double)));
+        HIPCHK(ctx, up(ctx, b->csc_val, t.csc_val.data(), nz * sizeof(double)));
     }
-    HIPCHK(ctx, up(ctx, b->logpi, logpi, (size_t)b->sumN * sizeof(double)));
-    HIPCHK(ctx, up(ctx, b->d_utt, b->utt.data(), (size_t)b->U * sizeof(UttDesc)));
+    HIPCHK(ctx, up(ctx, b->logpi, logpi, (size_t)b->shape.sumN * sizeof(double)));
+    HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_trans = true;
     b->have_fb = b->have_vit = false;
     return PCL_OK;
@@ -760,47 +696,9 @@ int pcl_batch_set_transitions(pcl_batch *b, const double *logA, const double *lo
     TRY(batch_join(b));
     if (!logA || !logpi) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_transitions: NULL argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // sparse structure: an entry is stored unless ln A == -inf
-    std::vector<int> row_ptr((size_t)b->sumN + b->U), col_ptr((size_t)b->sumN + b->U);
-    std::vector<int> col_idx, row_idx;
-    std::vector<double> csr_val, csc_val;
-    b->max_outdeg = b->max_indeg = 0;
-    for (int u = 0; u < b->U; ++u) {
-        UttDesc &d = b->utt[u];
-        const int N = d.N;
-        const double *A = logA + d.mat_off;
-        d.nnz_off = (int)col_idx.size();
-        int cnt = 0;
-        for (int i = 0; i < N; ++i) {
-            row_ptr[d.ptr_off + i] = cnt;
-            for (int j = 0; j < N; ++j) {
-                const double v = A[(size_t)i * N + j];
-                if (!(v == -INFINITY)) {
-                    col_idx.push_back(j);
-                    csr_val.push_back(v);
-                    ++cnt;
-                }
-            }
-            b->max_outdeg = std::max(b->max_outdeg, cnt - row_ptr[d.ptr_off + i]);
-        }
-        row_ptr[d.ptr_off + N] = cnt;
-        int cc = 0;
-        for (int j = 0; j < N; ++j) {
-            col_ptr[d.ptr_off + j] = cc;
-            for (int i = 0; i < N; ++i) {
-                const double v = A[(size_t)i * N + j];
-                if (!(v == -INFINITY)) {
-                    row_idx.push_back(i);
-                    csc_val.push_back(v);
-                    ++cc;
-                }
-            }
-            b->max_indeg = std::max(b->max_indeg, cc - col_ptr[d.ptr_off + j]);
-        }
-        col_ptr[d.ptr_off + N] = cc;
-        if (col_idx.size() > 0x7fffffffULL) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_transitions: too many transitions");
-    }
-    return pcl_batch_upload_sparse(b, row_ptr, col_idx, csr_val, col_ptr, row_idx, csc_val, logpi);
+    SparseTrans t;                                                 // an entry is stored unless ln A == -inf
+    TRY(plan_sparse_trans(ctx, "pcl_batch_set_transitions", b->shape.utt, dense_trans_rows(b->shape.utt, logA), &t));
+    return pcl_batch_upload_sparse(b, t, logpi);
 }
 
 int pcl_batch_set_states(pcl_batch *b, const int32_t *row_state) {
@@ -814,88 +712,13 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
     pcl_ctx *ctx = b->ctx;
     if (ctx->J == 0) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_set_states: upload a model first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    b->row_state.assign(row_state, row_state + b->sumN);
-    // count segments per state
-    std::vector<int> count(ctx->J, 0);
-    int max_state = -1;
-    for (int u = 0; u < b->U; ++u) {
-        const UttDesc &d = b->utt[u];
-        for (int n = 0; n < d.N; ++n) {
-            const int st = row_state[d.vec_off + n];
-            if (st >= ctx->J || st < PCL_ROW_EXIT) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_states: utterance %d row %d has state %d outside [0,%d)", u, n, st, ctx->J);
-            if (st >= 0) {
-                if (d.frame0 < 0) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_set_states: batch was created without frame_begin");
-                ++count[st];
-                max_state = std::max(max_state, st);
-            }
-        }
-    }
-    std::vector<int> start(ctx->J + 1, 0);
-    for (int j = 0; j < ctx->J; ++j) start[j + 1] = start[j] + count[j];
-    b->n_segs = start[ctx->J];
-    b->segs.assign(b->n_segs, ScoreSeg());
-    // A label that names a unit twice has the same (frames, state) pair on two rows: the reference scores it once per label
-    // position (AcousticModel.py:897-902).  Here the FIRST row of a state in an utterance is scored (a state's segments list
-    // those first: scoring tiles cover [lo, hip)), the others are copies of its emission row (dup_rows_kernel); the accumulate
-    // pass walks all of a state's segments, each row has its own posteriors.
-    std::vector<int> fill(start.begin(), start.end() - 1), nprim(ctx->J, 0);
-    std::vector<long long> vtot(ctx->J, 0);
-    std::vector<int> first_row(ctx->J, -1), touched;
-    std::vector<char> is_dup((size_t)b->sumN, 0);
-    b->dups.clear();
-    for (int u = 0; u < b->U; ++u) {
-        const UttDesc &d = b->utt[u];
-        touched.clear();
-        for (int n = 0; n < d.N; ++n) {
-            const int st = row_state[d.vec_off + n];
-            if (st < 0) continue;
-            if (first_row[st] < 0) {
-                first_row[st] = n;
-                touched.push_back(st);
-                ++nprim[st];
-            } else {
-                is_dup[d.vec_off + n] = 1;
-                b->dups.push_back(DupRow{d.b_off + first_row[st], d.b_off + n, d.T, d.N});
-            }
-        }
-        for (int st : touched) first_row[st] = -1;
-    }
-    b->seg_of_row.assign((size_t)b->sumN, -1);
-    b->max_N = 0;
-    for (int u = 0; u < b->U; ++u) b->max_N = std::max(b->max_N, b->utt[u].N);
-    for (int pass = 0; pass < 2; ++pass)                         // the scored rows of every state first, then the copies
-        for (int u = 0; u < b->U; ++u) {
-            const UttDesc &d = b->utt[u];
-            for (int n = 0; n < d.N; ++n) {
-                const int st = row_state[d.vec_off + n];
-                if (st < 0 || (int)is_dup[d.vec_off + n] != pass) continue;
-                b->seg_of_row[d.vec_off + n] = fill[st];
-                ScoreSeg &s = b->segs[fill[st]++];
-                s.frame0 = d.frame0;
-                s.out0 = d.b_off + n;
-                s.len = d.T;
-                s.out_stride = d.N;
-                if (vtot[st] + d.T > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_states: state %d has too many frames", st);
-                s.vstart = (int)vtot[st];
-                s.pad = st;
-                vtot[st] += d.T;
-            }
-        }
-    b->work_states.clear();
-    b->state_seg_lo.clear();
-    b->state_seg_hi.clear();
-    b->state_seg_hip.clear();
-    for (int j = 0; j < ctx->J; ++j)
-        if (count[j]) {
-            b->work_states.push_back(j);
-            b->state_seg_lo.push_back(start[j]);
-            b->state_seg_hi.push_back(start[j + 1]);
-            b->state_seg_hip.push_back(start[j] + nprim[j]);
-        }
+    ScorePlan plan;
+    TRY(plan_score(ctx, b->shape.utt, row_state, ctx->J, &plan));   // (refused: the batch keeps the lists it had, on the host as on the device)
+    b->plan = std::move(plan);
     b->d_dups.release();
-    if (!b->dups.empty()) {
-        TRY(b->d_dups.alloc(ctx, b->dups.size()));
-        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_dups, b->dups.data(), b->dups.size() * sizeof(DupRow)));
+    if (!b->plan.dups.empty()) {
+        TRY(b->d_dups.alloc(ctx, b->plan.dups.size()));
+        HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_dups, b->plan.dups.data(), b->plan.dups.size() * sizeof(DupRow)));
     }
     b->d_segs.release();
     b->d_tiles.release();
@@ -905,17 +728,16 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
     b->d_tile_flags_c.release();
     b->n_tiles_s = b->n_tiles_c = 0;
     b->tile_frames = 0;
-    TRY(b->d_segs.alloc(ctx, (size_t)b->n_segs));
-    if (b->n_segs) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_segs, b->segs.data(), (size_t)b->n_segs * sizeof(ScoreSeg)));
+    TRY(b->d_segs.alloc(ctx, (size_t)b->plan.n_segs));
+    if (b->plan.n_segs) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_segs, b->plan.segs.data(), (size_t)b->plan.n_segs * sizeof(ScoreSeg)));
     b->d_seg_of_row.release();
-    TRY(b->d_seg_of_row.alloc(ctx, (size_t)b->sumN));
-    if (b->sumN) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_seg_of_row, b->seg_of_row.data(), (size_t)b->sumN * sizeof(int)));
+    TRY(b->d_seg_of_row.alloc(ctx, (size_t)b->shape.sumN));
+    if (b->shape.sumN) HIPCHK(ctx, pcl_h2d_fresh(ctx, b->d_seg_of_row, b->plan.seg_of_row.data(), (size_t)b->shape.sumN * sizeof(int)));
     auto up = b->launched ? pcl_h2d : pcl_h2d_fresh;             // (batch-lifetime buffers: fresh only while nothing was launched)
-    HIPCHK(ctx, up(ctx, b->d_row_state, row_state, (size_t)b->sumN * sizeof(int32_t)));
-    HIPCHK(ctx, up(ctx, b->d_utt, b->utt.data(), (size_t)b->U * sizeof(UttDesc)));
+    HIPCHK(ctx, up(ctx, b->d_row_state, row_state, (size_t)b->shape.sumN * sizeof(int32_t)));
+    HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_states = true;
     b->virt_rows_filled = false;
-    b->max_state = max_state;
     b->model_J = ctx->J;
     return PCL_OK;
 }
@@ -925,17 +747,17 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
 // NOW before any kernel indexes them.
 static int batch_revalidate(pcl_batch *b, const char *who) {
     pcl_ctx *ctx = b->ctx;
-    if (b->max_frame_end > ctx->F)
+    if (b->shape.max_frame_end > ctx->F)
         PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch refers to frame rows up to %lld but the frame matrix now has %lld rows (re-uploaded after the batch was created)",
-                 who, b->max_frame_end, (long long)ctx->F);
-    if (b->have_states && (b->max_state >= ctx->J || b->model_J != ctx->J))
+                 who, b->shape.max_frame_end, (long long)ctx->F);
+    if (b->have_states && (b->plan.max_state >= ctx->J || b->model_J != ctx->J))
         PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch was laid out for a model of %d states (largest id used %d) but the model now has %d (re-uploaded after pcl_batch_set_states)",
-                 who, b->model_J, b->max_state, ctx->J);
+                 who, b->model_J, b->plan.max_state, ctx->J);
     return PCL_OK;
 }
 
 static int ensure_tmp(pcl_batch *b) {
-    if (!b->tmp) TRY(b->tmp.alloc(b->ctx, (size_t)b->sumNT));
+    if (!b->tmp) TRY(b->tmp.alloc(b->ctx, (size_t)b->shape.sumNT));
     return PCL_OK;
 }
 
@@ -947,8 +769,8 @@ int pcl_batch_set_emissions(pcl_batch *b, const double *B) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TRY(ensure_tmp(b));
     b->launched = true;
-    HIPCHK(ctx, pcl_h2d(ctx, b->d_utt, b->utt.data(), (size_t)b->U * sizeof(UttDesc)));
-    HIPCHK(ctx, hipMemcpyAsync(b->tmp, B, (size_t)b->sumNT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, pcl_h2d(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
+    HIPCHK(ctx, hipMemcpyAsync(b->tmp, B, (size_t)b->shape.sumNT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TRY(pcl_launch_transpose(ctx, b, b->tmp, b->Bt, 1));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     b->have_B = true;
@@ -964,9 +786,9 @@ int pcl_batch_set_posteriors(pcl_batch *b, const double *lgamma) {
     if (!lgamma) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_set_posteriors: NULL argument");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TRY(ensure_tmp(b));
-    if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
-    HIPCHK(ctx, pcl_h2d(ctx, b->d_utt, b->utt.data(), (size_t)b->U * sizeof(UttDesc)));
-    HIPCHK(ctx, hipMemcpyAsync(b->tmp, lgamma, (size_t)b->sumNT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->shape.sumNT));
+    HIPCHK(ctx, pcl_h2d(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
+    HIPCHK(ctx, hipMemcpyAsync(b->tmp, lgamma, (size_t)b->shape.sumNT * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TRY(pcl_launch_transpose(ctx, b, b->tmp, b->lgam, 1));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     b->have_post = true;
@@ -980,36 +802,6 @@ static int ensure_frames64(pcl_ctx *ctx) {
     return pcl_launch_cast(ctx, nullptr, ctx->frames32, ctx->frames64, n);   // float -> double is exact
 }
 
-// XCD-aware tile order for a subset of the batch's states: workgroups are dealt round-robin over the 8 XCDs
-// (block b -> XCD b % 8, observed, speed only), so all tiles of one state are placed at block indices with the
-// same residue mod 8: the state's parameter block is then fetched into ONE XCD's L2 instead of eight.
-// Shorter queues are padded with empty tiles (seg_lo == seg_hi), which exit immediately.
-static std::vector<ScoreTile> make_tiles(const pcl_batch *b, const std::vector<size_t> &which, int tf) {
-    constexpr int NXCD = 8;
-    std::vector<ScoreTile> queue[NXCD];
-    std::vector<long long> load(NXCD, 0);
-    for (size_t k : which) {
-        const int lo = b->state_seg_lo[k], hi = b->state_seg_hip[k];      // (the scored rows; the copies sit behind them)
-        const long long tot = (long long)b->segs[hi - 1].vstart + b->segs[hi - 1].len;
-        int g = 0;
-        for (int x = 1; x < NXCD; ++x)
-            if (load[x] < load[g]) g = x;          // least-loaded XCD queue
-        int s0 = lo;
-        for (long long v = 0; v < tot; v += tf) {
-            while (s0 + 1 < hi && b->segs[s0 + 1].vstart <= v) ++s0;
-            queue[g].push_back(ScoreTile{b->work_states[k], lo, hi, (int)v, s0});
-        }
-        load[g] += (tot + tf - 1) / tf;
-    }
-    size_t depth = 0;
-    for (int x = 0; x < NXCD; ++x) depth = std::max(depth, queue[x].size());
-    std::vector<ScoreTile> tiles;
-    tiles.reserve(depth * NXCD);
-    for (size_t q = 0; q < depth; ++q)
-        for (int x = 0; x < NXCD; ++x) tiles.push_back(q < queue[x].size() ? queue[x][q] : ScoreTile{0, 0, 0, 0, 0});
-    return tiles;
-}
-
 static int build_tiles(pcl_batch *b, int precision) {
     pcl_ctx *ctx = b->ctx;
     const int route = pcl_route(ctx, precision, ctx->D);
@@ -1019,18 +811,18 @@ static int build_tiles(pcl_batch *b, int precision) {
     if (b->d_tiles && b->tile_frames == tf && b->tile_gen == ctx->model_gen) return PCL_OK;
     // MFMA mode: states whose centred expansion is ill conditioned go to the direct-form VALU kernel
     std::vector<size_t> good, bad;
-    for (size_t k = 0; k < b->work_states.size(); ++k) (mfma && pcl_state_uses_valu(ctx, b->work_states[k]) ? bad : good).push_back(k);
-    const std::vector<ScoreTile> tiles = make_tiles(b, good, tf);
-    const std::vector<ScoreTile> tiles_v = bad.empty() ? std::vector<ScoreTile>() : make_tiles(b, bad, pcl_score_tile_frames(ctx->D, PCL_F32));
+    for (size_t k = 0; k < b->plan.work_states.size(); ++k) (mfma && pcl_state_uses_valu(ctx, b->plan.work_states[k]) ? bad : good).push_back(k);
+    const std::vector<ScoreTile> tiles = plan_tiles(b->plan, good, tf);
+    const std::vector<ScoreTile> tiles_v = bad.empty() ? std::vector<ScoreTile>() : plan_tiles(b->plan, bad, pcl_score_tile_frames(ctx->D, PCL_F32));
     // split states: on the matrix pipe (in `good`) AND, for their off-pipe mixtures, in a list of their own at the direct-form tile size
     std::vector<size_t> split;
     if (mfma)
         for (size_t k : good)
-            if (pcl_state_is_split(ctx, b->work_states[k])) split.push_back(k);
+            if (pcl_state_is_split(ctx, b->plan.work_states[k])) split.push_back(k);
     // ... at the direct-form tile size (the subset launch, rounds 4-5) or, with the coarse pass, at the matrix pipe's
     const bool coarse = route == PCL_ROUTE_SPLIT16 && pcl_coarse_enabled(ctx);
-    const std::vector<ScoreTile> tiles_s = (split.empty() || coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_score_subset_tile_frames(ctx->D));
-    const std::vector<ScoreTile> tiles_c = (split.empty() || !coarse) ? std::vector<ScoreTile>() : make_tiles(b, split, pcl_coarse_tile_frames());
+    const std::vector<ScoreTile> tiles_s = (split.empty() || coarse) ? std::vector<ScoreTile>() : plan_tiles(b->plan, split, pcl_score_subset_tile_frames(ctx->D));
+    const std::vector<ScoreTile> tiles_c = (split.empty() || !coarse) ? std::vector<ScoreTile>() : plan_tiles(b->plan, split, pcl_coarse_tile_frames());
     b->d_tiles.release();
     b->d_tiles_v.release();
     b->d_tiles_s.release();
@@ -1123,12 +915,12 @@ int pcl_batch_forward_backward(pcl_batch *b, int fix_pi, double threshold) {
         b->fetch_pending = false;
     }
     if (!b->alpha) {
-        TRY(b->alpha.alloc(ctx, (size_t)b->sumNT));
-        TRY(b->beta.alloc(ctx, (size_t)b->sumNT));
-        if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->sumNT));
-        TRY(b->pi_out.alloc(ctx, (size_t)b->sumN));
-        TRY(b->gamma_out.alloc(ctx, (size_t)b->sumN));
-        TRY(b->ksai.alloc(ctx, (size_t)b->sumNN));
+        TRY(b->alpha.alloc(ctx, (size_t)b->shape.sumNT));
+        TRY(b->beta.alloc(ctx, (size_t)b->shape.sumNT));
+        if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->shape.sumNT));
+        TRY(b->pi_out.alloc(ctx, (size_t)b->shape.sumN));
+        TRY(b->gamma_out.alloc(ctx, (size_t)b->shape.sumN));
+        TRY(b->ksai.alloc(ctx, (size_t)b->shape.sumNN));
         TRY(b->logp.alloc(ctx, (size_t)b->U));
         TRY(b->qtrace.alloc(ctx, (size_t)b->U * PCL_MAX_PASS));
         TRY(b->npass.alloc(ctx, (size_t)b->U));
@@ -1159,8 +951,8 @@ int pcl_batch_viterbi(pcl_batch *b, int end_state_back) {
         b->fetch_pending = false;
     }
     if (!b->bp) {
-        TRY(b->bp.alloc(ctx, (size_t)b->sumNT));
-        TRY(b->path.alloc(ctx, (size_t)b->sumT));
+        TRY(b->bp.alloc(ctx, (size_t)b->shape.sumNT));
+        TRY(b->path.alloc(ctx, (size_t)b->shape.sumT));
         TRY(b->point.alloc(ctx, (size_t)b->U));
     }
     if (ctx->dp_async) {
@@ -1186,13 +978,13 @@ int pcl_batch_regroup(pcl_batch *b, const int32_t *row_unit, int gmm_num, int32_
     if (!b->have_vit) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_regroup: run pcl_batch_viterbi first");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf<int32_t> d_ru, d_fu, d_fk;                       // (released with the device-wide wait, as ever, on every path)
-    TRY(d_ru.alloc(ctx, (size_t)b->sumN));
-    TRY(d_fu.alloc(ctx, (size_t)b->sumT));
-    TRY(d_fk.alloc(ctx, (size_t)b->sumT));
-    HIPCHK(ctx, hipMemcpyAsync(d_ru, row_unit, (size_t)b->sumN * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(d_ru.alloc(ctx, (size_t)b->shape.sumN));
+    TRY(d_fu.alloc(ctx, (size_t)b->shape.sumT));
+    TRY(d_fk.alloc(ctx, (size_t)b->shape.sumT));
+    HIPCHK(ctx, hipMemcpyAsync(d_ru, row_unit, (size_t)b->shape.sumN * 4, hipMemcpyHostToDevice, ctx->stream));
     TRY(pcl_launch_regroup(ctx, b, d_ru, gmm_num, d_fu, d_fk));
-    HIPCHK(ctx, hipMemcpyAsync(frame_unit, d_fu, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(frame_k, d_fk, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(frame_unit, d_fu, (size_t)b->shape.sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(frame_k, d_fk, (size_t)b->shape.sumT * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }
@@ -1208,25 +1000,25 @@ static int align_precheck(pcl_batch *b, const char *who) {
             PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the model has %d GMM states, the batch was made over %d tied states", who, ctx->J, b->tied_J);
     } else if (ctx->n_units < 1 || e < 1 || ctx->J != ctx->n_units * e)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the model has %d GMM states, %d units x %d emitting states need %d", who, ctx->J, ctx->n_units, e, ctx->n_units * e);
-    if (b->label_max >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch names unit %d, the inventory now has %d units", who, b->label_max, ctx->n_units);
+    if (b->lab.label_max >= ctx->n_units) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch names unit %d, the inventory now has %d units", who, b->lab.label_max, ctx->n_units);
     for (int u = 0; u < b->U; ++u)
-        if (b->utt[u].N != e * b->label_len[u] + 2)
+        if (b->shape.utt[u].N != e * b->lab.label_len[u] + 2)
             PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has %d rows for %d label units, the inventory now has %d emitting states per unit", who, u,
-                     b->utt[u].N, b->label_len[u], e);
+                     b->shape.utt[u].N, b->lab.label_len[u], e);
     if (!ctx->frames32 || ctx->F == 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: no frames uploaded", who);
-    if (b->max_frame_end > ctx->F)
+    if (b->shape.max_frame_end > ctx->F)
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the batch refers to frame rows up to %lld but the frame matrix now has %lld rows (re-uploaded after the batch was created)",
-                 who, b->max_frame_end, (long long)ctx->F);
+                 who, b->shape.max_frame_end, (long long)ctx->F);
     if (ctx->F > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame matrix of %lld rows", who, (long long)ctx->F);
     {   // a frame has one owner: the utterances' row ranges are disjoint
         std::vector<int> by(b->U);
         for (int u = 0; u < b->U; ++u) by[u] = u;
-        std::sort(by.begin(), by.end(), [&](int x, int y) { return b->utt[x].frame0 != b->utt[y].frame0 ? b->utt[x].frame0 < b->utt[y].frame0 : x < y; });
+        std::sort(by.begin(), by.end(), [&](int x, int y) { return b->shape.utt[x].frame0 != b->shape.utt[y].frame0 ? b->shape.utt[x].frame0 < b->shape.utt[y].frame0 : x < y; });
         long long end = 0;
         int prev = -1;
         for (int u : by) {
-            if (b->utt[u].frame0 < end) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterances %d and %d overlap in the frame matrix", who, prev, u);
-            end = b->utt[u].frame0 + b->utt[u].T;
+            if (b->shape.utt[u].frame0 < end) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterances %d and %d overlap in the frame matrix", who, prev, u);
+            end = b->shape.utt[u].frame0 + b->shape.utt[u].T;
             prev = u;
         }
     }
@@ -1237,13 +1029,12 @@ static int align_precheck(pcl_batch *b, const char *who) {
 static int align_labels_up(pcl_batch *b) {
     pcl_ctx *ctx = b->ctx;
     if (!b->d_labels) {
-        std::vector<int> loff((size_t)b->U + 1, 0);
-        for (int u = 0; u < b->U; ++u) loff[u + 1] = loff[u] + b->label_len[u];
+        const std::vector<int> &loff = b->lab.label_off;
         b->d_label_off.release();                                   // (left by a call whose second allocation failed)
         TRY(b->d_label_off.alloc(ctx, loff.size()));
-        TRY(b->d_labels.alloc(ctx, b->labels.size()));
+        TRY(b->d_labels.alloc(ctx, b->lab.labels.size()));
         HIPCHK(ctx, pcl_h2d(ctx, b->d_label_off, loff.data(), loff.size() * sizeof(int)));
-        HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->labels.data(), b->labels.size() * sizeof(int32_t)));
+        HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->lab.labels.data(), b->lab.labels.size() * sizeof(int32_t)));
     }
     return PCL_OK;
 }
@@ -1265,7 +1056,7 @@ int pcl_batch_align_segments(pcl_batch *b, int32_t *frame_state_out, int32_t *dr
         TRY(d_state.alloc(ctx, (size_t)F));
         TRY(d_drop.alloc(ctx, (size_t)b->U));
         HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
-        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, e, d_state, d_drop));
+        TRY(pcl_launch_align_segments(ctx, b, b->lab.label_len_max, e, d_state, d_drop));
         if (b->tied) TRY(pcl_launch_tied_owner(ctx, b, e, d_state));            // unit * P + slice -> the position's tied state of that slice
         if (frame_state_out) HIPCHK(ctx, hipMemcpyAsync(frame_state_out, d_state, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         if (dropped_out) HIPCHK(ctx, hipMemcpyAsync(dropped_out, d_drop, (size_t)b->U * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1302,7 +1093,7 @@ int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
         TRY(d_state.alloc(ctx, (size_t)F));
         TRY(d_drop.alloc(ctx, (size_t)b->U));
         HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
-        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, ctx->S - 2, d_state, d_drop));
+        TRY(pcl_launch_align_segments(ctx, b, b->lab.label_len_max, ctx->S - 2, d_state, d_drop));
         if (b->tied) TRY(pcl_launch_tied_owner(ctx, b, ctx->S - 2, d_state));
         HIPCHK(ctx, pcl_batch_mark(b));
         return PCL_OK;
@@ -1316,8 +1107,8 @@ int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
         std::vector<int32_t> T(b->U);
         std::vector<int64_t> begin(b->U);
         for (int u = 0; u < b->U; ++u) {
-            T[u] = b->utt[u].T;
-            begin[u] = b->utt[u].frame0;
+            T[u] = b->shape.utt[u].T;
+            begin[u] = b->shape.utt[u].frame0;
         }
         rc = pcl_launch_lda_accumulate(ctx, who, b->U, T.data(), begin.data(), d_state, state_class, ctx->J);   // (waits for its kernels)
         if (rc != PCL_OK) (void)hipStreamSynchronize(ctx->stream);  // ... unless it gave up half-way
@@ -1341,7 +1132,7 @@ int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event) {
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the statistics hold %d rows, no multiple of the inventory's %d emitting states per unit", who, ctx->tree_R, P);
     const int E = ctx->tree_R / P;
     if (!label_event) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: label_event is NULL", who);
-    for (size_t i = 0; i < b->labels.size(); ++i)
+    for (size_t i = 0; i < b->lab.labels.size(); ++i)
         if (label_event[i] < -1 || label_event[i] >= E)
             PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: label_event[%zu] = %d is neither -1 nor an event in [0, %d)", who, i, (int)label_event[i], E);
     TRY(batch_join(b));
@@ -1353,11 +1144,11 @@ int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event) {
         TRY(d_state.alloc(ctx, (size_t)F));
         TRY(d_row.alloc(ctx, (size_t)F));
         TRY(d_drop.alloc(ctx, (size_t)b->U));
-        TRY(d_event.alloc(ctx, b->labels.size()));
-        HIPCHK(ctx, pcl_h2d(ctx, d_event, label_event, b->labels.size() * sizeof(int32_t)));
+        TRY(d_event.alloc(ctx, b->lab.labels.size()));
+        HIPCHK(ctx, pcl_h2d(ctx, d_event, label_event, b->lab.labels.size() * sizeof(int32_t)));
         HIPCHK(ctx, hipMemsetAsync(d_state, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(d_row, 0xff, (size_t)F * sizeof(int32_t), ctx->stream));
-        TRY(pcl_launch_align_segments(ctx, b, b->label_len_max, P, d_state, d_drop));
+        TRY(pcl_launch_align_segments(ctx, b, b->lab.label_len_max, P, d_state, d_drop));
         TRY(pcl_launch_tree_label_rows(ctx, b, d_event, P, d_state, d_row));
         HIPCHK(ctx, pcl_batch_mark(b));
         return PCL_OK;
@@ -1371,8 +1162,8 @@ int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event) {
         std::vector<int32_t> T(b->U);
         std::vector<int64_t> begin(b->U);
         for (int u = 0; u < b->U; ++u) {
-            T[u] = b->utt[u].T;
-            begin[u] = b->utt[u].frame0;
+            T[u] = b->shape.utt[u].T;
+            begin[u] = b->shape.utt[u].frame0;
         }
         rc = pcl_launch_tree_accumulate(ctx, who, b->U, T.data(), begin.data(), d_row);   // (waits for its kernels)
         if (rc != PCL_OK) (void)hipStreamSynchronize(ctx->stream);  // ... unless it gave up half-way
@@ -1409,7 +1200,7 @@ int pcl_batch_get(pcl_batch *b, int what, void *host) {
         DevBuf<double> logs;
         if ((what == PCL_GET_ALPHA || what == PCL_GET_BETA) && b->fb_linear) {
             // the scaled forward-backward keeps (mantissa, exponent) pairs; the logarithms the reference holds are made here, on demand
-            TRY(logs.alloc(ctx, (size_t)b->sumNT));
+            TRY(logs.alloc(ctx, (size_t)b->shape.sumNT));
             TRY(pcl_launch_fb_to_log(ctx, b, mat, what == PCL_GET_ALPHA ? b->alpha_e : b->beta_e, logs));
             mat = logs;
         }
@@ -1420,25 +1211,25 @@ int pcl_batch_get(pcl_batch *b, int what, void *host) {
             logs.release();
         }
         TRY(rt);
-        HIPCHK(ctx, hipMemcpyAsync(host, b->tmp, (size_t)b->sumNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(host, b->tmp, (size_t)b->shape.sumNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         return PCL_OK;
     }
     const void *src = nullptr;
     size_t bytes = 0;
     switch (what) {
-        case PCL_GET_KSAI: src = b->ksai; bytes = (size_t)b->sumNN * 8; break;
+        case PCL_GET_KSAI: src = b->ksai; bytes = (size_t)b->shape.sumNN * 8; break;
         case PCL_GET_KSAI_NZ:
-            if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->nnz));
+            if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->trans.nnz));
             TRY(pcl_launch_ksai_gather(ctx, b, b->nz_tmp));
-            src = b->nz_tmp; bytes = (size_t)b->nnz * 8;
+            src = b->nz_tmp; bytes = (size_t)b->trans.nnz * 8;
             break;
-        case PCL_GET_GAMMA: src = b->gamma_out; bytes = (size_t)b->sumN * 8; break;
-        case PCL_GET_PI: src = b->pi_out; bytes = (size_t)b->sumN * 8; break;
+        case PCL_GET_GAMMA: src = b->gamma_out; bytes = (size_t)b->shape.sumN * 8; break;
+        case PCL_GET_PI: src = b->pi_out; bytes = (size_t)b->shape.sumN * 8; break;
         case PCL_GET_LOGP: src = b->logp; bytes = (size_t)b->U * 8; break;
         case PCL_GET_NPASS: src = b->npass; bytes = (size_t)b->U * 4; break;
         case PCL_GET_QTRACE: src = b->qtrace; bytes = (size_t)b->U * PCL_MAX_PASS * 8; break;
-        case PCL_GET_PATH: src = b->path; bytes = (size_t)b->sumT * 4; break;
+        case PCL_GET_PATH: src = b->path; bytes = (size_t)b->shape.sumT * 4; break;
         case PCL_GET_POINT: src = b->point; bytes = (size_t)b->U * 8; break;
         default: PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_get: unknown selector %d", what);
     }
@@ -1449,10 +1240,10 @@ int pcl_batch_get(pcl_batch *b, int what, void *host) {
 
 int pcl_batch_sizes(pcl_batch *b, int64_t *sum_nt, int64_t *sum_n, int64_t *sum_t, int64_t *nnz) {
     if (!b) return PCL_ERR_INVALID;
-    if (sum_nt) *sum_nt = b->sumNT;
-    if (sum_n) *sum_n = b->sumN;
-    if (sum_t) *sum_t = b->sumT;
-    if (nnz) *nnz = b->nnz;
+    if (sum_nt) *sum_nt = b->shape.sumNT;
+    if (sum_n) *sum_n = b->shape.sumN;
+    if (sum_t) *sum_t = b->shape.sumT;
+    if (nnz) *nnz = b->trans.nnz;
     return PCL_OK;
 }
 
@@ -1475,16 +1266,16 @@ int pcl_batch_fetch_async(pcl_batch *b, double *logp, double *lgamma_tm, double 
         if (b->dp_pending) HIPCHK(ctx, hipStreamWaitEvent(ds, b->ev_dp, 0));
     }
     if (ksai_nz) {
-        if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->nnz));
+        if (!b->nz_tmp) TRY(b->nz_tmp.alloc(ctx, (size_t)b->trans.nnz));
         {
             pcl_stream_scope on_d2h(ctx, ds);
             TRY(pcl_launch_ksai_gather(ctx, b, b->nz_tmp));
         }
-        HIPCHK(ctx, hipMemcpyAsync(ksai_nz, b->nz_tmp, (size_t)b->nnz * 8, hipMemcpyDeviceToHost, ds));
+        HIPCHK(ctx, hipMemcpyAsync(ksai_nz, b->nz_tmp, (size_t)b->trans.nnz * 8, hipMemcpyDeviceToHost, ds));
     }
     if (logp) HIPCHK(ctx, hipMemcpyAsync(logp, b->logp, (size_t)b->U * 8, hipMemcpyDeviceToHost, ds));
-    if (lgamma_tm) HIPCHK(ctx, hipMemcpyAsync(lgamma_tm, b->lgam, (size_t)b->sumNT * 8, hipMemcpyDeviceToHost, ds));
-    if (path) HIPCHK(ctx, hipMemcpyAsync(path, b->path, (size_t)b->sumT * 4, hipMemcpyDeviceToHost, ds));
+    if (lgamma_tm) HIPCHK(ctx, hipMemcpyAsync(lgamma_tm, b->lgam, (size_t)b->shape.sumNT * 8, hipMemcpyDeviceToHost, ds));
+    if (path) HIPCHK(ctx, hipMemcpyAsync(path, b->path, (size_t)b->shape.sumT * 4, hipMemcpyDeviceToHost, ds));
     if (point) HIPCHK(ctx, hipMemcpyAsync(point, b->point, (size_t)b->U * 8, hipMemcpyDeviceToHost, ds));
     HIPCHK(ctx, hipEventRecord(b->ev_fetch, ds));
     b->fetch_pending = true;

@@ -16,44 +16,11 @@
 #include "../../include/poccala_hip.h"
 #include "pcl_own.h"
 #include "pcl_desc.h"
+#include "batch_plan.h"
 #include "frontend_host.h"
 
 // ---------------------------------------------------------------- device-side descriptors
-// One scoring segment = one (utterance, emitting row): `len` consecutive frames starting at frame
-// row `frame0`, written to out[out0 + t*out_stride].  Segments are sorted by GMM state; `vstart`
-// is the segment's offset inside the state's virtual concatenation of frames (H4, state-major).
-struct ScoreSeg {
-    long long frame0;
-    long long out0;
-    int len;
-    int out_stride;
-    int vstart;
-    int pad;
-};
-// An emission row that repeats another row of its utterance (the label names the unit twice): T values at stride N.
-struct DupRow {
-    long long src, dst;
-    int T, N;
-};
-// One workgroup of the scoring kernel: frames [vstart, vstart+tile) of `state`'s concatenation.
-struct ScoreTile {
-    int state;
-    int seg_lo, seg_hi;  // the state's segments are segs[seg_lo, seg_hi)
-    int vstart;
-    int seg0;            // the segment that contains vstart: a frame of the tile is almost always in seg0 or seg0 + 1
-};
-// One sentence HMM (time-major device matrices: element (t, n) at b_off + t*N + n).
-struct UttDesc {
-    long long b_off;    // into Bt / alpha / beta / lgam
-    long long mat_off;  // into the ragged dense (N,N) xi output
-    long long frame0;   // first frame row (or -1)
-    int T, N;
-    int vec_off;   // into ragged (N,) vectors
-    int ptr_off;   // into row_ptr / col_ptr (N+1 entries per utterance)
-    int nnz_off;   // into CSR / CSC entry arrays
-    int path_off;  // into ragged (T,) vectors
-};
-
+// (ScoreSeg, DupRow, ScoreTile, UttDesc: batch_plan.h, with the host code that fills them)
 // One surviving (frame, state) pair of the accumulate pass.
 struct ActiveFrame {
     long long frame;  // row of the frame matrix
@@ -320,19 +287,17 @@ struct BatchDecodeDev {
 // Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_api.hip).
 struct pcl_batch : BatchDecodeDev {
     pcl_ctx *ctx = nullptr;
-    int U = 0, Nmax = 0, Tmax = 0;
-    bool has_one_frame = false;   // an utterance of ONE frame: the reference's Baum-Welch raises on it (golden G15) and it adds nothing to any accumulator
-    long long sumNT = 0, sumN = 0, sumT = 0, sumNN = 0;
-    long long max_frame_end = 0;   // max over utterances of frame_begin + T: re-validated against the CURRENT frame matrix
+    int U = 0;
+    // What the host planned for the kernels (batch_plan.h), each the host copy of what the device holds: replaced as a whole by the call
+    // that plans it again, and only once the plan has been accepted
+    BatchShape shape;              // pcl_batch_create: the utterances' offsets (d_utt)
+    TransShape trans;              // pcl_batch_set_transitions / the sentence HMMs of the labels: what the CSR / CSC arrays below look like
+    ScorePlan plan;                // pcl_batch_set_states: the row -> state map and the scoring work lists (d_row_state, d_segs, d_dups, d_seg_of_row)
+    LabelPlan lab;                 // label-built batches: the labels and per unit the list of its occurrences (occ_ptr / occ_utt / occ_row0)
     int model_J = 0;               // J of the model the state lists were built for
-    int max_state = -1;            // largest GMM state id any row refers to: re-validated against the CURRENT model
-    std::vector<UttDesc> utt;  // host copy
-    std::vector<int32_t> row_state;
     bool have_trans = false, have_states = false, have_B = false, have_fb = false, have_vit = false, have_post = false;
     bool launched = false;           // a kernel that reads this batch's descriptors may be in flight: their re-upload goes through the main stream
     bool virt_rows_filled = false;   // the constant entry / exit rows of Bt are in place for the current row map
-    int max_outdeg = 0, max_indeg = 0;
-    long long nnz = 0;
     // device
     DevBuf<UttDesc> d_utt;
     DevBuf<double> Bt, alpha, beta, lgam;
@@ -351,18 +316,12 @@ struct pcl_batch : BatchDecodeDev {
     DevBuf<double> fb_dump;
     DevBuf<double> fb_part_m;                  // per utterance, sum and wave: the posterior kernel's partial sums (mantissa, exponent)
     DevBuf<int> fb_part_e;
-    bool left_right = false;                      // every state is reached from itself / the state before it only (AcousticModel.embedded)
     bool fb_linear = false;                       // the last forward-backward left (mantissa, exponent) pairs in alpha / beta
     DevBuf<unsigned short> bp;                 // Viterbi back-pointers, time-major (t, n)
     DevBuf<int32_t> d_row_state;
     // scoring work lists
     DevBuf<ScoreSeg> d_segs;
-    std::vector<ScoreSeg> segs;              // host copy, sorted by state
-    std::vector<int> state_seg_lo, state_seg_hi;  // per state with work: segment range
-    std::vector<int> state_seg_hip;               // ... of which [lo, hip) are scored and [hip, hi) are copies of a scored row
-    std::vector<DupRow> dups;
     DevBuf<DupRow> d_dups;
-    std::vector<int> work_states;
     DevBuf<ScoreTile> d_tiles;            // tiles for the precision last scored with (MFMA kernel in MFMA mode)
     std::vector<int> acc_ws, acc_lo, acc_hi, acc_split; // accumulate's state order (well-conditioned first)
     LazyEvent ev_main, ev_dp;   // main stream -> stream_dp hand-over, and back
@@ -377,25 +336,20 @@ struct pcl_batch : BatchDecodeDev {
     DevBuf<ScoreTile> d_tiles_c;          // ... and for the coarse pass (gmm_score_coarse.hip): the same states at the matrix-pipe tile size
     DevBuf<int> d_tile_flags_c;           // coarse pass: per tile, 1 = a scaled feature left the f16 range (the direct-form subset kernel rescored it)
     int n_tiles_c = 0;
-    int n_segs = 0, n_tiles = 0, n_tiles_v = 0, n_tiles_s = 0, tile_frames = 0, tile_gen = -1;
+    int n_tiles = 0, n_tiles_v = 0, n_tiles_s = 0, tile_frames = 0, tile_gen = -1;
     DevBuf<double> tmp;                   // sumNT staging buffer for layout conversion
     DevBuf<double> nz_tmp;                // nnz staging buffer for the sparse xi download
-    std::vector<int> seg_of_row;              // (utterance, row) -> its segment (-1: not a GMM row); d_seg_of_row: the device copy (sumN ints)
-    DevBuf<int> d_seg_of_row;
-    int max_N = 0;                            // rows of the largest sentence HMM of the batch
+    DevBuf<int> d_seg_of_row;                 // ScorePlan::seg_of_row (sumN ints)
     bool counted = false;                     // in ctx->live_batches (a batch pcl_batch_create gave out)
     // (the accumulate pass's device work lists and tile images are the CONTEXT's scratch, pcl_ctx::acc; the host staging of its state order is acc_ws ... above)
     // decoder state: BatchDecodeDev
     bool have_dec = false;
-    // label-built batches (pcl_batch_create_labels): the labels, and per unit the list of its occurrences
+    // label-built batches (pcl_batch_create_labels): `lab`, and
     bool from_labels = false;
-    std::vector<int32_t> label_len, labels;
     std::vector<double> logpi_u;             // ln pi of every state of utterance u (uniform 1/N, AcousticModel.py:1003-1006)
-    int n_occ = 0;
     DevBuf<int> occ_ptr, occ_utt, occ_row0;   // unit -> [occ_ptr[u], occ_ptr[u+1]) -> (utterance, first emitting row)
     DevBuf<int32_t> d_labels;             // the labels on the device and the U + 1 offsets into them: uploaded by the first
     DevBuf<int> d_label_off;              // pcl_batch_align_segments of the batch, kept for the next
-    int label_max = 0, label_len_max = 0;    // largest unit id / longest label of the batch
     // ... over tied states (pcl_batch_create_labels_tied): the tied state of every (label position, state position), written by the walk
     // when the batch was made and the batch's own from then on -- a later pcl_tying_upload / pcl_tying_drop does not reach it
     bool tied = false;
@@ -533,9 +487,7 @@ static inline int pcl_run_on_dp_stream(pcl_batch *b, bool after_fetch, Launch la
 
 // shared by pcl_api.hip and hmm_units.hip (C linkage, internal)
 extern "C" {
-int pcl_batch_upload_sparse(pcl_batch *b, const std::vector<int> &row_ptr, const std::vector<int> &col_idx,
-                            const std::vector<double> &csr_val, const std::vector<int> &col_ptr,
-                            const std::vector<int> &row_idx, const std::vector<double> &csc_val, const double *logpi);
+int pcl_batch_upload_sparse(pcl_batch *b, const SparseTrans &t, const double *logpi);
 int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state);
 }
 void pcl_timer_begin(pcl_ctx *ctx, const char *which);

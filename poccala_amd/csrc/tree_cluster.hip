@@ -285,8 +285,8 @@ int pcl_tree_accumulate_ready(pcl_ctx *ctx, const char *who) {
 }
 
 int pcl_launch_tree_label_rows(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_label_event, int P, const int32_t *d_frame_state, int32_t *d_frame_row) {
-    if (b->Tmax <= 0) return PCL_OK;
-    hipLaunchKernelGGL(tree_label_rows_kernel, dim3((unsigned)std::min(64, (b->Tmax + 255) / 256), (unsigned)b->U), dim3(256), 0, ctx->stream, b->d_utt.p,
+    if (b->shape.Tmax <= 0) return PCL_OK;
+    hipLaunchKernelGGL(tree_label_rows_kernel, dim3((unsigned)std::min(64, (b->shape.Tmax + 255) / 256), (unsigned)b->U), dim3(256), 0, ctx->stream, b->d_utt.p,
                        b->path.p, b->d_label_off.p, d_label_event, P, d_frame_state, d_frame_row);
     HIPCHK(ctx, hipGetLastError());
     return PCL_OK;

@@ -156,19 +156,18 @@ void pcl_lexicon_untie_release(pcl_ctx *ctx) {
 
 int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state) {
     const int P = ctx->ty_P;
-    std::vector<int> loff((size_t)b->U + 1, 0);
+    const std::vector<int> &loff = b->lab.label_off;
     for (int u = 0; u < b->U; ++u) {
-        loff[u + 1] = loff[u] + b->label_len[u];
-        if (b->utt[u].vec_off != P * loff[u] + 2 * u || b->utt[u].N != P * b->label_len[u] + 2)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels_tied: utterance %d: rows at %d (%d of them), expected at %d", u, b->utt[u].vec_off, b->utt[u].N,
+        if (b->shape.utt[u].vec_off != P * loff[u] + 2 * u || b->shape.utt[u].N != P * b->lab.label_len[u] + 2)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_create_labels_tied: utterance %d: rows at %d (%d of them), expected at %d", u, b->shape.utt[u].vec_off, b->shape.utt[u].N,
                      P * loff[u] + 2 * u);
     }
-    const size_t tot = b->labels.size();
+    const size_t tot = b->lab.labels.size();
     TRY(b->d_label_off.alloc(ctx, loff.size()));
     TRY(b->d_labels.alloc(ctx, tot));
     TRY(b->pos_state.alloc(ctx, tot * P));
     HIPCHK(ctx, pcl_h2d(ctx, b->d_label_off, loff.data(), loff.size() * sizeof(int)));
-    HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->labels.data(), tot * sizeof(int32_t)));
+    HIPCHK(ctx, pcl_h2d(ctx, b->d_labels, b->lab.labels.data(), tot * sizeof(int32_t)));
     const size_t shm = qbits_shm(ctx);
     pcl_timer_begin(ctx, "tying");
     // (the batch's d_row_state is the destination: pcl_batch_set_states_impl writes the same values over it afterwards)
@@ -180,15 +179,15 @@ int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state)
                            ctx->ty_W, ctx->ty_units, b->d_labels.p, b->d_label_off.p, b->pos_state.p, b->d_row_state.p);
     pcl_timer_end(ctx, "tying");
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, pcl_d2h_queue(ctx, row_state, b->d_row_state, (size_t)b->sumN * sizeof(int32_t)));
+    HIPCHK(ctx, pcl_d2h_queue(ctx, row_state, b->d_row_state, (size_t)b->shape.sumN * sizeof(int32_t)));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }
 
 int pcl_launch_tied_owner(pcl_ctx *ctx, pcl_batch *b, int P, int32_t *d_frame_state) {
-    if (b->Tmax <= 0) return PCL_OK;
+    if (b->shape.Tmax <= 0) return PCL_OK;
     pcl_timer_begin(ctx, "tying_owner");
-    hipLaunchKernelGGL(tied_owner_kernel, dim3((unsigned)std::min(64, (b->Tmax + 255) / 256), (unsigned)b->U), dim3(256), 0, ctx->stream, b->d_utt.p, b->path.p,
+    hipLaunchKernelGGL(tied_owner_kernel, dim3((unsigned)std::min(64, (b->shape.Tmax + 255) / 256), (unsigned)b->U), dim3(256), 0, ctx->stream, b->d_utt.p, b->path.p,
                        b->d_label_off.p, b->pos_state.p, P, d_frame_state);
     pcl_timer_end(ctx, "tying_owner");
     HIPCHK(ctx, hipGetLastError());
@@ -244,7 +243,7 @@ int pcl_batch_get_states(pcl_batch *b, int32_t *row_state, int32_t *pos_state) {
     if (!b->have_states) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the batch has no row -> state map yet", who);
     if (pos_state && !b->tied) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: pos_state is kept by batches over tied states only (pcl_batch_create_labels_tied)", who);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (row_state) HIPCHK(ctx, pcl_d2h_queue(ctx, row_state, b->d_row_state, (size_t)b->sumN * sizeof(int32_t)));
+    if (row_state) HIPCHK(ctx, pcl_d2h_queue(ctx, row_state, b->d_row_state, (size_t)b->shape.sumN * sizeof(int32_t)));
     if (pos_state) HIPCHK(ctx, pcl_d2h_queue(ctx, pos_state, b->pos_state, b->pos_state.cap * sizeof(int32_t)));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;

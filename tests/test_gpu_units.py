@@ -1153,3 +1153,26 @@ def test_impossible_utterance_as_the_reference_has_it(eng, golden):
     assert not st['acc'].any() and not st['alpha_acc'].any() and not st['mean_acc'].any() and not st['cov_acc'].any()
     assert np.isfinite(st['acc']).all() and np.isneginf(ks).all() and np.isneginf(ga).all()
     b.close()
+
+
+def test_refused_set_states_leaves_the_batch_as_it_was(eng):
+    """pcl_batch_set_states plans before it touches the batch (batch_plan.h; the planner's all-or-nothing is tests/test_batch_plan_host.py's):
+    a map with a state id == J is refused and the next scoring gives the bits of the one before, the device's row map is the accepted one."""
+    from poccala_amd import PCL_F32, PoccalaHipError
+    rng = np.random.default_rng(11)
+    J, M, D = 2, 1, 2
+    eng.load_model(rng.normal(size=(J, M, D)), rng.uniform(0.5, 1.5, size=(J, M, D)), np.ones((J, M)))
+    eng.load_frames(rng.normal(size=(7, D)).astype(np.float32))
+    b = eng.batch([4, 3], [3, 4], [0, 3])
+    good = [np.array([-1, 0, 1, -2], dtype=np.int32), np.array([-1, 1, -2], dtype=np.int32)]
+    b.set_states(good)
+    b.score(PCL_F32)
+    B0, rows0 = [x.copy() for x in b.get('B')], [x.copy() for x in b.row_states()]
+    assert all(np.array_equal(r, g) for r, g in zip(rows0, good))
+    with pytest.raises(PoccalaHipError, match=r'utterance 1 row 1 has state 2 outside \[0,2\)'):
+        b.set_states([good[0], np.array([-1, J, -2], dtype=np.int32)])
+    b.score(PCL_F32)
+    for u in range(2):
+        assert B0[u].tobytes() == b.get('B')[u].tobytes()
+        assert np.array_equal(b.row_states()[u], rows0[u])
+    b.close()
