@@ -140,8 +140,8 @@ __global__ void hmm_fb_kernel(const UttDesc *__restrict__ utts, const double *__
     for (long long e = i; e < (long long)N * N; e += NP) ksai[d.mat_off + e] = -INFINITY;
     __syncthreads();
 
-    double q = -INFINITY;
-    int npass = 0;
+    FbPassRule rule(fix_pi, threshold);
+    double *const trace = qtrace + (long long)blockIdx.x * PCL_MAX_PASS;
     for (;;) {
         // ---------------------------------------------------------------- forward (LHMM.py:335-351)
         double a = -INFINITY;
@@ -193,17 +193,9 @@ __global__ void hmm_fb_kernel(const UttDesc *__restrict__ utts, const double *__
         }
         // Q = LSE_i alpha_{T-1}(i)   (LHMM.py:412-422, datasize == 1 on this path)
         const double qnew = block_lse(act ? a : -INFINITY, red, slot);
-        bool final_pass = !(qnew - q > threshold) || (npass + 1 >= PCL_MAX_PASS);   // LHMM.py:539
-        if (i == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-        ++npass;
-        if (fix_pi && !final_pass && threshold >= 0.0 && npass < PCL_MAX_PASS) {
-            // quirk Q6: with pi locked nothing changes between passes, so the next pass would
-            // reproduce this one bit for bit and then stop (Q - Q = 0 <= threshold).  Take its
-            // statistics now and report the pass the reference would have run.
-            if (i == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-            ++npass;
-            final_pass = true;
-        }
+        const FbPassRule::Verdict v = rule.judge(qnew);
+        const bool final_pass = v.final_pass;
+        rule.record(v, qnew, trace, i == 0);
 
         // ---------------------------------------------------------------- backward (LHMM.py:353-366)
         // beta_{T-1} = 0 for every state (quirk Q8).  The vector exchanged through LDS is
@@ -341,14 +333,9 @@ __global__ void hmm_fb_kernel(const UttDesc *__restrict__ utts, const double *__
                         ksai[d.mat_off + (long long)i * N + col_idx[k]] = (xi_s[k] > 0.0) ? xi_m[k] + log(xi_s[k]) : -INFINITY;
                 }
             }
-            if (i == 0) {
-                logp[blockIdx.x] = qnew;
-                npass_out[blockIdx.x] = npass;
-                for (int k = npass; k < PCL_MAX_PASS; ++k) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + k] = NAN;
-            }
+            if (i == 0) rule.finish(qnew, logp + blockIdx.x, npass_out + blockIdx.x, trace);
             break;
         }
-        q = qnew;
     }
 }
 
@@ -502,8 +489,8 @@ __device__ __forceinline__ void hmm_fb2_body(const UttDesc *__restrict__ utts, c
     const bool shift = __all(near) != 0;                            // (both waves hold the same states: the same answer)
     if (w == 0) lpi[i] = act ? logpi_in[d.vec_off + i] : -INFINITY;
     __syncthreads();
-    double q = -INFINITY;
-    int npass = 0;
+    FbPassRule rule(fix_pi, threshold);
+    double *const trace = qtrace + (long long)blockIdx.x * PCL_MAX_PASS;
     for (;;) {
         if (w == 0) {
             // ---------------------------------------------------------------- forward (LHMM.py:335-351)
@@ -584,15 +571,9 @@ __device__ __forceinline__ void hmm_fb2_body(const UttDesc *__restrict__ utts, c
         }
         __syncthreads();
         const double qnew = s_q;
-        bool final_pass = !(qnew - q > threshold) || (npass + 1 >= PCL_MAX_PASS);   // LHMM.py:539
-        if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-        ++npass;
-        if (fix_pi && !final_pass && threshold >= 0.0 && npass < PCL_MAX_PASS) {
-            // quirk Q6: with pi locked the next pass would reproduce this one bit for bit and then stop
-            if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-            ++npass;
-            final_pass = true;
-        }
+        const FbPassRule::Verdict v = rule.judge(qnew);
+        const bool final_pass = v.final_pass;
+        rule.record(v, qnew, trace, threadIdx.x == 0);
         // ---------------------------------------------------------------- pi (LHMM.py:447-452,470-471), wave 0
         if (w == 0) {
             if (!fix_pi) {
@@ -607,14 +588,9 @@ __device__ __forceinline__ void hmm_fb2_body(const UttDesc *__restrict__ utts, c
         }
         if (final_pass) {
             // xi / gamma / the per-frame posteriors are parallel over t: hmm_post_kernel, eight waves per utterance, right behind
-            if (threadIdx.x == 0) {
-                logp[blockIdx.x] = qnew;
-                npass_out[blockIdx.x] = npass;
-                for (int k = npass; k < PCL_MAX_PASS; ++k) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + k] = NAN;
-            }
+            if (threadIdx.x == 0) rule.finish(qnew, logp + blockIdx.x, npass_out + blockIdx.x, trace);
             break;
         }
-        q = qnew;
         __syncthreads();
     }
 }
@@ -923,7 +899,7 @@ int pcl_launch_fb_linear_post(pcl_ctx *ctx, pcl_batch *b) {
                        b->csr_val, b->alpha, b->alpha_e, b->beta, b->beta_e, b->lgam, b->ksai, b->logp, b->fb_dump, b->fb_part_m, b->fb_part_e)
         if (NPp == 128) LAUNCH_PM(2); else if (NPp == 192) LAUNCH_PM(3); else LAUNCH_PM(4);
 #undef LAUNCH_PM
-        hipLaunchKernelGGL(hmm_postlm_merge_kernel, dim3(b->U), dim3(NPp), 0, ctx->stream, b->d_utt, b->fb_kmax, b->row_ptr, b->col_idx, b->fb_part_m,
+        hipLaunchKernelGGL(hmm_postl_merge_kernel, dim3(b->U), dim3(NPp), 0, ctx->stream, b->d_utt, b->fb_kmax, b->row_ptr, b->col_idx, b->fb_part_m,
                            b->fb_part_e, b->ksai, b->gamma_out);
         HIPCHK(ctx, hipGetLastError());
         return PCL_OK;

@@ -187,6 +187,121 @@ static_assert(PACK_BLOCKS + 2 <= PCL_FB_KREC, "the per-utterance record holds th
 
 constexpr int FBL_BLK = 4;      // frames of packed emissions in flight ahead of the recursion = steps between renormalisations
 
+// ------------------------------------------------------------------------------------------------
+// What the single-wave kernels here and the multi-wave kernels of hmm_fb_linear_mw.inc share: straight-line pieces only.  What
+// decides a schedule -- where the neighbour's value comes from, the stores, the barrier, the double-buffered block / tail loop --
+// stays written out in the two walks (le_chain here, le_chain_mw there).
+// ------------------------------------------------------------------------------------------------
+// m 2^e brought to the exponent E >= e of a sum (far below it: an exact 0.0)
+__device__ __forceinline__ double le_align(double m, int e, int E) { return ldexp(m, max(le_sub(e, E), -4000)); }
+// one more term into a lane's running sum  S = sm 2^se
+__device__ __forceinline__ void le_accumulate(double g, int ge, double &sm, int &se) {
+    const int e1 = max(se, ge);
+    sm = le_align(sm, se, e1) + le_align(g, ge, e1);
+    se = e1;
+}
+// state i's two stored transitions: to itself (s) and to the next state (o); absent, or a lane beyond N = a zero factor
+struct LeTrans {
+    double as_m = 1.0, ao_m = 1.0;
+    int as_e = LE_ZADD, ao_e = LE_ZADD;
+};
+__device__ __forceinline__ LeTrans le_transitions(const UttDesc &d, int i, bool act, const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                  const double *__restrict__ csr_val) {
+    LeTrans a;
+    if (act) {
+        const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
+        for (int k = sr0; k < sr1; ++k) {
+            const int j = col_idx[k];
+            if (j == i) exp_split(csr_val[k], a.as_m, a.as_e);
+            else if (j == i + 1) exp_split(csr_val[k], a.ao_m, a.ao_e);
+        }
+    }
+    return a;
+}
+// One step of a chain for one lane.  The loop-carried chain is  mul -> (DPP) -> ldexp -> add.  Three pieces, because the walks put
+// their own work between them and the order in the source is the order the scheduler starts from (one function that took the
+// neighbour's value and did the rest moved the publish in front of the stores: the same instructions in another order, measured 0.5-2 % slower):
+//   LeStep st(...)  the step's unpacked emission (cb, kb) folded into the two transitions the lane publishes along: off the chain
+//   [the walk selects the neighbour's published value (pn, epn)]
+//   st.sum()        the step's sum s 2^e0 (alpha_t = s b_t, beta_t = s)
+//   [the walk stores]
+//   st.publish()    the lane's two published values move on
+struct LeStep {
+    double cz, cp;
+    int kz, kp;
+    __device__ __forceinline__ LeStep(double cb, int kb, double as_m, int as_e, double ap_m, int ap_e)
+        : cz(cb * as_m), cp(cb * ap_m), kz(floor_add(kb, as_e)), kp(floor_add(kb, ap_e)) {}
+    __device__ __forceinline__ void sum(double z, int ez, double pn, int epn, double &s, int &e0) const {
+        e0 = max(ez, epn);
+        s = ldexp(z, le_sub(ez, e0)) + ldexp(pn, le_sub(epn, e0));
+    }
+    __device__ __forceinline__ void publish(double s, int e0, double &z, int &ez, double &p, int &ep) const {
+        z = s * cz;
+        p = s * cp;
+        ez = floor_add(e0, kz);
+        ep = floor_add(e0, kp);
+    }
+};
+// one common power of two for the lane's two published values
+__device__ __forceinline__ void le_renorm(double &z, int &ez, double &p, int &ep) {
+    const int x = __builtin_amdgcn_frexp_exp(z + p);
+    z = ldexp(z, -x);
+    p = ldexp(p, -x);
+    ez = floor_add(ez, x);
+    ep = floor_add(ep, x);
+}
+// alpha_0(i) = pi_i b_i(o_0) (LHMM.py:335-351) as a mantissa in [0.5, 1) and its exponent, kept in a pass that stores; the lane's first
+// published values
+__device__ __forceinline__ void le_alpha0(double lpi_i, const unsigned long long *__restrict__ Bl, const LeTrans &a, bool store, double *__restrict__ Am,
+                                          int *__restrict__ Ae, double &m, int &e, double &z, int &ez, double &p, int &ep) {
+    double pm, bm;
+    int pe, bk;
+    exp_split(lpi_i, pm, pe);
+    emis_unpack(Bl[0], bm, bk);
+    m = pm * bm;
+    e = floor_add(pe, bk);
+    {
+        const int x = __builtin_amdgcn_frexp_exp(m);
+        m = __builtin_amdgcn_frexp_mant(m);
+        e = floor_add(e, x);
+    }
+    if (store) {
+        Am[0] = m;
+        Ae[0] = e;
+    }
+    z = m * a.as_m;
+    p = m * a.ao_m;
+    ez = floor_add(e, a.as_e);
+    ep = floor_add(e, a.ao_e);
+}
+// alpha_{T-1}(i) = s b_{T-1} from the forward walk's last step (T == 1: alpha_0, which (am, ae) hold already)
+__device__ __forceinline__ void le_alpha_last(const unsigned long long *__restrict__ Bl, int N, int T, double s_l, int e_l, double &am, int &ae) {
+    if (T > 1) {
+        double cb;
+        int kb;
+        emis_unpack(Bl[(long long)(T - 1) * N], cb, kb);
+        am = s_l * cb;
+        ae = floor_add(e_l, kb);
+    }
+}
+// beta_{T-1} = 1 (LHMM.py:353-366, quirk Q8), stored; published: w_{T-1}(i) = b_i(o_{T-1}) * 1 along a_ii and the transition INTO
+// the state (an); a lane beyond N: zero
+__device__ __forceinline__ void le_beta_last(const unsigned long long *__restrict__ Bl, int N, int T, bool act, const LeTrans &a, double an_m, int an_e,
+                                             double *__restrict__ Bm, int *__restrict__ Be, long long sstride, double &z, int &ez, double &p, int &ep) {
+    double bm;
+    int bk;
+    Bm[(long long)(T - 1) * sstride] = 1.0;
+    Be[(long long)(T - 1) * sstride] = 0;
+    emis_unpack(Bl[(long long)(T - 1) * N], bm, bk);
+    z = bm * a.as_m;
+    p = bm * an_m;
+    ez = act ? floor_add(bk, a.as_e) : LE_FLOOR;
+    ep = act ? floor_add(bk, an_e) : LE_FLOOR;
+}
+// Q = LSE_i alpha_{T-1}(i) (LHMM.py:412-422, datasize == 1 on this path) = le_log(S, eM) with eM the largest exponent and S the sum of
+// these terms; util.log_sum_exp returns the maximum itself when it is -inf (quirk Q4), as le_log does
+__device__ __forceinline__ double le_q_term(bool act, double am, int ae, int eM) { return act ? le_align(am, ae, eM) : 0.0; }
+
 // One walk along the chain: `nsteps` steps starting at frame t0 (forward: t0, t0 + 1, ...; backward: t0, t0 - 1, ...).
 // State in / out: the lane's two published values (z for itself, p for its neighbour) with their exponents.
 //   forward  (FWD):  neighbour = lane before (wave_shr); stored value of a step = alpha_t = s b_t       (STORE only)
@@ -208,15 +323,13 @@ __device__ __forceinline__ void le_chain(const unsigned long long *__restrict__ 
     double s_last = s_out;
     int e_last = e_out;
     auto one = [&](unsigned long long wq, int t) {
-        double cb;
-        int kb;
+        double cb, s;
+        int kb, e0;
         emis_unpack(wq, cb, kb);
-        const double cz = cb * as_m, cp = cb * ap_m;
-        const int kz = floor_add(kb, as_e), kp = floor_add(kb, ap_e);
+        const LeStep st(cb, kb, as_m, as_e, ap_m, ap_e);
         const double pn = FWD ? shr_d(p) : shl_d(p);
         const int epn = FWD ? shr_i(ep, LE_FLOOR) : shl_i(ep, LE_FLOOR);
-        const int e0 = max(ez, epn);
-        const double s = ldexp(z, le_sub(ez, e0)) + ldexp(pn, le_sub(epn, e0));
+        st.sum(z, ez, pn, epn, s, e0);
         if (FWD) {
             if (STORE) {
                 sm[(long long)t * sstride] = s * cb;
@@ -228,17 +341,7 @@ __device__ __forceinline__ void le_chain(const unsigned long long *__restrict__ 
         }
         s_last = s;
         e_last = e0;
-        z = s * cz;
-        p = s * cp;
-        ez = floor_add(e0, kz);
-        ep = floor_add(e0, kp);
-    };
-    auto renorm = [&]() {                      // one common power of two for the lane's two published values
-        const int x = __builtin_amdgcn_frexp_exp(z + p);
-        z = ldexp(z, -x);
-        p = ldexp(p, -x);
-        ez = floor_add(ez, x);
-        ep = floor_add(ep, x);
+        st.publish(s, e0, z, ez, p, ep);
     };
     // two register sets of packed emissions, used alternately (a copy "next -> current" at the end of a block is hoisted by
     // the compiler to right behind the loads, with a wait for them: the prefetch would be waited for inside its own block)
@@ -253,13 +356,13 @@ __device__ __forceinline__ void le_chain(const unsigned long long *__restrict__ 
     auto block = [&](unsigned long long (&q)[FBL_BLK], int blk) {
 #pragma unroll
         for (int k = 0; k < FBL_BLK; ++k) one(q[k], FWD ? t0 + blk * FBL_BLK + k : t0 - blk * FBL_BLK - k);
-        renorm();
+        le_renorm(z, ez, p, ep);
     };
     auto tail = [&](unsigned long long (&q)[FBL_BLK], int blk, int rem) {      // rem < FBL_BLK steps whose frames are in q already
 #pragma unroll
         for (int k = 0; k < FBL_BLK - 1; ++k)
             if (k < rem) one(q[k], FWD ? t0 + blk * FBL_BLK + k : t0 - blk * FBL_BLK - k);
-        if (rem > 0) renorm();
+        if (rem > 0) le_renorm(z, ez, p, ep);
     };
     const int nblk = nsteps / FBL_BLK, rem = nsteps - nblk * FBL_BLK;
     load(qa, 0);
@@ -324,106 +427,51 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     double *Am = act ? alpha + d.b_off + i : dm, *Bm = act ? beta + d.b_off + i : dm;
     int *Ae = act ? alpha_e + d.b_off + i : de, *Be = act ? beta_e + d.b_off + i : de;
     const long long sstride = act ? N : 0;
-    // the lane's two stored transitions: to itself and to the next state (absent = a zero factor)
-    double as_m = 1.0, ao_m = 1.0;
-    int as_e = LE_ZADD, ao_e = LE_ZADD;
-    if (act) {
-        const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
-        for (int k = sr0; k < sr1; ++k) {
-            const int j = col_idx[k];
-            if (j == i) exp_split(csr_val[k], as_m, as_e);
-            else if (j == i + 1) exp_split(csr_val[k], ao_m, ao_e);
-        }
-    }
+    const LeTrans a = le_transitions(d, i, act, row_ptr, col_idx, csr_val);
     // the transition INTO this lane from the one before it (= that lane's a_{i-1,i}): what the backward chain publishes with
-    const double an_m = __hiloint2double(shr_i(__double2hiint(ao_m), 0x3ff00000), shr_i(__double2loint(ao_m), 0));
-    const int an_e = shr_i(ao_e, LE_ZADD);
+    const double an_m = __hiloint2double(shr_i(__double2hiint(a.ao_m), 0x3ff00000), shr_i(__double2loint(a.ao_m), 0));
+    const int an_e = shr_i(a.ao_e, LE_ZADD);
     if (w == 0) lpi[i] = act ? logpi_in[d.vec_off + i] : -INFINITY;
     __syncthreads();
-    double q = -INFINITY;
-    int npass = 0;
+    FbPassRule rule(fix_pi, threshold);
+    double *const trace = qtrace + (long long)blockIdx.x * PCL_MAX_PASS;
     bool beta_done = false;
     for (;;) {
-        // alpha goes to HBM only in a pass that can be the last: the first with a locked pi (quirk Q6), the third with a free one
-        bool store = (fix_pi != 0) || npass >= 2;
-        bool final_pass = false, q6 = false;
+        bool store = rule.may_be_last();
+        FbPassRule::Verdict v{false, false};
         double qnew = 0.0;
         for (;;) {
             if (w == 0) {
                 // ---------------------------------------------------------------- forward (LHMM.py:335-351)
-                double am = 0.0;                                          // alpha_{T-1}(i)
-                int ae = LE_FLOOR;
-                {
-                    double m, pm, bm;
-                    int e, pe, bk;
-                    exp_split(act ? lpi[i] : -INFINITY, pm, pe);
-                    emis_unpack(Bl[0], bm, bk);
-                    m = pm * bm;
-                    e = floor_add(pe, bk);
-                    {
-                        const int x = __builtin_amdgcn_frexp_exp(m);
-                        m = __builtin_amdgcn_frexp_mant(m);
-                        e = floor_add(e, x);
-                    }
-                    if (store) {
-                        Am[0] = m;
-                        Ae[0] = e;
-                    }
-                    a0s[i] = act ? le_log(m, e) : -INFINITY;
-                    double z = m * as_m, p = m * ao_m;
-                    int ez = floor_add(e, as_e), ep = floor_add(e, ao_e);
-                    double s_l = 0.0;
-                    int e_l = LE_FLOOR;
-                    if (store) le_chain<true, true>(Bl, N, T - 1, 1, T, as_m, as_e, ao_m, ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l);
-                    else le_chain<true, false>(Bl, N, T - 1, 1, T, as_m, as_e, ao_m, ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l);
-                    am = m;
-                    ae = e;
-                    if (T > 1) {
-                        double cb;
-                        int kb;
-                        emis_unpack(Bl[(long long)(T - 1) * N], cb, kb);
-                        am = s_l * cb;
-                        ae = floor_add(e_l, kb);
-                    }
-                }
-                // Q = LSE_i alpha_{T-1}(i) (LHMM.py:412-422, datasize == 1 on this path); util.log_sum_exp returns the maximum itself when it is -inf (Q4)
+                double m, z, p, am, s_l = 0.0;                            // (am, ae): alpha_{T-1}(i)
+                int e, ez, ep, ae, e_l = LE_FLOOR;
+                le_alpha0(act ? lpi[i] : -INFINITY, Bl, a, store, Am, Ae, m, e, z, ez, p, ep);
+                a0s[i] = act ? le_log(m, e) : -INFINITY;
+                if (store) le_chain<true, true>(Bl, N, T - 1, 1, T, a.as_m, a.as_e, a.ao_m, a.ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l);
+                else le_chain<true, false>(Bl, N, T - 1, 1, T, a.as_m, a.as_e, a.ao_m, a.ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l);
+                am = m;
+                ae = e;
+                le_alpha_last(Bl, N, T, s_l, e_l, am, ae);
                 const int eM = wave_max_i(act ? ae : LE_FLOOR);
-                const double S = wave_sum_d(act ? ldexp(am, max(le_sub(ae, eM), -4000)) : 0.0);
-                if (i == 0) s_q = (eM < LE_PZ || !(S > 0.0)) ? -INFINITY : fma((double)eM, LN2_HI, fma((double)eM, LN2_LO, log(S)));
+                const double S = wave_sum_d(le_q_term(act, am, ae, eM));
+                if (i == 0) s_q = le_log(S, eM);
             } else if (!beta_done) {
-                // ---------------------------------------------------------------- backward (LHMM.py:353-366); beta_{T-1} = 1 (quirk Q8)
-                {
-                    double bm;
-                    int bk;
-                    Bm[(long long)(T - 1) * sstride] = 1.0;
-                    Be[(long long)(T - 1) * sstride] = 0;
-                    emis_unpack(Bl[(long long)(T - 1) * N], bm, bk);
-                    // w_{T-1}(i) = b_i(o_{T-1}) * 1   (a lane beyond N: zero)
-                    double z = bm * as_m, p = bm * an_m;
-                    int ez = act ? floor_add(bk, as_e) : LE_FLOOR, ep = act ? floor_add(bk, an_e) : LE_FLOOR;
-                    double s_l = 1.0;
-                    int e_l = 0;
-                    le_chain<false, true>(Bl, N, T - 1, T - 2, T, as_m, as_e, an_m, an_e, z, ez, p, ep, Bm, Be, sstride, s_l, e_l);
-                    b0s[i] = act ? le_log(s_l, e_l) : -INFINITY;         // ln beta_0(i) (T == 1: ln 1 = 0)
-                }
+                // ---------------------------------------------------------------- backward (LHMM.py:353-366)
+                double z, p, s_l = 1.0;
+                int ez, ep, e_l = 0;
+                le_beta_last(Bl, N, T, act, a, an_m, an_e, Bm, Be, sstride, z, ez, p, ep);
+                le_chain<false, true>(Bl, N, T - 1, T - 2, T, a.as_m, a.as_e, an_m, an_e, z, ez, p, ep, Bm, Be, sstride, s_l, e_l);
+                b0s[i] = act ? le_log(s_l, e_l) : -INFINITY;             // ln beta_0(i) (T == 1: ln 1 = 0)
             }
             beta_done = true;
             __syncthreads();
             qnew = s_q;
-            const bool natural = !(qnew - q > threshold) || (npass + 1 >= PCL_MAX_PASS);   // LHMM.py:539
-            // quirk Q6: with pi locked the next pass would reproduce this one bit for bit and then stop
-            q6 = fix_pi && !natural && threshold >= 0.0 && npass + 1 < PCL_MAX_PASS;
-            final_pass = natural || q6;
-            if (!final_pass || store) break;
+            v = rule.judge(qnew);
+            if (!FbPassRule::replay(v, store)) break;
             store = true;                                                // the pass turned out to be the last: once more, with alpha going to HBM
             __syncthreads();
         }
-        if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-        ++npass;
-        if (q6) {
-            if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-            ++npass;
-        }
+        rule.record(v, qnew, trace, threadIdx.x == 0);
         // ---------------------------------------------------------------- pi (LHMM.py:447-452,470-471), wave 0
         if (w == 0) {
             if (!fix_pi) {
@@ -434,40 +482,121 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 const double n0 = isinf(mx) ? mx : mx + log(wave_sum_d(exp(p0 - mx)));
                 const double pv = exp(p0 - n0);                  // the reference stores pi = exp(.) and takes np.log of it again
                 lpi[i] = act ? log(pv) : -INFINITY;
-                if (final_pass && act) pi_out[d.vec_off + i] = pv;
-            } else if (final_pass && act) {
+                if (v.final_pass && act) pi_out[d.vec_off + i] = pv;
+            } else if (v.final_pass && act) {
                 pi_out[d.vec_off + i] = exp(lpi[i]);
             }
         }
-        if (final_pass) {
-            if (threadIdx.x == 0) {
-                logp[blockIdx.x] = qnew;
-                npass_out[blockIdx.x] = npass;
-                for (int k = npass; k < PCL_MAX_PASS; ++k) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + k] = NAN;
-            }
+        if (v.final_pass) {
+            if (threadIdx.x == 0) rule.finish(qnew, logp + blockIdx.x, npass_out + blockIdx.x, trace);
             break;
         }
-        q = qnew;
         __syncthreads();
     }
 }
 
-// one more term into a lane's running sum  S = sm 2^se
-__device__ __forceinline__ void le_accumulate(double g, int ge, double &sm, int &se) {
-    const int e1 = max(se, ge);
-    sm = ldexp(sm, max(le_sub(se, e1), -4000)) + ldexp(g, max(le_sub(ge, e1), -4000));
-    se = e1;
-}
-
 // ------------------------------------------------------------------------------------------------
 // xi, gamma and the per-frame posteriors of the last pass (LHMM.py:394-405,431-445,486-500) from the (m, e) alpha / beta the
-// chain kernel left: eight waves per utterance, wave w takes frames w, w + 8, ...; per lane three running sums (gamma_i,
-// xi_ii, xi_{i,i+1}) as m 2^e pairs, merged over the waves in wave order (deterministic, independent of the batch).
+// chain kernel left: POSTL_W frame blocks per utterance; per lane three running sums (gamma_i, xi_ii, xi_{i,i+1}) as m 2^e pairs,
+// merged over the blocks in block order (deterministic, independent of the batch).
 //   ln gamma_t(i) - sum_value[t]:  sum_value[t] = LSE_i (alpha + beta) is ln P(O) up to rounding, so with
-//   ssum = sum_i gamma / 2^eQ and c0 = P(O) / 2^eQ:  sum_value[t] = ln P(O) + ln(ssum / c0), the logarithm of a number within
+//   ssum = sum_i gamma / 2^eQ / c0 and c0 = P(O) / 2^eQ:  sum_value[t] = ln P(O) + ln ssum, the logarithm of a number within
 //   1e-4 of 1 (three terms of its series; anything else takes log()).
 // ------------------------------------------------------------------------------------------------
 constexpr int POSTL_W = 8;
+// the per-utterance constants of that, from ln P(O)
+struct LePostConst {
+    double qnew, rc0;                                                // ln P(O); 1 / c0, c0 = P(O) / 2^eQ in [0.7, 1.42]
+    int eQ;
+    bool dead;                                                       // P(O) = 0: every l is -inf, l - sum_value is NaN as in the reference
+    __device__ __forceinline__ explicit LePostConst(double q) : qnew(q) {
+        dead = !(qnew > -INFINITY);
+        const double kq = rint(qnew * LOG2E);
+        eQ = dead ? 0 : (int)kq;
+        const double lc0 = dead ? 0.0 : fma(-kq, LN2_LO, fma(-kq, LN2_HI, qnew));
+        rc0 = dead ? 1.0 : exp(-lc0);
+    }
+    // the lane's term of the frame's  sum_i gamma_t(i) / 2^eQ  (times rc0: ssum)
+    __device__ __forceinline__ double term(double g, int ge) const { return le_align(g, ge, eQ); }
+    // l[i,t] - sum_value[t] (LHMM.py:486-500) of gamma_t(i) = g 2^ge
+    __device__ __forceinline__ double lgamma(double g, int ge, double ssum) const {
+        const double u1 = ssum - 1.0;
+        double corr;                                                 // sum_value[t] - ln P(O)
+        if (fabs(u1) < 1.0e-4) corr = u1 * (1.0 - u1 * (0.5 - u1 * (1.0 / 3.0)));
+        else corr = log(ssum);
+        if (dead) return NAN;
+        if (ge < LE_PZ || !(g > 0.0)) return -INFINITY;
+        return (fma((double)ge, LN2_HI, fma((double)ge, LN2_LO, log(g))) - qnew) - corr;
+    }
+};
+// A frame's row as the posterior kernels read it: alpha_t, beta_t and the packed emission of the lane's state
+struct LeRow {
+    double am, bm;
+    int ae, be;
+    unsigned long long w;
+    // gamma_t(i) = alpha beta = g 2^ge, and alpha's exponent (a lane beyond N read column 0: its values count as zero)
+    __device__ __forceinline__ void gamma(bool act, double &g, int &ge, int &ae_l) const {
+        g = am * bm;
+        ae_l = act ? ae : LE_FLOOR;
+        ge = act ? floor_add(ae, be) : LE_FLOOR;
+    }
+    // w_t(i) = b_i(o_t) beta_t(i)
+    __device__ __forceinline__ void w_value(bool act, double &wm, int &we) const {
+        double bm1;
+        int bk1;
+        emis_unpack(w, bm1, bk1);
+        wm = bm * bm1;
+        we = act ? floor_add(be, bk1) : LE_FLOOR;
+    }
+};
+// The rows of the CONTIGUOUS frames [t0, t1) through proc(row t, row t + 1, t): frame t needs alpha_t, beta_t and w_{t+1}, and row
+// t + 1 is the block's own next row -- every row is read once (32 B per (t, j); with frames dealt round-robin, t, t + 8, ..., every
+// block read its successor's row again: 44 B, and the kernel ran at the HBM's rate).  Three register sets in rotation, two rows
+// in flight, loads unconditional (clamped frame, column `col` = 0 for lanes beyond N) so that the compiler counts its waits.
+template <class Proc>
+__device__ __forceinline__ void le_post_rows(const UttDesc &d, const double *__restrict__ alpha, const int *__restrict__ alpha_e,
+                                             const double *__restrict__ beta, const int *__restrict__ beta_e, const unsigned long long *__restrict__ Bp,
+                                             long long col, int t0, int t1, Proc proc) {
+    const unsigned long long *B = Bp + d.b_off;
+    const double *Am = alpha + d.b_off, *Bm = beta + d.b_off;
+    const int *Ae = alpha_e + d.b_off, *Be = beta_e + d.b_off;
+    const int N = d.N, T = d.T;
+    auto ld = [&](LeRow &r, int t) {
+        const long long o = (long long)min(t, T - 1) * N + col;
+        r.am = Am[o]; r.ae = Ae[o]; r.bm = Bm[o]; r.be = Be[o]; r.w = B[o];
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if (t0 < t1) {
+        LeRow r0, r1, r2;
+        ld(r0, t0);
+        ld(r1, t0 + 1);
+        int t = t0;
+        for (;;) {
+            ld(r2, t + 2); proc(r0, r1, t); if (++t >= t1) break;
+            ld(r0, t + 2); proc(r1, r2, t); if (++t >= t1) break;
+            ld(r1, t + 2); proc(r2, r0, t); if (++t >= t1) break;
+        }
+    }
+}
+// frame t < T - 1 into the lane's three running sums: gamma_i (LHMM.py:442-445) and
+// xi_ij (+)= alpha_t(i) a_ij b_j(o_{t+1}) beta_{t+1}(j) (LHMM.py:394-405) for j = i (w) and j = i + 1 (the neighbour's: wn)
+__device__ __forceinline__ void le_post_accumulate(const LeTrans &a, double am, int ae_l, double g, int ge, double wm, int we, double wn, int wen,
+                                                   double (&sm)[3], int (&se)[3]) {
+    le_accumulate(g, ge, sm[0], se[0]);
+    le_accumulate(am * a.as_m * wm, floor_add(floor_add(ae_l, a.as_e), we), sm[1], se[1]);
+    le_accumulate(am * a.ao_m * wn, floor_add(floor_add(ae_l, a.ao_e), wen), sm[2], se[2]);
+}
+// the block's three sums of state i into the utterance's partial sums ([u][3][POSTL_W][NP]) for hmm_postl_merge_kernel
+__device__ __forceinline__ void le_post_store_parts(double *__restrict__ part_m, int *__restrict__ part_e, int u, int w, int NP, int i, bool act,
+                                                    const double (&sm)[3], const int (&se)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const size_t o = (((size_t)u * 3 + c) * POSTL_W + w) * NP + i;
+        part_m[o] = sm[c];
+        part_e[o] = act ? se[c] : LE_FLOOR;
+    }
+}
+
 // ONE wave per workgroup, POSTL_W workgroups per utterance (grid (POSTL_W, U)): beside the scoring kernel a 512-thread workgroup needs
 // room for 2 x 114 VGPRs on all four SIMDs of one CU at once -- two of the CU's three scoring workgroups gone together -- and the
 // scoring kernel refills every slot the moment ONE retires, so the eight-wave kernel of rounds 3-4 spanned 9.6 ms per call inside the
@@ -490,108 +619,46 @@ __global__ __launch_bounds__(64) void hmm_postl_kernel(const UttDesc *__restrict
         return;
     }
     const bool act = i < N;
-    const unsigned long long *B = Bp + d.b_off;
-    const double *Am = alpha + d.b_off, *Bm = beta + d.b_off;
-    const int *Ae = alpha_e + d.b_off, *Be = beta_e + d.b_off;
-    double *G = lgam + d.b_off;
     for (long long e = w * 64 + i; e < (long long)N * N; e += 64 * POSTL_W) ksai[d.mat_off + e] = -INFINITY;   // LHMM.py:404: ln 0 entries (the merge kernel writes the stored ones)
-    double as_m = 1.0, ao_m = 1.0;
-    int as_e = LE_ZADD, ao_e = LE_ZADD;
-    bool has_s = false, has_o = false;
-    if (act) {
-        const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
-        for (int k = sr0; k < sr1; ++k) {
-            const int j = col_idx[k];
-            if (j == i) { exp_split(csr_val[k], as_m, as_e); has_s = true; }
-            else if (j == i + 1) { exp_split(csr_val[k], ao_m, ao_e); has_o = true; }
-        }
-    }
-    const double qnew = logp[u];
-    const bool dead = !(qnew > -INFINITY);                           // P(O) = 0: every l is -inf, l - sum_value is NaN as in the reference
-    const double kq = rint(qnew * LOG2E);
-    const int eQ = dead ? 0 : (int)kq;
-    const double lc0 = dead ? 0.0 : fma(-kq, LN2_LO, fma(-kq, LN2_HI, qnew));   // ln c0, c0 = P(O) / 2^eQ in [0.7, 1.42]
-    const double rc0 = dead ? 1.0 : exp(-lc0);
+    const LeTrans a = le_transitions(d, i, act, row_ptr, col_idx, csr_val);
+    const LePostConst pc(logp[u]);
     double sm[3] = {0.0, 0.0, 0.0};
     int se[3] = {LE_FLOOR, LE_FLOOR, LE_FLOOR};
-    // Wave w takes the CONTIGUOUS frames [t0, t1): frame t needs alpha_t, beta_t and w_{t+1} = b(o_{t+1}) beta_{t+1}, and row t + 1 is
-    // the wave's own next row -- every row is read once (32 B per (t, j); with frames dealt round-robin, t, t + 8, ..., every
-    // wave read its successor's row again: 44 B, and the kernel ran at the HBM's rate).  Three register sets in rotation, two rows
-    // in flight, loads unconditional (clamped frame, column 0 for lanes beyond N) so that the compiler counts its waits.
-    struct Row { double am, bm; int ae, be; unsigned long long w; };
     const int chunk = (T + POSTL_W - 1) / POSTL_W, t0 = w * chunk, t1 = min(T, t0 + chunk);
-    const long long col = act ? i : 0;
-    auto ld = [&](Row &r, int t) {
-        const long long o = (long long)min(t, T - 1) * N + col;
-        r.am = Am[o]; r.ae = Ae[o]; r.bm = Bm[o]; r.be = Be[o]; r.w = B[o];
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    double *Gl = act ? G + i : dump + i;                                   // lanes beyond N "store" into a dump slot (stride 0)
+    double *Gl = act ? lgam + d.b_off + i : dump + i;                      // lanes beyond N "store" into a dump slot (stride 0)
     const long long gstride = act ? N : 0;
-    auto proc = [&](const Row &r, const Row &n, int t) {
-        const double g = r.am * r.bm;
-        const int ae_l = act ? r.ae : LE_FLOOR;                          // (a lane beyond N read column 0: its values count as zero)
-        const int ge = act ? floor_add(r.ae, r.be) : LE_FLOOR;
-        const double ssum = wave_sum_d(ldexp(g, max(le_sub(ge, eQ), -4000))) * rc0, u1 = ssum - 1.0;
-        double corr;                                                     // sum_value[t] - ln P(O)
-        if (fabs(u1) < 1.0e-4) corr = u1 * (1.0 - u1 * (0.5 - u1 * (1.0 / 3.0)));
-        else corr = log(ssum);
-        double lg;
-        if (dead) lg = NAN;
-        else if (ge < LE_PZ || !(g > 0.0)) lg = -INFINITY;
-        else lg = (fma((double)ge, LN2_HI, fma((double)ge, LN2_LO, log(g))) - qnew) - corr;
-        Gl[(long long)t * gstride] = lg;                                 // l[:,t] - sum_value[t] (:486-500)
+    le_post_rows(d, alpha, alpha_e, beta, beta_e, Bp, act ? i : 0, t0, t1, [&](const LeRow &r, const LeRow &n, int t) {
+        double g, wm;
+        int ge, ae_l, we;
+        r.gamma(act, g, ge, ae_l);
+        const double ssum = wave_sum_d(pc.term(g, ge)) * pc.rc0;
+        Gl[(long long)t * gstride] = pc.lgamma(g, ge, ssum);
         if (t < T - 1) {
-            double bm1;
-            int bk1;
-            emis_unpack(n.w, bm1, bk1);
-            const double wm = n.bm * bm1;                                // w_{t+1}(i) = b_i(o_{t+1}) beta_{t+1}(i)
-            const int we = act ? floor_add(n.be, bk1) : LE_FLOOR;
-            const double wn = shl_d(wm);
-            const int wen = shl_i(we, LE_FLOOR);
-            le_accumulate(g, ge, sm[0], se[0]);                          // gamma_i over t < T-1 (:442-445)
-            // xi_ij (+)= alpha_t(i) a_ij b_j(o_{t+1}) beta_{t+1}(j)   (LHMM.py:394-405)
-            le_accumulate(r.am * as_m * wm, floor_add(floor_add(ae_l, as_e), we), sm[1], se[1]);
-            le_accumulate(r.am * ao_m * wn, floor_add(floor_add(ae_l, ao_e), wen), sm[2], se[2]);
+            n.w_value(act, wm, we);
+            le_post_accumulate(a, r.am, ae_l, g, ge, wm, we, shl_d(wm), shl_i(we, LE_FLOOR), sm, se);
         }
-    };
-    if (t0 < t1) {
-        Row r0, r1, r2;
-        ld(r0, t0);
-        ld(r1, t0 + 1);
-        int t = t0;
-        for (;;) {
-            ld(r2, t + 2); proc(r0, r1, t); if (++t >= t1) break;
-            ld(r0, t + 2); proc(r1, r2, t); if (++t >= t1) break;
-            ld(r1, t + 2); proc(r2, r0, t); if (++t >= t1) break;
-        }
-    }
-    (void)has_s; (void)has_o;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const size_t o = (((size_t)u * 3 + c) * POSTL_W + w) * 64 + i;
-        part_m[o] = sm[c];
-        part_e[o] = act ? se[c] : LE_FLOOR;
-    }
+    });
+    le_post_store_parts(part_m, part_e, u, w, 64, i, act, sm, se);
 }
 
-// the eight waves' partial sums of an utterance, added in wave order (deterministic, independent of the batch): ln gamma_i, ln xi_ii, ln xi_{i,i+1}
-__global__ __launch_bounds__(64) void hmm_postl_merge_kernel(const UttDesc *__restrict__ utts, const int *__restrict__ kmax, const int *__restrict__ row_ptr,
-                                                            const int *__restrict__ col_idx, const double *__restrict__ part_m,
-                                                            const int *__restrict__ part_e, double *__restrict__ ksai, double *__restrict__ gamma_out) {
-    const int u = blockIdx.x, i = threadIdx.x;
+// the partial sums of the POSTL_W frame blocks of an utterance, added in block order (deterministic, independent of the batch): ln gamma_i,
+// ln xi_ii, ln xi_{i,i+1}; blockDim = NP = the posterior kernel's (64 for hmm_postl_kernel, 64 NWC for hmm_postlm_kernel<NWC>)
+__global__ __launch_bounds__(256) void hmm_postl_merge_kernel(const UttDesc *__restrict__ utts, const int *__restrict__ kmax, const int *__restrict__ row_ptr,
+                                                             const int *__restrict__ col_idx, const double *__restrict__ part_m,
+                                                             const int *__restrict__ part_e, double *__restrict__ ksai, double *__restrict__ gamma_out) {
+    const int u = blockIdx.x, i = threadIdx.x, NP = blockDim.x;
     const UttDesc d = utts[u];
-    if (!pcl_fb_linear_ok(kmax, u, d.T) || i >= d.N) return;         // (the log-domain body wrote its results itself)
+    if (!pcl_fb_linear_ok(kmax, u, d.T) || i >= d.N) return;         // (the log-domain kernel wrote its results itself)
     double outv[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const size_t o = ((size_t)u * 3 + c) * POSTL_W * 64 + i;
+        const size_t o = ((size_t)u * 3 + c) * POSTL_W * NP + i;
         int E = LE_FLOOR;
 #pragma unroll
-        for (int v = 0; v < POSTL_W; ++v) E = max(E, part_e[o + v * 64]);
+        for (int v = 0; v < POSTL_W; ++v) E = max(E, part_e[o + (size_t)v * NP]);
         double tsum = 0.0;
 #pragma unroll
-        for (int v = 0; v < POSTL_W; ++v) tsum += ldexp(part_m[o + v * 64], max(le_sub(part_e[o + v * 64], E), -4000));
+        for (int v = 0; v < POSTL_W; ++v) tsum += le_align(part_m[o + (size_t)v * NP], part_e[o + (size_t)v * NP], E);
         outv[c] = le_log(tsum, E);
     }
     gamma_out[d.vec_off + i] = outv[0];

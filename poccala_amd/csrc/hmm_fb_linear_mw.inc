@@ -1,16 +1,14 @@
 // hmm_fb_linear_mw.inc -- the scaled linear-domain forward-backward of hmm_fb_linear.inc for sentence HMMs of MORE than 64 states
-// (included by hmm_dp.hip behind it; same reference lines: LHMM.py:335-366, 412-471, 486-500, 526-544).
+// (included by hmm_dp.hip behind it; same reference lines, same helpers, same pass rule, same range test).
 //
-// A label of 21 units already has 65 states (AcousticModel.embedded: N = 3 L + 2).  Up to round 4 such an utterance left the scaled
-// kernels for the log-domain multi-wave kernel (hmm_fb_kernel<2>): 1.47 ms for 128 utterances of 65 states where 62 states take 0.13 --
-// an 11x cliff between L = 20 and L = 21.  Here a chain is spread over NWC = ceil(N / 64) wavefronts (N <= 256): state i sits on lane
+// A label of 21 units already has 65 states (AcousticModel.embedded: N = 3 L + 2); the log-domain multi-wave kernel (hmm_fb_kernel<2>)
+// takes 11x the time per utterance there.  Here a chain is spread over NWC = ceil(N / 64) wavefronts (N <= 256): state i sits on lane
 // i % 64 of chain wave i / 64; inside a wave the neighbour's value still comes through a DPP wave shift, and the ONE value that crosses
 // a wave boundary per step (lane 63 -> lane 0 of the next wave, forward; lane 0 -> lane 63 of the wave before, backward) goes through
 // LDS: the publishing lane writes its (mantissa, exponent) pair into a slot of the step's parity, all waves of the workgroup meet at one
 // barrier per step, the reading lane picks it up -- two slots per wave, so that a wave running ahead cannot overwrite what a slower one
 // still has to read.  The workgroup is 2 NWC waves: the first NWC walk alpha, the others walk beta once (and then only stand at the
-// barriers: the same step loop, the same barrier, nothing to do in between); everything else -- the packed emissions, zero living in the exponent, alpha stored only in the pass that can be
-// the last, the pass loop, the range test -- is hmm_fb_linear.inc's.  Lanes beyond N are not switched off (every wave must reach
+// barriers: the same step loop, the same barrier, nothing to do in between).  Lanes beyond N are not switched off (every wave must reach
 // every barrier, and a batch mixes utterances of different lengths): they carry zeros in their exponents, read column 0 and "store"
 // into a dump slot with stride 0.  An utterance outside the exponent range is left to hmm_fb_kernel<2>, launched behind with the
 // range record, which returns at once for the others.
@@ -25,11 +23,11 @@ struct MwShared {
 
 // One walk along the chain (see le_chain) for EVERY wave of the workgroup, whatever it has to do in this pass: a forward chain wave (alpha),
 // a backward chain wave (beta), or a backward wave whose beta is done and which only has to be at the barriers.
-// Round 6 (VERDICT r5 next #6): rounds 4-5 instantiated this function three times (forward / forward without stores / backward) plus a bare
-// loop of barriers for the idle waves, so the waves of a workgroup met at `__syncthreads()` calls of four different call sites -- the
-// hardware counts arrivals and does not care, the programming model does.  Now every wave of the workgroup runs the SAME instance in any
-// given pass (two exist: with and without stores in the loop, chosen workgroup-uniformly), with ONE step loop and ONE barrier in it,
-// and the loop body is straight-line code for every role: the direction is DATA (`fwd`, wave-uniform: both wave shifts are made and
+// Every wave of the workgroup runs the SAME instance in any given pass (two exist: with and without stores in the loop, chosen
+// workgroup-uniformly), with ONE step loop and ONE barrier in it: the programming model promises that the waves of a workgroup meet at
+// ONE `__syncthreads()`, not that barriers of different call sites count as the same one (a walk with an instance per role and a bare
+// barrier loop for the idle waves was 14-20 % faster; DESIGN.md section 4.3, profiles/r06_fb_barrier_ab.txt).  The loop body is
+// straight-line code for every role: the direction is DATA (`fwd`, wave-uniform: both wave shifts are made and
 // one is selected; what is stored is selected the same way), a forward walk that keeps nothing and an idle wave store into the dump slot
 // with stride 0 and read column 0.  (A first version chose the role by wave-uniform BRANCHES around the loads and stores: 45-60 % slower,
 // because with memory operations under control flow the compiler waits for vmcnt(0) in every block instead of counting -- see le_chain.)
@@ -47,11 +45,10 @@ __device__ __forceinline__ void le_chain_mw(const bool fwd, const unsigned long 
     double s_last = s_out;
     int e_last = e_out;
     auto one = [&](unsigned long long wq, int t, bool renorm_now) {
-        double cb;
-        int kb;
+        double cb, s;
+        int kb, e0;
         emis_unpack(wq, cb, kb);
-        const double cz = cb * as_m, cp = cb * ap_m;
-        const int kz = floor_add(kb, as_e), kp = floor_add(kb, ap_e);
+        const LeStep st(cb, kb, as_m, as_e, ap_m, ap_e);
         const double pr = shr_d(p), pl = shl_d(p);
         const int er = shr_i(ep, LE_FLOOR), el = shl_i(ep, LE_FLOOR);
         double pn = fwd ? pr : pl;
@@ -62,25 +59,15 @@ __device__ __forceinline__ void le_chain_mw(const bool fwd, const unsigned long 
             pn = edge_in ? xl : pn;
             epn = edge_in ? xe_ : epn;
         }
-        const int e0 = max(ez, epn);
-        const double s = ldexp(z, le_sub(ez, e0)) + ldexp(pn, le_sub(epn, e0));
+        st.sum(z, ez, pn, epn, s, e0);
         if (ANY_STORE) {                                     // (workgroup-uniform, compile time: a pass in which NO wave keeps anything has no store in its loop)
             sm[(long long)t * sstride] = fwd ? s * cb : s;   // alpha_t = s b_t, beta_t = s (a wave that keeps nothing in this pass: the dump slot, stride 0)
             se[(long long)t * sstride] = fwd ? floor_add(e0, kb) : e0;
         }
         s_last = s;
         e_last = e0;
-        z = s * cz;
-        p = s * cp;
-        ez = floor_add(e0, kz);
-        ep = floor_add(e0, kp);
-        if (renorm_now) {
-            const int x = __builtin_amdgcn_frexp_exp(z + p);
-            z = ldexp(z, -x);
-            p = ldexp(p, -x);
-            ez = floor_add(ez, x);
-            ep = floor_add(ep, x);
-        }
+        st.publish(s, e0, z, ez, p, ep);
+        if (renorm_now) le_renorm(z, ez, p, ep);
         if (edge_out) {
             sh.xm[dir][c][par ^ 1] = p;
             sh.xe[dir][c][par ^ 1] = ep;
@@ -123,108 +110,6 @@ __device__ __forceinline__ void le_chain_mw(const bool fwd, const unsigned long 
     e_out = e_last;
 }
 
-#ifdef PCL_FB_MW_SPLIT_SITES
-// The round 4-5 walk, for A/B only (tools/build_variant.sh fbsites "-DPCL_FB_MW_SPLIT_SITES" hmm_dp.hip): three instances + a bare barrier loop, i.e.
-// the waves of a workgroup meet at `__syncthreads()` of different call sites.  14-20 % faster at N > 64 (0.72 against 0.86 ms for 1024
-// utterances of 65 states, 2.03 against 2.31 at 254), the same bits; not the default because the programming model does not promise it.
-// one walk along the chain (see le_chain); c = this wave's place in its chain; `par` = parity of the boundary slots the NEXT read uses
-template <bool FWD, bool STORE, int NWC>
-__device__ __forceinline__ void le_chain_mw_sites(const unsigned long long *__restrict__ Bl, long long bstride, int nsteps, int t0, int T, double as_m,
-                                            int as_e, double ap_m, int ap_e, double &z, int &ez, double &p, int &ep, double *__restrict__ sm,
-                                            int *__restrict__ se, long long sstride, double &s_out, int &e_out, int c, int lane,
-                                            MwShared<NWC> &sh, int &par) {
-    constexpr int DIR = FWD ? 0 : 1;
-    const int nb = FWD ? c - 1 : c + 1;                      // the chain wave whose boundary lane feeds this wave's edge lane
-    const bool has_nb = nb >= 0 && nb < NWC;
-    const bool edge_in = lane == (FWD ? 0 : 63), edge_out = lane == (FWD ? 63 : 0);
-    auto frame = [&](int step) {
-        const int t = FWD ? t0 + step : t0 - step;
-        return min(max(t, 0), T - 1);
-    };
-    double s_last = s_out;
-    int e_last = e_out;
-    auto one = [&](unsigned long long wq, int t, bool renorm_now) {
-        double cb;
-        int kb;
-        emis_unpack(wq, cb, kb);
-        const double cz = cb * as_m, cp = cb * ap_m;
-        const int kz = floor_add(kb, as_e), kp = floor_add(kb, ap_e);
-        double pn = FWD ? shr_d(p) : shl_d(p);
-        int epn = FWD ? shr_i(ep, LE_FLOOR) : shl_i(ep, LE_FLOOR);
-        if (has_nb) {                                        // (wave-uniform) the value from across the wave boundary, published one step ago
-            const double pl = sh.xm[DIR][nb][par];
-            const int el = sh.xe[DIR][nb][par];
-            pn = edge_in ? pl : pn;
-            epn = edge_in ? el : epn;
-        }
-        const int e0 = max(ez, epn);
-        const double s = ldexp(z, le_sub(ez, e0)) + ldexp(pn, le_sub(epn, e0));
-        if (FWD) {
-            if (STORE) {
-                sm[(long long)t * sstride] = s * cb;
-                se[(long long)t * sstride] = floor_add(e0, kb);
-            }
-        } else {
-            sm[(long long)t * sstride] = s;
-            se[(long long)t * sstride] = e0;
-        }
-        s_last = s;
-        e_last = e0;
-        z = s * cz;
-        p = s * cp;
-        ez = floor_add(e0, kz);
-        ep = floor_add(e0, kp);
-        if (renorm_now) {
-            const int x = __builtin_amdgcn_frexp_exp(z + p);
-            z = ldexp(z, -x);
-            p = ldexp(p, -x);
-            ez = floor_add(ez, x);
-            ep = floor_add(ep, x);
-        }
-        if (edge_out) {
-            sh.xm[DIR][c][par ^ 1] = p;
-            sh.xe[DIR][c][par ^ 1] = ep;
-        }
-        __syncthreads();
-        par ^= 1;
-    };
-    unsigned long long qa[FBL_BLK], qb[FBL_BLK];
-    auto load = [&](unsigned long long (&q)[FBL_BLK], int blk) {
-#pragma unroll
-        for (int k = 0; k < FBL_BLK; ++k) q[k] = Bl[(long long)frame(blk * FBL_BLK + k) * bstride];
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto block = [&](unsigned long long (&q)[FBL_BLK], int blk) {
-#pragma unroll
-        for (int k = 0; k < FBL_BLK; ++k) one(q[k], FWD ? t0 + blk * FBL_BLK + k : t0 - blk * FBL_BLK - k, k == FBL_BLK - 1);
-    };
-    auto tail = [&](unsigned long long (&q)[FBL_BLK], int blk, int rem) {
-#pragma unroll
-        for (int k = 0; k < FBL_BLK - 1; ++k)
-            if (k < rem) one(q[k], FWD ? t0 + blk * FBL_BLK + k : t0 - blk * FBL_BLK - k, k == rem - 1);
-    };
-    const int nblk = nsteps / FBL_BLK, rem = nsteps - nblk * FBL_BLK;
-    load(qa, 0);
-    int b = 0;
-    for (; b + 2 <= nblk; b += 2) {
-        load(qb, b + 1);
-        block(qa, b);
-        load(qa, b + 2);
-        block(qb, b + 1);
-    }
-    if (b < nblk) {
-        load(qb, b + 1);
-        block(qa, b);
-        tail(qb, b + 1, rem);
-    } else {
-        tail(qa, b, rem);
-    }
-    s_out = s_last;
-    e_out = e_last;
-}
-
-#endif
-
 template <int NWC>
 __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__restrict__ utts, const unsigned long long *__restrict__ Bp,
                                                             const int *__restrict__ kmax, const int *__restrict__ row_ptr,
@@ -252,30 +137,22 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
     double *Am = act ? alpha + d.b_off + i : dm, *Bm = act ? beta + d.b_off + i : dm;
     int *Ae = act ? alpha_e + d.b_off + i : de, *Be = act ? beta_e + d.b_off + i : de;
     const long long sstride = act ? N : 0;
-    double as_m = 1.0, ao_m = 1.0;
-    int as_e = LE_ZADD, ao_e = LE_ZADD;
-    if (act) {
-        const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
-        for (int k = sr0; k < sr1; ++k) {
-            const int j = col_idx[k];
-            if (j == i) exp_split(csr_val[k], as_m, as_e);
-            else if (j == i + 1) exp_split(csr_val[k], ao_m, ao_e);
-        }
-    }
+    const LeTrans a = le_transitions(d, i, act, row_ptr, col_idx, csr_val);
     if (fwd) {
-        aom[i] = ao_m;
-        aoe[i] = ao_e;
+        aom[i] = a.ao_m;
+        aoe[i] = a.ao_e;
         lpi[i] = act ? logpi_in[d.vec_off + i] : -INFINITY;
     }
     __syncthreads();
     const double an_m = i > 0 ? aom[i - 1] : 1.0;                    // the transition INTO this state from the one before it
     const int an_e = i > 0 ? aoe[i - 1] : LE_ZADD;
-    double q = -INFINITY;
-    int npass = 0, par = 0;
+    FbPassRule rule(fix_pi, threshold);
+    double *const trace = qtrace + (long long)blockIdx.x * PCL_MAX_PASS;
+    int par = 0;
     bool beta_done = false;
     for (;;) {
-        bool store = (fix_pi != 0) || npass >= 2;
-        bool final_pass = false, q6 = false;
+        bool store = rule.may_be_last();
+        FbPassRule::Verdict v{false, false};
         double qnew = 0.0;
         for (;;) {
             double z = 0.0, p = 0.0, am = 0.0, s_l = 0.0;
@@ -283,43 +160,15 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
             const bool walk_b = !fwd && !beta_done;
             if (fwd) {
                 // ---------------------------------------------------------------- forward (LHMM.py:335-351): alpha_0
-                double m, pm, bm;
-                int e, pe, bk;
-                exp_split(act ? lpi[i] : -INFINITY, pm, pe);
-                emis_unpack(Bl[0], bm, bk);
-                m = pm * bm;
-                e = floor_add(pe, bk);
-                {
-                    const int x = __builtin_amdgcn_frexp_exp(m);
-                    m = __builtin_amdgcn_frexp_mant(m);
-                    e = floor_add(e, x);
-                }
-                if (store) {
-                    Am[0] = m;
-                    Ae[0] = e;
-                }
-                a0s[i] = act ? le_log(m, e) : -INFINITY;
-                z = m * as_m;
-                p = m * ao_m;
-                ez = floor_add(e, as_e);
-                ep = floor_add(e, ao_e);
-                am = m;
-                ae = e;
+                le_alpha0(act ? lpi[i] : -INFINITY, Bl, a, store, Am, Ae, am, ae, z, ez, p, ep);
+                a0s[i] = act ? le_log(am, ae) : -INFINITY;
                 if (lane == 63) {
                     sh.xm[0][c][par] = p;
                     sh.xe[0][c][par] = ep;
                 }
             } else if (walk_b) {
-                // ---------------------------------------------------------------- backward (LHMM.py:353-366); beta_{T-1} = 1 (quirk Q8)
-                double bm;
-                int bk;
-                Bm[(long long)(T - 1) * sstride] = 1.0;
-                Be[(long long)(T - 1) * sstride] = 0;
-                emis_unpack(Bl[(long long)(T - 1) * N], bm, bk);
-                z = bm * as_m;
-                p = bm * an_m;
-                ez = act ? floor_add(bk, as_e) : LE_FLOOR;
-                ep = act ? floor_add(bk, an_e) : LE_FLOOR;
+                // ---------------------------------------------------------------- backward (LHMM.py:353-366)
+                le_beta_last(Bl, N, T, act, a, an_m, an_e, Bm, Be, sstride, z, ez, p, ep);
                 s_l = 1.0;
                 e_l = 0;
                 if (lane == 0) {
@@ -328,52 +177,21 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
                 }
             }
             __syncthreads();                                             // the first boundary values are there
-#ifdef PCL_FB_MW_SPLIT_SITES
-            if (fwd) {
-                if (store) le_chain_mw_sites<true, true, NWC>(Bl, N, T - 1, 1, T, as_m, as_e, ao_m, ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l, c, lane, sh, par);
-                else le_chain_mw_sites<true, false, NWC>(Bl, N, T - 1, 1, T, as_m, as_e, ao_m, ao_e, z, ez, p, ep, Am, Ae, sstride, s_l, e_l, c, lane, sh, par);
-                if (T > 1) {
-                    double cb;
-                    int kb;
-                    emis_unpack(Bl[(long long)(T - 1) * N], cb, kb);
-                    am = s_l * cb;
-                    ae = floor_add(e_l, kb);
-                }
-            } else if (walk_b) {
-                le_chain_mw_sites<false, true, NWC>(Bl, N, T - 1, T - 2, T, as_m, as_e, an_m, an_e, z, ez, p, ep, Bm, Be, sstride, s_l, e_l, c, lane, sh, par);
-                b0s[i] = act ? le_log(s_l, e_l) : -INFINITY;             // ln beta_0(i) (T == 1: ln 1 = 0)
-            } else {
-                for (int s = 0; s < T - 1; ++s) {                        // beta is done: keep the barriers company
-                    __syncthreads();
-                    par ^= 1;
-                }
-            }
-#else
             // every wave of the workgroup through the SAME walk (one call, one step loop, one barrier per step).  A forward wave in a pass that
             // keeps nothing and a backward wave whose beta is done write into the dump slot (stride 0); the idle wave also walks on zeros
             // (its z / p start at the floor and it publishes what nobody reads -- the slots of direction 1 belong to the backward chain alone)
             const bool keep = fwd ? store : walk_b;
             // (which of the two instances: a WORKGROUP-uniform choice -- every wave takes the same one, so the barrier inside is the same barrier)
             if (store || !beta_done)
-                le_chain_mw<true, NWC>(fwd, keep || fwd ? Bl : Bp + d.b_off, N, T - 1, fwd ? 1 : T - 2, T, as_m, as_e, fwd ? ao_m : an_m, fwd ? ao_e : an_e, z, ez, p, ep,
+                le_chain_mw<true, NWC>(fwd, keep || fwd ? Bl : Bp + d.b_off, N, T - 1, fwd ? 1 : T - 2, T, a.as_m, a.as_e, fwd ? a.ao_m : an_m, fwd ? a.ao_e : an_e, z, ez, p, ep,
                                        keep ? (fwd ? Am : Bm) : dm, keep ? (fwd ? Ae : Be) : de, keep ? sstride : 0, s_l, e_l, c, lane, sh, par);
             else
-                le_chain_mw<false, NWC>(fwd, keep || fwd ? Bl : Bp + d.b_off, N, T - 1, fwd ? 1 : T - 2, T, as_m, as_e, fwd ? ao_m : an_m, fwd ? ao_e : an_e, z, ez, p, ep,
+                le_chain_mw<false, NWC>(fwd, keep || fwd ? Bl : Bp + d.b_off, N, T - 1, fwd ? 1 : T - 2, T, a.as_m, a.as_e, fwd ? a.ao_m : an_m, fwd ? a.ao_e : an_e, z, ez, p, ep,
                                         dm, de, 0, s_l, e_l, c, lane, sh, par);
-            if (fwd) {
-                if (T > 1) {
-                    double cb;
-                    int kb;
-                    emis_unpack(Bl[(long long)(T - 1) * N], cb, kb);
-                    am = s_l * cb;
-                    ae = floor_add(e_l, kb);
-                }
-            } else if (walk_b) {
-                b0s[i] = act ? le_log(s_l, e_l) : -INFINITY;             // ln beta_0(i) (T == 1: ln 1 = 0)
-            }
-#endif
+            if (fwd) le_alpha_last(Bl, N, T, s_l, e_l, am, ae);
+            else if (walk_b) b0s[i] = act ? le_log(s_l, e_l) : -INFINITY;             // ln beta_0(i) (T == 1: ln 1 = 0)
             beta_done = true;
-            // Q = LSE_i alpha_{T-1}(i) over the chain's waves (LHMM.py:412-422); the maximum itself when it is -inf (quirk Q4)
+            // Q over the chain's waves
             if (fwd) {
                 const int em = wave_max_i(act ? ae : LE_FLOOR);
                 if (lane == 0) sh.red_i[c] = em;
@@ -383,7 +201,7 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
 #pragma unroll
             for (int k = 0; k < NWC; ++k) eM = max(eM, sh.red_i[k]);
             if (fwd) {
-                const double sc = wave_sum_d(act ? ldexp(am, max(le_sub(ae, eM), -4000)) : 0.0);
+                const double sc = wave_sum_d(le_q_term(act, am, ae, eM));
                 if (lane == 0) sh.red_d[c] = sc;
             }
             __syncthreads();
@@ -391,23 +209,16 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
                 double S = 0.0;
 #pragma unroll
                 for (int k = 0; k < NWC; ++k) S += sh.red_d[k];
-                s_q = (eM < LE_PZ || !(S > 0.0)) ? -INFINITY : fma((double)eM, LN2_HI, fma((double)eM, LN2_LO, log(S)));
+                s_q = le_log(S, eM);
             }
             __syncthreads();
             qnew = s_q;
-            const bool natural = !(qnew - q > threshold) || (npass + 1 >= PCL_MAX_PASS);   // LHMM.py:539
-            q6 = fix_pi && !natural && threshold >= 0.0 && npass + 1 < PCL_MAX_PASS;       // quirk Q6
-            final_pass = natural || q6;
-            if (!final_pass || store) break;
+            v = rule.judge(qnew);
+            if (!FbPassRule::replay(v, store)) break;
             store = true;                                                // the pass turned out to be the last: once more, with alpha going to HBM
             __syncthreads();
         }
-        if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-        ++npass;
-        if (q6) {
-            if (threadIdx.x == 0) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + npass] = qnew;
-            ++npass;
-        }
+        rule.record(v, qnew, trace, threadIdx.x == 0);
         // ---------------------------------------------------------------- pi (LHMM.py:447-452,470-471), the forward waves
         if (!fix_pi) {
             const double p0 = (fwd && act) ? a0s[i] + b0s[i] : -INFINITY;
@@ -430,20 +241,15 @@ __global__ __launch_bounds__(128 * NWC) void hmm_fblm_kernel(const UttDesc *__re
             const double pv = exp(p0 - n0);                      // the reference stores pi = exp(.) and takes np.log of it again
             if (fwd) {
                 lpi[i] = act ? log(pv) : -INFINITY;
-                if (final_pass && act) pi_out[d.vec_off + i] = pv;
+                if (v.final_pass && act) pi_out[d.vec_off + i] = pv;
             }
-        } else if (final_pass && fwd && act) {
+        } else if (v.final_pass && fwd && act) {
             pi_out[d.vec_off + i] = exp(lpi[i]);
         }
-        if (final_pass) {
-            if (threadIdx.x == 0) {
-                logp[blockIdx.x] = qnew;
-                npass_out[blockIdx.x] = npass;
-                for (int k = npass; k < PCL_MAX_PASS; ++k) qtrace[(long long)blockIdx.x * PCL_MAX_PASS + k] = NAN;
-            }
+        if (v.final_pass) {
+            if (threadIdx.x == 0) rule.finish(qnew, logp + blockIdx.x, npass_out + blockIdx.x, trace);
             break;
         }
-        q = qnew;
         __syncthreads();
     }
 }
@@ -467,49 +273,21 @@ __global__ __launch_bounds__(64 * NWC) void hmm_postlm_kernel(const UttDesc *__r
     __shared__ double ps[2][NWC], wbm[2][NWC];
     __shared__ int wbe[2][NWC];
     const bool act = i < N;
-    const long long col = act ? i : 0;
-    const unsigned long long *B = Bp + d.b_off;
-    const double *Am = alpha + d.b_off, *Bm = beta + d.b_off;
-    const int *Ae = alpha_e + d.b_off, *Be = beta_e + d.b_off;
     for (long long e = w * NP + threadIdx.x; e < (long long)N * N; e += (long long)NP * POSTL_W) ksai[d.mat_off + e] = -INFINITY;   // LHMM.py:404
-    double as_m = 1.0, ao_m = 1.0;
-    int as_e = LE_ZADD, ao_e = LE_ZADD;
-    if (act) {
-        const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
-        for (int k = sr0; k < sr1; ++k) {
-            const int j = col_idx[k];
-            if (j == i) exp_split(csr_val[k], as_m, as_e);
-            else if (j == i + 1) exp_split(csr_val[k], ao_m, ao_e);
-        }
-    }
-    const double qnew = logp[u];
-    const bool dead = !(qnew > -INFINITY);
-    const double kq = rint(qnew * LOG2E);
-    const int eQ = dead ? 0 : (int)kq;
-    const double lc0 = dead ? 0.0 : fma(-kq, LN2_LO, fma(-kq, LN2_HI, qnew));
-    const double rc0 = dead ? 1.0 : exp(-lc0);
+    const LeTrans a = le_transitions(d, i, act, row_ptr, col_idx, csr_val);
+    const LePostConst pc(logp[u]);
     double sm[3] = {0.0, 0.0, 0.0};
     int se[3] = {LE_FLOOR, LE_FLOOR, LE_FLOOR};
-    struct Row { double am, bm; int ae, be; unsigned long long w; };
     const int chunk = (T + POSTL_W - 1) / POSTL_W, t0 = w * chunk, t1 = min(T, t0 + chunk);
-    auto ld = [&](Row &r, int t) {
-        const long long o = (long long)min(t, T - 1) * N + col;
-        r.am = Am[o]; r.ae = Ae[o]; r.bm = Bm[o]; r.be = Be[o]; r.w = B[o];
-        __builtin_amdgcn_sched_barrier(0);
-    };
     double *Gl = act ? lgam + d.b_off + i : dump + lane;
     const long long gstride = act ? N : 0;
     int par = 0;
-    auto proc = [&](const Row &r, const Row &n, int t) {
-        const double g = r.am * r.bm;
-        const int ae_l = act ? r.ae : LE_FLOOR;
-        const int ge = act ? floor_add(r.ae, r.be) : LE_FLOOR;
-        const double part = wave_sum_d(ldexp(g, max(le_sub(ge, eQ), -4000)));
-        double bm1;
-        int bk1;
-        emis_unpack(n.w, bm1, bk1);
-        const double wm = n.bm * bm1;                                    // w_{t+1}(i) = b_i(o_{t+1}) beta_{t+1}(i)
-        const int we = act ? floor_add(n.be, bk1) : LE_FLOOR;
+    le_post_rows(d, alpha, alpha_e, beta, beta_e, Bp, act ? i : 0, t0, t1, [&](const LeRow &r, const LeRow &n, int t) {
+        double g, wm;
+        int ge, ae_l, we;
+        r.gamma(act, g, ge, ae_l);
+        const double part = wave_sum_d(pc.term(g, ge));
+        n.w_value(act, wm, we);
         if (lane == 0) {
             ps[par][c] = part;
             wbm[par][c] = wm;
@@ -519,7 +297,7 @@ __global__ __launch_bounds__(64 * NWC) void hmm_postlm_kernel(const UttDesc *__r
         double ssum = 0.0;
 #pragma unroll
         for (int k = 0; k < NWC; ++k) ssum += ps[par][k];
-        ssum *= rc0;
+        ssum *= pc.rc0;
         double wn = shl_d(wm);
         int wen = shl_i(we, LE_FLOOR);
         if (c + 1 < NWC) {                                               // lane 63's neighbour sits on the next wave
@@ -529,64 +307,8 @@ __global__ __launch_bounds__(64 * NWC) void hmm_postlm_kernel(const UttDesc *__r
             wen = lane == 63 ? xe_ : wen;
         }
         par ^= 1;
-        const double u1 = ssum - 1.0;
-        double corr;                                                     // sum_value[t] - ln P(O)
-        if (fabs(u1) < 1.0e-4) corr = u1 * (1.0 - u1 * (0.5 - u1 * (1.0 / 3.0)));
-        else corr = log(ssum);
-        double lg;
-        if (dead) lg = NAN;
-        else if (ge < LE_PZ || !(g > 0.0)) lg = -INFINITY;
-        else lg = (fma((double)ge, LN2_HI, fma((double)ge, LN2_LO, log(g))) - qnew) - corr;
-        Gl[(long long)t * gstride] = lg;                                 // l[:,t] - sum_value[t] (:486-500)
-        if (t < T - 1) {
-            le_accumulate(g, ge, sm[0], se[0]);                          // gamma_i over t < T-1 (:442-445)
-            le_accumulate(r.am * as_m * wm, floor_add(floor_add(ae_l, as_e), we), sm[1], se[1]);      // xi_ii, xi_{i,i+1} (LHMM.py:394-405)
-            le_accumulate(r.am * ao_m * wn, floor_add(floor_add(ae_l, ao_e), wen), sm[2], se[2]);
-        }
-    };
-    if (t0 < t1) {
-        Row r0, r1, r2;
-        ld(r0, t0);
-        ld(r1, t0 + 1);
-        int t = t0;
-        for (;;) {
-            ld(r2, t + 2); proc(r0, r1, t); if (++t >= t1) break;
-            ld(r0, t + 2); proc(r1, r2, t); if (++t >= t1) break;
-            ld(r1, t + 2); proc(r2, r0, t); if (++t >= t1) break;
-        }
-    }
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-        const size_t o = (((size_t)u * 3 + cc) * POSTL_W + w) * NP + i;
-        part_m[o] = sm[cc];
-        part_e[o] = act ? se[cc] : LE_FLOOR;
-    }
-}
-
-// the partial sums of the POSTL_W frame blocks of an utterance, added in block order; blockDim = NP = the posterior kernel's
-__global__ void hmm_postlm_merge_kernel(const UttDesc *__restrict__ utts, const int *__restrict__ kmax, const int *__restrict__ row_ptr,
-                                        const int *__restrict__ col_idx, const double *__restrict__ part_m, const int *__restrict__ part_e,
-                                        double *__restrict__ ksai, double *__restrict__ gamma_out) {
-    const int u = blockIdx.x, i = threadIdx.x, NP = blockDim.x;
-    const UttDesc d = utts[u];
-    if (!pcl_fb_linear_ok(kmax, u, d.T) || i >= d.N) return;
-    double outv[3];
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-        const size_t o = ((size_t)u * 3 + cc) * POSTL_W * NP + i;
-        int E = LE_FLOOR;
-#pragma unroll
-        for (int v = 0; v < POSTL_W; ++v) E = max(E, part_e[o + (size_t)v * NP]);
-        double tsum = 0.0;
-#pragma unroll
-        for (int v = 0; v < POSTL_W; ++v) tsum += ldexp(part_m[o + (size_t)v * NP], max(le_sub(part_e[o + (size_t)v * NP], E), -4000));
-        outv[cc] = le_log(tsum, E);
-    }
-    gamma_out[d.vec_off + i] = outv[0];
-    const int sr0 = row_ptr[d.ptr_off + i] + d.nnz_off, sr1 = row_ptr[d.ptr_off + i + 1] + d.nnz_off;
-    for (int k = sr0; k < sr1; ++k) {
-        const int j = col_idx[k];
-        if (j == i) ksai[d.mat_off + (long long)i * d.N + i] = outv[1];
-        else if (j == i + 1) ksai[d.mat_off + (long long)i * d.N + i + 1] = outv[2];
-    }
+        Gl[(long long)t * gstride] = pc.lgamma(g, ge, ssum);
+        if (t < T - 1) le_post_accumulate(a, r.am, ae_l, g, ge, wm, we, wn, wen, sm, se);
+    });
+    le_post_store_parts(part_m, part_e, u, w, NP, i, act, sm, se);
 }

@@ -309,7 +309,7 @@ struct pcl_batch : BatchDecodeDev {
     DevBuf<int> col_ptr, row_idx;   // CSC (predecessors, ascending source index)
     DevBuf<double> csc_val;
     DevBuf<double> xi_m, xi_s;      // per CSR entry online-LSE state
-    // scaled linear-domain forward-backward (hmm_fb_linear.hip): packed exp(B), the int32 exponents of alpha / beta (their
+    // scaled linear-domain forward-backward (hmm_fb_linear.inc): packed exp(B), the int32 exponents of alpha / beta (their
     // mantissas live in `alpha` / `beta`), per utterance the exponent maxima of the range test
     DevBuf<unsigned long long> Bp;
     DevBuf<int> alpha_e, beta_e, fb_kmax;
@@ -357,7 +357,47 @@ struct pcl_batch : BatchDecodeDev {
     DevBuf<int32_t> pos_state;               // [sum L][P]
 };
 
-// ---------------------------------------------------------------- scaled linear-domain forward-backward (hmm_fb_linear.hip)
+// ---------------------------------------------------------------- the Baum-Welch pass loop's stopping rule and trace
+// LHMM.baulm_welch (LHMM.py:539) with quirk Q6, for the four forward-backward kernels of hmm_dp.hip (log domain) and
+// hmm_fb_linear*.inc (scaled): one pass = judge(Q of the pass) -> record() -> [finish() and leave | next pass].
+struct FbPassRule {
+    struct Verdict { bool final_pass, q6; };
+    const bool fix_pi;
+    const double threshold;
+    double q = -INFINITY;                 // Q of the pass before
+    int npass = 0;                        // passes the reference would have run so far
+    __device__ __forceinline__ FbPassRule(int fix_pi_, double threshold_) : fix_pi(fix_pi_ != 0), threshold(threshold_) {}
+    // is the pass that gave qnew the last one?
+    __device__ __forceinline__ Verdict judge(double qnew) const {
+        const bool natural = !(qnew - q > threshold) || (npass + 1 >= PCL_MAX_PASS);   // LHMM.py:539
+        // quirk Q6: with pi locked nothing changes between passes, so the next pass would reproduce this one bit for bit and
+        // then stop (Q - Q = 0 <= threshold): this pass's statistics are taken, the pass the reference would have run is reported
+        const bool q6 = fix_pi && !natural && threshold >= 0.0 && npass + 1 < PCL_MAX_PASS;
+        return {natural || q6, q6};
+    }
+    // Q of the pass into the utterance's trace (`writer`: the one thread of the workgroup that stores), two slots under Q6
+    __device__ __forceinline__ void record(Verdict v, double qnew, double *__restrict__ trace, bool writer) {
+        if (writer) trace[npass] = qnew;
+        ++npass;
+        if (v.q6) {
+            if (writer) trace[npass] = qnew;
+            ++npass;
+        }
+        q = qnew;
+    }
+    // the loop's results behind the final pass (the writer thread alone calls this); unused trace slots are NaN
+    __device__ __forceinline__ void finish(double qnew, double *__restrict__ logp_u, int32_t *__restrict__ npass_u, double *__restrict__ trace) const {
+        *logp_u = qnew;
+        *npass_u = npass;
+        for (int k = npass; k < PCL_MAX_PASS; ++k) trace[k] = NAN;
+    }
+    // The scaled kernels write alpha to HBM only in a pass that can be the last one -- the first with a locked pi (Q6), the third
+    // with a free one -- and repeat a pass that ended the loop without its stores (same inputs, same bits).
+    __device__ __forceinline__ bool may_be_last() const { return fix_pi || npass >= 2; }
+    static __device__ __forceinline__ bool replay(Verdict v, bool stored) { return v.final_pass && !stored; }
+};
+
+// ---------------------------------------------------------------- scaled linear-domain forward-backward (hmm_fb_linear.inc)
 // value = m 2^e, e an int32 per lane.  Zero lives in the exponent: below LE_PZ a value IS zero; a zero factor (ln 0) adds
 // LE_ZADD; sums are floored at LE_FLOOR so that nothing wraps; real exponents stay inside (-LE_LIMIT, LE_LIMIT).
 constexpr int LE_ZADD = -(1 << 29);

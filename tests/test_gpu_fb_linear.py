@@ -1,4 +1,4 @@
-"""The scaled linear-domain forward-backward (csrc/hmm_fb_linear.hip: value = m 2^e per lane, exp(B) split off the chain) against
+"""The scaled linear-domain forward-backward (csrc/hmm_fb_linear.inc: value = m 2^e per lane, exp(B) split off the chain) against
 the log-domain kernels it replaces on the default route (csrc/hmm_dp.hip, PCL_FB_LINEAR=0) and against the oracle
 (LHMM.__forward_algorithm / __backward_algorithm / __maximization / baulm_welch, StatisticalModel/LHMM.py:335-471,526-544).
 
@@ -242,6 +242,92 @@ def test_left_to_right_hmms_of_any_size_match_the_oracle(eng, fix_pi, wide):
             hold(tag, 'ln xi (sum over t)', lin['ksai'][u][fk], bw['ksai'][fk], 1e-10, 1e-9)
             hold(tag, 'ln gamma (sum over t)', lin['gamma'][u], bw['gamma'], 1e-10, 1e-9)
         np.testing.assert_allclose(lin['pi'][u], bw['pi'], rtol=1e-9, atol=1e-300)
+
+
+PASS_THRESHOLDS = (0.64, 1e9, -1.0)
+# route -> (utterance sizes (N, T), left-to-right?, PCL_FB_LINEAR): the four kernels that hold the pass loop's stopping rule
+PASS_ROUTES = {
+    'scaled, N > 64': ([(65, 12), (5, 9)], True, None),               # hmm_fblm_kernel<2>
+    'log-domain, N > 64': ([(65, 12), (5, 9)], True, '0'),            # hmm_fb_kernel<2>
+    'general, small': ([(4, 10)], False, None),                       # hmm_fb_kernel<0>
+    'general, N > 64': ([(70, 6)], False, None),                      # hmm_fb_kernel<0>, two waves
+}
+
+
+def pass_rule_hmm(rng, n, t, left_right):
+    """a left-to-right HMM as in test_left_to_right_hmms_of_any_size_match_the_oracle (no -inf emissions), or an ergodic one (dense rows)"""
+    if left_right:
+        a = np.zeros((n, n))
+        for i in range(n - 1):
+            x = rng.uniform(0.1, 0.9)
+            a[i, i], a[i, i + 1] = x, 1.0 - x
+        a[n - 1, n - 1] = 1.0
+        if n > 4:
+            a[2, 2], a[2, 3] = 0.0, 1.0                     # no self-loop
+            a[n - 1, n - 1] = 0.0                           # the last state leads nowhere
+        p = rng.dirichlet(np.ones(n))
+        if n > 3:
+            p[1] = 0.0
+            p /= p.sum()
+    else:
+        a = rng.dirichlet(np.ones(n), size=n)
+        p = rng.dirichlet(np.ones(n))
+    b = -60.0 + 25.0 * rng.standard_normal((n, t))
+    b[0, 0] = -50.0
+    return a, p, b
+
+
+@pytest.fixture(scope='module')
+def pass_rule_oracle():
+    """the inputs of every route and the oracle's baum_welch at PCL_MAX_PASS = 16 for every threshold and both values of fix_pi, once"""
+    hmms, want = {}, {}
+    for sizes, left_right, _ in PASS_ROUTES.values():
+        key = (tuple(sizes), left_right)
+        if key in hmms:
+            continue
+        rng = np.random.default_rng(177)
+        hmms[key] = [pass_rule_hmm(rng, n, t, left_right) for n, t in sizes]
+        for thr in PASS_THRESHOLDS:
+            for fix_pi in (False, True):
+                with np.errstate(all='ignore'):
+                    want[key, thr, fix_pi] = [po.baum_welch(a, p, [b], fix_code=1 if fix_pi else 0, threshold=thr, max_pass=16) for a, p, b in hmms[key]]
+    return hmms, want
+
+
+@pytest.mark.parametrize('fix_pi', [False, True])
+@pytest.mark.parametrize('thr', PASS_THRESHOLDS)
+@pytest.mark.parametrize('route', list(PASS_ROUTES))
+def test_pass_rule_on_every_route(eng, pass_rule_oracle, route, thr, fix_pi):
+    """LHMM.baulm_welch's stopping rule (LHMM.py:539) with quirk Q6, the Q trace and the pass cap in each of the four kernels that run
+    the pass loop, against the oracle: an exit after the second pass (a threshold nothing reaches; a locked pi: Q6), after the third
+    (0.64 nats with a free pi) and at the cap of 16 (a negative threshold)."""
+    hmms, want = pass_rule_oracle
+    counts = {bw['n_pass'] for bws in want.values() for bw in bws}
+    assert {2, 3, 16} <= counts, 'the inputs no longer reach every exit of the pass loop: %s' % sorted(counts)
+    sizes, left_right, linear = PASS_ROUTES[route]
+    key = (tuple(sizes), left_right)
+    Ts = [t for _, t in sizes]
+    old = os.environ.pop('PCL_FB_LINEAR', None)
+    if linear is not None:
+        os.environ['PCL_FB_LINEAR'] = linear
+    try:
+        eng.load_frames(np.zeros((sum(Ts), max(eng.D, 1)), dtype=np.float32))
+        b = eng.batch([n for n, _ in sizes], Ts, np.concatenate([[0], np.cumsum(Ts[:-1])]))
+        with np.errstate(divide='ignore'):
+            b.set_transitions([np.log(h[0]) for h in hmms[key]], [np.log(h[1]) for h in hmms[key]])
+        b.set_emissions([h[2] for h in hmms[key]])
+        b.forward_backward(fix_pi=fix_pi, threshold=thr)
+        npass, qtrace, logp = b.get('npass'), b.get('qtrace'), b.get('logp')
+        b.close()
+    finally:
+        os.environ.pop('PCL_FB_LINEAR', None)
+        if old is not None:
+            os.environ['PCL_FB_LINEAR'] = old
+    for u, bw in enumerate(want[key, thr, fix_pi]):
+        assert np.isfinite(bw['logp'][0])
+        assert npass[u] == bw['n_pass'], (u, npass[u], bw['n_pass'])
+        assert np.all(np.isfinite(qtrace[u][:npass[u]])) and np.all(np.isnan(qtrace[u][npass[u]:])), (u, qtrace[u])
+        hold('pass rule on every route (%s)' % route, 'ln P(O)', logp[u], bw['logp'][0], 1e-10)
 
 
 @pytest.mark.parametrize('n', [2, 3, 4, 6])
