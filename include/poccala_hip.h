@@ -556,6 +556,50 @@ int pcl_model_transform_means(pcl_ctx *ctx, int R, const int32_t *state_class /*
                               const double *W /* host R*D*(D+1), or NULL = the resident last estimate */);
 int pcl_mstep_map(pcl_ctx *ctx, double tau);
 
+/* ----------------------------------------------------------------- discriminative training (row f18): MMI by extended Baum-Welch
+ * The last training stage: means, variances and weights from TWO statistics sets of pcl_batch_accumulate, both accumulated under the
+ * current model -- the numerator (the label batches) and the denominator (a competing graph: any general batch) -- without the model or
+ * either set leaving the device (csrc/model_ebw.hip).  Not in the reference.  Everything is float64.  The objective is the caller's:
+ * sum logp of the numerator batches - sum logp of the denominator batches.
+ *
+ * pcl_ebw_hold copies the live statistics block into a second resident block of the same layout, the NUMERATOR set; the live block keeps
+ * its bits and is then the caller's to clear and fill with the denominator.  The held set belongs to the model it was accumulated under
+ * (cov_acc is centred on that model's means): any call that makes a new model (an upload, a flat start, a mix-up, the segmental trainers)
+ * or changes the resident one (pcl_mstep, pcl_em_exchange, pcl_batch_accumulate_exchange, pcl_mstep_map, pcl_model_transform_means,
+ * pcl_mstep_ebw itself) drops it, as the resident MLLR estimate is dropped with its model.  pcl_ebw_drop drops it by hand (no held set:
+ * nothing happens).  pcl_ebw_stats_download is pcl_stats_download of the held set; NULLs are skipped.  With more than one rank the caller
+ * runs pcl_stats_allreduce before pcl_ebw_hold and again before pcl_mstep_ebw, the rule pcl_mstep_map documents.
+ *
+ * pcl_mstep_ebw: numerator = the held set (suffix n), denominator = the live block (suffix d).  In coordinates centred on the current mean
+ * mu, so that the bias of mean_acc never cancels against a large term: per mixture (j, m), m < M, feature dimension d, and set,
+ *     g = acc      x = mean_acc - (bias + mu) acc      c = cov_acc                                     (bias = 100)
+ * I-smoothing, numerator only, when gn is finite and > 0:   xn += tau xn / gn,  cn += tau cn / gn,  gn += tau.   Then
+ *     g = gn - gd,  x = xn - xd,  c = cn - cd
+ *     Dmin = max over d of the larger real root of  v D^2 + (c + g v) D + (c g - x^2) = 0  (0 where the roots are complex or not positive)
+ *     D = max(E gd, 2 Dmin)
+ *     delta = x / (g + D)      mu' = mu + delta      v' = max((c + D v) / (g + D) - delta^2, c_covariance)
+ * A mixture KEEPS mu and v bit for bit when its gn, gd, any x or any c is not finite, when gn (unsmoothed) and gd are both 0, or when
+ * g + D is not finite or not > 0.
+ * Weights (Povey's iteration), per state, on the UNSMOOTHED gn: k_m = gd_m / w_m over the mixtures with w_m > 0, kmax = max k_m, c^0 = w,
+ * weight_iters times  c_m <- (gn_m + (kmax - k_m) c_m) / sum_m' (gn_m' + (kmax - k_m') c_m');  a mixture with w_m = 0 stays 0.  A state
+ * whose gn and gd are all 0, or one of whose sums is not finite or not > 0, keeps its weights.  The ORDER of that sum is part of the rule
+ * (in any other order the weights of a state of a thousand mixtures drift past rounding over 100 iterations): mixture m belongs to thread
+ * m mod 256 of the state's workgroup; a thread adds its mixtures in ascending order starting from 0; the 64 lanes of a wave are summed by a
+ * butterfly with partner lane ^ 32, 16, 8, 4, 2, 1; the four waves' sums are added in ascending order.
+ * Then the derive pass pcl_mstep runs: every scoring path sees the model an upload of the downloaded arrays would give.
+ * D_out (J, M) = the constant used, 0 for a kept mixture.  counts_out (4,) = mixtures updated, mixtures kept, variance elements floored,
+ * states whose weights were kept.  Padding mixtures and padding dimensions of the device layout are never read into a result and never
+ * change.  No floating-point atomics and every sum in a fixed order: two calls on the same inputs give the same bits.
+ * Transitions stay maximum-likelihood (pcl_mstep_transitions); there is no acoustic scale on the denominator (kappa = 1).
+ * No model, or no held set for this model: PCL_ERR_STATE.  E, tau or c_covariance negative or not finite, E == 0, weight_iters < 0:
+ * PCL_ERR_INVALID.  All checked before anything is changed.  Synchronous.  pcl_kernel_time group "ebw": the update's kernel ("derive":
+ * the pass behind it). */
+int pcl_ebw_hold(pcl_ctx *ctx);
+int pcl_ebw_drop(pcl_ctx *ctx);
+int pcl_ebw_stats_download(pcl_ctx *ctx, double *acc, double *alpha_acc, double *mean_acc, double *cov_acc);
+int pcl_mstep_ebw(pcl_ctx *ctx, double E, double tau, double c_covariance, int weight_iters, double *D_out /* J*M or NULL */,
+                  int64_t *counts_out /* 4 or NULL */);
+
 /* ----------------------------------------------------------------- fMLLR (row f11): per-speaker transforms of the FEATURES, y = b + A x
  * Constrained MLLR (Gales 1998, section 3.2 and appendix B) on the resident frames (csrc/frame_adapt.hip).  The model stays untouched; every
  * speaker of a batch gets a transform of its own; the transformed frames stay where scoring, forward-backward, decode and the segmental

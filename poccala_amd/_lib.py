@@ -73,6 +73,10 @@ PROTOTYPES = {
     'pcl_mllr_estimate': (_i, [_vp, _i, _vp, _d, _vp, _vp, _vp]),
     'pcl_model_transform_means': (_i, [_vp, _i, _vp, _vp]),
     'pcl_mstep_map': (_i, [_vp, _d]),
+    'pcl_ebw_hold': (_i, [_vp]),
+    'pcl_ebw_drop': (_i, [_vp]),
+    'pcl_ebw_stats_download': (_i, [_vp, _vp, _vp, _vp, _vp]),
+    'pcl_mstep_ebw': (_i, [_vp, _d, _d, _d, _i, _vp, _vp]),
     'pcl_fmllr_zero': (_i, [_vp, _i]),
     'pcl_batch_accumulate_fmllr': (_i, [_vp, _vp]),
     'pcl_fmllr_stats_download': (_i, [_vp, _vp, _vp, _vp]),

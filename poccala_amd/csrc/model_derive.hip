@@ -484,6 +484,7 @@ int pcl_derive_finish(pcl_ctx *ctx) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->nbad.data(), ctx->d_nbad, (size_t)ctx->J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ++ctx->model_gen;
+    pcl_ebw_release(ctx);                                         // (cov_acc of a held numerator set is centred on the means that just went)
     return PCL_OK;
 }
 
@@ -504,6 +505,7 @@ int pcl_launch_derive(pcl_ctx *ctx) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->nbad.data(), ctx->d_nbad, (size_t)ctx->J * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ++ctx->model_gen;
+    pcl_ebw_release(ctx);                                         // (cov_acc of a held numerator set is centred on the means that just went)
     return PCL_OK;
 }
 

@@ -1490,13 +1490,22 @@ int pcl_stats_download(pcl_ctx *ctx, double *acc, double *alpha_acc, double *mea
     if (!ctx->stats) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_stats_download: no model uploaded");
     HIPCHK(ctx, pcl_stats_join(ctx));
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // [acc | alpha | mean | cov]: only as far as the caller asks (the two moment blocks are 99 % of the bytes)
-    const size_t need = cov_acc ? ctx->stats_len : mean_acc ? (size_t)(ctx->st_cov - ctx->stats) : (size_t)(ctx->st_mean - ctx->stats);
-    std::vector<double> h(need);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->stats, need * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return pcl_stats_block_download(ctx, ctx->stats, acc, alpha_acc, mean_acc, cov_acc);
+}
+
+}  // extern "C"
+
+// A statistics block [acc | alpha | mean | cov] of the current model's shape -> the caller's dense arrays (NULLs are skipped): the live block
+// (pcl_stats_download) or the held numerator set (pcl_ebw_stats_download, model_ebw.hip)
+int pcl_stats_block_download(pcl_ctx *ctx, const double *block, double *acc, double *alpha_acc, double *mean_acc, double *cov_acc) {
     const int J = ctx->J, M = ctx->M, Mp = ctx->Mpad, D = ctx->Dhost, Dd = ctx->D;
-    const double *a = h.data(), *al = a + (size_t)J * Mp, *me = al + J, *co = me + (size_t)J * Mp * Dd;
+    const size_t o_alpha = (size_t)J * Mp, o_mean = o_alpha + J, o_cov = o_mean + (size_t)J * Mp * Dd;
+    // only as far as the caller asks (the two moment blocks are 99 % of the bytes)
+    const size_t need = cov_acc ? ctx->stats_len : mean_acc ? o_cov : o_mean;
+    std::vector<double> h(need);
+    HIPCHK(ctx, hipMemcpyAsync(h.data(), block, need * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    const double *a = h.data(), *al = a + o_alpha, *me = a + o_mean, *co = a + o_cov;
     for (int j = 0; j < J; ++j) {
         if (alpha_acc) alpha_acc[j] = al[j];
         for (int m = 0; m < M; ++m) {
@@ -1509,5 +1518,3 @@ int pcl_stats_download(pcl_ctx *ctx, double *acc, double *alpha_acc, double *mea
     }
     return PCL_OK;
 }
-
-}  // extern "C"

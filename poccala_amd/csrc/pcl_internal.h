@@ -94,6 +94,7 @@ struct ModelDev {
     DevBuf<double> fmllr_beta;   // [fmllr_S] occupancies
     DevBuf<double> fmllr_W;      // the last pcl_fmllr_estimate's transforms [fmllr_S][Dhost][Dhost + 1]; pcl_fmllr_zero drops it
     DevBuf<double> mllr_W;       // the last pcl_mllr_estimate's transforms [mllr_R][Dhost][Dhost + 1] (model_adapt.hip): gone with the model they were estimated for
+    DevBuf<double> ebw_num;      // pcl_ebw_hold's copy of `stats`, same layout (model_ebw.hip): the numerator set of pcl_mstep_ebw; gone with the model it was accumulated under
     DevBuf<double> mllt_F;       // MLLT statistics (frame_mllt.hip): the frame side F[Dhost][Dhost][Dhost], full symmetric matrices; gone with the model
     DevBuf<double> mllt_beta;    // [1] their occupancy
     DevBuf<int> mllt_keep;       // [J] pcl_mllt_zero's state_keep on the device (empty: every state is kept) ...
@@ -639,6 +640,10 @@ int pcl_launch_score_subset_flagged(pcl_ctx *ctx, pcl_batch *b, const ScoreTile 
 inline float pcl_split_threshold(const pcl_ctx *ctx) { return ctx->split_max > 0 ? ctx->cond_max : 3.0e38f; }   // cond_m above this: off the pipe
 int pcl_launch_cast(pcl_ctx *ctx, const double *src64, float *f32, double *dst64, size_t n);
 int pcl_launch_mstep(pcl_ctx *ctx, double floor_var);
+// the held numerator statistics (model_ebw.hip) describe the model they were accumulated under: every pass that makes a new model generation drops them
+inline void pcl_ebw_release(pcl_ctx *ctx) { ctx->ebw_num.release(); }
+// pcl_stats_download of `block`, a statistics block in the live block's layout (pcl_api.hip); waits for the main stream
+int pcl_stats_block_download(pcl_ctx *ctx, const double *block, double *acc, double *alpha_acc, double *mean_acc, double *cov_acc);
 int pcl_launch_mstep_range(pcl_ctx *ctx, double floor_var, int j_lo, int j_hi);
 int pcl_launch_hmm_acc_merge_prepare(pcl_ctx *ctx, double *top);          // top[i] = acc[i] (copy for the max all-reduce)
 int pcl_launch_hmm_acc_merge_scale(pcl_ctx *ctx, const double *top);      // acc[i] = exp(acc[i] - top[i]) (0 where top = -inf)

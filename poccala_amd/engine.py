@@ -574,6 +574,53 @@ class Engine(object):
         self._check(self._lib.pcl_mstep_map(self._ctx, float(tau)))
         self._model_key = None
 
+    # ------------------------------------------------------------------ discriminative training: MMI by extended Baum-Welch
+    def ebw_hold(self):
+        """Keep the statistics accumulated so far as the NUMERATOR set of mstep_ebw() (pcl_ebw_hold): a second resident block; the live
+        block keeps its bits, and is the caller's to clear (stats_zero) and fill with the denominator.  The held set goes with the model
+        it was accumulated under: load_model, flat starts, mixup and every mstep*/transform_means drop it."""
+        self._check(self._lib.pcl_ebw_hold(self._ctx))
+
+    def ebw_drop(self):
+        self._check(self._lib.pcl_ebw_drop(self._ctx))
+
+    def ebw_stats(self):
+        """stats_download() of the held numerator set."""
+        acc, al = np.empty((self.J, self.M)), np.empty((self.J,))
+        me, co = np.empty((self.J, self.M, self.D)), np.empty((self.J, self.M, self.D))
+        self._check(self._lib.pcl_ebw_stats_download(self._ctx, ptr(acc), ptr(al), ptr(me), ptr(co)))
+        return dict(acc=acc, alpha_acc=al, mean_acc=me, cov_acc=co)
+
+    def mstep_ebw(self, E=2.0, tau=100.0, c_covariance=1e-3, weight_iters=100, want_D=False):
+        """Extended Baum-Welch update of means, variances and weights (pcl_mstep_ebw): numerator = the set ebw_hold() kept, denominator =
+        the live statistics, both accumulated under the current model.  D = max(E gd, 2 Dmin) per mixture, I-smoothing tau on the
+        numerator, Povey's weight iteration.  Returns the counts dict(updated, kept, floored, weights_kept), and with want_D=True
+        (counts, D (J, M)): the smoothing constant used, 0 for a mixture that kept its parameters."""
+        D = np.empty((self.J, self.M)) if want_D else None
+        counts = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.pcl_mstep_ebw(self._ctx, float(E), float(tau), float(c_covariance), int(weight_iters), ptr(D), ptr(counts)))
+        self._model_key = None
+        out = dict(zip(('updated', 'kept', 'floored', 'weights_kept'), (int(c) for c in counts)))
+        return (out, D) if want_D else out
+
+    def loop_batch(self, T, frame_begin, unit_trans, unit_prior=None, s=5):
+        """A unit-loop denominator graph over the whole inventory, as a general batch: rows [entry, every state 0..J-1, exit] (as
+        all_state_batch); unit i's emitting rows carry unit_trans[i][1:-1] inside their own block; the mass a row sends to its unit's
+        exit column is spread over the FIRST emitting row of every unit in proportion to unit_prior (default uniform); the entry row
+        goes to those first rows with unit_prior; pi is uniform 1/N, as embedded_structure makes it.  Dense (J+2)^2 matrices per
+        utterance: for inventories of a few hundred states."""
+        a, pi = loop_structure(unit_trans, unit_prior, s)
+        if a.shape[0] != self.J + 2:
+            raise ValueError('%d units of %d emitting states do not cover the model\'s %d states' % (len(unit_trans), s - 2, self.J))
+        T = as_c(T, np.int32).reshape(-1)
+        b = Batch(self, np.full(len(T), self.J + 2, dtype=np.int32), T, frame_begin)
+        with np.errstate(divide='ignore'):
+            la, lpi = np.log(a), np.log(pi)
+        b.set_transitions([la] * b.U, [lpi] * b.U)
+        rows = np.concatenate([[PCL_ROW_ENTRY], np.arange(self.J), [PCL_ROW_EXIT]]).astype(np.int32)
+        b.set_states([rows] * b.U)
+        return b
+
     # ------------------------------------------------------------------ fMLLR: per-speaker transforms of the resident frames
     def fmllr_zero(self, n_speakers):
         """Make (or clear) the context's fMLLR statistics for n_speakers speakers (pcl_fmllr_zero); a resident estimate is dropped."""
@@ -1440,6 +1487,28 @@ def embedded_structure(n_units, unit_trans, s=5):
         a[lo:lo + e, lo - 1:lo - 1 + s] = unit_trans[i][1:-1]
     pi = np.ones(n) / n
     return a, pi
+
+
+def loop_structure(unit_trans, unit_prior=None, s=5):
+    """The (N,N) transition matrix and uniform pi of a unit loop over the whole inventory, N = (s-2) len(unit_trans) + 2 (Engine.loop_batch):
+    row 0 the entry, unit i's emitting rows 1 + i (s-2) ..., the last row the exit.  Inside its own block a row keeps unit_trans[i][1:-1];
+    what it sends to the unit's exit column goes to the first emitting row of every unit, times unit_prior (normalised; default uniform);
+    the entry row goes to those rows with unit_prior; the exit row has no successor."""
+    e, n_units = s - 2, len(unit_trans)
+    prior = np.ones(n_units) if unit_prior is None else np.asarray(unit_prior, dtype=np.float64).reshape(-1)
+    if prior.shape != (n_units,) or not (np.all(prior >= 0) and prior.sum() > 0):
+        raise ValueError('unit_prior must hold one weight >= 0 per unit, not all of them 0')
+    prior = prior / prior.sum()
+    n = e * n_units + 2
+    first = 1 + e * np.arange(n_units)
+    a = np.zeros((n, n))
+    a[0, first] = prior
+    for i in range(n_units):
+        t = np.asarray(unit_trans[i], dtype=np.float64)
+        lo = 1 + i * e
+        a[lo:lo + e, lo:lo + e] = t[1:-1, 1:-1]
+        a[lo:lo + e, first] += t[1:-1, -1][:, None] * prior[None, :]
+    return a, np.ones(n) / n
 
 
 def embedded_row_states(unit_state_ids, s=5):
