@@ -600,6 +600,57 @@ int pcl_ebw_stats_download(pcl_ctx *ctx, double *acc, double *alpha_acc, double 
 int pcl_mstep_ebw(pcl_ctx *ctx, double E, double tau, double c_covariance, int weight_iters, double *D_out /* J*M or NULL */,
                   int64_t *counts_out /* 4 or NULL */);
 
+/* ----------------------------------------------------------------- minimum Bayes risk (row f19): sMBR / MPFE and an acoustic scale
+ * One forward-backward of a batch under an acoustic scale kappa that carries the expected frame accuracy against a reference alignment
+ * beside alpha and beta (csrc/hmm_mbr.hip).  Not in the reference.  Float64 throughout.  For discriminative use it REPLACES
+ * pcl_batch_forward_backward (whose pass loop and pi re-estimation a discriminative pass must not run, and which has no scale): it runs ONE
+ * pass with the batch's ln pi as set; and it REPLACES scaling the emissions by hand, which is wrong because the accumulate pass reads Bt as
+ * ln b_j to form the mixture responsibilities.  What follows it stays: pcl_batch_mbr_posteriors puts a ln gamma into the batch where
+ * pcl_batch_accumulate (and _fmllr, _mllt) read it, pcl_ebw_hold / pcl_mstep_ebw turn a positive and a negative set into a model.  With
+ * this path the denominator of MMI has an acoustic scale: the "kappa = 1" of pcl_mstep_ebw's text describes pcl_batch_forward_backward only.
+ *
+ * The rule, per utterance of N rows and T >= 1 frames; ln a, ln pi, B as the batch holds them; bs_j(t) = kappa B[j,t]:
+ *     alpha_0(j) = ln pi_j + bs_j(0)          alpha_t(j) = LSE_i[alpha_{t-1}(i) + ln a_ij] + bs_j(t)
+ *     beta_{T-1} = 0                          beta_t(i)  = LSE_j[ln a_ij + (bs_j(t+1) + beta_{t+1}(j))]
+ *     ln P = LSE_j alpha_{T-1}(j)             ln gamma_t(j) = alpha_t(j) + beta_t(j) - LSE_i(alpha_t(i) + beta_t(i))
+ * (oracle.forward / oracle.backward's conventions: every row may end, quirk Q8; LSE returns a maximum of +-inf as itself, quirk Q4;
+ * ln gamma is normalised per frame as PCL_GET_LGAMMA is).
+ * Accuracy: A_t(j) = 1 when row_state[j] >= 0, frame_ref[t] >= 0 and row_state[j] / group == frame_ref[t] / group (integer division), else
+ * 0.  group = 1 compares states (sMBR); group = S - 2 compares units (phone-frame accuracy, MPFE).  Entry and exit rows and frames with
+ * frame_ref = -1 score 0.
+ * Expected accuracy.  Each LSE above is evaluated as  m = max_k v_k;  e_k = exp(v_k - m);  s = sum_k e_k;  result m + ln s  (m = +-inf:
+ * m itself).  The SAME e_k weigh the accuracies:  sp = sum_k e_k y_k,  mean = sp / s  (0 when m = +-inf), with
+ *     alpha'_0(j) = A_0(j)        alpha'_t(j) = mean over predecessors i of y = alpha'_{t-1}(i), + A_t(j);   0 where alpha_t(j) = -inf
+ *     beta'_{T-1}(i) = 0          beta'_t(i)  = mean over successors j of y = beta'_{t+1}(j) + A_{t+1}(j);    0 where beta_t(i) = -inf
+ *     c_avg = sum_j gamma_0(j) (alpha'_0(j) + beta'_0(j))                 (gamma = exp(ln gamma); terms with gamma = 0 are left out)
+ *     g_t(j) = kappa gamma_t(j) ((alpha'_t(j) + beta'_t(j)) - c_avg)      signed; 0 where gamma_t(j) = 0
+ * sum_j gamma_t(j) (alpha'_t(j) + beta'_t(j)) is the same number at every t -- the expected accuracy of the utterance; the pass takes it at
+ * frame 0, where it is known before the forward recursion starts.  g is d c_avg / d B[j,t], and sum_j g_t(j) = 0.  T = 1 is legal:
+ * c_avg = sum_j gamma_0(j) A_0(j).
+ * Order of the sums, part of the rule (tests/_mbr_twin.py repeats it): over predecessors in ascending source row (the CSC arrays), over
+ * successors in ascending target row (the CSR arrays), both from 0; across the rows of a frame (the normaliser, c_avg, ln P) row i belongs
+ * to lane i mod 64 of wave i / 64, the 64 lanes of a wave are summed by a butterfly with partner lane ^ 32, 16, 8, 4, 2, 1 (lanes past N
+ * hold 0, or -inf under a maximum), the waves' sums are added in ascending order.  No contraction, no floating-point atomics: two calls on
+ * the same inputs give the same bits.
+ *
+ * pcl_batch_mbr needs transitions, a row -> state map and emissions (pcl_batch_score or pcl_batch_set_emissions), not
+ * pcl_batch_forward_backward.  At most 1024 rows per utterance, any transition structure.  It keeps its results in buffers of its own and
+ * changes no bit of what pcl_batch_get returns (B, ALPHA .. QTRACE, PATH).  pcl_batch_mbr_get: ln P (U,), c_avg (U,), ln gamma and g
+ * ragged (N_u, T_u) row-major like PCL_GET_LGAMMA; NULLs are skipped.  pcl_batch_mbr_posteriors writes the batch's posteriors, in the
+ * layout pcl_batch_set_posteriors leaves: which = 0: ln gamma under kappa (the scaled MMI denominator; on a label batch the numerator);
+ * which = +1: ln max(g, 0); which = -1: ln max(-g, 0) -- the positive and the negative set of an sMBR / MPFE iteration, whose
+ * difference is g.  It marks the posteriors as set (as pcl_batch_set_posteriors does) and leaves the forward-backward results alone;
+ * PCL_GET_LGAMMA then reads what it wrote.
+ * PCL_ERR_STATE: pcl_batch_mbr without transitions, states or emissions; _get / _posteriors before pcl_batch_mbr, or after a call that
+ * invalidates the pass (pcl_batch_set_transitions, pcl_batch_refresh_transitions, pcl_batch_set_states, pcl_batch_set_emissions,
+ * pcl_batch_score).  PCL_ERR_INVALID: kappa not finite or <= 0, group < 1, a frame_ref outside [-1, J), more than 1024 rows, which outside
+ * {-1, 0, 1}.  All checked before anything is changed.  pcl_batch_mbr is queued on the main stream; _get is synchronous.
+ * pcl_kernel_time group "mbr": the pass ("mbr_post": the posteriors kernel). */
+int pcl_batch_mbr(pcl_batch *b, const int32_t *frame_ref /* ragged (T_u,), host: state id in [0,J) or -1 */, double kappa, int group);
+int pcl_batch_mbr_get(pcl_batch *b, double *logp /* U */, double *c_avg /* U */, double *lgamma /* ragged (N_u,T_u) */,
+                      double *g /* ragged (N_u,T_u), signed */);
+int pcl_batch_mbr_posteriors(pcl_batch *b, int which);
+
 /* ----------------------------------------------------------------- fMLLR (row f11): per-speaker transforms of the FEATURES, y = b + A x
  * Constrained MLLR (Gales 1998, section 3.2 and appendix B) on the resident frames (csrc/frame_adapt.hip).  The model stays untouched; every
  * speaker of a batch gets a transform of its own; the transformed frames stay where scoring, forward-backward, decode and the segmental

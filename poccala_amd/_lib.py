@@ -48,6 +48,9 @@ PROTOTYPES = {
     'pcl_batch_score': (_i, [_vp, _i]),
     'pcl_batch_forward_backward': (_i, [_vp, _i, _d]),
     'pcl_batch_viterbi': (_i, [_vp, _i]),
+    'pcl_batch_mbr': (_i, [_vp, _vp, _d, _i]),
+    'pcl_batch_mbr_get': (_i, [_vp, _vp, _vp, _vp, _vp]),
+    'pcl_batch_mbr_posteriors': (_i, [_vp, _i]),
     'pcl_batch_get': (_i, [_vp, _i, _vp]),
     'pcl_batch_sizes': (_i, [_vp, _vp, _vp, _vp, _vp]),
     'pcl_batch_fetch_async': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),

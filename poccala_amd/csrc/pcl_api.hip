@@ -686,7 +686,7 @@ int pcl_batch_upload_sparse(pcl_batch *b, const SparseTrans &t, const double *lo
     HIPCHK(ctx, up(ctx, b->logpi, logpi, (size_t)b->shape.sumN * sizeof(double)));
     HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_trans = true;
-    b->have_fb = b->have_vit = false;
+    b->have_fb = b->have_vit = b->have_mbr = false;
     return PCL_OK;
 }
 
@@ -737,6 +737,7 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
     HIPCHK(ctx, up(ctx, b->d_row_state, row_state, (size_t)b->shape.sumN * sizeof(int32_t)));
     HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_states = true;
+    b->have_mbr = false;                                           // (pcl_batch_mbr's accuracy was taken against the map that just went)
     b->virt_rows_filled = false;
     b->model_J = ctx->J;
     return PCL_OK;
@@ -775,7 +776,7 @@ int pcl_batch_set_emissions(pcl_batch *b, const double *B) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     b->have_B = true;
     b->virt_rows_filled = false;                                   // (the caller's matrix is in the buffer now)
-    b->have_fb = b->have_vit = false;
+    b->have_fb = b->have_vit = b->have_mbr = false;
     return PCL_OK;
 }
 
@@ -899,7 +900,7 @@ int pcl_batch_score(pcl_batch *b, int precision) {
     HIPCHK(ctx, pcl_batch_mark(b));
     b->mark_is_score = true;
     b->have_B = true;
-    b->have_fb = b->have_vit = false;
+    b->have_fb = b->have_vit = b->have_mbr = false;
     return PCL_OK;
 }
 
@@ -967,6 +968,74 @@ int pcl_batch_viterbi(pcl_batch *b, int end_state_back) {
         b->mark_is_score = false;
     }
     b->have_vit = true;
+    return PCL_OK;
+}
+
+// Minimum Bayes risk: one forward-backward under kappa with the expected accuracy against frame_ref (hmm_mbr.hip; the rule: poccala_hip.h).
+// On the main stream, behind whatever the batch has queued on either stream; it reads Bt, the transitions and the row map and writes the
+// pass's own buffers only.
+int pcl_batch_mbr(pcl_batch *b, const int32_t *frame_ref, double kappa, int group) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    const char *who = "pcl_batch_mbr";
+    if (!b->have_trans) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no transitions set", who);
+    if (!b->have_states) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: pcl_batch_set_states was not called (the accuracy compares row states)", who);
+    if (!b->have_B) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no emissions (score or set_emissions first)", who);
+    if (!frame_ref) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: NULL argument", who);
+    if (!(kappa > 0.0) || !std::isfinite(kappa)) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: kappa = %g is not a finite number > 0", who, kappa);
+    if (group < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: group = %d", who, group);
+    if (b->shape.Nmax > pcl_mbr_max_rows()) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: HMM with %d states exceeds the %d-state limit", who, b->shape.Nmax, pcl_mbr_max_rows());
+    std::vector<int32_t> ref_group((size_t)b->shape.sumT);
+    for (size_t t = 0; t < ref_group.size(); ++t) {
+        const int32_t r = frame_ref[t];
+        if (r < -1 || r >= b->model_J) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame_ref[%zu] = %d is outside [-1, %d)", who, t, (int)r, b->model_J);
+        ref_group[t] = r < 0 ? -1 : r / group;
+    }
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    b->have_mbr = false;                                           // (from here on the buffers are being rewritten)
+    TRY(pcl_mbr_reserve(ctx, b));
+    b->launched = true;
+    HIPCHK(ctx, pcl_h2d(ctx, b->mbr_ref, ref_group.data(), ref_group.size() * sizeof(int32_t)));
+    TRY(pcl_launch_mbr(ctx, b, kappa, group));
+    HIPCHK(ctx, pcl_batch_mark(b));                                // (the pass writes nothing a recursion reads: mark_is_score stays)
+    b->have_mbr = true;
+    return PCL_OK;
+}
+
+int pcl_batch_mbr_get(pcl_batch *b, double *logp, double *c_avg, double *lgamma, double *g) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    if (!b->have_mbr) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_mbr_get: run pcl_batch_mbr first (new emissions, transitions or states drop its results)");
+    TRY(batch_join(b));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (lgamma || g) TRY(ensure_tmp(b));
+    const size_t nt = (size_t)b->shape.sumNT * sizeof(double);
+    if (logp) HIPCHK(ctx, pcl_d2h_queue(ctx, logp, b->mbr_logp, (size_t)b->U * sizeof(double)));
+    if (c_avg) HIPCHK(ctx, pcl_d2h_queue(ctx, c_avg, b->mbr_cavg, (size_t)b->U * sizeof(double)));
+    const double *mats[2] = {b->mbr_lgam, b->mbr_g};
+    double *hosts[2] = {lgamma, g};
+    for (int k = 0; k < 2; ++k) {
+        if (!hosts[k]) continue;
+        TRY(pcl_launch_transpose(ctx, b, mats[k], b->tmp, 0));     // time-major -> the reference's (N_u, T_u); in stream order with the copy before it
+        HIPCHK(ctx, pcl_d2h_queue(ctx, hosts[k], b->tmp, nt));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PCL_OK;
+}
+
+int pcl_batch_mbr_posteriors(pcl_batch *b, int which) {
+    if (!b) return PCL_ERR_INVALID;
+    pcl_ctx *ctx = b->ctx;
+    if (!b->have_mbr) PCL_FAIL(ctx, PCL_ERR_STATE, "pcl_batch_mbr_posteriors: run pcl_batch_mbr first (new emissions, transitions or states drop its results)");
+    if (which < -1 || which > 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "pcl_batch_mbr_posteriors: which = %d is not -1, 0 or +1", which);
+    TRY(batch_join(b));                                            // (a forward-backward queued on the second stream writes lgam too)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!b->lgam) TRY(b->lgam.alloc(ctx, (size_t)b->shape.sumNT));
+    TRY(pcl_launch_mbr_posteriors(ctx, b, which));
+    HIPCHK(ctx, pcl_batch_mark(b));
+    b->mark_is_score = false;                                      // lgam changed behind the scoring: a later recursion waits for a fresh event
+    b->have_post = true;
     return PCL_OK;
 }
 

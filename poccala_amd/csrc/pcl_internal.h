@@ -285,8 +285,17 @@ struct BatchDecodeDev {
     bool dec_has_words = false;                      // the last decode was pcl_batch_decode_lm
 };
 
+// The minimum-Bayes-risk pass of a batch (hmm_mbr.hip; pcl_batch_mbr): its own buffers, made on first use -- nothing pcl_batch_get returns
+struct BatchMbrDev {
+    DevBuf<double> mbr_beta, mbr_betap;              // beta and beta' under kappa, time-major like `beta`: stored by the backward pass, read by the forward pass
+    DevBuf<double> mbr_lgam, mbr_g;                  // ln gamma under kappa and the signed g, time-major: what pcl_batch_mbr_posteriors turns into `lgam`
+    DevBuf<double> mbr_logp, mbr_cavg;               // [U]
+    DevBuf<int32_t> mbr_ref;                         // [sum T] frame_ref / group (-1 stays -1), uploaded by every pcl_batch_mbr
+    bool have_mbr = false;                           // the buffers hold a pass over the batch's CURRENT transitions, states and emissions
+};
+
 // Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_api.hip).
-struct pcl_batch : BatchDecodeDev {
+struct pcl_batch : BatchDecodeDev, BatchMbrDev {
     pcl_ctx *ctx = nullptr;
     int U = 0;
     // What the host planned for the kernels (batch_plan.h), each the host copy of what the device holds: replaced as a whole by the call
@@ -539,6 +548,11 @@ int pcl_launch_score(pcl_ctx *ctx, pcl_batch *b, int precision, const ScoreTile 
 int pcl_launch_fill_virtual_rows(pcl_ctx *ctx, pcl_batch *b);
 int pcl_launch_forward_backward(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshold);
 int pcl_launch_viterbi(pcl_ctx *ctx, pcl_batch *b, int end_state_back);
+// hmm_mbr.hip: the pass's buffers (grow only), the scaled forward-backward with the expected accuracy, and lgam <- ln gamma / ln max(+-g, 0)
+int pcl_mbr_reserve(pcl_ctx *ctx, pcl_batch *b);
+int pcl_mbr_max_rows();
+int pcl_launch_mbr(pcl_ctx *ctx, pcl_batch *b, double kappa, int group);
+int pcl_launch_mbr_posteriors(pcl_ctx *ctx, pcl_batch *b, int which);
 bool pcl_fb_linear_enabled();                                              // env PCL_FB_LINEAR=0: the log-domain kernels only
 int pcl_launch_fb_linear(pcl_ctx *ctx, pcl_batch *b, int fix_pi, double threshold);
 int pcl_launch_fb_linear_post(pcl_ctx *ctx, pcl_batch *b);

@@ -1124,6 +1124,35 @@ class Batch(object):
     def viterbi(self, end_state_back=False):
         self._check(self._lib.pcl_batch_viterbi(self._b, 1 if end_state_back else 0))
 
+    # ------------------------------------------------------------------ minimum Bayes risk: sMBR / MPFE, and MMI with an acoustic scale
+    def mbr(self, frame_ref, kappa=1.0, group=1):
+        """One forward-backward under the acoustic scale kappa with the expected frame accuracy against frame_ref (pcl_batch_mbr; the rule:
+        include/poccala_hip.h).  frame_ref[u] (T_u,) int32: the reference state of every frame in [0, J), or -1 (ref_states() of the
+        numerator batch gives it).  group = 1 compares states (sMBR), group = S - 2 units (MPFE).  Needs transitions, states and emissions,
+        not forward_backward(); leaves everything get() returns as it was."""
+        r = self._ragged(frame_ref, lambda u: (self.T[u],), dtype=np.int32)
+        self._check(self._lib.pcl_batch_mbr(self._b, ptr(r), float(kappa), int(group)))
+
+    def mbr_get(self, want=('logp', 'c_avg', 'lgamma', 'g')):
+        """The last mbr()'s results (pcl_batch_mbr_get) as a dict: logp (U,), c_avg (U,), lgamma and g lists of (N_u, T_u) arrays; g is signed."""
+        out = dict(logp=np.empty(self.U) if 'logp' in want else None, c_avg=np.empty(self.U) if 'c_avg' in want else None,
+                   lgamma=np.empty(int(self._nt_off[-1])) if 'lgamma' in want else None, g=np.empty(int(self._nt_off[-1])) if 'g' in want else None)
+        self._check(self._lib.pcl_batch_mbr_get(self._b, ptr(out['logp']), ptr(out['c_avg']), ptr(out['lgamma']), ptr(out['g'])))
+        for k in ('lgamma', 'g'):
+            if out[k] is not None:
+                out[k] = [out[k][self._nt_off[u]:self._nt_off[u + 1]].reshape(self.N[u], self.T[u]) for u in range(self.U)]
+        return {k: v for k, v in out.items() if v is not None}
+
+    def mbr_posteriors(self, which):
+        """The last mbr()'s posteriors into the batch, where accumulate() reads them (pcl_batch_mbr_posteriors): which = 0: ln gamma under
+        kappa; +1: ln max(g, 0), the positive set of an sMBR iteration; -1: ln max(-g, 0), its negative set."""
+        self._check(self._lib.pcl_batch_mbr_posteriors(self._b, int(which)))
+
+    def ref_states(self):
+        """The Viterbi alignment as mbr() takes it: per utterance the (T_u,) int32 state ids row_state[path[t]], -1 where the path sits in
+        an entry or exit row.  Host NumPy on get('path') and row_states(); viterbi() must have run."""
+        return [np.where(rs[p] >= 0, rs[p], -1).astype(np.int32) for rs, p in zip(self.row_states(), self.get('path'))]
+
     def accumulate(self, precision=PCL_F32):
         self._check(self._lib.pcl_batch_accumulate(self._b, int(precision)))
 
