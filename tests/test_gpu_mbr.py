@@ -5,6 +5,9 @@ Everything goes through the C-ABI; the twin is fed the emissions the batch holds
 Shapes: batches of 5 utterances of unequal N and T, N in {3, 62, 64, 65, 130} (one wave, a full wave, the two-wave edge, three waves),
 T in {1, 2, 3, 17}; a left-to-right chain (the register lists), a dense random matrix with holes, an unreachable row and an exit row that
 emits nothing (the general lists), and Engine.loop_batch over 3 and over 22 units (N = 11 and 68) on real scoring.
+The shapes this file does not reach are in tests/test_gpu_mbr_edges.py (cases: tests/_mbr_cases.py): up to sixteen waves and the 1024-row
+limit, the two list forms against each other bit for bit, -inf emissions on emitting rows, utterances with P(O) = 0 beside possible ones,
+mbr_post_kernel's grid-stride loop, and identities that do not go through the twin.  The helpers shared with it live in _mbr_cases.py.
 
 Bound.  Nothing here is a float32 path.  Per utterance the float64 twin is measured against the same code in long double; the device may
 differ from the float64 twin by 4x that distance plus an absolute term derived in _mbr_twin.allowances from ulp(max |alpha|) and the
@@ -21,13 +24,13 @@ import numpy as np
 import pytest
 
 import _ebw_twin as ebw
+import _mbr_cases as mc
 import _mbr_twin as tw
+from _mbr_cases import INVALID, STATE, WORST, against_twin, logs, refused, same_bits, share
 from _parity import hold
 
 pytestmark = pytest.mark.gpu
 F64_RTOL = 1e-9              # PCL_F64
-INVALID, STATE = -1, -3
-WORST = {}
 NS, TS = [3, 62, 64, 65, 130], [1, 2, 3, 17, 17]
 COMBOS = [(1.0, 1, 'viterbi'), (1.0, 3, 'random'), (0.1, 1, 'partly'), (0.1, 3, 'none'), (0.1, 1, 'viterbi'), (1.0, 1, 'partly'),
           (0.1, 3, 'random'), (1.0, 3, 'viterbi')]
@@ -40,15 +43,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def same_bits(a, b):
-    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
-
-
-def logs(a, pi):
-    with np.errstate(divide='ignore'):
-        return np.log(a), np.log(pi)
 
 
 _SETUPS = {}
@@ -71,8 +65,7 @@ def setup_of(kind):
         for n, t in zip(N, T):
             a, pi = tw.chain_structure(n, rng) if kind == 'chain' else tw.dense_structure(n, rng)
             rows = np.concatenate([[-1], rng.integers(0, J, n - 2), [-2]]).astype(np.int32)
-            B = rng.uniform(-40.0, 0.0, (n, t))
-            B[0], B[n - 1] = 0.0, -np.inf                            # the entry row's ln 1 and the exit row's ln 0, as scoring writes them
+            B = mc.emissions(n, t, rng)                              # uniform(-40, 0), the entry row's ln 1 and the exit row's ln 0
             if kind == 'chain' and t == 1:
                 B[0] = -3.0                                          # (one frame: something other than the entry row has to be possible)
             s['utts'].append(logs(a, pi) + (rows, B))
@@ -90,15 +83,11 @@ def setup_of(kind):
 def make_batch(eng, s):
     """the batch of a structure with its emissions in place -> (batch, per utterance (la, lpi, row_state))"""
     from poccala_amd import PCL_F64
-    from poccala_amd.engine import Batch, loop_structure
+    from poccala_amd.engine import loop_structure
+    if s['kind'] in ('chain', 'dense'):
+        return mc.make_batch(eng, s)
     eng.load_model(*s['model'])
     eng.load_frames(s['frames'])
-    if s['kind'] in ('chain', 'dense'):
-        b = Batch(eng, s['N'], s['T'], s['begin'])
-        b.set_transitions([u[0] for u in s['utts']], [u[1] for u in s['utts']])
-        b.set_states([u[2] for u in s['utts']])
-        b.set_emissions([u[3] for u in s['utts']])
-        return b, [u[:3] for u in s['utts']]
     b = eng.loop_batch(s['T'], s['begin'], s['trans'])
     b.score(PCL_F64)
     la, lpi = logs(*loop_structure(s['trans']))
@@ -117,33 +106,6 @@ def refs_of(b, kind, J, rng):
         for r in out:
             r[::2] = -1
     return out
-
-
-def share(tag, key, got, want, allow):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    fin = np.isfinite(want)
-    assert np.array_equal(np.isfinite(got), fin) and same_bits(got[~fin], want[~fin]), (tag, key, 'infinities and NaNs differ')
-    with np.errstate(invalid='ignore'):
-        used = float((np.abs(got - want)[fin] / np.broadcast_to(allow, want.shape)[fin]).max()) if fin.any() else 0.0
-    WORST[key] = max(WORST.get(key, 0.0), used)
-    assert used <= 1.0, '%s: %s uses %.3f of its allowance' % (tag, key, used)
-    return used
-
-
-def against_twin(tag, b, per_utt, Bs, refs, kappa, group):
-    """mbr_get of the batch against the twin, utterance by utterance -> (device results, twins, allowances)"""
-    got = b.mbr_get()
-    twins, allows = [], []
-    for u, (la, lpi, rows) in enumerate(per_utt):
-        t64 = tw.mbr(la, lpi, Bs[u], rows, refs[u], kappa=kappa, group=group)
-        tld = tw.mbr(la, lpi, Bs[u], rows, refs[u], kappa=kappa, group=group, dtype=np.longdouble)
-        al = tw.allowances(t64, tld, kappa)
-        used = [share('%s utt %d' % (tag, u), key, got[key][u], t64[key], al[key]) for key in ('logp', 'c_avg', 'lgamma', 'g')]
-        N = len(rows)
-        assert np.abs(got['g'][u].sum(axis=0)).max() <= N * al['g'].max()          # the gradient of an expectation of a constant total mass
-        twins.append(t64), allows.append(al)
-        print('%s utt %d (N=%d T=%d): c_avg %.6g; shares logp %.3f c_avg %.3f lgamma %.3f g %.3f' % ((tag, u, N, Bs[u].shape[1], got['c_avg'][u]) + tuple(used)))
-    return got, twins, allows
 
 
 @pytest.mark.parametrize('kind', STRUCTURES)
@@ -201,13 +163,6 @@ def test_results_of_other_passes_stay_and_two_runs_agree(eng):
     for k in ('lgamma', 'g'):
         assert all(same_bits(x, y) for x, y in zip(first[k], second[k]))
     b.close()
-
-
-def refused(code, call):
-    from poccala_amd import PoccalaHipError
-    with pytest.raises(PoccalaHipError) as e:
-        call()
-    assert e.value.code == code, e.value
 
 
 def test_refusals(eng):
