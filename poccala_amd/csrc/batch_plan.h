@@ -95,6 +95,27 @@ static int plan_batch_shape(pcl_ctx *ctx, int U, const int32_t *N, const int32_t
     return PCL_OK;
 }
 
+// Does a frame matrix of F rows hold every row the batch refers to?  (A batch outlives uploads: each caller words its own refusal.)
+static bool shape_fits_frames(const BatchShape &s, long long F) { return s.max_frame_end <= F; }
+
+// A frame has one owner: the utterances' row ranges are disjoint (touching is disjoint).  The first offending pair in the order of the first
+// rows, equal first rows by index: `second` starts before the end of `first`, the utterance ahead of it in that order (-1: none, frame0 < 0).
+struct UttOverlap { bool found; int first, second; };
+static UttOverlap shape_overlap(const BatchShape &s) {
+    const std::vector<UttDesc> &utt = s.utt;
+    std::vector<int> by(utt.size());
+    for (size_t u = 0; u < by.size(); ++u) by[u] = (int)u;
+    std::sort(by.begin(), by.end(), [&](int x, int y) { return utt[x].frame0 != utt[y].frame0 ? utt[x].frame0 < utt[y].frame0 : x < y; });
+    long long end = 0;
+    int prev = -1;
+    for (int u : by) {
+        if (utt[u].frame0 < end) return {true, prev, u};
+        end = utt[u].frame0 + utt[u].T;
+        prev = u;
+    }
+    return {false, -1, -1};
+}
+
 // ---------------------------------------------------------------- the label structure of a label-built batch
 // (AcousticModel.embedded, AcousticModel.py:957-1014: a sentence HMM is its label's unit HMMs, e = S - 2 emitting rows each, between an
 // entry and an exit row)

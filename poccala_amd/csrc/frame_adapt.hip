@@ -122,7 +122,7 @@ extern "C" int pcl_fmllr_zero(pcl_ctx *ctx, int S) {
     return PCL_OK;
 }
 
-// pcl_batch_accumulate_fmllr behind its checks of the batch (pcl_api.hip): the batch has emissions, posteriors and states, is joined, fits
+// pcl_batch_accumulate_fmllr behind its checks of the batch (pcl_batch.hip): the batch has emissions, posteriors and states, is joined, fits
 // the current frames and model, and the scoring rows (PCL_LAYOUT_P64) are derived
 int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_speaker) {
     const char *who = "pcl_batch_accumulate_fmllr";

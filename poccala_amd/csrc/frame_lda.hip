@@ -1,7 +1,7 @@
 // LDA (row f12): class statistics of SPLICED frames and the projection of the resident frame matrix to a new width.
 //   pcl_lda_zero               the context's class statistics (R, n, n), n = Ds + 1, made and cleared
 //   pcl_lda_accumulate         host class labels per frame row -> the statistics
-//   pcl_batch_accumulate_lda   the batch's Viterbi owner map (pcl_api.hip runs the alignment; the map never leaves the device) -> the statistics
+//   pcl_batch_accumulate_lda   the batch's Viterbi owner map (pcl_batch.hip runs the alignment; the map never leaves the device) -> the statistics
 //   pcl_lda_stats_download     n_r, s_r, S_r taken apart on the host, S mirrored from the upper triangle
 //   pcl_frames_splice_project  y = b + A splice(x) into new buffers that replace the resident frame matrix (another width)
 //   pcl_frames_download        the resident frames as held, unpadded

@@ -211,7 +211,7 @@ extern "C" int pcl_mllt_zero(pcl_ctx *ctx, const int32_t *state_keep) {
     return PCL_OK;
 }
 
-// pcl_batch_accumulate_mllt behind its checks of the batch (pcl_api.hip): the batch has emissions, posteriors and states, is joined, fits
+// pcl_batch_accumulate_mllt behind its checks of the batch (pcl_batch.hip): the batch has emissions, posteriors and states, is joined, fits
 // the current frames and model, and the scoring rows (PCL_LAYOUT_P64) are derived
 int pcl_launch_mllt_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_keep) {
     const char *who = "pcl_batch_accumulate_mllt";

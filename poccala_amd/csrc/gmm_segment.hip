@@ -462,7 +462,7 @@ int pcl_seg_create(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *f
 
 }  // extern "C"
 
-// The owner array is on the device already (pcl_seg_create above; pcl_uniform_segments, bootstrap.hip; pcl_batch_align_segments, pcl_api.hip):
+// The owner array is on the device already (pcl_seg_create above; pcl_uniform_segments, bootstrap.hip; pcl_batch_align_segments, pcl_batch.hip):
 // counting sort (timer "seg_count") + scatter and gather (timer "seg_gather").
 int pcl_seg_create_device(pcl_ctx *ctx, int64_t n_frames_total, int J, const int32_t *d_state, pcl_seg **out) {
     *out = nullptr;

@@ -914,12 +914,9 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
 #endif
         return PCL_OK;
     };
-    if (ctx->dp_async) {
-        TRY(pcl_run_on_dp_stream(b, false, launch));
-    } else {
-        TRY(launch());
-        HIPCHK(ctx, pcl_batch_mark(b));
-    }
+    // no flag of pcl_run_recursion: the decoder writes its own workspace only -- nothing pcl_batch_fetch_async copies, nothing another
+    // recursion reads behind the scoring -- and the main stream was put behind a pending recursion above
+    TRY(pcl_run_recursion(b, 0, launch));
     b->have_dec = true;
     b->dec_has_words = with_lm;
     return PCL_OK;

@@ -294,7 +294,7 @@ struct BatchMbrDev {
     bool have_mbr = false;                           // the buffers hold a pass over the batch's CURRENT transitions, states and emissions
 };
 
-// Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_api.hip).
+// Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_batch.hip).
 struct pcl_batch : BatchDecodeDev, BatchMbrDev {
     pcl_ctx *ctx = nullptr;
     int U = 0;
@@ -535,10 +535,39 @@ static inline int pcl_run_on_dp_stream(pcl_batch *b, bool after_fetch, Launch la
     return PCL_OK;
 }
 
-// shared by pcl_api.hip and hmm_units.hip (C linkage, internal)
+// shared by pcl_batch.hip and hmm_units.hip, and below by pcl_batch.hip, pcl_api.hip and hmm_decode.hip (C linkage, internal)
 extern "C" {
 int pcl_batch_upload_sparse(pcl_batch *b, const SparseTrans &t, const double *logpi);
 int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state);
+int pcl_batch_reap(pcl_ctx *ctx, bool wait);   // pcl_batch.hip: frees the destroyed batches the GPU is done with (wait: all of them); returns how many are left
+int batch_join(pcl_batch *b);                  // pcl_batch.hip: the main stream behind the batch's pending recursion and result copies
+int ensure_frames64(pcl_ctx *ctx);             // pcl_api.hip: the float64 copy of the frame matrix, derived on first use
+// pcl_api.hip: what pcl_batch_accumulate_exchange and pcl_accumulate_exchange_idle (`who`) need of the context; joins a pending pcl_stats_zero
+int exchange_precheck(pcl_ctx *ctx, const char *who, int payload, int n_chunks, int update_transitions);
+}
+
+// The one entry into a recursion of batch `b` (forward-backward, Viterbi, decode): on the second stream (pcl_run_on_dp_stream), or with
+// PCL_DP_STREAM=0 on the main stream with the batch's mark behind it.  What the three callers do differently is said here.  The last two
+// are kept as each caller had them and change nothing today: dp_pending is set, and mark_is_score read, on the second stream's route alone.
+enum : unsigned {
+    PCL_REC_AFTER_FETCH = 1,     // the recursion rewrites buffers pcl_batch_fetch_async copies from: the main stream, and stream_dp (after_fetch), go behind pending copies
+    PCL_REC_JOIN_ON_MAIN = 2,    // main-stream route: batch_join first (Viterbi)
+    PCL_REC_RETIRES_MARK = 4     // main-stream route: ev_mark is no longer the scoring's event, mark_is_score goes (forward-backward, Viterbi)
+};
+template <typename Launch>
+static inline int pcl_run_recursion(pcl_batch *b, unsigned how, Launch launch) {
+    pcl_ctx *ctx = b->ctx;
+    const bool after_fetch = (how & PCL_REC_AFTER_FETCH) && b->fetch_pending;
+    if (after_fetch) {
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_fetch, 0));
+        b->fetch_pending = false;
+    }
+    if (ctx->dp_async) return pcl_run_on_dp_stream(b, after_fetch, launch);
+    if (how & PCL_REC_JOIN_ON_MAIN) TRY(batch_join(b));
+    TRY(launch());
+    HIPCHK(ctx, pcl_batch_mark(b));
+    if (how & PCL_REC_RETIRES_MARK) b->mark_is_score = false;
+    return PCL_OK;
 }
 void pcl_timer_begin(pcl_ctx *ctx, const char *which);
 void pcl_timer_end(pcl_ctx *ctx, const char *which);
@@ -573,7 +602,7 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
                               const int32_t *state_class, int J);
 void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (the next pcl_lda_zero)
 void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; the next pcl_cmvn_zero)
-// tree_cluster.hip, for pcl_batch_accumulate_tree (pcl_api.hip).  pcl_tree_accumulate_ready: statistics made, frames loaded, at the statistics'
+// tree_cluster.hip, for pcl_batch_accumulate_tree (pcl_batch.hip).  pcl_tree_accumulate_ready: statistics made, frames loaded, at the statistics'
 // width.  pcl_launch_tree_label_rows: the batch's owner map (d_frame_state, unit * P + slice) and the caller's label position -> event list
 // (d_label_event, on the device) -> the statistics row of every frame (d_frame_row, set to -1 before); queued on ctx->stream.
 // pcl_launch_tree_accumulate: behind the checks of both accumulate entries; d_src (rows of the frame matrix, on the device) = the
@@ -585,7 +614,7 @@ void pcl_tree_release(pcl_ctx *ctx);                 // the tree statistics (the
 // tying.hip.  pcl_launch_tied_label_states, for pcl_batch_create_labels_tied (hmm_units.hip): the batch's labels and their offsets go to the
 // device (d_labels / d_label_off), one walk per (label position, k) of the resident tying fills b->pos_state and the row -> state map, which
 // comes back to the host (row_state, sum N entries) for pcl_batch_set_states_impl's bookkeeping.  Complete on return.
-// pcl_launch_tied_owner, for the label-based entry points (pcl_api.hip): d_frame_state holds pcl_launch_align_segments' owner map of the
+// pcl_launch_tied_owner, for the label-based entry points (pcl_batch.hip): d_frame_state holds pcl_launch_align_segments' owner map of the
 // batch (unit * P + slice, -1 = not kept); every kept frame's entry becomes pos_state[i * P + slice], i = the label position of its path row.
 // Queued on ctx->stream.
 int pcl_launch_tied_label_states(pcl_ctx *ctx, pcl_batch *b, int32_t *row_state);

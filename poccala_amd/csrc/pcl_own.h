@@ -39,7 +39,7 @@ int pcl_ctx_device(const pcl_ctx *ctx);
         if (_r != PCL_OK) return _r; \
     } while (0)
 
-// Device memory comes from a process-wide caching pool (pcl_api.hip): hipMalloc / hipFree cost 0.1-1 ms each and hipFree
+// Device memory comes from a process-wide caching pool (pcl_pool.hip): hipMalloc / hipFree cost 0.1-1 ms each and hipFree
 // waits for the whole device, which a library that creates and drops a batch per utterance (the drop-in classes) or per
 // chunk (streaming) cannot afford.  A freed block goes back to the pool; dev_free first waits for the device, as hipFree
 // did, unless the caller has already made sure the GPU is done with the block (pcl_free_synced_scope).

@@ -2,7 +2,7 @@
 // questions, the tied-state map, and a one-Gaussian-per-leaf seed model written where the model lives.
 //   pcl_tree_zero               the context's statistics n (R) int64, s (R, D), q (R, D) made and cleared: ONE pool block of 8 R (2 D + 1) bytes
 //   pcl_tree_accumulate         a host map frame row -> statistics row -> the statistics
-//   pcl_batch_accumulate_tree   the batch's Viterbi owner map and the caller's label position -> event list (pcl_api.hip runs the alignment;
+//   pcl_batch_accumulate_tree   the batch's Viterbi owner map and the caller's label position -> event list (pcl_batch.hip runs the alignment;
 //                               the map never leaves the device) -> the statistics
 //   pcl_tree_stats_shape / pcl_tree_stats_download / pcl_tree_stats_upload
 //   pcl_tree_build              greedy growth; optionally the (J_t, 1, D) model

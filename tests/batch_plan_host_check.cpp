@@ -1,7 +1,7 @@
-// Stand-alone check of the batch planners of poccala_amd/csrc/batch_plan.h (plan_batch_shape, plan_sparse_trans with both of its row
-// enumerators, plan_score, plan_tiles, plan_labels) against a stub context.  Built with the host sanitizers and run as its own process by
-// tests/test_batch_plan_host.py: exit status 0 and no sanitizer report = pass.  Expected values are written out by hand or computed by the
-// naive restatements below (dense double scans, per-state searches), never by the code under test.
+// Stand-alone check of the batch planners of poccala_amd/csrc/batch_plan.h (plan_batch_shape with shape_overlap and shape_fits_frames,
+// plan_sparse_trans with both of its row enumerators, plan_score, plan_tiles, plan_labels) against a stub context.  Built with the host
+// sanitizers and run as its own process by tests/test_batch_plan_host.py: exit status 0 and no sanitizer report = pass.  Expected values
+// are written out by hand or computed by the naive restatements below (dense double scans, per-state searches), never by the code under test.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -264,6 +264,44 @@ static void check_shape(pcl_ctx *ctx) {
     }
 }
 
+// the checks of a planned shape against the frame matrix: every utterance one row of the HMM, ranges [begin, begin + T)
+static UttOverlap overlap_of(pcl_ctx *ctx, const std::vector<int64_t> &begin, const std::vector<int32_t> &T) {
+    const std::vector<int32_t> N(T.size(), 1);
+    BatchShape s;
+    CHECK(plan_batch_shape(ctx, (int)T.size(), N.data(), T.data(), begin.data(), 1000, &s) == PCL_OK);
+    return shape_overlap(s);
+}
+static bool is_pair(UttOverlap o, int first, int second) { return o.found && o.first == first && o.second == second; }
+
+static void check_ranges(pcl_ctx *ctx) {
+    CHECK(!shape_overlap(BatchShape()).found);                                   // empty batch
+    CHECK(!overlap_of(ctx, {7}, {5}).found);                                     // one utterance
+    CHECK(!overlap_of(ctx, {0, 5, 9}, {5, 4, 1}).found);                         // touching: end == next begin
+    CHECK(is_pair(overlap_of(ctx, {0, 4, 9}, {5, 5, 1}), 0, 1));                 // one row shared (row 4)
+    CHECK(is_pair(overlap_of(ctx, {0, 5, 9}, {5, 5, 1}), 1, 2));                 // ... further on (row 9)
+    CHECK(is_pair(overlap_of(ctx, {3, 3}, {4, 4}), 0, 1));                       // identical ranges
+    CHECK(is_pair(overlap_of(ctx, {20, 6, 6}, {2, 9, 1}), 1, 2));                // equal first rows: the lower index is `first`, whatever the lengths
+    CHECK(is_pair(overlap_of(ctx, {20, 6, 6}, {2, 1, 9}), 1, 2));
+    CHECK(!overlap_of(ctx, {30, 0, 20, 10}, {5, 10, 10, 10}).found);             // not in row order: disjoint ...
+    CHECK(is_pair(overlap_of(ctx, {30, 0, 20, 10}, {5, 10, 11, 10}), 2, 0));     // ... and utterance 2 running into utterance 0, a row later
+    CHECK(is_pair(overlap_of(ctx, {30, 0, 20, 10}, {5, 11, 11, 10}), 1, 3));     // two overlaps: the one at the lower rows is reported
+    CHECK(is_pair(overlap_of(ctx, {0, 2, 5}, {10, 1, 1}), 0, 1));                // an utterance inside another
+    {   // a batch made without frames (frame0 = -1): nothing precedes the first utterance
+        const int32_t N[2] = {1, 1}, T[2] = {3, 3};
+        BatchShape s;
+        CHECK(plan_batch_shape(ctx, 2, N, T, nullptr, 0, &s) == PCL_OK);
+        CHECK(is_pair(shape_overlap(s), -1, 0));
+    }
+    {   // the rows the batch refers to against a matrix of F rows
+        const int32_t N[2] = {1, 1}, T[2] = {3, 4};
+        const int64_t fb[2] = {6, 0};
+        BatchShape s;
+        CHECK(plan_batch_shape(ctx, 2, N, T, fb, 9, &s) == PCL_OK && s.max_frame_end == 9);
+        CHECK(shape_fits_frames(s, 9) && shape_fits_frames(s, 10) && !shape_fits_frames(s, 8) && !shape_fits_frames(s, 0));
+        CHECK(shape_fits_frames(BatchShape(), 0));
+    }
+}
+
 static void check_sparse(pcl_ctx *ctx) {
     const double a = -0.1, b = -0.2, c = -0.3, d = -0.4, e = -0.5;
     BatchShape sh;
@@ -507,6 +545,7 @@ int main() {
     static_assert(sizeof(UttDesc) == 48 && sizeof(ScoreSeg) == 32 && sizeof(DupRow) == 24 && sizeof(ScoreTile) == 20, "the descriptors as the kernels read them");
     pcl_ctx ctx;
     check_shape(&ctx);
+    check_ranges(&ctx);
     check_sparse(&ctx);
     check_states(&ctx);
     check_tiles_cases(&ctx);

@@ -628,6 +628,44 @@ def test_cabi_error_codes(eng):
         eng.batch([0], [5])
 
 
+def test_exchange_refusals_name_their_entry_point():
+    """pcl_batch_accumulate_exchange and pcl_accumulate_exchange_idle refuse the same things of the context in the same words, each under
+    its own name, before the pipe is opened: the model stays as it was, and the batch's next exchange runs."""
+    from poccala_amd import PCL_F64, Engine, PoccalaHipError
+    INVALID, STATE = -1, -3
+    rng = np.random.default_rng(3)
+    eng = Engine(0)                                                  # (its own context: no units uploaded, no communicator)
+    try:
+        eng.load_model(rng.standard_normal((2, 2, 13)), np.ones((2, 2, 13)), np.ones((2, 2)) / 2)
+        eng.load_frames(rng.standard_normal((21, 13)))
+        b = eng.batch([4, 4], [9, 12], [0, 9])
+        b.set_states([np.array([-1, 0, 1, -2], dtype=np.int32)] * 2)
+        a = np.array([[0, 1, 0, 0], [0, .5, .5, 0], [0, 0, .5, .5], [0, 0, 0, 0.]])
+        with np.errstate(divide='ignore'):
+            b.set_transitions([np.log(a)] * 2, [np.log(np.array([1., 0, 0, 0]))] * 2)
+        eng.stats_zero()
+        b.score(PCL_F64)
+        b.forward_backward()
+        before = eng.model_download()
+        entries = (('pcl_batch_accumulate_exchange', lambda **kw: b.accumulate_exchange(PCL_F64, 1e-3, **kw)),
+                   ('pcl_accumulate_exchange_idle', lambda **kw: eng.accumulate_exchange_idle(1e-3, **kw)))
+        for who, call in entries:
+            for code, text, kw in ((INVALID, 'payload 7', dict(payload=7)), (INVALID, 'n_chunks 0', dict(n_chunks=0)), (INVALID, 'n_chunks -2', dict(n_chunks=-2)),
+                                   (STATE, 'update_transitions without pcl_units_upload', dict(update_transitions=True))):
+                with pytest.raises(PoccalaHipError) as ei:
+                    call(**kw)
+                print(ei.value)
+                assert ei.value.code == code and str(ei.value) == 'libpoccala_hip: %s: %s (status %d)' % (who, text, code)
+        for x, y in zip(before, eng.model_download()):
+            assert np.array_equal(x, y)
+        b.accumulate_exchange(PCL_F64, 1e-3, n_chunks=2)
+        after = eng.model_download()
+        assert all(np.isfinite(x).all() for x in after) and not np.array_equal(before[0], after[0])
+        b.close()
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------ ill-conditioned states leave the matrix-core path
 def mixed_conditioning_model(seed, units=3, M=64, D=39):
     """Every unit's middle state is hard for the centred f32 expansion (means spread over 5 sigma, small variances,

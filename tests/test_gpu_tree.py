@@ -409,5 +409,40 @@ def test_refusals_of_the_batch_entry(eng):
     b.close()
 
 
+def test_a_refused_batch_entry_leaves_the_batch_to_the_other_owner_map_pass(eng):
+    """pcl_batch_accumulate_tree and pcl_batch_align_segments make the same owner map of the batch's paths.  A call of the first that is
+    refused for its own argument says so in these words, and the next call on the same batch -- the other pass -- makes the whole map;
+    the tree pass then counts exactly the frames that map gives an owner."""
+    from poccala_amd import PCL_F64, synth
+    from poccala_amd.AcousticModel.ContextTree import triphone_events
+    S, n_units, D = 5, 2, 13
+    P = S - 2
+    labels = [[0], [1, 0]]
+    T, begin, F = np.array([8, 12], dtype=np.int32), np.array([0, 8], dtype=np.int64), 20
+    rng = np.random.default_rng(10)
+    mean, var, w, _ = synth.make_model(n_units, 2, D, seed=44, s=S)
+    eng.load_model(mean, var, w)
+    eng.load_units(np.stack([synth.random_left_right_transmat(rng, S) for _ in range(n_units)]))
+    eng.load_frames(rng.standard_normal((F, D)))
+    event_ctx, label_event = triphone_events(labels, n_units)
+    E = len(event_ctx)
+    assert (label_event >= 0).all()
+    eng.tree_zero(E * P)
+    b = eng.label_batch([np.asarray(l, dtype=np.int32) for l in labels], T, begin)
+    b.score(PCL_F64)
+    b.viterbi()
+    bad = label_event.copy()
+    bad[1] = E
+    refused(eng, INVALID, 'pcl_batch_accumulate_tree: label_event[1] = %d is neither -1 nor an event in [0, %d)' % (E, E), lambda: b.accumulate_tree(bad))
+    seg, dropped, state = b.align_segments(want_map=True)
+    kept = int((state >= 0).sum())
+    print('owner map after the refusal: %d of %d frames kept, dropped %s' % (kept, F, dropped))
+    assert state.shape == (F,) and int(seg.counts.sum()) == kept and 0 < kept <= F and (state < n_units * P).all()
+    seg.close()
+    b.accumulate_tree(label_event)
+    assert int(eng.tree_stats()[0].sum()) == kept
+    b.close()
+
+
 def drive_build(eng, c):
     return eng.tree_build(c['event_ctx'], c['P'], c['n_units'], c['q_member'], c['root_of'], n_roots=c['R0'])

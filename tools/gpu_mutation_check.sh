@@ -1,7 +1,7 @@
 #!/bin/bash
 # The mutation builds: the library with a known, fixed bug restored must FAIL the test that guards the fix.  Build them HERE first:
 #   tools/build_variant.sh lseflush "-DPCL_LSE_FLUSH_REPRO -fno-slp-vectorize" gmm_score_split.hip gmm_score_mfma.hip
-#   tools/build_variant.sh race "-DPCL_DESC_RACE_REPRO" pcl_api.hip hmm_units.hip
+#   tools/build_variant.sh race "-DPCL_DESC_RACE_REPRO" pcl_batch.hip hmm_units.hip
 #   tools/build_variant.sh coarsemargin "-DPCL_COARSE_MARGIN_REPRO" gmm_score_coarse.hip      (round 6: the coarse pass rules out pairs that matter)
 #   tools/build_variant.sh coarselast "-DPCL_COARSE_LASTSTAGE_REPRO" gmm_score_coarse.hip      (a give-up in the coarse pass's last stage drops its tiles)
 #   tools/build_variant.sh coarseclamp "-DPCL_COARSE_CLAMP_REPRO" gmm_score_coarse.hip         (pairs ruled out under a clamped threshold stand)
