@@ -59,7 +59,7 @@ def check_outputs(out, raw, lag, rate, lmin, what):
 def against_the_twin(sigs, rate, what, **kw):
     from poccala_amd.StatisticalModel.AudioProcessing import pitch_batch
     rows, info = pitch_batch(sigs, rate, details=True, **kw)
-    tw = {k: kw[k] for k in ('f_min', 'f_max', 'ballast', 'soft_min_f0', 'pf') if k in kw}
+    tw = {k: kw[k] for k in ('sampletime', 'overlap', 'f_min', 'f_max', 'ballast', 'soft_min_f0', 'pf') if k in kw}
     for u, x in enumerate(sigs):
         ref = pt.pitch(x, rate, **tw)
         tag = '%s utterance %d' % (what, u)
