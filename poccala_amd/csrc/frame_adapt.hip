@@ -133,7 +133,7 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
         if (utt_speaker[u] >= 0 && b->shape.utt[u].frame0 < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: utterance %d has no frames (the batch was made without frame_begin)", who, u);
     // virtual frame order: speakers ascending, a speaker's utterances in batch order; a speaker's frames cut into chunks
     const long long chunk = std::min<long long>(mllr_chunk(), 1 << 30);
-    std::vector<int> vbase(U, -1), spk_v0(S + 1, 0), spk_frames(S, 0), spk_chunk0, chunk_v0, chunk_n;
+    std::vector<int> vbase(U, -1), spk_v0(S + 1, 0), spk_frames(S, 0);
     long long V = 0;
     for (int s = 0; s < S; ++s) {
         spk_v0[s] = (int)V;
@@ -146,29 +146,22 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
     }
     spk_v0[S] = (int)V;                                           // (V <= sum T < 2^31: pcl_batch_create)
     if (V == 0) return PCL_OK;
-    plan_chunks(spk_frames, chunk, &spk_chunk0, &chunk_v0, &chunk_n);
-    const int C = (int)chunk_v0.size();
+    ChunkLists plan;                                              // one upload: [vbase | spk_v0 | spk_chunk0 | chunk_v0 | chunk_n]
+    plan.plan({&vbase, &spk_v0}, spk_frames, chunk);
+    const int C = plan.C;
     const int NT = (Dh + 2 + 15) / 16, ntiles = NT * (NT + 1) / 2;
     if ((long long)C * Dh > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: %d chunks x %d dimensions do not fit a grid: raise PCL_MLLR_CHUNK", who, C, Dh);
-    std::vector<int> lists;                                       // one upload: [vbase | spk_v0 | spk_chunk0 | chunk_v0 | chunk_n]
-    const size_t o_v0 = U, o_chunk0 = o_v0 + S + 1, o_cv0 = o_chunk0 + S + 1, o_cn = o_cv0 + C;
-    lists.insert(lists.end(), vbase.begin(), vbase.end());
-    lists.insert(lists.end(), spk_v0.begin(), spk_v0.end());
-    lists.insert(lists.end(), spk_chunk0.begin(), spk_chunk0.end());
-    lists.insert(lists.end(), chunk_v0.begin(), chunk_v0.end());
-    lists.insert(lists.end(), chunk_n.begin(), chunk_n.end());
 
     hipStream_t st = ctx->stream;
-    DevBuf<int> d_lists;
     DevBuf<double> d_P, d_Q, d_B, d_partial;
     DevBuf<long long> d_vrow;
-    TRY(d_lists.alloc(ctx, lists.size()));
+    TRY(plan.upload(ctx));
+    const int *d_lists = plan.d_lists;
     TRY(d_P.alloc(ctx, (size_t)V * Dh));
     TRY(d_Q.alloc(ctx, (size_t)V * Dh));
     TRY(d_B.alloc(ctx, (size_t)V));
     TRY(d_vrow.alloc(ctx, (size_t)V));
     TRY(d_partial.alloc(ctx, (size_t)C * Dh * ntiles * 256));
-    HIPCHK(ctx, pcl_h2d(ctx, d_lists, lists.data(), lists.size() * sizeof(int)));
 
     pcl_timer_begin(ctx, "fmllr");                               // the whole call's kernels; "fmllr_frames" / "fmllr_gk": its two halves
     pcl_timer_begin(ctx, "fmllr_frames");
@@ -186,12 +179,12 @@ int pcl_launch_fmllr_accumulate(pcl_ctx *ctx, pcl_batch *b, const int32_t *utt_s
         }
 #undef FRAMES_CASE
     }
-    hipLaunchKernelGGL(fmllr_beta_kernel, dim3(S), dim3(256), 0, st, d_B, d_lists + o_v0, ctx->fmllr_beta);
+    hipLaunchKernelGGL(fmllr_beta_kernel, dim3(S), dim3(256), 0, st, d_B, d_lists + U, ctx->fmllr_beta);
     pcl_timer_end(ctx, "fmllr_frames");
     pcl_timer_begin(ctx, "fmllr_gk");
-    FrameSrc g{ctx->frames64, ctx->frames32, d_vrow, d_P, d_Q, d_lists + o_cv0, d_lists + o_cn, ctx->FD, Dh};
+    FrameSrc g{ctx->frames64, ctx->frames32, d_vrow, d_P, d_Q, plan.chunk_v0(), plan.chunk_n(), ctx->FD, Dh};
     launch_gk(mllr_use_valu(), NT, C * Dh, st, g, d_partial);
-    hipLaunchKernelGGL(gk_reduce_kernel, dim3(S * Dh), dim3(256), 0, st, d_partial, d_lists + o_chunk0, Dh, NT, ctx->fmllr_Gk, true);
+    hipLaunchKernelGGL(gk_reduce_kernel, dim3(S * Dh), dim3(256), 0, st, d_partial, plan.chunk0(), Dh, NT, ctx->fmllr_Gk, true);
     pcl_timer_end(ctx, "fmllr_gk");
     pcl_timer_end(ctx, "fmllr");
     HIPCHK(ctx, hipGetLastError());

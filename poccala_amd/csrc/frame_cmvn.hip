@@ -314,31 +314,11 @@ int cmvn_check_ranges(pcl_ctx *ctx, const char *who, int U, const int32_t *T, co
     return spans_check(ctx, who, "a frame is normalised ONCE", U, T, frame_begin, Tmax_out);
 }
 
-int cmvn_ready(pcl_ctx *ctx, const char *who) {
-    if (!ctx->cmvn_sq || ctx->cmvn_S <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no statistics: pcl_cmvn_zero first", who);
-    if (ctx->FDhost != ctx->cmvn_D)
-        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the statistics were made for %d-dimensional frames; the frame matrix now has %d dimensions: pcl_cmvn_zero again", who,
-                 ctx->cmvn_D, ctx->FDhost);
-    return PCL_OK;
-}
-
 // the sliding form's rows per group of utterances (env PCL_CMVN_GROUP_ROWS, read on every call): the prefix block of a group holds
 // 2 x rows x D doubles.  Default: 2^28 / D rows (4 GiB).  The result does not depend on it.
-long long cmvn_group_rows(int Dh) {
-    if (const char *e = getenv("PCL_CMVN_GROUP_ROWS")) {
-        const long long v = atoll(e);
-        if (v > 0) return v;
-    }
-    return (1ll << 28) / Dh;
-}
+long long cmvn_group_rows(int Dh) { return env_positive_ll("PCL_CMVN_GROUP_ROWS", (1ll << 28) / Dh); }
 
 }  // namespace
-
-void pcl_cmvn_release(pcl_ctx *ctx) {
-    ctx->cmvn_n.release();
-    ctx->cmvn_sq.release();
-    ctx->cmvn_S = ctx->cmvn_D = 0;
-}
 
 extern "C" int pcl_cmvn_zero(pcl_ctx *ctx, int S) {
     if (!ctx) return PCL_ERR_INVALID;
@@ -347,14 +327,13 @@ extern "C" int pcl_cmvn_zero(pcl_ctx *ctx, int S) {
     if (S < 1 || S > 65535) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: S = %d speakers, need 1 .. 65535", who, S);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int Dh = ctx->FDhost;
-    pcl_cmvn_release(ctx);
-    TRY(ctx->cmvn_n.alloc(ctx, (size_t)S));
-    TRY(ctx->cmvn_sq.alloc(ctx, (size_t)S * 2 * Dh));
-    ctx->cmvn_S = S;
-    ctx->cmvn_D = Dh;
-    HIPCHK(ctx, hipMemsetAsync(ctx->cmvn_n, 0, (size_t)S * sizeof(long long), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->cmvn_sq, 0, (size_t)S * 2 * Dh * sizeof(double), ctx->stream));
+    CmvnStats fresh{{}, {}, S, Dh};                               // the statistics in place stay until the new set is there and cleared
+    TRY(fresh.n.alloc(ctx, (size_t)S));
+    TRY(fresh.sq.alloc(ctx, (size_t)S * 2 * Dh));
+    HIPCHK(ctx, hipMemsetAsync(fresh.n, 0, (size_t)S * sizeof(long long), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(fresh.sq, 0, (size_t)S * 2 * Dh * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cmvn = std::move(fresh);
     return PCL_OK;
 }
 
@@ -363,8 +342,8 @@ extern "C" int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
     const char *who = "pcl_cmvn_accumulate";
     int Tmax = 0;
     TRY(cmvn_check_ranges(ctx, who, U, T, frame_begin, &Tmax));
-    TRY(cmvn_ready(ctx, who));
-    const int S = ctx->cmvn_S, Dh = ctx->cmvn_D;
+    TRY(stats_fits(ctx, who, ctx->cmvn));
+    const int S = ctx->cmvn.S, Dh = ctx->cmvn.D;
     TRY(speakers_check(ctx, who, U, utt_speaker, S));
     // per utterance the offset of its chunks' partials; per speaker the list of its utterances with frames, ascending
     std::vector<long long> choff(U, 0);
@@ -402,8 +381,8 @@ extern "C" int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
     pcl_timer_begin(ctx, "cmvn_stats");
     hipLaunchKernelGGL(cmvn_partial_kernel, dim3((unsigned)((Tspk + CH_ROWS - 1) / CH_ROWS), (unsigned)U), dim3(256), 0, st, d.T, d.begin, d.spk, d_choff,
                        ctx->frames64.p, ctx->frames32, ctx->FD, Dh, d_partial.p);
-    hipLaunchKernelGGL(cmvn_speaker_kernel, dim3((unsigned)S), dim3(128), 0, st, d.T, d_choff, d_lists.p, d_lists.p + o_list, d_partial.p, Dh, ctx->cmvn_n.p,
-                       ctx->cmvn_sq.p);
+    hipLaunchKernelGGL(cmvn_speaker_kernel, dim3((unsigned)S), dim3(128), 0, st, d.T, d_choff, d_lists.p, d_lists.p + o_list, d_partial.p, Dh, ctx->cmvn.n.p,
+                       ctx->cmvn.sq.p);
     pcl_timer_end(ctx, "cmvn_stats");
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));                        // (the locals above are free to go)
@@ -413,17 +392,17 @@ extern "C" int pcl_cmvn_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
 extern "C" int pcl_cmvn_stats_download(pcl_ctx *ctx, int64_t *n, double *s, double *q) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_cmvn_stats_download";
-    TRY(cmvn_ready(ctx, who));
-    const int S = ctx->cmvn_S, Dh = ctx->cmvn_D;
+    TRY(stats_fits(ctx, who, ctx->cmvn));
+    const int S = ctx->cmvn.S, Dh = ctx->cmvn.D;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (n) {
         static_assert(sizeof(long long) == sizeof(int64_t), "n travels as it is held");
-        HIPCHK(ctx, hipMemcpyAsync(n, ctx->cmvn_n, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(n, ctx->cmvn.n, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (s || q) {
         std::vector<double> host((size_t)S * 2 * Dh);
-        HIPCHK(ctx, hipMemcpyAsync(host.data(), ctx->cmvn_sq, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(host.data(), ctx->cmvn.sq, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         for (int sp = 0; sp < S; ++sp) {
             if (s) memcpy(s + (size_t)sp * Dh, &host[((size_t)sp * 2) * Dh], (size_t)Dh * sizeof(double));
@@ -439,12 +418,12 @@ extern "C" int pcl_frames_cmvn(pcl_ctx *ctx, int U, const int32_t *T, const int6
     const char *who = "pcl_frames_cmvn";
     int Tmax = 0;
     TRY(cmvn_check_ranges(ctx, who, U, T, frame_begin, &Tmax));
-    TRY(cmvn_ready(ctx, who));
-    if (S != ctx->cmvn_S) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: S = %d speakers, the resident statistics hold %d", who, S, ctx->cmvn_S);
+    TRY(stats_fits(ctx, who, ctx->cmvn));
+    if (S != ctx->cmvn.S) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: S = %d speakers, the resident statistics hold %d", who, S, ctx->cmvn.S);
     TRY(speakers_check(ctx, who, U, utt_speaker, S));
     if (norm_vars && !(var_floor > 0.0 && std::isfinite(var_floor))) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: var_floor = %g is not a finite number > 0", who, var_floor);
     if (min_count < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: min_count = %lld, need at least 1", who, (long long)min_count);
-    const int Dh = ctx->cmvn_D, FD = ctx->FD;
+    const int Dh = ctx->cmvn.D, FD = ctx->FD;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     DevSpans d;
@@ -454,7 +433,7 @@ extern "C" int pcl_frames_cmvn(pcl_ctx *ctx, int U, const int32_t *T, const int6
     TRY(d_status.alloc(ctx, (size_t)S));
     TRY(d_ms.alloc(ctx, (size_t)S * 2 * Dh));
     pcl_timer_begin(ctx, "cmvn_apply");
-    hipLaunchKernelGGL(cmvn_decide_kernel, dim3((unsigned)S), dim3(64), 0, st, ctx->cmvn_n.p, ctx->cmvn_sq.p, Dh, (long long)min_count,
+    hipLaunchKernelGGL(cmvn_decide_kernel, dim3((unsigned)S), dim3(64), 0, st, ctx->cmvn.n.p, ctx->cmvn.sq.p, Dh, (long long)min_count,
                        norm_vars ? var_floor : 0.0, d_status.p, d_ms.p);
     if (Tmax > 0) {
         if (ctx->frames64) {

@@ -6,11 +6,10 @@
 //   pcl_frames_splice_project  y = b + A splice(x) into new buffers that replace the resident frame matrix (another width)
 //   pcl_frames_download        the resident frames as held, unpadded
 // The rule and every operation order are stated in include/poccala_hip.h; tests/_lda_twin.py is its NumPy twin.  The statistics are one
-// product [x | 1][x | 1]^T per class in float64: the kept rows are counting-sorted by class (gmm_segment.hip's histogram / scan / stable
-// scatter), a class's rows are cut into K-chunks of PCL_LDA_CHUNK rows that never straddle a class, one workgroup per (chunk, tile group)
-// forms the chunk's upper-triangular 16 x 16 tiles on v_mfma_f64_16x16x4_f64 (or on the VALU under PCL_LDA_VALU=1), and the chunks'
-// partials are added onto the running statistics in chunk order.  No floating-point atomics: two runs give the same bits.  Built with
-// -ffp-contract=off: the projection runs one rounded operation at a time.
+// product [x | 1][x | 1]^T per class in float64: frame_keyed.h's pass sorts the kept rows by class and cuts a class's rows into
+// K-chunks of PCL_LDA_CHUNK rows, one workgroup per (chunk, tile group) forms the chunk's upper-triangular 16 x 16 tiles on
+// v_mfma_f64_16x16x4_f64 (or on the VALU under PCL_LDA_VALU=1), and the chunks' partials are added onto the running statistics in chunk
+// order.  No floating-point atomics: two runs give the same bits.  Built with -ffp-contract=off: the projection runs one rounded operation at a time.
 // Every index a kernel forms is bounded by what the host validated: classes < R, rows < F, a spliced row inside its utterance's
 // [lo, hi) within [0, F), operand columns < 16 NT <= 128, output columns < D_out <= the new row stride.
 #include <math.h>
@@ -19,7 +18,8 @@
 
 namespace {
 
-#include "frame_spans.h"                      // the checks and the upload of a call's utterances, the chunk plan
+#include "frame_spans.h"                      // the checks and the upload of a call's utterances and row labels, the chunk plan
+#include "frame_keyed.h"                      // the keys, the counting sort and the chunks of the kept rows
 
 constexpr int LDA_N_MAX = 128;                // order Ds + 1 of the statistics: 8 x 8 tiles of 16
 constexpr int KB = 32;                        // K-elements (rows) staged in LDS per step: 8 MFMA k-steps, two per wave
@@ -37,20 +37,6 @@ bool lda_use_valu() {                         // env PCL_LDA_VALU=1 (read on eve
 }
 
 __device__ __forceinline__ int lda_tile_index(int tp, int tq, int NT) { return tp * NT - tp * (tp - 1) / 2 + (tq - tp); }
-
-// key[g] = the class of row g (-1: not kept), span[g] = the utterance's rows [lo, hi): one thread per (utterance, frame).  src: the class
-// of every row, or (state_class given) its owner state, mapped here.  key was set to -1 everywhere before.
-__global__ __launch_bounds__(256) void lda_key_kernel(const int *__restrict__ T, const long long *__restrict__ begin, const int *__restrict__ src,
-                                                      const int *__restrict__ state_class, int *__restrict__ key, int2 *__restrict__ span) {
-    const int u = blockIdx.y, Tu = T[u];
-    const long long lo = begin[u];
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < Tu; t += gridDim.x * 256) {
-        int c = src[lo + t];
-        if (c >= 0 && state_class) c = state_class[c];
-        key[lo + t] = c;
-        span[lo + t] = int2{(int)lo, (int)lo + Tu};
-    }
-}
 
 // What the product kernels read: the sorted rows, their utterances' spans, the frames, the splice.
 struct LdaSrc {
@@ -252,23 +238,13 @@ __global__ __launch_bounds__(256) void lda_project_kernel(const int *__restrict_
 
 // T / frame_begin of a call: inside the frame matrix, disjoint (a row has ONE utterance: its splice clamps are the utterance's)
 int lda_check_ranges(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, int *Tmax_out) {
-    TRY(spans_args_check(ctx, who, U, T, frame_begin));           // (before the frames, as it always was here: the status of a call with both defects)
+    TRY(spans_args_check(ctx, who, U, T, frame_begin));           // (before the frames: the order of the LDA launcher's row in pcl_internal.h's table)
     TRY(frames_loaded_check(ctx, who));
     if (ctx->F > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame matrix of %lld rows", who, (long long)ctx->F);
     return spans_check(ctx, who, "a frame is spliced inside ONE utterance", U, T, frame_begin, Tmax_out);
 }
 
-const char *lda_ready(pcl_ctx *ctx) {         // nullptr, or why the statistics cannot be used
-    if (!ctx->lda_stats || ctx->lda_R <= 0) return "no statistics: pcl_lda_zero first";
-    return nullptr;
-}
-
 }  // namespace
-
-void pcl_lda_release(pcl_ctx *ctx) {
-    ctx->lda_stats.release();
-    ctx->lda_R = ctx->lda_left = ctx->lda_right = ctx->lda_D = 0;
-}
 
 extern "C" int pcl_lda_zero(pcl_ctx *ctx, int R, int left, int right) {
     if (!ctx) return PCL_ERR_INVALID;
@@ -284,14 +260,11 @@ extern "C" int pcl_lda_zero(pcl_ctx *ctx, int R, int left, int right) {
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: R = %d classes, need 1 .. min(65535, 2^32 / %llu bytes per class = %llu)", who, R, per, (1ull << 32) / per);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t len = (size_t)R * (Ds + 1) * (Ds + 1);
-    pcl_lda_release(ctx);
-    TRY(ctx->lda_stats.alloc(ctx, len));
-    ctx->lda_R = R;
-    ctx->lda_left = left;
-    ctx->lda_right = right;
-    ctx->lda_D = D;
-    HIPCHK(ctx, hipMemsetAsync(ctx->lda_stats, 0, len * sizeof(double), ctx->stream));
+    LdaStats fresh{{}, R, left, right, D};                        // the statistics in place stay until the new set is there and cleared
+    TRY(fresh.stats.alloc(ctx, len));
+    HIPCHK(ctx, hipMemsetAsync(fresh.stats, 0, len * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->lda = std::move(fresh);
     return PCL_OK;
 }
 
@@ -299,11 +272,9 @@ extern "C" int pcl_lda_zero(pcl_ctx *ctx, int R, int left, int right) {
 // J entries on the host, validated here) an owner state in [-1, J).  Rows outside the U utterances are not kept.
 int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src,
                               const int32_t *state_class, int J) {
-    if (const char *why = lda_ready(ctx)) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: %s", who, why);
-    const int R = ctx->lda_R, D = ctx->lda_D, left = ctx->lda_left, Ds = (ctx->lda_left + ctx->lda_right + 1) * D, n = Ds + 1;
-    if (ctx->FDhost != D)
-        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the statistics were made for context (%d, %d) of %d-dimensional frames (order %d); the frame matrix now has %d dimensions: pcl_lda_zero again",
-                 who, left, ctx->lda_right, D, n, ctx->FDhost);
+    const LdaStats &lda = ctx->lda;
+    TRY(stats_fits(ctx, who, lda));
+    const int R = lda.R, n = lda.n();
     int Tmax = 0;
     TRY(lda_check_ranges(ctx, who, U, T, frame_begin, &Tmax));
     if (state_class)
@@ -312,43 +283,21 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
     if (Tmax == 0) return PCL_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const long long F = ctx->F;
-    DevSpans d;
-    DevBuf<int> d_sc, d_key, d_order, d_lists;
-    DevBuf<int2> d_span;
+    DevBuf<int> d_sc;
+    KeyedRows rows;
     DevBuf<double> d_partial;
-    TRY(d.upload(ctx, U, T, frame_begin, nullptr));
-    TRY(d_key.alloc(ctx, (size_t)F));
-    TRY(d_span.alloc(ctx, (size_t)F));
     if (state_class) {
         TRY(d_sc.alloc(ctx, (size_t)J));
         HIPCHK(ctx, pcl_h2d(ctx, d_sc, state_class, (size_t)J * sizeof(int32_t)));
     }
-    pcl_timer_begin(ctx, "lda_sort");                            // pcl_kernel_time groups: "lda_sort" (keys and counting sort), "lda_stats" (product and reduction)
-    HIPCHK(ctx, hipMemsetAsync(d_key, 0xff, (size_t)F * sizeof(int), st));
-    hipLaunchKernelGGL(lda_key_kernel, dim3((unsigned)std::min(64, (Tmax + 255) / 256), (unsigned)U), dim3(256), 0, st, d.T, d.begin, d_src,
-                       state_class ? d_sc.p : nullptr, d_key, d_span);
-    std::vector<int> counts;
-    const int rc = pcl_count_sort_device(ctx, F, R, d_key, &counts, &d_order);
-    pcl_timer_end(ctx, "lda_sort");
-    TRY(rc);
-    // chunks of one class each, classes ascending
-    const long long chunk = lda_chunk();
-    std::vector<int> cls_chunk0, chunk_v0, chunk_n;
-    plan_chunks(counts, chunk, &cls_chunk0, &chunk_v0, &chunk_n);
-    const int C = (int)chunk_v0.size();
+    TRY(rows.build<true>(ctx, "lda_sort", U, T, frame_begin, Tmax, d_src, d_sc.p, R, lda_chunk()));
+    const int C = rows.C;
     if (C == 0) return PCL_OK;
+    const std::vector<int> &cls_chunk0 = rows.group_chunk0;
     const int NT = (n + 15) / 16, ntiles = NT * (NT + 1) / 2;
-    std::vector<int> lists;                                       // one upload: [cls_chunk0 | chunk_v0 | chunk_n]
-    const size_t o_cv0 = R + 1, o_cn = o_cv0 + C;
-    lists.insert(lists.end(), cls_chunk0.begin(), cls_chunk0.end());
-    lists.insert(lists.end(), chunk_v0.begin(), chunk_v0.end());
-    lists.insert(lists.end(), chunk_n.begin(), chunk_n.end());
-    TRY(d_lists.alloc(ctx, lists.size()));
     TRY(d_partial.alloc(ctx, (size_t)std::min(C, LDA_ROUND) * ntiles * 256));
-    HIPCHK(ctx, pcl_h2d(ctx, d_lists, lists.data(), lists.size() * sizeof(int)));
-    pcl_timer_begin(ctx, "lda_stats");
-    const LdaSrc g{ctx->frames64, ctx->frames32, d_order, d_span, d_lists + o_cv0, d_lists + o_cn, ctx->FD, D, left, Ds};
+    pcl_timer_begin(ctx, "lda_stats");                           // pcl_kernel_time groups: "lda_sort" (keys and counting sort), "lda_stats" (product and reduction)
+    const LdaSrc g{ctx->frames64, ctx->frames32, rows.d_order, rows.d_span, rows.chunk_v0(), rows.chunk_n(), ctx->FD, lda.D, lda.left, lda.Ds()};
     const bool valu = lda_use_valu();
     int r_lo = 0;
     for (int c0 = 0; c0 < C; c0 += LDA_ROUND) {                   // (the rounds add in the same chunk order as one launch would)
@@ -358,7 +307,7 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
         while (r_hi + 1 < R && cls_chunk0[r_hi + 1] < c1) ++r_hi;
         launch_lda(valu, NT, c1 - c0, c0, st, g, d_partial);
         hipLaunchKernelGGL(lda_reduce_kernel, dim3((unsigned)(r_hi - r_lo + 1), (unsigned)std::min(8, (n * n + 255) / 256)), dim3(256), 0, st, d_partial,
-                           d_lists.p, r_lo, c0, c1, n, NT, ctx->lda_stats.p);
+                           rows.chunk0(), r_lo, c0, c1, n, NT, lda.stats.p);
     }
     pcl_timer_end(ctx, "lda_stats");
     HIPCHK(ctx, hipGetLastError());
@@ -369,27 +318,20 @@ int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_
 extern "C" int pcl_lda_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *frame_class) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_lda_accumulate";
-    if (const char *why = lda_ready(ctx)) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: %s", who, why);
-    if (!frame_class) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame_class is NULL", who);
-    if (!ctx->frames32 || ctx->F <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no frames loaded", who);
-    for (int64_t f = 0; f < ctx->F; ++f)
-        if (frame_class[f] < -1 || frame_class[f] >= ctx->lda_R)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame_class[%lld] = %d is neither -1 nor a class in [0, %d)", who, (long long)f, (int)frame_class[f], ctx->lda_R);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TRY(stats_have(ctx, who, ctx->lda));
     DevBuf<int32_t> d_cls;
-    TRY(d_cls.alloc(ctx, (size_t)ctx->F));
-    HIPCHK(ctx, pcl_h2d(ctx, d_cls, frame_class, (size_t)ctx->F * sizeof(int32_t)));
+    TRY(upload_row_labels(ctx, who, "frame_class", "class", frame_class, ctx->lda.R, &d_cls));
     return pcl_launch_lda_accumulate(ctx, who, U, T, frame_begin, d_cls, nullptr, 0);
 }
 
 extern "C" int pcl_lda_stats_download(pcl_ctx *ctx, double *n_out, double *s_out, double *S_out) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_lda_stats_download";
-    if (const char *why = lda_ready(ctx)) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: %s", who, why);
-    const int R = ctx->lda_R, Ds = (ctx->lda_left + ctx->lda_right + 1) * ctx->lda_D, n = Ds + 1;
+    TRY(stats_have(ctx, who, ctx->lda));
+    const int R = ctx->lda.R, Ds = ctx->lda.Ds(), n = ctx->lda.n();
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<double> host((size_t)R * n * n);
-    HIPCHK(ctx, hipMemcpyAsync(host.data(), ctx->lda_stats, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(host.data(), ctx->lda.stats, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int r = 0; r < R; ++r) {
         const double *src = &host[(size_t)r * n * n];

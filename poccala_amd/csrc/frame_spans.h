@@ -1,7 +1,8 @@
 // What every entry point that walks utterances of the resident frame matrix says once: the checks of a call's (U, T, frame_begin,
-// utt_speaker), their upload, the cut of groups of rows into chunks, and the reader of a chunk length from the environment.  Host code
-// only.  Included inside the including file's unnamed namespace, so it includes nothing itself: the including file has pcl_ctx (F,
-// frames32), DevBuf, pcl_h2d, <algorithm> and <vector> in sight (pcl_internal.h; tests/frame_spans_host_check.cpp brings a stub of its
+// utt_speaker), their upload, the check and upload of a label per frame row, the cut of groups of rows into chunks and its one packed
+// list, and the reader of a chunk length from the environment.  Host code only (frame_keyed.h: the keyed pass that ends in a chunk plan).
+// Included inside the including file's unnamed namespace, so it includes nothing itself: the including file has pcl_ctx (device,
+// F, frames32), DevBuf, pcl_h2d, <algorithm> and <vector> in sight (pcl_internal.h; tests/frame_spans_host_check.cpp brings a stub of its
 // own and runs these under the host sanitizers).
 #pragma once
 
@@ -84,4 +85,48 @@ static void plan_chunks(const std::vector<int> &counts, long long chunk, std::ve
         V += counts[g];
         (*group_chunk0)[g + 1] = (int)chunk_v0->size();
     }
+}
+
+// A chunk plan as ONE list for one upload, behind whatever lists the caller puts in front: [prefix ... | group_chunk0 (groups + 1) |
+// chunk_v0 (C) | chunk_n (C)].  group_chunk0 stays on the host as well; the three on the device after upload().
+struct ChunkLists {
+    std::vector<int> lists, group_chunk0;
+    size_t o_chunk0 = 0, o_cv0 = 0, o_cn = 0;
+    int C = 0;
+    DevBuf<int> d_lists;
+    const int *chunk0() const { return d_lists.p + o_chunk0; }
+    const int *chunk_v0() const { return d_lists.p + o_cv0; }
+    const int *chunk_n() const { return d_lists.p + o_cn; }
+    void plan(std::initializer_list<const std::vector<int> *> prefix, const std::vector<int> &counts, long long chunk) {
+        std::vector<int> v0, n;
+        plan_chunks(counts, chunk, &group_chunk0, &v0, &n);
+        C = (int)v0.size();
+        lists.clear();
+        for (const std::vector<int> *p : prefix) lists.insert(lists.end(), p->begin(), p->end());
+        o_chunk0 = lists.size();
+        o_cv0 = o_chunk0 + group_chunk0.size();
+        o_cn = o_cv0 + C;
+        lists.insert(lists.end(), group_chunk0.begin(), group_chunk0.end());
+        lists.insert(lists.end(), v0.begin(), v0.end());
+        lists.insert(lists.end(), n.begin(), n.end());
+    }
+    int upload(pcl_ctx *ctx) {
+        TRY(d_lists.alloc(ctx, lists.size()));
+        HIPCHK(ctx, pcl_h2d(ctx, d_lists, lists.data(), lists.size() * sizeof(int)));
+        return PCL_OK;
+    }
+};
+
+// A caller's label of every row of the frame matrix (`name`, F entries) onto the device: not NULL, frames loaded (F is theirs), every entry
+// -1 (the row is not kept) or a `noun` in [0, R); the first offender is the one named.
+static int upload_row_labels(pcl_ctx *ctx, const char *who, const char *name, const char *noun, const int32_t *labels, int R, DevBuf<int32_t> *d_out) {
+    if (!labels) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: %s is NULL", who, name);
+    TRY(frames_loaded_check(ctx, who));
+    for (int64_t f = 0; f < ctx->F; ++f)
+        if (labels[f] < -1 || labels[f] >= R)
+            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: %s[%lld] = %d is neither -1 nor a %s in [0, %d)", who, name, (long long)f, (int)labels[f], noun, R);
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    TRY(d_out->alloc(ctx, (size_t)ctx->F));
+    HIPCHK(ctx, pcl_h2d(ctx, *d_out, labels, (size_t)ctx->F * sizeof(int32_t)));
+    return PCL_OK;
 }

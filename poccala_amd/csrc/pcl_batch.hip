@@ -571,10 +571,10 @@ int pcl_batch_accumulate_lda(pcl_batch *b, const int32_t *state_class) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
     const char *who = "pcl_batch_accumulate_lda";
-    if (!ctx->lda_stats || ctx->lda_R <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no statistics: pcl_lda_zero first", who);
+    TRY(stats_have(ctx, who, ctx->lda));
     TRY(align_precheck(b, who));
-    if (!state_class && ctx->J > ctx->lda_R)
-        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: state_class is NULL (every state its own class) but the model has %d states and the statistics %d classes", who, ctx->J, ctx->lda_R);
+    if (!state_class && ctx->J > ctx->lda.R)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: state_class is NULL (every state its own class) but the model has %d states and the statistics %d classes", who, ctx->J, ctx->lda.R);
     TRY(batch_join(b));
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // tied owners: state_class maps the model's states
@@ -592,9 +592,9 @@ int pcl_batch_accumulate_tree(pcl_batch *b, const int32_t *label_event) {
     TRY(pcl_tree_accumulate_ready(ctx, who));
     TRY(align_precheck(b, who));
     const int P = ctx->S - 2;
-    if (ctx->tree_R % P != 0)
-        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the statistics hold %d rows, no multiple of the inventory's %d emitting states per unit", who, ctx->tree_R, P);
-    const int E = ctx->tree_R / P;
+    if (ctx->tree.R % P != 0)
+        PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: the statistics hold %d rows, no multiple of the inventory's %d emitting states per unit", who, ctx->tree.R, P);
+    const int E = ctx->tree.R / P;
     if (!label_event) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: label_event is NULL", who);
     for (size_t i = 0; i < b->lab.labels.size(); ++i)
         if (label_event[i] < -1 || label_event[i] >= E)

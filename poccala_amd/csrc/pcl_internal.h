@@ -140,6 +140,41 @@ struct TyingDev {
     DevBuf<int> ty_root;                          // [n_units * P] root_of
 };
 
+// The three resident statistics sets of the frame rows.  Each is made and cleared by its pcl_*_zero (frames loaded: the set takes its width
+// D from the frame matrix then) and goes with the next pcl_*_zero that SUCCEEDS and with pcl_destroy, with nothing else: a zero that is
+// refused or fails leaves the set in place as it was.  Release is `ctx->lda = {}`.  An entry point asks a set one of two questions, in one
+// form (below pcl_ctx): have, was it made, and fits, was it made and at the frame matrix's CURRENT width.  An entry's checks in order:
+//   pcl_lda_accumulate          have, frame_class NULL, frames loaded, labels in [-1, R) | the LDA launcher's
+//   pcl_batch_accumulate_lda    have, the batch (align_precheck), state_class NULL with J > R | the LDA launcher's
+//   the LDA launcher            fits, U / NULL lists, frames loaded, F < 2^31, the spans, state_class in [-1, R)
+//   pcl_tree_accumulate         have, frames loaded, fits, F < 2^31 (pcl_tree_accumulate_ready), frame_row NULL, labels in [-1, R) | the spans
+//   pcl_batch_accumulate_tree   pcl_tree_accumulate_ready, the batch, R % P, label_event | the spans
+//   pcl_cmvn_accumulate         frames loaded, the spans, fits, the speakers (pcl_frames_cmvn: fits, S, the speakers, the rest); the downloads: have (CMVN's: fits)
+struct LdaStats {                                 // frame_lda.hip: [R][n][n], the upper triangle of sum [x | 1][x | 1]^T over the class's spliced rows
+    static constexpr const char *rule = "lda";
+    DevBuf<double> stats;
+    int R = 0, left = 0, right = 0, D = 0;
+    bool have() const { return stats && R > 0; }
+    int Ds() const { return (left + right + 1) * D; }
+    int n() const { return Ds() + 1; }
+};
+struct CmvnStats {                                // frame_cmvn.hip: n [S] rows, sq [S][2][D] = (sum x | sum x^2)
+    static constexpr const char *rule = "cmvn";
+    DevBuf<long long> n;
+    DevBuf<double> sq;
+    int S = 0, D = 0;
+    bool have() const { return sq && S > 0; }
+};
+struct TreeStats {                                // tree_cluster.hip: ONE block [n (R) int64 | s (R, D) | q (R, D)]
+    static constexpr const char *rule = "tree";
+    DevBuf<double> stats;
+    int R = 0, D = 0;
+    bool have() const { return stats && R > 0; }
+    long long *n() const { return reinterpret_cast<long long *>(stats.p); }
+    double *s() const { return stats.p + R; }
+    double *q() const { return stats.p + (size_t)R * (1 + D); }
+};
+
 // The context's own streams (the int16 front-end's staging stream lives with its buffers, PcmStage::stream; pcl_ctx::streams() lists all seven).
 struct CtxStreams {
     Stream stream_main;          // the owner of the main stream; launchers read the VIEW pcl_ctx::stream, which pcl_stream_scope redirects
@@ -205,19 +240,9 @@ struct pcl_ctx : CtxStreams, ModelDev, CoarseDev, UnitsDev, LexiconDev, TyingDev
     // What was made ON the current frame matrix and is alive for the caller (pcl_batch_create .. pcl_batch_destroy, pcl_seg_create ..
     // pcl_seg_destroy): pcl_frames_splice_project changes the matrix's width under an unchanged row count and refuses while any is left
     int live_batches = 0, live_segs = 0;
-    // LDA class statistics (frame_lda.hip): [lda_R][n][n], n = (lda_left + lda_right + 1) lda_D + 1, the upper triangle of sum [x | 1][x | 1]^T
-    // over the class's spliced rows; lda_D = the frame dimension pcl_lda_zero saw.  Freed by pcl_destroy and by the next pcl_lda_zero.
-    DevBuf<double> lda_stats;
-    int lda_R = 0, lda_left = 0, lda_right = 0, lda_D = 0;
-    // CMVN speaker statistics (frame_cmvn.hip): cmvn_n [cmvn_S] rows, cmvn_sq [cmvn_S][2][cmvn_D] = (sum x | sum x^2); cmvn_D = the frame
-    // dimension pcl_cmvn_zero saw.  Freed by pcl_destroy and by the next pcl_cmvn_zero.
-    DevBuf<long long> cmvn_n;
-    DevBuf<double> cmvn_sq;
-    int cmvn_S = 0, cmvn_D = 0;
-    // Decision-tree context statistics (tree_cluster.hip): ONE block [n (tree_R) int64 | s (tree_R, tree_D) | q (tree_R, tree_D)]; tree_D = the
-    // frame dimension pcl_tree_zero saw.  Freed by pcl_destroy and by the next pcl_tree_zero.
-    DevBuf<double> tree_stats;
-    int tree_R = 0, tree_D = 0;
+    LdaStats lda;                      // the statistics sets of the frame rows (above): each goes with its next pcl_*_zero and with pcl_destroy
+    CmvnStats cmvn;
+    TreeStats tree;
     // streaming: two frame slots (grow only); pcl_frames_stage copies the next chunk into the slot that is not current on stream_aux,
     // pcl_frames_swap makes it current
     DevBuf<float> frames_slot[2];
@@ -600,17 +625,34 @@ void pcl_accumulate_release(pcl_ctx *ctx);           // the context's accumulate
 // class of every row, or with state_class (host, J entries) its owner state; -1 = not kept
 int pcl_launch_lda_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src,
                               const int32_t *state_class, int J);
-void pcl_lda_release(pcl_ctx *ctx);                  // the LDA statistics (the next pcl_lda_zero)
-void pcl_cmvn_release(pcl_ctx *ctx);                 // the CMVN statistics (frame_cmvn.hip; the next pcl_cmvn_zero)
-// tree_cluster.hip, for pcl_batch_accumulate_tree (pcl_batch.hip).  pcl_tree_accumulate_ready: statistics made, frames loaded, at the statistics'
-// width.  pcl_launch_tree_label_rows: the batch's owner map (d_frame_state, unit * P + slice) and the caller's label position -> event list
+// Readiness of a statistics set (LdaStats, CmvnStats, TreeStats), one form for all three: PCL_OK, or `who` fails with the message
+template <typename Set>
+static inline int stats_have(pcl_ctx *ctx, const char *who, const Set &set) {
+    if (!set.have()) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no statistics: pcl_%s_zero first", who, Set::rule);
+    return PCL_OK;
+}
+template <typename Set>
+static inline int stats_fits(pcl_ctx *ctx, const char *who, const Set &set) {
+    TRY(stats_have(ctx, who, set));
+    if (ctx->FDhost != set.D)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the statistics were made for %d-dimensional frames; the frame matrix now has %d dimensions: pcl_%s_zero again", who, set.D,
+                 ctx->FDhost, Set::rule);
+    return PCL_OK;
+}
+static inline int stats_fits(pcl_ctx *ctx, const char *who, const LdaStats &set) {   // (a set that has a context to name as well)
+    TRY(stats_have(ctx, who, set));
+    if (ctx->FDhost != set.D)
+        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the statistics were made for context (%d, %d) of %d-dimensional frames (order %d); the frame matrix now has %d dimensions: pcl_lda_zero again",
+                 who, set.left, set.right, set.D, set.n(), ctx->FDhost);
+    return PCL_OK;
+}
+// tree_cluster.hip, for pcl_batch_accumulate_tree (pcl_batch.hip).  pcl_tree_accumulate_ready: its row of the table at LdaStats.
+// pcl_launch_tree_label_rows: the batch's owner map (d_frame_state, unit * P + slice) and the caller's label position -> event list
 // (d_label_event, on the device) -> the statistics row of every frame (d_frame_row, set to -1 before); queued on ctx->stream.
-// pcl_launch_tree_accumulate: behind the checks of both accumulate entries; d_src (rows of the frame matrix, on the device) = the
-// statistics row of every frame row in [-1, R); waits for its kernels.
+// pcl_launch_tree_accumulate: behind the checks of both entries; d_src (F entries on the device) = per frame row a statistics row in [-1, R).
 int pcl_tree_accumulate_ready(pcl_ctx *ctx, const char *who);
 int pcl_launch_tree_label_rows(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_label_event, int P, const int32_t *d_frame_state, int32_t *d_frame_row);
 int pcl_launch_tree_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src);
-void pcl_tree_release(pcl_ctx *ctx);                 // the tree statistics (the next pcl_tree_zero)
 // tying.hip.  pcl_launch_tied_label_states, for pcl_batch_create_labels_tied (hmm_units.hip): the batch's labels and their offsets go to the
 // device (d_labels / d_label_off), one walk per (label position, k) of the resident tying fills b->pos_state and the row -> state map, which
 // comes back to the host (row_state, sum N entries) for pcl_batch_set_states_impl's bookkeeping.  Complete on return.

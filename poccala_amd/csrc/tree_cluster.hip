@@ -8,9 +8,9 @@
 //   pcl_tree_build              greedy growth; optionally the (J_t, 1, D) model
 // The rule and every summation order are stated in include/poccala_hip.h; tests/_tree_twin.py is its NumPy twin.  Everything is float64;
 // no floating-point atomics: two runs give the same bits.  Built with -ffp-contract=off: every kernel runs one rounded operation at a time.
-// STATISTICS: the kept frame rows are counting-sorted by statistics row (gmm_segment.hip's histogram / scan / stable scatter), a row's
-// frames are cut into chunks of PCL_TREE_CHUNK that never straddle a row, a group of 64 / G lanes adds a chunk's frames in ascending
-// order from 0 (G columns a lane, one 16-byte load a frame), and the chunks' partials are added onto the resident sums in chunk order.
+// STATISTICS: frame_keyed.h's pass sorts the kept frame rows by statistics row and cuts a row's frames into chunks of PCL_TREE_CHUNK,
+// a group of 64 / G lanes adds a chunk's frames in ascending order from 0 (G columns a lane, one 16-byte load a frame), and the chunks'
+// partials are added onto the resident sums in chunk order.
 // BUILD: the rows of a leaf are a segment of ONE device list, ascending; an evaluation workgroup owns (leaf, 8 candidates) and walks the
 // segment once, lane j adding column j of [s | q] onto the yes- or the no-sum of each of its candidates under the event's answer bit --
 // the masked product of the issue in its VALU form: adding +0.0 leaves a sum's bits, so a side's sum IS the sum of its rows in ascending
@@ -26,7 +26,8 @@
 
 namespace {
 
-#include "frame_spans.h"                      // the checks and the upload of a call's utterances, the chunk plan
+#include "frame_spans.h"                      // the checks and the upload of a call's utterances and row labels, the chunk plan
+#include "frame_keyed.h"                      // the keys, the counting sort and the chunks of the kept rows
 
 constexpr long long TREE_CHUNK_DEFAULT = 256; // frames per chunk of a statistics row
 constexpr int CG = 8;                         // candidates per evaluation workgroup: one answer byte per (event, group)
@@ -37,14 +38,6 @@ constexpr double ONE_PLUS_LN_2PI = 2.8378770664093453;   // 1 + ln 2 pi, the dou
 
 // Chunk length in frames, env PCL_TREE_CHUNK, read on EVERY call (as PCL_MLLR_CHUNK is): tests force several chunks on a small input.
 long long tree_chunk() { return std::min<long long>(env_positive_ll("PCL_TREE_CHUNK", TREE_CHUNK_DEFAULT), 1 << 30); }
-
-// key[g] = the statistics row of frame row g for the rows of the U utterances; key was set to -1 everywhere before.
-__global__ __launch_bounds__(256) void tree_key_kernel(const int *__restrict__ T, const long long *__restrict__ begin, const int *__restrict__ src,
-                                                       int *__restrict__ key) {
-    const int u = blockIdx.y, Tu = T[u];
-    const long long lo = begin[u];
-    for (int t = blockIdx.x * 256 + threadIdx.x; t < Tu; t += gridDim.x * 256) key[lo + t] = src[lo + t];
-}
 
 // Source (b): frame_state = the owner map of pcl_batch_align_segments (unit * P + slice, -1: not kept, a dropped utterance).  The label
 // position of a frame is the one its path row belongs to (hmm_align_segments_kernel's row -> position map), its slice the owner map's.
@@ -257,29 +250,13 @@ __global__ __launch_bounds__(256) void tree_install_kernel(const int *__restrict
     if (d == 0) w64[(size_t)jt * Mpad + m] = m == 0 ? 1.0 : 0.0;
 }
 
-long long *tree_n(pcl_ctx *ctx) { return reinterpret_cast<long long *>(ctx->tree_stats.p); }
-double *tree_s(pcl_ctx *ctx) { return ctx->tree_stats.p + ctx->tree_R; }
-double *tree_q(pcl_ctx *ctx) { return ctx->tree_stats.p + (size_t)ctx->tree_R * (1 + ctx->tree_D); }
-
-int tree_have(pcl_ctx *ctx, const char *who) {
-    if (!ctx->tree_stats || ctx->tree_R <= 0) PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no statistics: pcl_tree_zero first", who);
-    return PCL_OK;
-}
-
 }  // namespace
-
-void pcl_tree_release(pcl_ctx *ctx) {
-    ctx->tree_stats.release();
-    ctx->tree_R = ctx->tree_D = 0;
-}
 
 // What both accumulate entries need of the context, in the order the header states: statistics, frames, their width
 int pcl_tree_accumulate_ready(pcl_ctx *ctx, const char *who) {
-    TRY(tree_have(ctx, who));
+    TRY(stats_have(ctx, who, ctx->tree));
     TRY(frames_loaded_check(ctx, who));
-    if (ctx->FDhost != ctx->tree_D)
-        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: the statistics were made for %d-dimensional frames; the frame matrix now has %d dimensions: pcl_tree_zero again", who,
-                 ctx->tree_D, ctx->FDhost);
+    TRY(stats_fits(ctx, who, ctx->tree));
     if (ctx->F > 0x7fffffffLL) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame matrix of %lld rows", who, (long long)ctx->F);
     return PCL_OK;
 }
@@ -292,52 +269,33 @@ int pcl_launch_tree_label_rows(pcl_ctx *ctx, pcl_batch *b, const int32_t *d_labe
     return PCL_OK;
 }
 
-// Both accumulate entries behind their checks: d_src (F entries on the device) holds per frame row a statistics row in [-1, R).  Rows
-// outside the U utterances are not kept.  The utterances are checked HERE, once for either entry, before anything is queued.  Waits for
-// its kernels.
+// Both accumulate entries behind their checks: d_src (F entries on the device) holds per frame row a statistics row in [-1, R).  Rows outside
+// the U utterances are not kept.  The utterances are checked HERE, once for either entry, before anything is queued.  Waits for its kernels.
 int pcl_launch_tree_accumulate(pcl_ctx *ctx, const char *who, int U, const int32_t *T, const int64_t *frame_begin, const int32_t *d_src) {
     int Tmax = 0;
     TRY(spans_check(ctx, who, "a frame is counted ONCE", U, T, frame_begin, &Tmax));
     if (Tmax == 0) return PCL_OK;
-    const int R = ctx->tree_R, Dh = ctx->tree_D;
+    const TreeStats &tree = ctx->tree;
+    const int R = tree.R, Dh = tree.D;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const long long F = ctx->F;
-    DevSpans d;
-    DevBuf<int> d_key, d_order, d_lists;
+    KeyedRows rows;
     DevBuf<double> d_partial;
-    TRY(d.upload(ctx, U, T, frame_begin, nullptr));
-    TRY(d_key.alloc(ctx, (size_t)F));
-    pcl_timer_begin(ctx, "tree_sort");                           // pcl_kernel_time groups: "tree_sort" (keys and counting sort), "tree_stats" (partials and reduction)
-    HIPCHK(ctx, hipMemsetAsync(d_key, 0xff, (size_t)F * sizeof(int), st));
-    hipLaunchKernelGGL(tree_key_kernel, dim3((unsigned)std::min(64, (Tmax + 255) / 256), (unsigned)U), dim3(256), 0, st, d.T.p, d.begin.p, d_src, d_key.p);
-    std::vector<int> counts;
-    const int rc = pcl_count_sort_device(ctx, F, R, d_key, &counts, &d_order);
-    pcl_timer_end(ctx, "tree_sort");
-    TRY(rc);
-    std::vector<int> row_chunk0, chunk_v0, chunk_n;
-    plan_chunks(counts, tree_chunk(), &row_chunk0, &chunk_v0, &chunk_n);
-    const int C = (int)chunk_v0.size();
+    TRY(rows.build<false>(ctx, "tree_sort", U, T, frame_begin, Tmax, d_src, nullptr, R, tree_chunk()));
+    const int C = rows.C;
     if (C == 0) return PCL_OK;
-    std::vector<int> lists;                                       // one upload: [row_chunk0 | chunk_v0 | chunk_n]
-    const size_t o_cv0 = (size_t)R + 1, o_cn = o_cv0 + C;
-    lists.insert(lists.end(), row_chunk0.begin(), row_chunk0.end());
-    lists.insert(lists.end(), chunk_v0.begin(), chunk_v0.end());
-    lists.insert(lists.end(), chunk_n.begin(), chunk_n.end());
-    TRY(d_lists.alloc(ctx, lists.size()));
     TRY(d_partial.alloc(ctx, (size_t)C * 2 * Dh));
-    HIPCHK(ctx, pcl_h2d(ctx, d_lists, lists.data(), lists.size() * sizeof(int)));
-    pcl_timer_begin(ctx, "tree_stats");
-    const long long n_elems = F * ctx->FD;
+    pcl_timer_begin(ctx, "tree_stats");                          // pcl_kernel_time groups: "tree_sort" (keys and counting sort), "tree_stats" (partials and reduction)
+    const long long n_elems = ctx->F * ctx->FD;
     if (ctx->frames64)
         hipLaunchKernelGGL((tree_partial_kernel<double, 2>), dim3((unsigned)((C + 7) / 8)), dim3(256), 0, st, (const double *)ctx->frames64.p, n_elems, ctx->FD, Dh,
-                           d_order.p, d_lists.p + o_cv0, d_lists.p + o_cn, C, d_partial.p);
+                           rows.d_order.p, rows.chunk_v0(), rows.chunk_n(), C, d_partial.p);
     else
         hipLaunchKernelGGL((tree_partial_kernel<float, 4>), dim3((unsigned)((C + 15) / 16)), dim3(256), 0, st, (const float *)ctx->frames32, n_elems, ctx->FD, Dh,
-                           d_order.p, d_lists.p + o_cv0, d_lists.p + o_cn, C, d_partial.p);
+                           rows.d_order.p, rows.chunk_v0(), rows.chunk_n(), C, d_partial.p);
     const long long cells = (long long)R * (2 * Dh + 1);
-    hipLaunchKernelGGL(tree_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, d_partial.p, d_lists.p, d_lists.p + o_cn, R, Dh, tree_n(ctx),
-                       tree_s(ctx), tree_q(ctx));
+    hipLaunchKernelGGL(tree_reduce_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, d_partial.p, rows.chunk0(), rows.chunk_n(), R, Dh, tree.n(),
+                       tree.s(), tree.q());
     pcl_timer_end(ctx, "tree_stats");
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));                        // (the locals above are free to go)
@@ -354,13 +312,11 @@ extern "C" int pcl_tree_zero(pcl_ctx *ctx, int R) {
         PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: R = %d rows, need 1 .. 2^32 / %llu bytes per row = %llu", who, R, per, (1ull << 32) / per);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t len = (size_t)R * (2 * D + 1);
-    DevBuf<double> fresh;                                         // the statistics in place stay until the new block is there and cleared
-    TRY(fresh.alloc(ctx, len));
-    HIPCHK(ctx, hipMemsetAsync(fresh, 0, len * sizeof(double), ctx->stream));
+    TreeStats fresh{{}, R, D};                                    // the statistics in place stay until the new set is there and cleared
+    TRY(fresh.stats.alloc(ctx, len));
+    HIPCHK(ctx, hipMemsetAsync(fresh.stats, 0, len * sizeof(double), ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tree_stats = std::move(fresh);
-    ctx->tree_R = R;
-    ctx->tree_D = D;
+    ctx->tree = std::move(fresh);
     return PCL_OK;
 }
 
@@ -368,35 +324,28 @@ extern "C" int pcl_tree_accumulate(pcl_ctx *ctx, int U, const int32_t *T, const 
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_tree_accumulate";
     TRY(pcl_tree_accumulate_ready(ctx, who));
-    if (!frame_row) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame_row is NULL", who);
-    for (int64_t f = 0; f < ctx->F; ++f)
-        if (frame_row[f] < -1 || frame_row[f] >= ctx->tree_R)
-            PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: frame_row[%lld] = %d is neither -1 nor a row in [0, %d)", who, (long long)f, (int)frame_row[f], ctx->tree_R);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     DevBuf<int32_t> d_row;                                        // (the utterances are checked by the launcher, before anything resident is touched)
-    TRY(d_row.alloc(ctx, (size_t)ctx->F));
-    HIPCHK(ctx, pcl_h2d(ctx, d_row, frame_row, (size_t)ctx->F * sizeof(int32_t)));
+    TRY(upload_row_labels(ctx, who, "frame_row", "row", frame_row, ctx->tree.R, &d_row));
     return pcl_launch_tree_accumulate(ctx, who, U, T, frame_begin, d_row);
 }
 
 extern "C" int pcl_tree_stats_shape(pcl_ctx *ctx, int32_t *R, int32_t *D) {
     if (!ctx) return PCL_ERR_INVALID;
-    const bool have = ctx->tree_stats && ctx->tree_R > 0;
-    if (R) *R = have ? ctx->tree_R : 0;
-    if (D) *D = have ? ctx->tree_D : 0;
+    if (R) *R = ctx->tree.R;                                      // (0, 0 without statistics: a set is made and dropped as a whole)
+    if (D) *D = ctx->tree.D;
     return PCL_OK;
 }
 
 extern "C" int pcl_tree_stats_download(pcl_ctx *ctx, int64_t *n, double *s, double *q) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_tree_stats_download";
-    TRY(tree_have(ctx, who));
+    TRY(stats_have(ctx, who, ctx->tree));
     static_assert(sizeof(long long) == sizeof(int64_t), "n travels as it is held");
-    const size_t R = (size_t)ctx->tree_R, RD = R * ctx->tree_D;
+    const size_t R = (size_t)ctx->tree.R, RD = R * ctx->tree.D;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (n) HIPCHK(ctx, hipMemcpyAsync(n, tree_n(ctx), R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (s) HIPCHK(ctx, hipMemcpyAsync(s, tree_s(ctx), RD * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (q) HIPCHK(ctx, hipMemcpyAsync(q, tree_q(ctx), RD * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(n, ctx->tree.n(), R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (s) HIPCHK(ctx, hipMemcpyAsync(s, ctx->tree.s(), RD * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (q) HIPCHK(ctx, hipMemcpyAsync(q, ctx->tree.q(), RD * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }
@@ -404,17 +353,17 @@ extern "C" int pcl_tree_stats_download(pcl_ctx *ctx, int64_t *n, double *s, doub
 extern "C" int pcl_tree_stats_upload(pcl_ctx *ctx, const int64_t *n, const double *s, const double *q) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_tree_stats_upload";
-    TRY(tree_have(ctx, who));
+    TRY(stats_have(ctx, who, ctx->tree));
     if (!n || !s || !q) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: n, s or q is NULL", who);
-    const size_t R = (size_t)ctx->tree_R, RD = R * ctx->tree_D;
+    const size_t R = (size_t)ctx->tree.R, RD = R * ctx->tree.D;
     for (size_t r = 0; r < R; ++r)
         if (n[r] < 0) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: n[%zu] = %lld is negative", who, r, (long long)n[r]);
     for (size_t x = 0; x < RD; ++x)
         if (!std::isfinite(s[x]) || !std::isfinite(q[x])) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: s[%zu] = %g, q[%zu] = %g: not finite", who, x, s[x], x, q[x]);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    HIPCHK(ctx, pcl_h2d(ctx, tree_n(ctx), n, R * sizeof(int64_t)));
-    HIPCHK(ctx, pcl_h2d(ctx, tree_s(ctx), s, RD * sizeof(double)));
-    HIPCHK(ctx, pcl_h2d(ctx, tree_q(ctx), q, RD * sizeof(double)));
+    HIPCHK(ctx, pcl_h2d(ctx, ctx->tree.n(), n, R * sizeof(int64_t)));
+    HIPCHK(ctx, pcl_h2d(ctx, ctx->tree.s(), s, RD * sizeof(double)));
+    HIPCHK(ctx, pcl_h2d(ctx, ctx->tree.q(), q, RD * sizeof(double)));
     return PCL_OK;
 }
 
@@ -424,8 +373,8 @@ extern "C" int pcl_tree_build(pcl_ctx *ctx, int E, int P, const int32_t *event_c
                               double *leaf_s, double *leaf_q, int32_t *n_nodes_out, int32_t *n_states_out) {
     if (!ctx) return PCL_ERR_INVALID;
     const char *who = "pcl_tree_build";
-    TRY(tree_have(ctx, who));
-    const int R = ctx->tree_R, Dh = ctx->tree_D;
+    TRY(stats_have(ctx, who, ctx->tree));
+    const int R = ctx->tree.R, Dh = ctx->tree.D;
     if (E < 1 || P < 1 || (long long)E * P != R) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: E = %d events x P = %d positions, the statistics hold %d rows", who, E, P, R);
     if (n_units < 1) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: n_units = %d", who, n_units);
     if (Q < 1 || 3 * (long long)Q > TREE_Q_MAX) PCL_FAIL(ctx, PCL_ERR_INVALID, "%s: Q = %d questions, need 1 <= Q and 3 Q <= %d", who, Q, TREE_Q_MAX);
@@ -511,7 +460,7 @@ extern "C" int pcl_tree_build(pcl_ctx *ctx, int E, int P, const int32_t *event_c
         for (int i = first; i < first + count; ++i) batch.push_back(EvalLeaf{nodes[i].lo, nodes[i].hi, i, 0});
         HIPCHK(ctx, pcl_h2d(ctx, d_leaves, batch.data(), batch.size() * sizeof(EvalLeaf)));
         pcl_timer_begin(ctx, "tree_build");
-        hipLaunchKernelGGL(tree_eval_kernel, dim3((unsigned)count, (unsigned)NCB), dim3(EVAL_T), 0, st, d_leaves.p, d_rows.p, tree_n(ctx), tree_s(ctx), tree_q(ctx), Dh,
+        hipLaunchKernelGGL(tree_eval_kernel, dim3((unsigned)count, (unsigned)NCB), dim3(EVAL_T), 0, st, d_leaves.p, d_rows.p, ctx->tree.n(), ctx->tree.s(), ctx->tree.q(), Dh,
                            P, d_ansb.p, NCB, NC, (long long)min_count, min_gain, var_floor, d_gbest.p, d_node_n.p, d_node_sq.p);
         hipLaunchKernelGGL(tree_best_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, st, d_gbest.p, count, NCB, d_best.p);
         pcl_timer_end(ctx, "tree_build");

@@ -1,5 +1,5 @@
-// Stand-alone check of the host helpers of poccala_amd/csrc/frame_spans.h (spans_check, speakers_check, DevSpans, plan_chunks,
-// env_positive_ll) against a stub context and a malloc-backed stub pool.  Built with the host sanitizers and run as its own process by
+// Stand-alone check of the host helpers of poccala_amd/csrc/frame_spans.h (spans_check, speakers_check, DevSpans, plan_chunks, ChunkLists,
+// upload_row_labels, env_positive_ll) against a stub context and a malloc-backed stub pool.  Built with the host sanitizers and run as its own process by
 // tests/test_frame_spans_host.py: exit status 0 and no sanitizer report = pass.  Every expected value is written out by hand.
 #include <stdint.h>
 #include <stdio.h>
@@ -41,6 +41,8 @@ static hipError_t pcl_h2d(pcl_ctx *, void *dst, const void *src, size_t bytes) {
     memcpy(dst, src, bytes);
     return hipSuccess;
 }
+
+#define hipSetDevice(device) ((void)(device), hipSuccess)            // (the stub pool has no device to set)
 
 namespace {
 #include "../poccala_amd/csrc/frame_spans.h"
@@ -139,6 +141,48 @@ int main() {
         plan_chunks({}, 50, &g0, &v0, &n);
         CHECK((g0 == std::vector<int>{0}) && v0.empty() && n.empty());
     }
+    {   // the plan as one list: R + 1 group offsets, then C and C entries, behind nothing and behind two prefix lists; uploaded as it is
+        ChunkLists p;
+        p.plan({}, {0, 50, 51, 7}, 50);
+        CHECK(p.C == 4 && p.o_chunk0 == 0 && p.o_cv0 == 5 && p.o_cn == 9);
+        CHECK((p.lists == std::vector<int>{0, 0, 1, 3, 4, 0, 50, 100, 101, 50, 50, 1, 7}) && (p.group_chunk0 == std::vector<int>{0, 0, 1, 3, 4}));
+        CHECK(p.upload(&ctx) == PCL_OK && g_live.size() == 1 && p.d_lists.cap == 13);
+        CHECK(p.chunk0()[4] == 4 && p.chunk_v0()[3] == 101 && p.chunk_n()[0] == 50 && p.chunk_n()[3] == 7);
+        const std::vector<int> a{9, 8, 7}, b{6};
+        ChunkLists q;
+        q.plan({&a, &b}, {0, 50, 51, 7}, 50);
+        CHECK(q.C == 4 && q.o_chunk0 == 4 && q.o_cv0 == 9 && q.o_cn == 13);
+        CHECK((q.lists == std::vector<int>{9, 8, 7, 6, 0, 0, 1, 3, 4, 0, 50, 100, 101, 50, 50, 1, 7}));
+        ChunkLists one;                                           // one group of one chunk
+        one.plan({}, {5}, 1ll << 30);
+        CHECK(one.C == 1 && one.o_cv0 == 2 && one.o_cn == 3 && (one.lists == std::vector<int>{0, 1, 0, 5}));
+        ChunkLists none;                                          // an empty plan: groups without rows, and no group at all
+        none.plan({&b}, {0, 0}, 50);
+        CHECK(none.C == 0 && none.o_chunk0 == 1 && none.o_cv0 == 4 && none.o_cn == 4 && (none.lists == std::vector<int>{6, 0, 0, 0}));
+        none.plan({}, {}, 50);
+        CHECK(none.C == 0 && none.o_cv0 == 1 && none.o_cn == 1 && (none.lists == std::vector<int>{0}));
+    }
+    CHECK(g_live.empty());
+    {   // a label per frame row (F = 100): NULL, -2 and R refused with the FIRST offender named, -1 and R - 1 accepted and uploaded
+        const int R = 3;
+        std::vector<int32_t> lab(100, 0);
+        DevBuf<int32_t> d;
+        CHECK(upload_row_labels(&ctx, WHO, "frame_class", "class", nullptr, R, &d) == PCL_ERR_INVALID && says(ctx, "who: frame_class is NULL") && !d);
+        lab[7] = -2;
+        lab[9] = R;
+        CHECK(upload_row_labels(&ctx, WHO, "frame_class", "class", lab.data(), R, &d) == PCL_ERR_INVALID &&
+              says(ctx, "who: frame_class[7] = -2 is neither -1 nor a class in [0, 3)") && !d);
+        lab[7] = 0;
+        CHECK(upload_row_labels(&ctx, WHO, "frame_row", "row", lab.data(), R, &d) == PCL_ERR_INVALID &&
+              says(ctx, "who: frame_row[9] = 3 is neither -1 nor a row in [0, 3)") && !d && g_live.empty());
+        lab[9] = R - 1;
+        lab[99] = -1;
+        CHECK(upload_row_labels(&ctx, WHO, "frame_row", "row", lab.data(), R, &d) == PCL_OK && d.cap == 100 && d[9] == R - 1 && d[99] == -1);
+        pcl_ctx empty;                                            // no frames: after the NULL check, before the scan
+        CHECK(upload_row_labels(&empty, WHO, "frame_row", "row", nullptr, R, &d) == PCL_ERR_INVALID);
+        CHECK(upload_row_labels(&empty, WHO, "frame_row", "row", lab.data(), R, &d) == PCL_ERR_STATE && says(empty, "who: no frames loaded"));
+    }
+    CHECK(g_live.empty());
     {   // a positive integer, else the fallback; read on every call
         unsetenv("PCL_TEST_CHUNK");
         CHECK(env_positive_ll("PCL_TEST_CHUNK", 4096) == 4096);

@@ -1,5 +1,5 @@
 """The host helpers every frame-level entry point shares (poccala_amd/csrc/frame_spans.h: the span and speaker checks, the upload, the
-chunk plan, the environment reader), without a GPU: tests/frame_spans_host_check.cpp is compiled against a stub context and a malloc-backed
+chunk plan and its one packed list, the check and upload of a label per frame row, the environment reader), without a GPU: tests/frame_spans_host_check.cpp is compiled against a stub context and a malloc-backed
 stub pool with the host's address and undefined-behaviour sanitizers and run as a process of its own."""
 import os
 import shutil

@@ -113,3 +113,72 @@ def test_refused_calls_leave_everything_as_it_was():
         assert eng.frames_download(np.float64).shape == (F, 4)
     finally:
         eng.close()
+
+
+def refusal(call):
+    from poccala_amd import PoccalaHipError
+    with pytest.raises(PoccalaHipError) as ei:
+        call()
+    print('status %d: %s' % (ei.value.code, ei.value))
+    return ei.value.code, str(ei.value)
+
+
+def test_a_refused_zero_keeps_the_statistics_in_place():
+    """pcl_lda_zero and pcl_cmvn_zero build the fresh set beside the one in place and move it in last (pcl_tree_zero's rule): a zero
+    refused at its bound -- before any allocation -- leaves the accumulated statistics resident, bit for bit."""
+    from poccala_amd import Engine
+    rng = np.random.default_rng(12)
+    cls = rng.integers(-1, 3, size=F).astype(np.int32)
+    eng = Engine(0)
+    try:
+        eng.load_frames(rng.standard_normal((F, D)))
+        eng.lda_zero(3, 1, 1)
+        eng.lda_accumulate(T, BEGIN, cls)
+        eng.cmvn_zero(S)
+        eng.cmvn_accumulate(T, BEGIN, SPK)
+        lda, cmvn = eng.lda_stats(), eng.cmvn_stats()
+        assert all(x.any() for x in lda + cmvn)
+        assert refusal(lambda: eng.lda_zero(65536, 1, 1))[0] == INVALID          # the documented bound: 65535 classes
+        assert all(same_bits(x, y) for x, y in zip(eng.lda_stats(), lda))
+        assert refusal(lambda: eng.cmvn_zero(65536))[0] == INVALID               # ... and 65535 speakers
+        assert all(same_bits(x, y) for x, y in zip(eng.cmvn_stats(), cmvn))
+        eng.lda_accumulate(T, BEGIN, cls)                                        # ... and both sets go on from where they were
+        eng.cmvn_accumulate(T, BEGIN, SPK)
+        assert same_bits(eng.lda_stats()[0], 2 * lda[0]) and same_bits(eng.cmvn_stats()[0], 2 * cmvn[0])
+    finally:
+        eng.close()
+
+
+def test_which_of_two_defects_is_reported():
+    """The order of the entries' checks where a call has two defects (the table at LdaStats, csrc/pcl_internal.h), as the library had it
+    before the checks were put behind one form: the labels of pcl_lda_accumulate are looked at before the statistics' width and before
+    the utterances, those of pcl_tree_accumulate after the width and before the utterances, and pcl_cmvn_accumulate looks at the
+    utterances before it asks for statistics."""
+    from poccala_amd import Engine
+    rng = np.random.default_rng(13)
+    cls = rng.integers(-1, 3, size=F).astype(np.int32)
+    bad = cls.copy()
+    bad[5], bad[40] = 3, -2
+    overlap = DEFECTS['overlap'][1]
+    eng = Engine(0)
+    try:
+        eng.load_frames(rng.standard_normal((F, D)))
+        code, text = refusal(lambda: eng.cmvn_accumulate(T, overlap, SPK))       # no statistics AND overlapping utterances
+        assert code == INVALID and 'overlap' in text
+        assert refusal(lambda: eng.cmvn_accumulate(T, BEGIN, SPK))[0] == STATE
+        eng.lda_zero(3, 1, 1)
+        eng.tree_zero(3)
+        for name, call in (('frame_class[5] = 3', eng.lda_accumulate), ('frame_row[5] = 3', eng.tree_accumulate)):
+            code, text = refusal(lambda: call(T, overlap, bad))                  # a label out of range (the first is named) AND overlapping utterances
+            assert code == INVALID and name in text
+            code, text = refusal(lambda: call(T, overlap, cls))
+            assert code == INVALID and 'overlap' in text
+        eng.load_frames(rng.standard_normal((F, D - 1)))                         # both sets were made for D dimensions
+        code, text = refusal(lambda: eng.lda_accumulate(T, BEGIN, bad))          # another width AND a label out of range
+        assert code == INVALID and 'frame_class[5] = 3' in text
+        code, text = refusal(lambda: eng.lda_accumulate(T, BEGIN, cls))
+        assert code == STATE and 'pcl_lda_zero again' in text
+        code, text = refusal(lambda: eng.tree_accumulate(T, BEGIN, bad))
+        assert code == STATE and 'pcl_tree_zero again' in text
+    finally:
+        eng.close()
