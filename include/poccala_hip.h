@@ -320,6 +320,69 @@ int pcl_lexicon_untie(pcl_ctx *ctx);
 int pcl_lexicon_states(pcl_ctx *ctx, int32_t *node_state /* n_nodes * 2 * P */);
 int pcl_batch_decode_tied(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit,
                           double logpi_two_units, int lm);
+/* WORD LATTICES (row f20).  The single tree with one history entry per frame is a time-conditioned search: every word that ends at
+ * frame t joins the same continuation, the frame's entry.  So a lattice needs no second search -- its nodes are the history entries, its
+ * arcs the word-end donors -- only a record of what the decode kernels see and drop.
+ * pcl_batch_decode_lattice = pcl_batch_decode (lm = 0, tied = 0), _lm (lm != 0), _tied (tied != 0; with lm != 0 its lm form) through the
+ * kernels' LAT = true instantiations (PCL_DEC_GENERAL=1 still forces the general one): EVERY output of pcl_batch_decode_get / _get_words is
+ * what that call gives on the same batch, bit for bit, whatever max_arcs.  Beside them the kernels write, per utterance,
+ *   one arc record per word-end donor -- a token that finished (D1) at frame t at a node where words end: frame t, tok = its index among
+ *     the frame's tokens, node, hist = its history entry or -1, score = its raw score s (float64), and under lm what rule D6 gave it:
+ *     term = max_w lm(v, w) and word = the chosen w (lm = 0: term 0.0, word 0);
+ *   per history entry, beside hist_prev / hist_node / hist_word: hist_frame = the frame it was made at, hist_seed = the winning offer
+ *     (s + term of the frame's best donor) that seeded the roots.
+ * At most max_arcs records per utterance are kept: beyond them nothing is written, lat_overflow[u] = 1, and n_arcs_wanted[u] still counts
+ * every donor (call again with a larger max_arcs).  The decode results of such an utterance are unaffected.
+ * THE LATTICE of an utterance: nodes START (index 0: history -1, seed 0, frame -1), entry k at index k + 1 (the entries ascend in frame:
+ * the index order is a topological order), END at index hist_n + 1.  A recorded arc goes from node hist + 1 to the entry made at its frame
+ * (a frame with a word-end donor makes one) with ac = score - seed(start node) (-inf for a score of -inf) and lm = term.  The closing arcs
+ * are the decoder's own ending, the n_final tokens pcl_batch_decode_get returns: from node hist + 1 to END, ac = score - seed(start), lm
+ * 0, word -1, frame T - 1, tok = the rank in the transfer; they are pending words, as final scores hold no term of a word pending at the
+ * token's node.  CANONICAL ORDER, built on the device behind the decode (pcl_kernel_time "lattice_build"): recorded arcs ascending in
+ * (frame, tok), closing arcs behind them in transfer order; so the arcs are sorted by end node (a CSR), and a stable counting sort gives
+ * the CSR by start node.  pcl_batch_lattice_get returns this order (NULLs are skipped): n_arcs (U,) = recorded + closing arcs held,
+ * n_arcs_wanted (U,), lat_overflow (U,), the arc arrays (U, max_arcs + candidate) -- frame, tok, node, hist, score, term, word, start node,
+ * end node -- and hist_frame / hist_seed (U, Tmax).
+ * pcl_batch_lattice_posteriors(kappa), float64, no fused multiply-add, no floating-point atomics ("lattice_post"): arc weight w = kappa ac
+ * + lm (the language-model tables are pre-scaled by the caller, as ever); forward over the nodes in index order, alpha(START) = 0,
+ * alpha(n) = LSE over the arcs into n of alpha(start) + w; Viterbi the same with max, the earliest arc on ties; backward in descending
+ * order, beta(END) = 0, beta(n) = LSE over the arcs out of n (ascending arc index) of w + beta(end); ln Z = alpha(END);
+ * ln p(a) = ((alpha(start) + w) + beta(end)) - ln Z.  Every LSE is max, then the sum of exp(v - max), over the node's list: thread i of 256
+ * takes list positions i, i + 256, ... in that order, the 64 lanes of a wave combine by a butterfly (partner lane ^ 32, 16, 8, 4, 2, 1),
+ * the four waves in ascending order; a maximum of +-inf is returned as itself -- a node that cannot be reached, or cannot reach END, and
+ * every arc at it hold -inf, never NaN.  The best path = the back-pointers from END, as arc indices in path order, its score the Viterbi
+ * value of END.  Every word of it (arc a*, frames tau in (frame(start node), frame(a*)]) gets a confidence, Wessel's C_max: the maximum
+ * over tau of P(tau) = the sum, in ascending arc order, of exp(ln p(a)) over the arcs a that cover tau the same way and share a*'s
+ * identity -- the word id after lm != 0 for a recorded arc, the node otherwise and for the closing arc; an empty span (a closing arc out
+ * of an entry made at the last frame) gives exp(ln p(a*)).  lat_status (U,): 0, or bits 1 = overflowed, 2 = n_final is 0, 4 = a record
+ * out of range, 8 = ln Z is -inf; then ln Z, the posteriors and the score are NaN and best_n is 0.
+ * pcl_batch_lattice_results (NULLs are skipped): lnZ (U,), arc_lnpost (U, max_arcs + candidate), best_n (U,), best_arc and best_conf
+ * (U, Tmax + 3), best_score (U,), lat_status (U,).
+ * Not here: exact bigram re-expansion over arc pairs (an arc carries the term the decoder gave it, under the one predecessor word its
+ * node kept), N-best lists, lattice-based MMI / MPE statistics, pruning or compaction of the lattice.
+ * PCL_ERR_STATE: what the underlying decode refuses (no lexicon, emissions, language model or tie the flags ask for); _get / _posteriors
+ * without a preceding pcl_batch_decode_lattice, _results without _posteriors -- new emissions, transitions, states, scoring or any other
+ * decode drop the lattice.  PCL_ERR_INVALID: max_arcs < 1; kappa not finite or not > 0.  All checked before anything is changed.  The
+ * buffers are the batch's own, made on first use.  The decode is queued like pcl_batch_decode; the other three are on the main stream,
+ * _get and _results synchronous. */
+int pcl_batch_decode_lattice(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit,
+                             double logpi_two_units, int lm, int tied, int max_arcs);
+int pcl_batch_lattice_get(pcl_batch *b, int32_t *n_arcs, int32_t *n_arcs_wanted, int32_t *lat_overflow, int32_t *arc_frame, int32_t *arc_tok,
+                          int32_t *arc_node, int32_t *arc_hist, double *arc_score, double *arc_term, int32_t *arc_word, int32_t *arc_start,
+                          int32_t *arc_end, int32_t *hist_frame, double *hist_seed);
+int pcl_batch_lattice_posteriors(pcl_batch *b, double kappa);
+int pcl_batch_lattice_results(pcl_batch *b, double *lnZ, double *arc_lnpost, int32_t *best_n, int32_t *best_arc, double *best_score,
+                              double *best_conf, int32_t *lat_status);
+/* TEST ENTRY.  A record set of the caller's in place of a decode's, so that the lattice pass can be held at list lengths and node counts
+ * no decode of a few seconds reaches: the arrays of pcl_batch_lattice_get ((U, max_arcs), as the kernels would have appended them: frames
+ * ascending, any order inside a frame) and of pcl_batch_decode_get (hist_n (U,), n_final (U,), final_* (U, candidate)), hist_frame /
+ * hist_seed (U, Tmax); n_arcs_wanted may exceed max_arcs.  The build runs on them as behind a decode; a record out of range sets
+ * lat_status bit 4 and is never used as an index.  T_u of the closing arcs' frame is the batch's.  with_words: as after lm != 0. */
+int pcl_batch_lattice_set_records(pcl_batch *b, int max_arcs, int candidate, int with_words, const int32_t *n_arcs_wanted,
+                                  const int32_t *arc_frame, const int32_t *arc_tok, const int32_t *arc_node, const int32_t *arc_hist,
+                                  const double *arc_score, const double *arc_term, const int32_t *arc_word, const int32_t *hist_n,
+                                  const int32_t *hist_frame, const double *hist_seed, const int32_t *n_final, const int32_t *final_node,
+                                  const double *final_score, const int32_t *final_hist);
 
 /* Copy a result to a caller buffer (layouts in pcl_get_what). */
 int pcl_batch_get(pcl_batch *b, int what, void *host);

@@ -84,8 +84,18 @@ def _report(res, tree):
     return out
 
 
+def _decode_timed(b, kappa, max_arcs, *args):
+    """Batch.decode with the word lattice beside it: every detail dict gains word_times = the lattice's best path as [(word id with a
+    language model -- else the word-end node --, first frame, last frame, confidence)], the word pending at the end last (by its node), and
+    lattice_status (0; 1: more word ends than max_arcs, no times)."""
+    res = b.decode(*args, lattice=True, max_arcs=max_arcs)
+    for r, p in zip(res, b.lattice_posteriors(kappa)):
+        r['word_times'], r['lattice_status'] = p['best'], p['status']
+    return res
+
+
 def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, candidate=5, max_tokens=4096, lm=None, lm_scale=1.0,
-                 word_penalty=0.0, tied=False):
+                 word_penalty=0.0, tied=False, word_times=False, kappa=1.0, max_arcs=None):
     """data_list: MFCC matrices (T_u, D), which are uploaded -- or the (lens, begin) of frames already resident (Engine.frontend /
     load_audio_batch(fetch=False)), the form AcousticModel's batch helpers take: nothing is uploaded, PCM goes to words without a host
     round trip.  Scores every GMM state for every frame (the decoder has no label) and runs the token passing.  Returns per utterance
@@ -93,8 +103,11 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
     reported as ([], -inf, None).  lm: a LanguageModel.Ngram -- compiled with lm_scale / word_penalty, uploaded, and applied at word
     ends (D6); every word then comes back as one string instead of the node's list of homophones.  tied: the loaded model is one over
     tied states and the tree was tied under its tying (load_inventory(tying=...)): the all-state batch has J_t + 2 rows and the token
-    passing reads each node's tied states."""
+    passing reads each node's tied states.  word_times=True: words, score and the detail's fields are what they are without it; the detail
+    gains word_times and lattice_status (_decode_timed: times and confidences from the word lattice under the acoustic scale kappa, at most
+    max_arcs word ends per utterance kept, default 128 per frame)."""
     engine = engine or default_engine()
+    run = (lambda b, *a: _decode_timed(b, kappa, max_arcs, *a)) if word_times else (lambda b, *a: b.decode(*a))
     compiled = load_language_model(engine, tree, lm, lm_scale, word_penalty) if lm is not None else None
     report = (lambda res: _report_lm(res, tree, compiled)) if lm is not None else (lambda res: _report(res, tree))
     if isinstance(data_list, tuple) and len(data_list) == 2 and np.ndim(data_list[0]) == 1:       # AcousticModel._resident's test
@@ -104,7 +117,7 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
         if len(keep):
             b = engine.all_state_batch(lens[keep], begin[keep])
             b.score(precision)
-            res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
+            res = run(b, beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
             b.close()
             for u, r in zip(keep, report(res)):
                 out[u] = r
@@ -114,7 +127,7 @@ def decode_batch(data_list, tree, engine=None, precision=PCL_F32, beam_=None, ca
     engine.load_frames(np.concatenate([np.asarray(d) for d in data_list], axis=0))
     b = engine.all_state_batch(lens, begin)
     b.score(precision)
-    res = b.decode(beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
+    res = run(b, beam if beam_ is None else beam_, 8, candidate, max_tokens, lm is not None, tied)
     b.close()
     return report(res)
 

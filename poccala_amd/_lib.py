@@ -151,6 +151,11 @@ PROTOTYPES = {
     'pcl_lexicon_untie': (_i, [_vp]),
     'pcl_lexicon_states': (_i, [_vp, _vp]),
     'pcl_batch_decode_tied': (_i, [_vp, _d, _i, _i, _i, _d, _d, _i]),
+    'pcl_batch_decode_lattice': (_i, [_vp, _d, _i, _i, _i, _d, _d, _i, _i, _i]),
+    'pcl_batch_lattice_get': (_i, [_vp] * 15),
+    'pcl_batch_lattice_posteriors': (_i, [_vp, _d]),
+    'pcl_batch_lattice_results': (_i, [_vp] * 8),
+    'pcl_batch_lattice_set_records': (_i, [_vp, _i, _i, _i] + [_vp] * 15),
     'pcl_comm_init_host': (_i, [_vp, _i, _i, _vp, _vp]),
     'pcl_comm_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     'pcl_em_exchange': (_i, [_vp, _d, _i, _i]),

@@ -182,8 +182,11 @@ __device__ __forceinline__ void step_range(const LaneCtx &c, const double *lt, c
 // TIED (compile time): a lane's emission row comes from its node's tied states (pcl_batch_decode_tied; DecTie, hmm_decode_common.h),
 // gathered in the step by the token's node id; TIED = false reads nothing of `tie`.  The TIED = true instantiations (with and without LM)
 // have a translation unit of their own too: hmm_decode_tied.hip defines PCL_DEC_TIED and includes this file.
-template <bool TLDS, int KMAX, bool LM, bool TIED>
-__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a, DecLmArg<LM> lm, DecTieArg<TIED> tie) {
+// LAT (compile time): the word lattice's records (pcl_batch_decode_lattice; DecLat, hmm_decode_common.h, states the rule): the donor phase
+// sees every word-end donor, and thread 0 the frame's entry.  LAT = false reads nothing of `lat`; all four (LM, TIED) combinations of
+// LAT = true are in hmm_decode_lat.hip, which defines PCL_DEC_LAT and includes this file.
+template <bool TLDS, int KMAX, bool LM, bool TIED, bool LAT>
+__global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecArgs a, DecLmArg<LM> lm, DecTieArg<TIED> tie, DecLatArg<LAT> lat) {
     extern __shared__ double dyn[];
     __shared__ int seg_l[SEG_LDS + 1];
     __shared__ unsigned int hist256[256];                          // pruning: the occupancy map, then the radix histogram
@@ -194,6 +197,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
     __shared__ unsigned long long s_sel;                           // pruning select: the chosen bin (pcl_select_kth's s_key)
     __shared__ int s_i[4];                                         // [0..2] the donor phase's winner; [3] the select's rank
     __shared__ double s_d[1];
+    [[maybe_unused]] __shared__ int lat_cnt;                       // LAT: the utterance's word-end donors so far
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const UttDesc d = a.utts[u];
@@ -247,6 +251,9 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
 
     // ---- frame 0: every first-character node starts (D3)
     if (tid < 256) hist256[tid] = 0u;                              // (the pruning steps take it zero and leave it zero)
+    if constexpr (LAT) {
+        if (tid == 0) lat_cnt = 0;                                 // (the barriers of frame 0 come before the first append)
+    }
     int cur = 0, n = min(a.n_roots, cap), ovf = a.n_roots > cap, nh = 0;
     for (int i = tid; i < n; i += DW) {
         const int node = a.roots[i];
@@ -287,6 +294,9 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         double bw = -INFINITY;
         for (int k = 0; k < C; k += 64) {
             const int i = w0 + k + lane;
+            [[maybe_unused]] bool rec = false;                     // LAT: this lane's token is a word-end donor, and its record
+            [[maybe_unused]] int r_node = 0, r_hist = 0, r_word = 0;
+            [[maybe_unused]] double r_score = 0.0, r_term = 0.0;
             if (i < n && (flag[i] & 1)) {
                 const int node = nd[i];
                 ++nd_cnt;
@@ -295,13 +305,30 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                     fw = min(fw, i);
                     double s = sc[i];
                     [[maybe_unused]] int wsel = 0;
-                    if constexpr (LM) s += pcl_lm_word_term(lm, hword, hs[i], node, wsel);   // D6: the offer to the roots
+                    if constexpr (LAT) {
+                        rec = true;
+                        r_node = node;
+                        r_hist = hs[i];
+                        r_score = s;
+                    }
+                    if constexpr (LM) {                            // D6: the offer to the roots
+                        const double term = pcl_lm_word_term(lm, hword, hs[i], node, wsel);
+                        if constexpr (LAT) {
+                            r_term = term;
+                            r_word = wsel;
+                        }
+                        s += term;
+                    }
                     if (bw_i == NONE || s > bw) {                  // (a thread's tokens come in ascending order)
                         bw = s;
                         bw_i = i;
                         if constexpr (LM) bw_word = wsel;
                     }
                 }
+            }
+            if constexpr (LAT) {                                   // (C is the workgroup's: every lane of the wave is here)
+                const unsigned long long rmask = __ballot(rec);
+                if (rmask != 0ull) pcl_lat_record(lat, u, pcl_lat_place(&lat_cnt, rmask, rec), t, i, r_node, r_hist, r_score, r_term, r_word);
             }
         }
         nd_cnt = pcl_wave_sum(nd_cnt);
@@ -336,6 +363,7 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
                         for (int w = 0; w < NWV; ++w)
                             if (red_i[0][w] == bi) hword[nh] = w_word[w];   // (the wave the winner came from: token indices are unique)
                     }
+                    if constexpr (LAT) pcl_lat_entry(lat, u, a.Tmax, nh, t, b);
                 }
                 s_i[2] = nh;
             }
@@ -529,21 +557,22 @@ __global__ __launch_bounds__(DW) PCL_DEC_WAVES_ATTR void hmm_decode_kernel(DecAr
         a.out_n[u] = n_out;
         a.hist_n[u] = min(nh, a.Tmax);
         a.overflow[u] = ovf;
+        if constexpr (LAT) lat.n_wanted[u] = lat_cnt;              // (behind the transfer's barriers: every append is in)
     }
     STAMP_END(a.stamps)
 }
 
 // The launch of one (LM, TIED) pair of instantiations, for the three translation units that hold them.
-template <bool LM, bool TIED>
-int dec_launch_kernel(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie) {
+template <bool LM, bool TIED, bool LAT = false>
+int dec_launch_kernel(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie, const DecLatArg<LAT> &lat = {}) {
     // the unit matrices and one emission row in LDS when they fit beside the kernel's static 18 KB
     const size_t table_bytes = ((size_t)ctx->n_units * ctx->S * ctx->S + (size_t)n_rows) * sizeof(double);
     const bool tlds = table_bytes <= 44u * 1024u;
     const int cap = a.cap;
 #define PCL_DEC_LAUNCH(K)                                                                                                                  \
     do {                                                                                                                                   \
-        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K, LM, TIED>), dim3(U), dim3(DW), table_bytes, ctx->stream, a, lma, tie);   \
-        else hipLaunchKernelGGL((hmm_decode_kernel<false, K, LM, TIED>), dim3(U), dim3(DW), 0, ctx->stream, a, lma, tie);                  \
+        if (tlds) hipLaunchKernelGGL((hmm_decode_kernel<true, K, LM, TIED, LAT>), dim3(U), dim3(DW), table_bytes, ctx->stream, a, lma, tie, lat);   \
+        else hipLaunchKernelGGL((hmm_decode_kernel<false, K, LM, TIED, LAT>), dim3(U), dim3(DW), 0, ctx->stream, a, lma, tie, lat);                  \
     } while (0)
     if (cap <= DW) PCL_DEC_LAUNCH(1);
     else if (cap <= 2 * DW) PCL_DEC_LAUNCH(2);
@@ -555,7 +584,14 @@ int dec_launch_kernel(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const D
     return PCL_OK;
 }
 
-#if defined(PCL_DEC_TIED)
+#if defined(PCL_DEC_LAT)
+}  // namespace
+int pcl_decode_general_launch_lat(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie *tie, const DecLat &lat) {
+    if (tie) return lm ? dec_launch_kernel<true, true, true>(ctx, a, U, n_rows, *lm, *tie, lat) : dec_launch_kernel<false, true, true>(ctx, a, U, n_rows, DecNoLm{}, *tie, lat);
+    return lm ? dec_launch_kernel<true, false, true>(ctx, a, U, n_rows, *lm, DecNoTie{}, lat)
+              : dec_launch_kernel<false, false, true>(ctx, a, U, n_rows, DecNoLm{}, DecNoTie{}, lat);
+}
+#elif defined(PCL_DEC_TIED)
 }  // namespace
 int pcl_decode_general_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie) {
     return lm ? dec_launch_kernel<true, true>(ctx, a, U, n_rows, *lm, tie) : dec_launch_kernel<false, true>(ctx, a, U, n_rows, DecNoLm{}, tie);
@@ -864,14 +900,18 @@ int pcl_lm_upload(pcl_ctx *ctx, int W, const double *uni, const double *bow, con
 }
 
 // pcl_batch_decode (with_lm = false: the LM = false kernels, nothing of the language model is touched), pcl_batch_decode_lm, and
-// pcl_batch_decode_tied (tied: the TIED = true kernels of either)
+// pcl_batch_decode_tied (tied: the TIED = true kernels of either); max_arcs > 0: pcl_batch_decode_lattice -- the LAT = true kernels of
+// whichever it is, and the lattice's build behind them
 static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, bool with_lm,
-                   bool tied = false) {
+                   bool tied = false, int max_arcs = 0) {
     if (!b) return PCL_ERR_INVALID;
     pcl_ctx *ctx = b->ctx;
+    const bool lattice = max_arcs > 0;
     TRY(dec_validate(b, beam, min_distinct, candidate, max_tokens, tied));
     if (with_lm && !ctx->lm_W)
-        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no language model (pcl_lm_upload after pcl_lexicon_upload)", tied ? "pcl_batch_decode_tied" : "pcl_batch_decode_lm");
+        PCL_FAIL(ctx, PCL_ERR_STATE, "%s: no language model (pcl_lm_upload after pcl_lexicon_upload)",
+                 lattice ? "pcl_batch_decode_lattice" : tied ? "pcl_batch_decode_tied" : "pcl_batch_decode_lm");
+    b->have_lat = b->have_lat_post = false;                                    // (any decode drops the lattice of the one before)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (b->dp_pending) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, b->ev_dp, 0));
@@ -901,14 +941,22 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
         HIPCHK(ctx, hipMemsetAsync(d_stamps, 0, PCL_DEC_N_STAMP * sizeof(long long), ctx->stream));
         a.stamps = d_stamps;
 #endif
+        DecLat lat = {};
+        if (lattice) {
+            TRY(pcl_lattice_reserve(ctx, b, max_arcs, candidate));
+            lat = pcl_lattice_dec_args(b);
+        }
         pcl_timer_begin(ctx, "decode");
         const DecLm *lmp = with_lm ? &lm : nullptr;
         const DecTie tie{ctx->lex_tie_lr, ctx->lex_tie_gen};
-        const int rc = tied ? (use_lr ? pcl_decode_lr_launch_tied(ctx, a, U, n_rows, lmp, tie) : pcl_decode_general_launch_tied(ctx, a, U, n_rows, lmp, tie))
-                            : (use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows, lmp) : dec_launch_general(ctx, a, U, n_rows, lmp));
+        const int rc = lattice ? (use_lr ? pcl_decode_lr_launch_lat(ctx, a, U, n_rows, lmp, tied ? &tie : nullptr, lat)
+                                         : pcl_decode_general_launch_lat(ctx, a, U, n_rows, lmp, tied ? &tie : nullptr, lat))
+                       : tied  ? (use_lr ? pcl_decode_lr_launch_tied(ctx, a, U, n_rows, lmp, tie) : pcl_decode_general_launch_tied(ctx, a, U, n_rows, lmp, tie))
+                               : (use_lr ? pcl_decode_lr_launch(ctx, a, U, n_rows, lmp) : dec_launch_general(ctx, a, U, n_rows, lmp));
         pcl_timer_end(ctx, "decode");
         TRY(rc);
         HIPCHK(ctx, hipGetLastError());
+        if (lattice) TRY(pcl_lattice_build(ctx, b, PclLatDecEnd{a.out_n, a.out_node, a.out_hist, a.hist_n, a.out_score, candidate}, with_lm));
 #ifdef PCL_DEC_STAMPS
         TRY(dec_print_stamps(ctx, d_stamps));
 #endif
@@ -919,6 +967,7 @@ static int dec_run(pcl_batch *b, double beam, int min_distinct, int candidate, i
     TRY(pcl_run_recursion(b, 0, launch));
     b->have_dec = true;
     b->dec_has_words = with_lm;
+    b->have_lat = lattice;
     return PCL_OK;
 }
 
@@ -932,6 +981,13 @@ int pcl_batch_decode_lm(pcl_batch *b, double beam, int min_distinct, int candida
 
 int pcl_batch_decode_tied(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, int lm) {
     return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, lm != 0, true);
+}
+
+int pcl_batch_decode_lattice(pcl_batch *b, double beam, int min_distinct, int candidate, int max_tokens, double logpi_one_unit, double logpi_two_units, int lm, int tied,
+                             int max_arcs) {
+    if (!b) return PCL_ERR_INVALID;
+    if (max_arcs < 1) PCL_FAIL(b->ctx, PCL_ERR_INVALID, "pcl_batch_decode_lattice: max_arcs = %d", max_arcs);
+    return dec_run(b, beam, min_distinct, candidate, max_tokens, logpi_one_unit, logpi_two_units, lm != 0, tied != 0, max_arcs);
 }
 
 // the chosen words of the history entries, on the stream the decoder ran on (before or after pcl_batch_decode_get)

@@ -62,6 +62,27 @@ struct DecNoTie {};
 template <bool TIED>
 using DecTieArg = std::conditional_t<TIED, DecTie, DecNoTie>;
 
+// The word lattice's records (pcl_batch_decode_lattice; the lattice pass: lattice.hip) for the LAT = true instantiations of the two kernels.
+// Like DecLm and DecTie a kernel argument of its own: DecArgs and the LAT = false kernels stay what they were.  The rule, once:
+//   every word-end donor of frame t (a finished token at a node where words end: exactly the tokens that take part in the frame's choice
+//   of a history entry) leaves ONE arc record (t, its token index in the frame, node, its history entry or -1, its raw score s, and under
+//   LM what pcl_lm_word_term returned for it: term and word; without LM 0.0 and 0), appended to the utterance's list at the next free
+//   place -- frames ascend in the list, the order inside a frame is whatever the waves' appends give (lattice.hip sorts it).  A record
+//   whose place is >= max_arcs is not written; the counter still counts it (n_wanted), so overflow = n_wanted > max_arcs.
+//   Every history entry gets the frame it was made at and the winning offer w_score that seeded the roots (hist_frame, hist_seed).
+// Nothing the decoder itself reads is written: its results are those of the LAT = false kernel, bit for bit, overflow or not.
+struct DecLat {
+    int max_arcs;
+    int *arc_frame, *arc_tok, *arc_node, *arc_hist, *arc_word;     // [U][max_arcs]
+    double *arc_score, *arc_term;                                  // [U][max_arcs]
+    int *n_wanted;                                                 // [U]: every word-end donor, written or not
+    int *hist_frame;                                               // [U][Tmax], beside hist_prev / hist_node / hist_word
+    double *hist_seed;                                             // [U][Tmax]
+};
+struct DecNoLat {};
+template <bool LAT>
+using DecLatArg = std::conditional_t<LAT, DecLat, DecNoLat>;
+
 constexpr int PCL_DEC_N_STAMP = 8;
 // A lane keeps the sort keys of the old tokens it owns in registers through the pruning phase, at most this many: a kernel of NT
 // threads takes cap <= 16 NT tokens per utterance.  The general kernel's 16 x 1024 is what pcl_batch_decode accepts; the
@@ -138,6 +159,31 @@ __host__ __device__ __forceinline__ double pcl_lm_word_term(const DecLm &lm, con
         }
     }
     return best;
+}
+
+// LAT: the wave's word-end donors of one ballot (`mask`, wave-uniform and not zero; `mine`: this lane is one) take their places in the
+// utterance's record list: one integer add on the workgroup's counter in LDS by lane 0, the lanes' places in lane order behind it.
+__device__ __forceinline__ int pcl_lat_place(int *counter, unsigned long long mask, bool mine) {
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(counter, __popcll(mask));
+    base = __shfl(base, 0, 64);
+    return mine ? base + __popcll(mask & ((1ull << lane) - 1ull)) : -1;
+}
+__device__ __forceinline__ void pcl_lat_record(const DecLat &lat, int u, int place, int frame, int tok, int node, int hist, double score, double term, int word) {
+    if (place < 0 || place >= lat.max_arcs) return;
+    const size_t x = (size_t)u * lat.max_arcs + place;
+    lat.arc_frame[x] = frame;
+    lat.arc_tok[x] = tok;
+    lat.arc_node[x] = node;
+    lat.arc_hist[x] = hist;
+    lat.arc_word[x] = word;
+    lat.arc_score[x] = score;
+    lat.arc_term[x] = term;
+}
+__device__ __forceinline__ void pcl_lat_entry(const DecLat &lat, int u, int Tmax, int entry, int frame, double seed) {
+    lat.hist_frame[(size_t)u * Tmax + entry] = frame;
+    lat.hist_seed[(size_t)u * Tmax + entry] = seed;
 }
 
 // (ob, oi) replaces (b, bi) as the best (score, index): greater, or equal and earlier; NONE = nothing yet
@@ -474,3 +520,16 @@ int pcl_decode_general_launch_lm(pcl_ctx *ctx, const DecArgs &a, int U, int n_ro
 // the TIED = true instantiations, with (lm) and without (nullptr) the language model: hmm_decode_lr_tied.hip, hmm_decode_tied.hip
 int pcl_decode_lr_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie);
 int pcl_decode_general_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie);
+// the LAT = true instantiations, all four (lm, tie) combinations (nullptr = without): hmm_decode_lr_lat.hip, hmm_decode_lat.hip
+int pcl_decode_lr_launch_lat(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie *tie, const DecLat &lat);
+int pcl_decode_general_launch_lat(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie *tie, const DecLat &lat);
+// lattice.hip: the batch's lattice buffers for (max_arcs, candidate), the kernels' view of them, and the build behind the decode kernel (on
+// ctx->stream) from the decoder's own ending -- what the transfer returned and how many history entries were made
+struct PclLatDecEnd {
+    const int *out_n, *out_node, *out_hist, *hist_n;               // [U], [U][candidate], [U][candidate], [U]
+    const double *out_score;                                       // [U][candidate]
+    int candidate;
+};
+int pcl_lattice_reserve(pcl_ctx *ctx, pcl_batch *b, int max_arcs, int candidate);
+DecLat pcl_lattice_dec_args(const pcl_batch *b);
+int pcl_lattice_build(pcl_ctx *ctx, pcl_batch *b, const PclLatDecEnd &end, bool with_lm);

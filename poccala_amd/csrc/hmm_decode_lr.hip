@@ -128,8 +128,11 @@ __device__ __forceinline__ void lr_step(const double *tab, const double *Bs, int
 // gathered from the per-node table by the node id each phase has at hand.  TIED = false reads nothing of `tie`.  For the same reason as
 // above the TIED = true instantiations (with and without LM) have a translation unit of their own: hmm_decode_lr_tied.hip defines
 // PCL_DECLR_TIED and includes this file.
-template <int KMAX, bool LM, bool TIED>
-__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP, DecLmArg<LM> lm, DecTieArg<TIED> tie) {
+// LAT (compile time): the word lattice's records (pcl_batch_decode_lattice; DecLat, hmm_decode_common.h, states the rule): phase A2 has a
+// lane per donor with everything a record holds, and thread 0 of phase C the frame's entry.  LAT = false reads nothing of `lat`; all four
+// (LM, TIED) combinations of LAT = true are in hmm_decode_lr_lat.hip, which defines PCL_DECLR_LAT and includes this file.
+template <int KMAX, bool LM, bool TIED, bool LAT>
+__global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(DecArgs a, int NbP, DecLmArg<LM> lm, DecTieArg<TIED> tie, DecLatArg<LAT> lat) {
     extern __shared__ double dyn[];                                // unit table [n_units][TS] | two emission rows [NbP]
     // one pool, two tenants: the donor lists (phases A - C) and the pruning select's histogram + candidates (phase E)
     __shared__ __attribute__((aligned(16))) unsigned char pool[POOL_BYTES];
@@ -148,6 +151,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
     __shared__ double red_d[LNW];
     __shared__ unsigned long long s_key;                           // the pruning select's result words (pcl_select_kth)
     __shared__ int s_int[4];
+    [[maybe_unused]] __shared__ int lat_cnt;                       // LAT: the utterance's word-end donors so far
     const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifndef PCL_DECLR_NOPRIO
     // latency bound, few instructions, 300 frames of dependent phases: beside the scoring kernel of the next chunk (the C5 pipeline)
@@ -190,6 +194,9 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
     }
     if (tid < 256) occ[tid] = 0u;
     if (tid == 0) s_int[2] = 0;
+    if constexpr (LAT) {
+        if (tid == 0) lat_cnt = 0;
+    }
     __syncthreads();
 
     // ---- frame 0: every first-character node starts (D3) and takes its first step
@@ -371,9 +378,16 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                         fw_end = __shfl(ofs + cnt, f, 64);
                     }
                     [[maybe_unused]] int wsel = 0;
+                    [[maybe_unused]] double s_raw = 0.0, s_term = 0.0;
+                    if constexpr (LAT) s_raw = s;
                     if constexpr (LM) {                            // D6: the offer to the roots (the children keep the raw score)
-                        if (word) s += pcl_lm_word_term(lm, hword, hs, node, wsel);
+                        if (word) {
+                            const double term = pcl_lm_word_term(lm, hword, hs, node, wsel);
+                            if constexpr (LAT) s_term = term;
+                            s += term;
+                        }
                     }
+                    if constexpr (LAT) pcl_lat_record(lat, u, pcl_lat_place(&lat_cnt, wmask, word), t, tok, node, hs, s_raw, s_term, wsel);
                     if (word && (bw_i == NONE || s > bw)) {        // (a lane's donors come in ascending token order)
                         bw = s;
                         bw_i = tok;
@@ -424,6 +438,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
                 hprev[nh] = w_dhist;
                 hnode[nh] = w_node;
                 if constexpr (LM) hword[nh] = w_word;
+                if constexpr (LAT) pcl_lat_entry(lat, u, a.Tmax, nh, t, w_score);
             }
             ++nh;
         }
@@ -612,6 +627,7 @@ __global__ __launch_bounds__(LW) PCL_DECLR_WAVES_ATTR void hmm_decode_lr_kernel(
         a.out_n[u] = n_out;
         a.hist_n[u] = min(nh, a.Tmax);
         a.overflow[u] = ovf;
+        if constexpr (LAT) lat.n_wanted[u] = lat_cnt;              // (behind the transfer's barriers: every append is in)
     }
     STAMP_END(a.stamps)
 }
@@ -624,15 +640,15 @@ size_t lr_dyn_bytes(const pcl_ctx *ctx, int n_rows) {
     return ((size_t)((ctx->n_units * TS + 1) & ~1) + 2 * (size_t)NbP) * sizeof(double);
 }
 
-template <bool LM, bool TIED>
-int lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie) {
+template <bool LM, bool TIED, bool LAT = false>
+int lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<LM> &lma, const DecTieArg<TIED> &tie, const DecLatArg<LAT> &lat = {}) {
     const int cap = a.cap, NbP = (n_rows + 1) & ~1;
     const size_t dyn = lr_dyn_bytes(ctx, n_rows);
 #define PCL_DECLR_LAUNCH(K)                                                                                                             \
     do {                                                                                                                                \
         if (dyn + LR_STATIC_LDS > 64u * 1024u)                                                                                          \
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K, LM, TIED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
-        hipLaunchKernelGGL((hmm_decode_lr_kernel<K, LM, TIED>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP, lma, tie);                 \
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)hmm_decode_lr_kernel<K, LM, TIED, LAT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn)); \
+        hipLaunchKernelGGL((hmm_decode_lr_kernel<K, LM, TIED, LAT>), dim3(U), dim3(LW), dyn, ctx->stream, a, NbP, lma, tie, lat);       \
     } while (0)
     if (cap <= 8 * LW) PCL_DECLR_LAUNCH(8);
     else PCL_DECLR_LAUNCH(16);
@@ -642,7 +658,12 @@ int lr_launch(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLmArg<
 
 }  // namespace
 
-#if defined(PCL_DECLR_TIED)
+#if defined(PCL_DECLR_LAT)
+int pcl_decode_lr_launch_lat(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie *tie, const DecLat &lat) {
+    if (tie) return lm ? lr_launch<true, true, true>(ctx, a, U, n_rows, *lm, *tie, lat) : lr_launch<false, true, true>(ctx, a, U, n_rows, DecNoLm{}, *tie, lat);
+    return lm ? lr_launch<true, false, true>(ctx, a, U, n_rows, *lm, DecNoTie{}, lat) : lr_launch<false, false, true>(ctx, a, U, n_rows, DecNoLm{}, DecNoTie{}, lat);
+}
+#elif defined(PCL_DECLR_TIED)
 int pcl_decode_lr_launch_tied(pcl_ctx *ctx, const DecArgs &a, int U, int n_rows, const DecLm *lm, const DecTie &tie) {
     return lm ? lr_launch<true, true>(ctx, a, U, n_rows, *lm, tie) : lr_launch<false, true>(ctx, a, U, n_rows, DecNoLm{}, tie);
 }

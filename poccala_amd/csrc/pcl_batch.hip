@@ -123,7 +123,7 @@ int pcl_batch_upload_sparse(pcl_batch *b, const SparseTrans &t, const double *lo
     HIPCHK(ctx, up(ctx, b->logpi, logpi, (size_t)b->shape.sumN * sizeof(double)));
     HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_trans = true;
-    b->have_fb = b->have_vit = b->have_mbr = false;
+    b->have_fb = b->have_vit = b->have_mbr = b->have_lat = false;
     return PCL_OK;
 }
 
@@ -174,7 +174,7 @@ int pcl_batch_set_states_impl(pcl_batch *b, const int32_t *row_state) {
     HIPCHK(ctx, up(ctx, b->d_row_state, row_state, (size_t)b->shape.sumN * sizeof(int32_t)));
     HIPCHK(ctx, up(ctx, b->d_utt, b->shape.utt.data(), (size_t)b->U * sizeof(UttDesc)));
     b->have_states = true;
-    b->have_mbr = false;                                           // (pcl_batch_mbr's accuracy was taken against the map that just went)
+    b->have_mbr = b->have_lat = false;                             // (pcl_batch_mbr's accuracy was taken against the map that just went; the lattice's decode too)
     b->virt_rows_filled = false;
     b->model_J = ctx->J;
     return PCL_OK;
@@ -213,7 +213,7 @@ int pcl_batch_set_emissions(pcl_batch *b, const double *B) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     b->have_B = true;
     b->virt_rows_filled = false;                                   // (the caller's matrix is in the buffer now)
-    b->have_fb = b->have_vit = b->have_mbr = false;
+    b->have_fb = b->have_vit = b->have_mbr = b->have_lat = false;
     return PCL_OK;
 }
 
@@ -330,7 +330,7 @@ int pcl_batch_score(pcl_batch *b, int precision) {
     HIPCHK(ctx, pcl_batch_mark(b));
     b->mark_is_score = true;
     b->have_B = true;
-    b->have_fb = b->have_vit = b->have_mbr = false;
+    b->have_fb = b->have_vit = b->have_mbr = b->have_lat = false;
     return PCL_OK;
 }
 

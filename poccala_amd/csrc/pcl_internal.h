@@ -319,8 +319,30 @@ struct BatchMbrDev {
     bool have_mbr = false;                           // the buffers hold a pass over the batch's CURRENT transitions, states and emissions
 };
 
+// The word lattice of a batch's last pcl_batch_decode_lattice (the records: the decode kernels' LAT instantiations; everything else:
+// lattice.hip): its own buffers, made on first use and re-made as a group when a call needs more room.  A = max_arcs + candidate arcs and
+// NN = Tmax + 3 node slots per utterance.
+struct BatchLatDev {
+    DevBuf<int> lat_raw_i;                           // [5][U][max_arcs] frame | tok | node | hist | word as the kernels appended them
+    DevBuf<double> lat_raw_f;                        // [2][U][max_arcs] score | term
+    DevBuf<int> lat_arc_i;                           // [7][U][A] canonical order: frame | tok | node | hist | word | start node | end node
+    DevBuf<double> lat_arc_f;                        // [4][U][A] score | term | arc weight under kappa | ln posterior
+    DevBuf<int> lat_out_idx;                         // [U][A] the arcs by start node (the counting sort)
+    DevBuf<int> lat_node_i;                          // [4][U][NN] in_ptr | out_ptr | Viterbi back-pointer | best path
+    DevBuf<double> lat_node_f;                       // [4][U][NN] seed | alpha | beta | Viterbi score
+    DevBuf<int> lat_hist_frame;                      // [U][Tmax]
+    DevBuf<double> lat_hist_seed;                    // [U][Tmax]
+    DevBuf<int> lat_utt_i;                           // [7][U] n_wanted | n_rec | n_arcs | n_nodes (entries) | overflow | status | best_n
+    DevBuf<double> lat_utt_f;                        // [2][U] ln Z | best score
+    DevBuf<double> lat_conf;                         // [U][NN] the confidence of every word of the best path
+    int lat_max_arcs = 0, lat_cand = 0;              // what the buffers were sized for
+    bool lat_lm = false;                             // the decode ran with the language model: a word's identity is its word id
+    bool have_lat = false;                           // the buffers hold the lattice of the batch's last decode
+    bool have_lat_post = false;                      // ... and pcl_batch_lattice_posteriors' results for it
+};
+
 // Every device array and event below is the batch's own: `delete b` gives them back (batch_free_now, pcl_batch.hip).
-struct pcl_batch : BatchDecodeDev, BatchMbrDev {
+struct pcl_batch : BatchDecodeDev, BatchMbrDev, BatchLatDev {
     pcl_ctx *ctx = nullptr;
     int U = 0;
     // What the host planned for the kernels (batch_plan.h), each the host copy of what the device holds: replaced as a whole by the call

@@ -1013,6 +1013,12 @@ class Engine(object):
         self._model_key = None
 
 
+class Lattice(object):
+    """One utterance's word lattice (Batch.lattice): plain arrays, documented there."""
+    __slots__ = ('frame', 'tok', 'node', 'hist', 'score', 'term', 'word', 'start', 'end', 'span', 'hist_frame', 'hist_seed', 'n_entries',
+                 'n_arcs_wanted', 'overflow')
+
+
 class Batch(object):
     """U sentence HMMs.  N[u] states, T[u] frames; matrices cross the boundary in the reference's
     (N,T) float64 layout, one array per utterance."""
@@ -1211,21 +1217,28 @@ class Batch(object):
         """Per-unit ksai_acc / gamma_acc of every label position (LHMM.update_acc + add_acc); label-built batches only."""
         self._check(self._lib.pcl_batch_accumulate_hmm(self._b))
 
-    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False):
+    def decode(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False, lattice=False, max_arcs=None):
         """Token passing over the loaded pronunciation tree (Decoder.py:91-167, 250-288) for every utterance of an all-state
         batch.  Returns a list (one dict per utterance): final = [(node, score, hist)] best first, history = [(prev, node)],
         n_tokens (T,) live tokens after every frame, overflow.  lm=True: with the loaded language model at word ends
         (Engine.load_language_model); history entries are then (prev, node, chosen word id).  tied=True: the emission rows are the
-        tied states Engine.tie_lexicon kept for the tree (pcl_batch_decode_tied): the model and the batch's rows are the tying's J_t states."""
-        self.decode_launch(beam, min_distinct, candidate, max_tokens, lm, tied)
+        tied states Engine.tie_lexicon kept for the tree (pcl_batch_decode_tied): the model and the batch's rows are the tying's J_t states.
+        lattice=True: the same results, bit for bit, and beside them the word lattice (pcl_batch_decode_lattice): at most max_arcs word-end
+        records per utterance (default 128 per frame of the longest utterance) for lattice() and lattice_posteriors()."""
+        self.decode_launch(beam, min_distinct, candidate, max_tokens, lm, tied, lattice, max_arcs)
         return self.decode_results()
 
-    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False):
+    def decode_launch(self, beam=0.85, min_distinct=8, candidate=5, max_tokens=4096, lm=False, tied=False, lattice=False, max_arcs=None):
         """Queue the token passing (on the library's second stream, behind this batch's scoring) and return at once."""
         e = self.eng.S - 2
         lp = np.log(np.array([1.0 / (e + 2), 1.0 / (2 * e + 2)]))               # np.log(np.ones(N) / N), AcousticModel.py:1005
         args = (self._b, float(beam), int(min_distinct), int(candidate), int(max_tokens), float(lp[0]), float(lp[1]))
-        if tied:
+        self._lat = None
+        if lattice:
+            max_arcs = 128 * int(self.T.max()) if max_arcs is None else int(max_arcs)
+            self._check(self._lib.pcl_batch_decode_lattice(*(args + (1 if lm else 0, 1 if tied else 0, max_arcs))))
+            self._lat = (max_arcs, int(candidate), bool(lm))
+        elif tied:
             self._check(self._lib.pcl_batch_decode_tied(*(args + (1 if lm else 0,))))
         else:
             self._check((self._lib.pcl_batch_decode_lm if lm else self._lib.pcl_batch_decode)(*args))
@@ -1263,6 +1276,61 @@ class Batch(object):
 
     def decode_results(self):
         return self.decode_unpack(self.decode_fetch())
+
+    # ------------------------------------------------------------------ the word lattice of the last decode(lattice=True)
+    def lattice_fetch(self):
+        """pcl_batch_lattice_get's arrays as a dict (canonical order; arc arrays (U, max_arcs + candidate), hist_* (U, Tmax))."""
+        if getattr(self, '_lat', None) is None:
+            raise RuntimeError('no lattice: decode(lattice=True) first')
+        max_arcs, cand, _ = self._lat
+        U, A, tm = self.U, max_arcs + cand, int(self.T.max())
+        i32, f64 = np.int32, np.float64
+        out = dict(n_arcs=np.zeros(U, i32), n_arcs_wanted=np.zeros(U, i32), overflow=np.zeros(U, i32), frame=np.zeros((U, A), i32),
+                   tok=np.zeros((U, A), i32), node=np.zeros((U, A), i32), hist=np.zeros((U, A), i32), score=np.zeros((U, A), f64),
+                   term=np.zeros((U, A), f64), word=np.zeros((U, A), i32), start=np.zeros((U, A), i32), end=np.zeros((U, A), i32),
+                   hist_frame=np.zeros((U, tm), i32), hist_seed=np.zeros((U, tm), f64))
+        self._check(self._lib.pcl_batch_lattice_get(self._b, *[ptr(out[k]) for k in (
+            'n_arcs', 'n_arcs_wanted', 'overflow', 'frame', 'tok', 'node', 'hist', 'score', 'term', 'word', 'start', 'end', 'hist_frame', 'hist_seed')]))
+        return out
+
+    def lattice(self):
+        """The word lattice of every utterance, a list of Lattice objects: the arcs in canonical order (ascending (frame, tok), the closing
+        arcs -- word -1 -- last), start / end node per arc (0 = START, entry k = node k + 1, END = n_entries + 1), span = (first, last)
+        frame per arc, hist_frame / hist_seed per entry, n_arcs_wanted and overflow."""
+        raw = self.lattice_fetch()
+        out = []
+        for u in range(self.U):
+            n = int(raw['n_arcs'][u])
+            nf = np.concatenate([[-1], raw['hist_frame'][u]]).astype(np.int64)
+            lat = Lattice()
+            for k in ('frame', 'tok', 'node', 'hist', 'score', 'term', 'word', 'start', 'end'):
+                setattr(lat, k, raw[k][u, :n].copy())
+            lat.n_entries = int((raw['hist_frame'][u] >= 0).sum())               # (the rows are cleared to -1 before every decode)
+            lat.hist_frame = raw['hist_frame'][u, :lat.n_entries].copy()
+            lat.hist_seed = raw['hist_seed'][u, :lat.n_entries].copy()
+            lat.span = np.stack([nf[lat.start] + 1, lat.frame.astype(np.int64)], axis=1) if n else np.zeros((0, 2), np.int64)
+            lat.n_arcs_wanted, lat.overflow = int(raw['n_arcs_wanted'][u]), bool(raw['overflow'][u])
+            out.append(lat)
+        return out
+
+    def lattice_posteriors(self, kappa=1.0):
+        """Forward-backward and Viterbi over the lattice under the acoustic scale kappa (pcl_batch_lattice_posteriors / _results; the rule:
+        include/poccala_hip.h).  Per utterance a dict: lnZ, lnpost (per arc of lattice()'s order), status (0 = fine), best_score, best_arcs,
+        and best = [(word id after a decode with lm -- else the node --, first frame, last frame, confidence)], the pending word of the
+        closing arc last, as (node, ...)."""
+        self._check(self._lib.pcl_batch_lattice_posteriors(self._b, float(kappa)))
+        max_arcs, cand, lm = self._lat
+        U, A, nn = self.U, max_arcs + cand, int(self.T.max()) + 3
+        lnz, lnp, bn = np.zeros(U), np.zeros((U, A)), np.zeros(U, np.int32)
+        ba, bs, bc, st = np.zeros((U, nn), np.int32), np.zeros(U), np.zeros((U, nn)), np.zeros(U, np.int32)
+        self._check(self._lib.pcl_batch_lattice_results(self._b, ptr(lnz), ptr(lnp), ptr(bn), ptr(ba), ptr(bs), ptr(bc), ptr(st)))
+        out = []
+        for u, lat in enumerate(self.lattice()):
+            arcs = ba[u, :bn[u]].copy()
+            best = [(int(lat.word[a]) if lm and lat.word[a] >= 0 else int(lat.node[a]), int(lat.span[a, 0]), int(lat.span[a, 1]), float(c))
+                    for a, c in zip(arcs, bc[u, :bn[u]])]
+            out.append(dict(lnZ=float(lnz[u]), lnpost=lnp[u, :len(lat.frame)].copy(), status=int(st[u]), best_score=float(bs[u]), best_arcs=arcs, best=best))
+        return out
 
     def refresh_transitions(self):
         """Take the engine's CURRENT unit transitions (after mstep_transitions / em_exchange); label-built batches only."""
